@@ -12,6 +12,12 @@ index offset — issued by the library on the handle's own communicator, SURVEY 
 owns its own shard of B scenes (weak scaling, no data-path collective).  The warm-start U is restored from a device copy
 inside the timed region, because the solve overwrites it.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line: value, ms_per_step and the figures derived from the
+timed steps themselves.  --full adds everything that takes runs of its own: the CPU baseline and the parity figures against
+the oracle (unless --no-cpu-baseline), the host-buffer entry point, two batches in flight, the run without the schedule hint
+and c1's device-side kernel timing.  --dump-outputs DIR writes, on rank 0, what the timed path computed in its last step as
+DIR/<name>.npy (float32 / float64; a fixed seeded sample of each array where all of them together would exceed 60 MB).
 """
 import argparse
 import json
@@ -73,6 +79,33 @@ def emit(obj):
         sys.stdout.flush()
     else:
         os.write(_REAL_STDOUT, line.encode())
+
+
+DUMP_BYTES = 60 * 1000 * 1000  # the whole dump, headers included, stays below 64 MB
+
+
+def dump_outputs(args, rank, **arrays):
+    """--dump-outputs: the named outputs of the last timed step (torch tensors or numpy arrays) as DIR/<name>.npy on rank 0.
+    float64 and integers are written as float64, everything else as float32.  The arrays share DUMP_BYTES smallest first, each
+    taking at most an even share of what is left; an array larger than its share is cut to a sample of its flattened elements
+    at indices drawn with a fixed seed (sorted, repeats dropped)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype in (np.float32, np.float16, np.int8, np.uint8) else np.float64)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_BYTES
+    for k, name in enumerate(sorted(out, key=lambda n: out[n].nbytes)):
+        a = out[name]
+        keep = budget // (len(out) - k) // a.itemsize
+        if keep < a.size:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, keep))
+            print("bench.py: %s.npy holds %d of %d elements (seeded sample)" % (name, idx.size, a.size), file=sys.stderr)
+            a = a.reshape(-1)[idx]
+        budget -= a.nbytes
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def cpu_rate(call, units, min_seconds=2.0, reps=3):
@@ -154,6 +187,7 @@ def bench_warp(args, rank, local_rank, world, dist, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump_outputs(args, rank, dst=dst.view(K, dg.cols, dg.rows).transpose(1, 2))  # K frames, each rows x cols
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     if rank == 0:
         cells = dg.rows * dg.cols
@@ -169,7 +203,7 @@ def bench_warp(args, rank, local_rank, world, dist, dev):
                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": recorded_traffic("warp" if K == 1 else "warp%d" % K, S)[0],
                             "traffic_source": recorded_traffic("warp" if K == 1 else "warp%d" % K, S)[1],
                             "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_launch}}
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             threads = O.max_threads()
@@ -236,6 +270,7 @@ def bench_blur(args, rank, local_rank, world, dist, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump_outputs(args, rank, out=out.view(g.cols, g.rows).T)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     if rank == 0:
         cells = g.rows * g.cols
@@ -250,7 +285,7 @@ def bench_blur(args, rank, local_rank, world, dist, dev):
                              "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel_ms": kern_ms,
                              "algorithmic_bytes_per_launch": bytes_launch,
                              "note": "fp64-VALU-bound: ~20-400 tested cells and ~20-80 exp() per output cell"}}
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             threads = O.max_threads()
@@ -328,6 +363,7 @@ def bench_occ(args, rank, local_rank, world, dist, dev):
         if e1 is not None:
             e1.record()
     elapsed, kern_ms = _timed(step, args, dist, dev)
+    dump_outputs(args, rank, layer=layer, occupancy=back)
     if rank == 0:
         bytes_launch = 5 * n
         achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
@@ -340,8 +376,9 @@ def bench_occ(args, rank, local_rank, world, dist, dev):
         to_layer_ms = float(np.mean([a.elapsed_time(b) for a, b in first]))
         out["occ_to_layer_kernel"] = {"kernel_ms": to_layer_ms, "achieved": bytes_launch / (to_layer_ms * 1e-3) / 1e9, "unit": "GB/s",
                                       "frac": bytes_launch / (to_layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        out["round_trip_exact"] = bool(torch.equal(back, occ))
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full:
+            out["round_trip_exact"] = bool(torch.equal(back, occ))
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             ns = min(n, 1 << 26)
@@ -398,6 +435,8 @@ def bench_frame(args, rank, local_rank, world, dist, dev):
         if e1 is not None:
             e1.record()
     elapsed, kern_ms = _timed(step, args, dist, dev)
+    dump_outputs(args, rank, vehicle=veh.view(dg.cols, dg.rows).T, uncertainty=unc.view(dg.cols, dg.rows).T,
+                 occupancy=occ.view(dg.cols, dg.rows).T)
     if rank == 0:
         bytes_launch = 13 * nd  # warp: 4 read + 4 write; blur: 4 read (+ neighbours from cache) + 4 + 1 write
         achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
@@ -408,7 +447,7 @@ def bench_frame(args, rank, local_rank, world, dist, dev):
                     {"bound": "hbm", "kernel": "warp_kernel + blur_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_launch,
                      "note": "both launches of one frame inside the event pair; the blur is fp64-VALU-bound, see DESIGN.md §4.5"})
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             threads = O.max_threads()
@@ -455,6 +494,7 @@ def bench_plan(args, rank, local_rank, world, dist, dev):
         if e1 is not None:
             e1.record()
     elapsed, kern_ms = _timed(step, args, dist, dev)
+    dump_outputs(args, rank, poly=poly, first_last=fl)
     if rank == 0:
         bytes_launch = B * (32 + 64) + 16 * P  # ego in, poly + first/last out, the shared path once
         achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
@@ -463,7 +503,7 @@ def bench_plan(args, rank, local_rank, world, dist, dev):
                     {"bound": "hbm", "kernel": "local_plan_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_launch,
                      "note": "serial-chain bound: one lane per fit, sums kept in the host pre-step's order"})
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             po = O.default_params(50)
@@ -484,14 +524,15 @@ def bench_c1(args, rank, local_rank, world, dist, dev):
     """BASELINE config 1 — the drop-in case: ONE solve per call (B=1, N=30, M=2; the known-answer scene of SURVEY §8c) through
     the host-buffer entry point `cilqr_solve_batch`, i.e. what replaces the reference's timed `run_step`
     (I/ilqr_uncertainty_node.cpp:117-122): H2D of the inputs + the solve + D2H of U, X, J every call.  A step = one call;
-    the latency is the median over --steps calls (default here: 1000)."""
+    the latency is the median over --steps calls (default here: 1000).  --full adds the kernel time of the same solve with its
+    inputs resident (HIP events on a torch stream), for the roofline block."""
     import cilqr_amd
     from cilqr_amd import scenes
     N, M = 30, 2
     if args.batch:  # other single-solve shapes: --batch encodes the horizon (50 → M=4, 80 → M=16: the other survey scenes)
         N = args.batch
         M = {30: 2, 50: 4, 80: 16}.get(N, 4)
-    steps = args.steps if args.steps != 50 else 1000
+    steps = args.steps
     p = cilqr_amd.default_params(N)
     sc = scenes.known_answer_scene(N, M, p)
     solver = cilqr_amd.Solver(p, max_batch=1, max_horizon=N, max_obstacles=M, device=local_rank)
@@ -502,26 +543,9 @@ def bench_c1(args, rank, local_rank, world, dist, dev):
         if k >= args.warmup:
             lat.append(time.perf_counter() - t)
     lat = np.array(lat)
-    # device-side part of the same call: the kernel pair between two events on a torch stream, inputs resident
-    dvt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    x0, U0, poly, xpl, pose, dim = (dvt(sc[k]) for k in ("x0", "U", "poly", "xplan_fl", "obs_pose", "obs_dim"))
-    U = U0.clone()
-    X = torch.zeros(4 * (N + 1), dtype=torch.float64, device=dev)
-    J = torch.zeros(1, dtype=torch.float64, device=dev)
-    it = torch.zeros(1, dtype=torch.int32, device=dev)
-    st = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def step(k, e0, e1):
-        U.copy_(U0)
-        if e0 is not None:
-            e0.record()
-        solver.solve_batch_device(stream, 1, N, M, x0.data_ptr(), U.data_ptr(), poly.data_ptr(), xpl.data_ptr(), pose.data_ptr(),
-                                  dim.data_ptr(), 0, X.data_ptr(), J.data_ptr(), it.data_ptr(), st.data_ptr())
-        if e1 is not None:
-            e1.record()
-    a2 = argparse.Namespace(steps=min(steps, 200), warmup=args.warmup)
-    elapsed, kern_ms = _timed(step, a2, dist, dev)
+    dump_outputs(args, rank, **{k: got[k] for k in ("U", "X", "J", "iters", "status")})
+    if args.full:
+        kern_ms = _c1_kernel_ms(args, solver, sc, N, M, steps, dist, dev)
     if rank == 0:
         med = float(np.median(lat))
         bytes_launch = algorithmic_bytes_per_solve(N, M)
@@ -532,13 +556,14 @@ def bench_c1(args, rank, local_rank, world, dist, dev):
                                       "known-answer scene of SURVEY 8(c)", "horizon": N, "obstacles": M,
                           "iterations": int(got["iters"][0]), "exit": int(got["status"][0])},
                "latency_ms": {"median": 1e3 * med, "p10": 1e3 * float(np.percentile(lat, 10)), "p90": 1e3 * float(np.percentile(lat, 90)),
-                              "min": 1e3 * float(lat.min())},
-               "roofline": {"bound": "hbm", "kernel": "cilqr_solve_share_kernel<%d>" % solver.solve_wavefronts(1, N, M) if solver.solve_wavefronts(1, N, M) >= 2 else "cilqr_solve_kernel",
-                            "achieved": bytes_launch / (kern_ms * 1e-3) / 1e9,
-                            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bytes_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                            "traffic": None, "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_launch,
-                            "note": "one solve on one CU (two wavefronts while it linearises, one otherwise): pure serial-chain latency, the rest of the chip idle"}}
-        if not args.no_cpu_baseline and world == 1:
+                              "min": 1e3 * float(lat.min())}}
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": "cilqr_solve_share_kernel<%d>" % solver.solve_wavefronts(1, N, M) if solver.solve_wavefronts(1, N, M) >= 2 else "cilqr_solve_kernel",
+                               "achieved": bytes_launch / (kern_ms * 1e-3) / 1e9,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bytes_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "traffic": None, "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_launch,
+                               "note": "one solve on one CU (two wavefronts while it linearises, one otherwise): pure serial-chain latency, the rest of the chip idle"}
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle as O
             O.build(ref=False)
             po = O.default_params(N)
@@ -557,17 +582,45 @@ def bench_c1(args, rank, local_rank, world, dist, dev):
         dist.destroy_process_group()
 
 
+def _c1_kernel_ms(args, solver, sc, N, M, steps, dist, dev):
+    """Device-side part of c1's call: the kernel pair between two events on a torch stream, inputs resident (mean, ms)."""
+    dvt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    x0, U0, poly, xpl, pose, dim = (dvt(sc[k]) for k in ("x0", "U", "poly", "xplan_fl", "obs_pose", "obs_dim"))
+    U = U0.clone()
+    X = torch.zeros(4 * (N + 1), dtype=torch.float64, device=dev)
+    J = torch.zeros(1, dtype=torch.float64, device=dev)
+    it = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def step(k, e0, e1):
+        U.copy_(U0)
+        if e0 is not None:
+            e0.record()
+        solver.solve_batch_device(stream, 1, N, M, x0.data_ptr(), U.data_ptr(), poly.data_ptr(), xpl.data_ptr(), pose.data_ptr(),
+                                  dim.data_ptr(), 0, X.data_ptr(), J.data_ptr(), it.data_ptr(), st.data_ptr())
+        if e1 is not None:
+            e1.record()
+    a2 = argparse.Namespace(steps=min(steps, 200), warmup=args.warmup)
+    return _timed(step, a2, dist, dev)[1]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; c1: 1000)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=0, help="solves per GPU per step (default: the config's own size)")
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c5", "warp", "blur", "occ", "frame", "plan"],
                     help="c2 (default, the config BASELINE.json's metric is quoted on): B=1024 N=50 M=4; c3: B=4096 N=50, 8x32 "
                          "sampled obstacles; c5: B=8192 per GPU N=80 M=16; warp: config 4, 1024x1024 costmap frames")
     ap.add_argument("--frames", type=int, default=1, help="warp only: K frames per launch (cilqr_warp_costmap_batch_device)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the oracle comparisons")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: CPU baseline and parity against the oracle, host-buffer "
+                         "entry point, two batches in flight, the schedule hint switched off, c1's kernel time")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--ticks", action="store_true",
                     help="solver workloads: every step solves the NEXT tick of a closed-loop planner sequence (ego moved one step along the "
                          "accepted plan, warm-started controls, re-fitted local plan, obstacles moved on, fresh pose noise) instead of the "
@@ -577,6 +630,10 @@ def main():
                     help="c3 only: pass the 256 sampled obstacles as 256 ordinary obstacle tables (cilqr_solve_batch_device) instead "
                          "of the compact nominal + offsets form (cilqr_solve_batch_sampled_device)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 1000 if args.workload == "c1" else 50
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     # stdout carries exactly ONE JSON line (rank 0).  Libraries underneath write there too (RCCL prints a version banner when a
     # communicator is first made): everything but that line goes to stderr, at the file-descriptor level.
@@ -726,6 +783,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump_outputs(args, rank, U=U, X=X, J=J, iters=iters, status=status, min_cost=np.array(best, dtype=np.float64))
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     total_solves = B * world * args.steps
@@ -780,7 +838,7 @@ def main():
             "min_cost": {"J": best[0], "global_index": best[1]},
         }
         wave_family = lanes == 64
-        if wave_family and B > 1024 and world == 1:
+        if args.full and wave_family and B > 1024 and world == 1:
             # Batches beyond one solve per SIMD are dispatched longest-first by the pass counts of the PREVIOUS call (DESIGN.md
             # §4.1d).  That only pays when consecutive batches resemble each other solve by solve: beside the timed figure, the same
             # launches on a handle created with the hint switched off.
@@ -832,7 +890,7 @@ def main():
                             "l2_hit_frac": (cnt["TCC_HIT_sum"] / cnt["TCC_REQ_sum"]) if cnt.get("TCC_REQ_sum") else None,
                             "note": "SQ_ACTIVE_INST_ANY / SQ_WAVE_CYCLES: share of resident-wavefront cycles in which an instruction "
                                     "issued (a lone wavefront issues one per 5.2 ticks, a matrix instruction 16.2)"}
-        if args.workload == "c2" and B <= 1024 and world == 1 and not use_ticks:
+        if args.full and args.workload == "c2" and B <= 1024 and world == 1 and not use_ticks:
             # A labelled note, never `value`: at one solve per SIMD a launch lasts as long as its slowest solve and most SIMDs idle
             # through its second half.  Do two INDEPENDENT batches in flight — two handles, two streams, as two
             # planners sharing the GPU would run — fill that tail?  (A single planner's consecutive ticks depend on each other.)
@@ -867,7 +925,7 @@ def main():
                                                     "independent batch picks up (little: measured 2.45 M against 2.32 M, the launches "
                                                     "barely overlap; one launch of 2048 solves does: bench.py --batch 2048)" % B}
         # SURVEY §8(d) also asks for the host-buffer entry point (H2D + kernel + D2H); reported, never `value`
-        reps = (5 if M <= 16 else 1) if world == 1 else 0
+        reps = (5 if M <= 16 else 1) if args.full and world == 1 else 0
         if reps:
             def host_call(src, out=None):
                 t = time.perf_counter()
@@ -893,7 +951,7 @@ def main():
                 hp = min(host_call(pin, pout) for _ in range(reps))
                 out["host_buffer_api"]["pinned"] = {"value": B / hp, "unit": "solves/s", "ms_per_batch": 1e3 * hp,
                                                     "note": "the same call with every buffer from cilqr_host_alloc"}
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 measurement
             from oracle import oracle as O
             O.build(ref=False)
             threads = O.max_threads()

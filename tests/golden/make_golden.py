@@ -7,6 +7,8 @@ Sources of the expected values
   ref_params.json, ref_quu.json, ref_polyfit.json, ref_gridmap.json, ref_blur.json, ref_gridmap_linear.json
       — produced by the REFERENCE's own code compiled in place (oracle/Makefile `make ref` → oracle/_ref/*.so):
         Parameters.cpp, the vendored Eigen 3.2.10 (EigenSolver, ColPivHouseholderQR) and grid_map_core.
+  ref_live_maps.npz
+      — the same library's warp and blur outputs on the larger maps of test_oracle.py's `*_vs_reference_live` tests.
   survey_known_answers.json
       — the three known-answer solves recorded in SURVEY.md §8(c) (outputs of the reference solver run during the
         survey); written out here verbatim as data.
@@ -253,6 +255,37 @@ def gen_gridmap_linear():
     dump("ref_gridmap_linear.json", out)
 
 
+def gen_live_maps():
+    """Outputs of the reference's grid_map_core on the larger maps of test_oracle.py's two `*_vs_reference_live` tests, whose
+    inputs those tests draw themselves (same seeds, same order): stored so that the tests run where oracle/_ref is not built."""
+    L = O.ref_lib("gridmap")
+    rng = np.random.default_rng(3)  # test_warp_random_poses_vs_reference_live
+    sgeo, dgeo = (40.0, 36.0, 0.2, 3.0, -2.0), (15.0, 10.0, 0.1, 7.5, 0.0)
+    sg, dg = O.map_geom(*sgeo), O.map_geom(*dgeo)
+    src = np.asfortranarray(rng.integers(0, 101, (sg.rows, sg.cols)).astype(np.float32))
+    poses, dsts, oobs = [], [], []
+    for _ in range(5):
+        pose = (3.0 + rng.uniform(-6, 6), -2.0 + rng.uniform(-6, 6), rng.uniform(-np.pi, np.pi))
+        chk = np.zeros((dg.rows, dg.cols), dtype=np.float32, order="F")
+        oobs.append(L.ref_warp(src.ctypes.data_as(fp), *map(C.c_double, sgeo), chk.ctypes.data_as(fp), *map(C.c_double, dgeo),
+                               *map(C.c_double, pose), None))
+        poses.append(pose)
+        dsts.append(chk)
+    rng = np.random.default_rng(21)  # test_blur_default_map_vs_reference_live
+    geom = (30.0, 20.0, 0.2, 15.0, 0.0)
+    g = O.map_geom(*geom)
+    src = rng.integers(0, 101, (g.rows, g.cols)).astype(np.float32)
+    blur_out, blur_cnt = [], []
+    for sig, th in (((0.16, 0.16, 0.017), -1.2), ((0.005, 0.005, 0.0125), 0.3)):
+        ro, rc, _ = O.ref_blur(src, geom, np.sin(th), np.cos(th), *sig)
+        blur_out.append(ro)
+        blur_cnt.append(rc)
+    np.savez_compressed(os.path.join(HERE, "ref_live_maps.npz"), warp_pose=np.array(poses), warp_dst=np.array(dsts),
+                        warp_n_out_of_range=np.array(oobs, dtype=np.int64), blur_out=np.array(blur_out),
+                        blur_count=np.array(blur_cnt))
+    print("wrote ref_live_maps.npz")
+
+
 if __name__ == "__main__":
     O.build(ref=True)
     gen_survey()
@@ -262,4 +295,5 @@ if __name__ == "__main__":
     gen_gridmap()
     gen_blur()
     gen_gridmap_linear()
+    gen_live_maps()
     gen_oracle_solves()

@@ -3,7 +3,7 @@
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/bench_all
 rm -rf $OUT && mkdir -p $OUT
-run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" 2>$OUT/$name.err | grep "^{" > $OUT/$name.json || echo "FAILED $name"; echo "$name: $(python -c "import json;d=json.load(open('$OUT/$name.json'));print(round(d['value'],1),d['unit'],'kernel_ms',round(d['roofline']['kernel_ms'],4))" 2>/dev/null)"; }
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full "$@" 2>$OUT/$name.err | grep "^{" > $OUT/$name.json || echo "FAILED $name"; echo "$name: $(python -c "import json;d=json.load(open('$OUT/$name.json'));print(round(d['value'],1),d['unit'],'kernel_ms',round(d['roofline']['kernel_ms'],4))" 2>/dev/null)"; }
 run c2
 run c3 --workload c3 --steps 10 --warmup 2
 run c3_materialised --workload c3 --materialised --steps 10 --warmup 2 --no-cpu-baseline
