@@ -13,7 +13,8 @@
  *   Parameters::Parameters()            I/Parameters.cpp:3-75   cilqr_params_default
  *   iLQR::iLQR(const Parameters&)       I/iLQR.cpp:3-19         cilqr_create (+ cilqr_default_control_seq)
  *   iLQR::get_optimal_control_seq       I/iLQR.cpp:201-245      cilqr_solve_batch / cilqr_solve_batch_device
- *   iLQR::set_Obstacle / clear_Obstacle I/iLQR.cpp:20-27        obs_* arguments of cilqr_solve_batch (M = 0 ⇒ cleared)
+ *   iLQR::set_Obstacle / clear_Obstacle I/iLQR.cpp:20-27        obs_* arguments of cilqr_solve_batch (M = 0 ⇒ cleared), or
+ *                                                                one shared / horizon-constant set: cilqr_solve_batch_obstacles(_device)
  *   iLQR::set_uncertainty_map / clear_uncertainty_map I/iLQR.cpp:28-35   cilqr_set_uncertainty_map(_device) / cilqr_clear_uncertainty_map
  *   Constraints::get_J                  I/Constraints.cpp:534-561   J_out of cilqr_solve_batch
  *   GridMapRosConverter::from/toOccupancyGrid G/grid_map_ros/src/GridMapRosConverter.cpp:225-307
@@ -235,6 +236,34 @@ int cilqr_solve_batch_device(cilqr_handle* h, void* stream, int B, int N, int M,
                              const double* obs_pose, const double* obs_dim, const double* obs_weight,
                              double* X_out, double* J_out, int32_t* iters_out, int32_t* status_out,
                              uint32_t flags);
+
+/* Obstacle inputs addressed by strides.  Units are ENTRIES: one entry = 4 pose doubles (x, y, v, theta) at pose + 4e and
+ * 2 dimension doubles (length, width) at dim + 2e.  Obstacle m of solve b at step t is entry
+ *     e = b*batch_stride + m*obstacle_stride + t*step_stride.
+ * cilqr_solve_batch's layout is (M*N, N, 1).  One scene shared by the batch: batch_stride = 0.  Constant over the horizon:
+ * step_stride = 0 (e.g. (0, 1, 0) = one static obstacle set for every solve, M entries in all). */
+typedef struct cilqr_obstacles {
+  const double* pose;
+  const double* dim;
+  const double* weight;          /* NULL => p.w_obstacle; else weight[b*weight_batch_stride + m] */
+  int64_t batch_stride, obstacle_stride, step_stride;
+  int64_t weight_batch_stride;   /* 0 = one weight vector [M] for the batch */
+} cilqr_obstacles;
+
+/* cilqr_solve_batch with the obstacles given by strides (above): the same results, bit for bit, as cilqr_solve_batch on the dense
+ * expansion of the same inputs, for every flag and kernel family, with or without an uncertainty map.  obs may be NULL only when
+ * M == 0; a negative stride is CILQR_ERR_ARG.  Only the span of entries the strides address is copied,
+ * (B-1)·batch_stride + (M-1)·obstacle_stride + (N-1)·step_stride + 1 entries, which must fit the B·M·N reserved at create.
+ * With one scene for the batch (batch_stride = 0 and weight_batch_stride = 0 or no weights), kernels that keep the obstacle
+ * table in device memory instead of LDS build it ONCE per call, in front of the solves, and every solve reads that copy. */
+int cilqr_solve_batch_obstacles(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly,
+                                const double* xplan_fl, const cilqr_obstacles* obs, double* X_out, double* J_out,
+                                int32_t* iters_out, int32_t* status_out, uint32_t flags);
+/* The same with every pointer (those inside *obs included) a DEVICE pointer, asynchronous on `stream` as
+ * cilqr_solve_batch_device.  *obs itself is a host struct, read before the call returns. */
+int cilqr_solve_batch_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* x0, double* U,
+                                       const double* poly, const double* xplan_fl, const cilqr_obstacles* obs, double* X_out,
+                                       double* J_out, int32_t* iters_out, int32_t* status_out, uint32_t flags);
 
 /* --- costmap-lookup uncertainty cost ------------------------------------------------------------------
  * iLQR::set_uncertainty_map / clear_uncertainty_map (I/iLQR.cpp:28-35 → I/Constraints.cpp:520-528): while a map is set, every

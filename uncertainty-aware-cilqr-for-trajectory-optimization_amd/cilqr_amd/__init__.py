@@ -20,7 +20,7 @@ EXIT_TOLERANCE, EXIT_LAMBDA_MAX, EXIT_MAX_ITER, EXIT_NUMERIC = 0, 1, 2, 3
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
     "cilqr_params_default", "cilqr_abi_version", "cilqr_device_count", "cilqr_last_error", "cilqr_default_control_seq",
-    "cilqr_local_plan", "cilqr_local_plan_batch", "cilqr_local_plan_batch_device", "cilqr_create", "cilqr_destroy", "cilqr_host_alloc", "cilqr_host_free", "cilqr_solve_batch", "cilqr_solve_batch_device", "cilqr_solve_batch_sampled", "cilqr_solve_batch_sampled_device",
+    "cilqr_local_plan", "cilqr_local_plan_batch", "cilqr_local_plan_batch_device", "cilqr_create", "cilqr_destroy", "cilqr_host_alloc", "cilqr_host_free", "cilqr_solve_batch", "cilqr_solve_batch_device", "cilqr_solve_batch_obstacles", "cilqr_solve_batch_obstacles_device", "cilqr_solve_batch_sampled", "cilqr_solve_batch_sampled_device",
     "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_map_geom_set",
     "cilqr_occupancy_to_layer", "cilqr_occupancy_to_layer_device", "cilqr_layer_to_occupancy", "cilqr_layer_to_occupancy_device",
     "cilqr_costmap_frame_device",
@@ -64,8 +64,54 @@ class UncertaintyMap(C.Structure):
                 ("probes_w", C.c_int32)]
 
 
+class Obstacles(C.Structure):
+    """`cilqr_obstacles` — obstacle inputs addressed by strides in entries (4 pose + 2 dimension doubles each): obstacle m of
+    solve b at step t is entry b*batch_stride + m*obstacle_stride + t*step_stride; weight[b*weight_batch_stride + m]."""
+    _fields_ = [("pose", C.c_void_p), ("dim", C.c_void_p), ("weight", C.c_void_p), ("batch_stride", C.c_int64),
+                ("obstacle_stride", C.c_int64), ("step_stride", C.c_int64), ("weight_batch_stride", C.c_int64)]
+
+
 class CilqrError(RuntimeError):
     pass
+
+
+def obstacle_strides(pose_shape, dim_shape, weight_shape, B, N):
+    """Strides of `cilqr_obstacles` from the shapes of C-contiguous pose / dim / weight arrays, as `Solver.local_plan_batch`
+    derives path_stride from the path's shape.  Returns (M, batch_stride, obstacle_stride, step_stride, weight_batch_stride):
+      pose (M, 4), dim (M, 2)            one static set shared by the batch   (0, 1, 0)
+      pose (B, M, 4), dim (B, M, 2)      static, one set per solve             (M, 1, 0)
+      pose (M, 4N), dim (M, 2N)          one moving set shared by the batch   (0, N, 1)
+      pose (B, M, 4N), dim (B, M, 2N)    dense, cilqr_solve_batch's layout    (M*N, N, 1)
+      weight None, (M,) (weight_batch_stride 0) or (B, M) (M).  Anything else raises CilqrError."""
+    pose_shape, dim_shape = tuple(int(d) for d in pose_shape), tuple(int(d) for d in dim_shape)
+    B, N = int(B), int(N)
+    if len(pose_shape) not in (2, 3) or len(dim_shape) != len(pose_shape):
+        raise CilqrError("obstacle_strides: pose %s / dim %s are not (M, 4[N]) or (B, M, 4[N])" % (pose_shape, dim_shape))
+    per_solve = len(pose_shape) == 3
+    if per_solve and (pose_shape[0] != B or dim_shape[0] != B):
+        raise CilqrError("obstacle_strides: batch dimension of pose %s / dim %s is not B = %d" % (pose_shape, dim_shape, B))
+    M, cols = pose_shape[-2], pose_shape[-1]
+    if dim_shape[-2] != M:
+        raise CilqrError("obstacle_strides: pose has %d obstacles, dim %d" % (M, dim_shape[-2]))
+    if cols == 4 and dim_shape[-1] == 2:
+        ms, ts = 1, 0  # constant over the horizon
+    elif cols == 4 * N and dim_shape[-1] == 2 * N:
+        ms, ts = N, 1  # one column per step
+    else:
+        raise CilqrError("obstacle_strides: pose %s / dim %s are neither (…, M, 4) / (…, M, 2) nor (…, M, %d) / (…, M, %d)"
+                         % (pose_shape, dim_shape, 4 * N, 2 * N))
+    bs = M * ms if per_solve else 0
+    if weight_shape is None:
+        wbs = 0
+    else:
+        weight_shape = tuple(int(d) for d in weight_shape)
+        if weight_shape == (M,):
+            wbs = 0
+        elif weight_shape == (B, M):
+            wbs = M
+        else:
+            raise CilqrError("obstacle_strides: weight %s is neither (%d,) nor (%d, %d)" % (weight_shape, M, B, M))
+    return M, bs, ms, ts, wbs
 
 
 _lib = None
@@ -219,6 +265,31 @@ class Solver:
                                        C.c_uint32(flags)))
         return dict(U=U, X=X, J=J, iters=iters, status=status)
 
+    def solve_batch_obstacles(self, N, x0, U, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, flags=0, out=None):
+        """`cilqr_solve_batch_obstacles`: solve_batch with the obstacles in any of the shapes of `obstacle_strides` — e.g. one
+        static set (M, 4) / (M, 2) for the whole batch — of which only those entries travel.  Same results as solve_batch on
+        the dense expansion, bit for bit."""
+        x0 = _np64(x0).reshape(-1, 4)
+        B = x0.shape[0]
+        U = _np64(U).reshape(B, 2 * N).copy() if out is None else out["U"]
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        M, obs = 0, None
+        if obs_pose is not None:
+            obs_pose, obs_dim, obs_weight = _np64(obs_pose), _np64(obs_dim), _np64(obs_weight)
+            M, bs, ms, ts, wbs = obstacle_strides(obs_pose.shape, obs_dim.shape, None if obs_weight is None else obs_weight.shape, B, N)
+            obs = Obstacles(obs_pose.ctypes.data, obs_dim.ctypes.data, None if obs_weight is None else obs_weight.ctypes.data,
+                            bs, ms, ts, wbs)
+        if out is None:
+            X, J = np.zeros((B, 4 * (N + 1))), np.zeros(B)
+            iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        else:
+            X, J, iters, status = out["X"], out["J"], out["iters"], out["status"]
+        _check(lib().cilqr_solve_batch_obstacles(self._h, B, int(N), int(M), _p(x0), _p(U), _p(poly), _p(xplan_fl),
+                                                 None if obs is None else C.byref(obs), _p(X), _p(J), _p(iters, _ip),
+                                                 _p(status, _ip), C.c_uint32(flags)))
+        return dict(U=U, X=X, J=J, iters=iters, status=status)
+
     def solve_batch_sampled(self, N, x0, U, poly, xplan_fl, nom_pose, nom_dim, offsets, weight, flags=0):
         """Sampled obstacles in compact form: nom_pose (B, n_obs, 4N), nom_dim (B, n_obs, 2N), offsets (B, n_obs, S, 3)."""
         x0 = _np64(x0).reshape(-1, 4)
@@ -254,6 +325,17 @@ class Solver:
         _check(lib().cilqr_solve_batch_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(x0), _vp(U), _vp(poly),
                                               _vp(xplan_fl), _vp(obs_pose), _vp(obs_dim), _vp(obs_weight), _vp(X_out),
                                               _vp(J_out), _vp(iters_out), _vp(status_out), C.c_uint32(flags)))
+
+    def solve_batch_obstacles_device(self, stream, B, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, strides, X_out,
+                                     J_out, iters_out, status_out, flags=0):
+        """`cilqr_solve_batch_obstacles_device`: device addresses as solve_batch_device; strides = (batch_stride,
+        obstacle_stride, step_stride, weight_batch_stride) in entries (`obstacle_strides` maps shapes to them)."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None,
+                        int(obs_weight) if obs_weight else None, bs, ms, ts, wbs)
+        _check(lib().cilqr_solve_batch_obstacles_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(x0), _vp(U), _vp(poly),
+                                                        _vp(xplan_fl), C.byref(obs), _vp(X_out), _vp(J_out), _vp(iters_out),
+                                                        _vp(status_out), C.c_uint32(flags)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

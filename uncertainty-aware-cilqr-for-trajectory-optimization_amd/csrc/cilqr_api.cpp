@@ -173,6 +173,60 @@ static int launch_wave_scheduled(cilqr_handle* h, cilqr::SolveArgs& a, void* str
   return CILQR_OK;
 }
 
+namespace {
+
+// Obstacle strides of cilqr_solve_batch_obstacles*: none negative, obs given when M > 0; *span / *w_span (may be null) receive the
+// entries and weights the strides address (0 when M == 0 or there are no weights).
+int check_obstacles(int B, int N, int M, const cilqr_obstacles* o, size_t* span, size_t* w_span) {
+  if (span) *span = 0;
+  if (w_span) *w_span = 0;
+  if (M == 0) return CILQR_OK;
+  if (!o) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: M = %d but obs is null", M);
+  if (!o->pose || !o->dim) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: M > 0 but obs->pose or obs->dim is null");
+  if (o->batch_stride < 0 || o->obstacle_stride < 0 || o->step_stride < 0 || o->weight_batch_stride < 0)
+    return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: negative stride");
+  const int64_t lim = (int64_t)1 << 40;  // (keeps every entry index of the kernels far inside 64 bits)
+  if (o->batch_stride > lim || o->obstacle_stride > lim || o->step_stride > lim || o->weight_batch_stride > lim)
+    return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: stride beyond 2^40 entries");
+  const int64_t b1 = B > 0 ? B - 1 : 0;
+  if (span) *span = (size_t)(b1 * o->batch_stride + (int64_t)(M - 1) * o->obstacle_stride + (int64_t)(N - 1) * o->step_stride + 1);
+  if (w_span && o->weight) *w_span = (size_t)(b1 * o->weight_batch_stride + M);
+  return CILQR_OK;
+}
+
+// The solve behind cilqr_solve_batch_device and cilqr_solve_batch_obstacles_device (arguments checked by the caller).
+int solve_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* x0, double* U, const double* poly,
+                 const double* xplan_fl, const cilqr_obstacles& o, double* X_out, double* J_out, int32_t* iters_out,
+                 int32_t* status_out, uint32_t flags) {
+  cilqr::SolveArgs a;
+  a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
+  a.obs_pose = o.pose; a.obs_dim = o.dim; a.obs_weight = M > 0 ? o.weight : nullptr;
+  a.obs_bs = o.batch_stride; a.obs_ms = o.obstacle_stride; a.obs_ts = o.step_stride; a.obs_wbs = o.weight_batch_stride;
+  // one scene for the batch: the kernels that keep their table in the workspace read one table built in front of them
+  a.obs_shared = M > 0 && B > 1 && o.batch_stride == 0 && (!a.obs_weight || o.weight_batch_stride == 0) ? 1 : 0;
+  a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
+  a.samp_off = nullptr; a.n_samples = 0; a.samp_w = 0.0;
+  a.obs_tab = h->d_obs_tab;
+  a.fwd = h->d_ws;  // (the grouped family's workspace: 42·N + 12 doubles per solve ≥ the 16·(N + 1) needed here; never both at once)
+  a.order = nullptr; a.hint_passes = nullptr; a.pair = 0; a.tab_budget = 0; a.steal = h->steal_off ? 0 : 1; a.split = 0;
+  a.redo = h->d_redo;
+  a.diag = h->diag;
+  a.passes = h->passes;
+  a.unc = h->unc;
+  a.B = B; a.N = N; a.M = M; a.flags = flags;
+  a.kp = h->kp;
+  HIP_TRY(hipSetDevice(h->device));
+  const int G = pick_group_lanes(h, B, N, M);
+  if (G == 64 && cilqr::solve_lds_bytes(N, h->kp.n_samples) > cilqr::SOLVE_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch: horizon %d needs %zu bytes of LDS per solve (limit %zu)", N,
+                cilqr::solve_lds_bytes(N, h->kp.n_samples), cilqr::SOLVE_LDS_MAX);
+  if (G == 64) return launch_wave_scheduled(h, a, stream);
+  HIP_TRY(cilqr::launch_solve_groups(a, G, h->d_ws, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int cilqr_abi_version(void) { return CILQR_ABI_VERSION; }
@@ -260,7 +314,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   const size_t B = max_batch, N = max_horizon, M = max_obstacles;
   hipError_t err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   {  // arena of the host-buffer entry points: the larger of the two layouts that can be asked for (cilqr_host_io.cpp)
-    const cilqr::IoLayout plain = cilqr::io_layout(B, N, M, true, 0), sampled = cilqr::io_layout(B, N, M, false, 1);
+    const cilqr::IoLayout plain = cilqr::io_layout(B, N, B * M * N, B * M, 0), sampled = cilqr::io_layout(B, N, B * M * N, 0, B * M);
     h->arena_cap = plain.end > sampled.end ? plain.end : sampled.end;
     if (err == hipSuccess) err = hipMalloc((void**)&h->d_arena, h->arena_cap);
     h->stage_cap = h->arena_cap < ((size_t)1 << 20) ? h->arena_cap : ((size_t)1 << 20);  // pinned: calls up to 1 MiB travel packed
@@ -500,28 +554,21 @@ int cilqr_solve_batch_device(cilqr_handle* h, void* stream, int B, int N, int M,
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: null required pointer");
   if (M > 0 && (!obs_pose || !obs_dim)) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: M > 0 but obstacle tables are null");
-  cilqr::SolveArgs a;
-  a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
-  a.obs_pose = obs_pose; a.obs_dim = obs_dim; a.obs_weight = M > 0 ? obs_weight : nullptr;
-  a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
-  a.samp_off = nullptr; a.n_samples = 0; a.samp_w = 0.0;
-  a.obs_tab = h->d_obs_tab;
-  a.fwd = h->d_ws;  // (the grouped family's workspace: 42·N + 12 doubles per solve ≥ the 16·(N + 1) needed here; never both at once)
-  a.order = nullptr; a.hint_passes = nullptr; a.pair = 0; a.tab_budget = 0; a.steal = h->steal_off ? 0 : 1; a.split = 0;
-  a.redo = h->d_redo;
-  a.diag = h->diag;
-  a.passes = h->passes;
-  a.unc = h->unc;
-  a.B = B; a.N = N; a.M = M; a.flags = flags;
-  a.kp = h->kp;
-  HIP_TRY(hipSetDevice(h->device));
-  const int G = pick_group_lanes(h, B, N, M);
-  if (G == 64 && cilqr::solve_lds_bytes(N, h->kp.n_samples) > cilqr::SOLVE_LDS_MAX)
-    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch: horizon %d needs %zu bytes of LDS per solve (limit %zu)", N,
-                cilqr::solve_lds_bytes(N, h->kp.n_samples), cilqr::SOLVE_LDS_MAX);
-  if (G == 64) return launch_wave_scheduled(h, a, stream);
-  HIP_TRY(cilqr::launch_solve_groups(a, G, h->d_ws, (hipStream_t)stream));
-  return CILQR_OK;
+  const cilqr_obstacles o{obs_pose, obs_dim, obs_weight, (int64_t)M * N, N, 1, M};  // the dense layout
+  return solve_device(h, stream, B, N, M, x0, U, poly, xplan_fl, o, X_out, J_out, iters_out, status_out, flags);
+}
+
+int cilqr_solve_batch_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* x0, double* U,
+                                       const double* poly, const double* xplan_fl, const cilqr_obstacles* obs, double* X_out,
+                                       double* J_out, int32_t* iters_out, int32_t* status_out, uint32_t flags) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, nullptr, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: null required pointer");
+  const cilqr_obstacles none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+  return solve_device(h, stream, B, N, M, x0, U, poly, xplan_fl, M > 0 ? *obs : none, X_out, J_out, iters_out, status_out, flags);
 }
 
 }  // extern "C"
@@ -537,6 +584,28 @@ int cilqr_solve_batch(cilqr_handle* h, int B, int N, int M, const double* x0, do
   if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: null required pointer");
   if (M > 0 && (!obs_pose || !obs_dim)) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: M > 0 but obstacle tables are null");
   cilqr::HostBatch q{B, N, M, 0, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, nullptr, 0.0, X_out, J_out, iters_out, status_out, flags};
+  rc = cilqr::host_solve_enqueue(h, q);  // (on failure: stream drained, handle free again)
+  if (rc) return rc;
+  return cilqr::host_solve_finish(h);
+}
+
+int cilqr_solve_batch_obstacles(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly,
+                                const double* xplan_fl, const cilqr_obstacles* obs, double* X_out, double* J_out,
+                                int32_t* iters_out, int32_t* status_out, uint32_t flags) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  size_t span = 0, w_span = 0;
+  rc = check_obstacles(B, N, M, obs, &span, &w_span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: null required pointer");
+  cilqr::HostBatch q{B, N, M, 0, x0, U, poly, xplan_fl, nullptr, nullptr, nullptr, nullptr, 0.0, X_out, J_out, iters_out, status_out, flags};
+  if (M > 0) {  // only the span the strides address travels (cilqr_host_io.cpp)
+    q.obs_pose = obs->pose; q.obs_dim = obs->dim; q.obs_weight = obs->weight;
+    q.strided = true;
+    q.obs_bs = obs->batch_stride; q.obs_ms = obs->obstacle_stride; q.obs_ts = obs->step_stride; q.obs_wbs = obs->weight_batch_stride;
+    q.obs_span = span; q.w_span = w_span;
+  }
   rc = cilqr::host_solve_enqueue(h, q);  // (on failure: stream drained, handle free again)
   if (rc) return rc;
   return cilqr::host_solve_finish(h);
@@ -560,6 +629,7 @@ int cilqr_solve_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N
   cilqr::SolveArgs a;
   a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
   a.obs_pose = nom_pose; a.obs_dim = nom_dim; a.obs_weight = nullptr;
+  a.obs_bs = (long long)n_obs * N; a.obs_ms = N; a.obs_ts = 1; a.obs_wbs = 0; a.obs_shared = 0;  // (sampled_prologue reads them densely)
   a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
   a.samp_off = sample_offset; a.n_samples = n_samples; a.samp_w = sample_weight;
   a.obs_tab = h->d_obs_tab;  // n_obs·N·8 doubles per solve ≤ the n_obs·n_samples·N·6 reserved for the materialised form

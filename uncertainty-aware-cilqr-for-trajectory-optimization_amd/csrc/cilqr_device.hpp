@@ -497,6 +497,18 @@ __device__ __forceinline__ ObsEntry make_obs_entry(const KParams& kp, const doub
   e.ib2 = 1.0 / eb / eb;
   return e;
 }
+// Obstacle m of solve b at step t, read through the strides of SolveArgs (entry e: pose + 4e, dim + 2e).
+__device__ __forceinline__ long long obs_entry_index(const SolveArgs& a, int b, int m, int t) {
+  return (long long)b * a.obs_bs + (long long)m * a.obs_ms + (long long)t * a.obs_ts;
+}
+__device__ __forceinline__ ObsEntry obs_entry_at(const KParams& kp, const SolveArgs& a, int b, int m, int t) {
+  const long long e = obs_entry_index(a, b, m, t);
+  return make_obs_entry(kp, a.obs_pose + 4 * e, a.obs_dim + 2 * e);
+}
+// Solve b's weight vector (indexed by m), or null: Parameters::w_obstacle.
+__device__ __forceinline__ const double* obs_weights(const SolveArgs& a, int b) {
+  return a.obs_weight ? a.obs_weight + (long long)b * a.obs_wbs : nullptr;
+}
 
 // ---- costmap-lookup uncertainty cost ---------------------------------------------------------------------------
 // Uncertainty::get_uncertainty_cost(state) → {x, vx, mx}, added to l_x / l_xx with weight w_uncertainty where

@@ -15,7 +15,8 @@ namespace cilqr {
 struct IoLayout {
   size_t x0, poly, xplan, obs_w, samp_off, obs_pose, obs_dim, U, X, J, iters, status, end;
 };
-IoLayout io_layout(size_t B, size_t N, size_t M, bool weights, size_t n_samples);
+// obs_entries: obstacle entries (4 pose + 2 dimension doubles each); w_entries: weights; samp_entries: sample-offset records (3 doubles)
+IoLayout io_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries);
 // One host-buffer solve call (M = obstacles, or nominal obstacles of the sampled form when n_samples > 0).
 struct HostBatch {
   int B, N, M, n_samples;
@@ -26,6 +27,10 @@ struct HostBatch {
   double *X_out, *J_out;
   int32_t *iters_out, *status_out;
   uint32_t flags;
+  // cilqr_solve_batch_obstacles: obstacles by strides (entries), of which only the span travels; false: the dense [B][M][N] layout
+  bool strided;
+  int64_t obs_bs, obs_ms, obs_ts, obs_wbs;
+  size_t obs_span, w_span;  // entries and weights the strides address
 };
 struct PendingOut {
   bool active, packed;

@@ -2,6 +2,9 @@
 // cilqr_multi_solve_batch): how a batch given in host memory reaches the kernels and comes back.  SURVEY §8(b) "Ownership":
 // the caller owns every host buffer, the library owns device buffers sized at create and allocates nothing per call.
 //
+// Obstacles given by strides (cilqr_solve_batch_obstacles) travel as the span of entries the strides address — one static obstacle
+// set for the whole batch is M entries — and reach the kernels with the same strides.
+//
 // One device arena per handle holds a call's arrays packed in a fixed order,
 //     [ x0 | poly | xplan | obs_weight | sample_offset | obs_pose | obs_dim | U ][ X | J | iters | status ]
 // inputs first, the in/out U at the seam, outputs last: the inputs are one contiguous prefix and what returns (U … status) one
@@ -23,16 +26,16 @@ namespace {
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 }  // namespace
 
-IoLayout io_layout(size_t B, size_t N, size_t M, bool weights, size_t n_samples) {
+IoLayout io_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries) {
   IoLayout L;
   size_t o = 0;
   L.x0 = o; o = up16(o + B * 4 * sizeof(double));
   L.poly = o; o = up16(o + B * CILQR_POLY_COEFFS * sizeof(double));
   L.xplan = o; o = up16(o + B * 2 * sizeof(double));
-  L.obs_w = o; o = up16(o + (weights ? B * M * sizeof(double) : 0));
-  L.samp_off = o; o = up16(o + B * M * n_samples * 3 * sizeof(double));
-  L.obs_pose = o; o = up16(o + B * M * N * 4 * sizeof(double));
-  L.obs_dim = o; o = up16(o + B * M * N * 2 * sizeof(double));
+  L.obs_w = o; o = up16(o + w_entries * sizeof(double));
+  L.samp_off = o; o = up16(o + samp_entries * 3 * sizeof(double));
+  L.obs_pose = o; o = up16(o + obs_entries * 4 * sizeof(double));
+  L.obs_dim = o; o = up16(o + obs_entries * 2 * sizeof(double));
   L.U = o; o = up16(o + B * 2 * N * sizeof(double));
   L.X = o; o = up16(o + B * 4 * (N + 1) * sizeof(double));
   L.J = o; o = up16(o + B * sizeof(double));
@@ -65,15 +68,17 @@ int enqueue_steps(cilqr_handle* h, const HostBatch& q) {
   const bool sampled = q.n_samples > 0;
   const size_t B = q.B, N = q.N, M = q.M;
   const bool have_w = !sampled && q.obs_weight && M > 0;
-  const IoLayout L = io_layout(B, N, M, have_w, sampled ? q.n_samples : 0);
+  // obstacle entries and weights that travel: the span the strides address (cilqr_solve_batch_obstacles), else the dense tables
+  const size_t n_ent = q.strided ? q.obs_span : B * M * N, n_went = !have_w ? 0 : q.strided ? q.w_span : B * M;
+  const IoLayout L = io_layout(B, N, n_ent, n_went, sampled ? B * M * q.n_samples : 0);
   if (L.end > h->arena_cap) return fail(CILQR_ERR_ARG, "batch does not fit the device buffers reserved at create");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   char* dv = h->d_arena;
   const bool packed = L.end <= h->stage_cap;
   const size_t n_x0 = B * 4 * sizeof(double), n_poly = B * CILQR_POLY_COEFFS * sizeof(double), n_fl = B * 2 * sizeof(double);
-  const size_t n_w = have_w ? B * M * sizeof(double) : 0, n_off = B * M * (sampled ? (size_t)q.n_samples : 0) * 3 * sizeof(double);
-  const size_t n_pose = B * M * N * 4 * sizeof(double), n_dim = B * M * N * 2 * sizeof(double), n_U = B * 2 * N * sizeof(double);
+  const size_t n_w = n_went * sizeof(double), n_off = B * M * (sampled ? (size_t)q.n_samples : 0) * 3 * sizeof(double);
+  const size_t n_pose = n_ent * 4 * sizeof(double), n_dim = n_ent * 2 * sizeof(double), n_U = B * 2 * N * sizeof(double);
   if (packed) {
     char* st = h->stage;
     memcpy(st + L.x0, q.x0, n_x0);
@@ -111,7 +116,12 @@ int enqueue_steps(cilqr_handle* h, const HostBatch& q) {
     rc = cilqr_solve_batch_sampled_device(h, s, q.B, q.N, q.M, q.n_samples, (const double*)(dv + L.x0), dU, (const double*)(dv + L.poly),
                                           (const double*)(dv + L.xplan), (const double*)(dv + L.obs_pose), (const double*)(dv + L.obs_dim),
                                           (const double*)(dv + L.samp_off), q.samp_w, dX, dJ, dI, dS, q.flags);
-  else
+  else if (q.strided) {
+    const cilqr_obstacles o{(const double*)(dv + L.obs_pose), (const double*)(dv + L.obs_dim), n_w ? (const double*)(dv + L.obs_w) : nullptr,
+                            q.obs_bs, q.obs_ms, q.obs_ts, q.obs_wbs};
+    rc = cilqr_solve_batch_obstacles_device(h, s, q.B, q.N, q.M, (const double*)(dv + L.x0), dU, (const double*)(dv + L.poly),
+                                            (const double*)(dv + L.xplan), &o, dX, dJ, dI, dS, q.flags);
+  } else
     rc = cilqr_solve_batch_device(h, s, q.B, q.N, q.M, (const double*)(dv + L.x0), dU, (const double*)(dv + L.poly),
                                   (const double*)(dv + L.xplan), M > 0 ? (const double*)(dv + L.obs_pose) : nullptr,
                                   M > 0 ? (const double*)(dv + L.obs_dim) : nullptr, n_w ? (const double*)(dv + L.obs_w) : nullptr, dX, dJ, dI,

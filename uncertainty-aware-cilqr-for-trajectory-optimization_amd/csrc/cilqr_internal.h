@@ -49,6 +49,12 @@ struct SolveArgs {
   const double* obs_pose;
   const double* obs_dim;
   const double* obs_weight;  // may be null
+  // obstacle m of solve b at step t: pose + 4e, dim + 2e with e = b*obs_bs + m*obs_ms + t*obs_ts (entries; dense: M*N, N, 1);
+  // weight of obstacle m of solve b: obs_weight[b*obs_wbs + m].  The sampled form keeps its dense nominal layout.
+  long long obs_bs, obs_ms, obs_ts, obs_wbs;
+  // 1: one scene for the batch, and obs_tab starts with ONE [M][N][6] table built in front of the solve kernels
+  // (launch_obstacle_table) that every solve of the kernels keeping their table in the workspace reads and none writes
+  int32_t obs_shared;
   double* X_out;
   double* J_out;        // may be null
   int32_t* iters_out;   // may be null
@@ -93,6 +99,8 @@ size_t solve_sampled_tab_doubles(int n_obs, int N);         // its workspace nee
 // G lanes per solve (G in {1,2,4,8,16,32}), workspace `ws` of solve_groups_ws_doubles(B, N) doubles (cilqr_solve_groups.hip).
 hipError_t launch_solve_groups(const SolveArgs& a, int G, double* ws, hipStream_t stream);
 size_t solve_groups_ws_doubles(int B, int N);
+// One scene for the batch (a.obs_shared): the M·N entries of solve 0's obstacle table → a.obs_tab[(m*N + t)*6 ...] (obstacle_table.hip)
+hipError_t launch_obstacle_table(const SolveArgs& a, hipStream_t stream);
 // Test hook: the map cost alone at n states [n][4] → cost[n], vx[n][2], mx[n][3] (solve 0's layer and pose).
 hipError_t launch_unc_cost(const UncArgs& u, int n, const double* states, double* cost, double* vx, double* mx, hipStream_t stream);
 hipError_t launch_quu_inverse(int n, const double* q, const double* lamb, double* out, int general, hipStream_t stream);

@@ -876,7 +876,9 @@ __global__ __launch_bounds__(WAVE, UNC ? 1 : 2) void cilqr_solve_kernel(SolveArg
   double* kK = rec;  // the gains overlay the records (store_gains)
   double* cst = rec + N * RECW;  // {0, 1, dt, 2·w_vel}: riccati_mfma's constant entries
   double* fwd = a.fwd + (size_t)b * (N + 1) * FREC;  // forward-pass records of this solve (production kernel)
-  double* tab = TAB == 1 ? cst + RCST : a.obs_tab + (size_t)b * M * (TAB == 2 ? NOMF : TABF) * N;
+  // TAB == 0 with one scene for the batch (a.obs_shared): every solve reads the one table launch_obstacle_table built, and writes none
+  const bool tab_shared = TAB == 0 && a.obs_shared;
+  double* tab = TAB == 1 ? cst + RCST : tab_shared ? a.obs_tab : a.obs_tab + (size_t)b * M * (TAB == 2 ? NOMF : TABF) * N;
   double* off = cst + RCST;  // TAB == 2: offset records [o][s][OFFF], then rmax[o]
   double* rmax = off + (size_t)M * a.n_samples * OFFF;
 
@@ -894,13 +896,16 @@ __global__ __launch_bounds__(WAVE, UNC ? 1 : 2) void cilqr_solve_kernel(SolveArg
   for (int i = lane; i < 2 * N; i += WAVE) Ua[i] = Ug[i];
   if (lane < 16 && (lane & 7) < 5) cst[(lane & 7) + (lane >> 3) * RECF] = (lane & 7) == 0 ? 0.0 : (lane & 7) == 1 ? 1.0 : (lane & 7) == 2 ? kp.dt : (lane & 7) == 3 ? kp.w_vel * 2 : 2.0;
 
-  const double* wts = (TAB != 2 && a.obs_weight) ? a.obs_weight + (size_t)b * M : nullptr;
+  const double* wts = TAB != 2 ? obs_weights(a, b) : nullptr;
   if (TAB == 2) {
     sampled_prologue<WAVE>(a, kp, b, N, M, tab, off, rmax);
-  } else {
+  } else if (!tab_shared) {
+    const bool held = a.obs_ts == 0;  // constant over the horizon: one entry per obstacle, written to its N rows
     for (int m = 0; m < M; ++m) {  // obstacle table, I/Obstacle.cpp:41-62
+      ObsEntry e;
+      if (held) e = obs_entry_at(kp, a, b, m, 0);
       for (int t = lane; t < N; t += WAVE) {
-        const ObsEntry e = make_obs_entry(kp, a.obs_pose + (((size_t)b * M + m) * N + t) * 4, a.obs_dim + (((size_t)b * M + m) * N + t) * 2);
+        if (!held) e = obs_entry_at(kp, a, b, m, t);
         double* o = tab + ((size_t)m * N + t) * TABF;
         o[0] = e.ox; o[1] = e.oy; o[2] = e.co; o[3] = e.so; o[4] = e.ia2; o[5] = e.ib2;
       }
@@ -1287,10 +1292,10 @@ __global__ __launch_bounds__(2 * WAVE) void cilqr_solve_pair_kernel(SolveArgs a)
   const double* Ug = a.U + (size_t)b * 2 * N;
   for (int i = tid; i < 2 * N; i += 2 * WAVE) Ua[i] = Ug[i];
   if (tid < 16 && (tid & 7) < 5) cst[(tid & 7) + (tid >> 3) * RECF] = (tid & 7) == 0 ? 0.0 : (tid & 7) == 1 ? 1.0 : (tid & 7) == 2 ? kp.dt : (tid & 7) == 3 ? kp.w_vel * 2 : 2.0;
-  const double* wts = a.obs_weight ? a.obs_weight + (size_t)b * M : nullptr;
+  const double* wts = obs_weights(a, b);
   for (int m = wave; m < M; m += 2) {  // obstacle table, I/Obstacle.cpp:41-62
     for (int t = lane; t < N; t += WAVE) {
-      const ObsEntry e = make_obs_entry(kp, a.obs_pose + (((size_t)b * M + m) * N + t) * 4, a.obs_dim + (((size_t)b * M + m) * N + t) * 2);
+      const ObsEntry e = obs_entry_at(kp, a, b, m, t);
       double* o = tab + ((size_t)m * N + t) * TABF;
       o[0] = e.ox; o[1] = e.oy; o[2] = e.co; o[3] = e.so; o[4] = e.ia2; o[5] = e.ib2;
     }
@@ -1707,7 +1712,7 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
   for (int i = tid; i < 2 * N; i += W * WAVE) Ua[i] = Ug[i];
   if (tid < 16 && (tid & 7) < 5) cst[(tid & 7) + (tid >> 3) * RECF] = (tid & 7) == 0 ? 0.0 : (tid & 7) == 1 ? 1.0 : (tid & 7) == 2 ? kp.dt : (tid & 7) == 3 ? kp.w_vel * 2 : 2.0;
   if (tid == 0) cmd[0] = 0;
-  const double* wts = a.obs_weight ? a.obs_weight + (size_t)b * M : nullptr;
+  const double* wts = obs_weights(a, b);
   UncPose upose{0, 0, 1, 0};
   if (UNC) upose = unc_pose(a.unc, b);
   __syncthreads();  // the controls are in LDS
@@ -1718,8 +1723,9 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
   } else {
     // (W = 3: the two aux wavefronts share the table; samples and their largest step on the first)
     const int al = lane + (wave - 1) * WAVE, an = (W - 1) * WAVE;
-    for (int i = al; i < M * N; i += an) {  // obstacle table, I/Obstacle.cpp:41-62 (entry i = m·N + t, as the inputs lie)
-      const ObsEntry e = make_obs_entry(kp, a.obs_pose + ((size_t)b * M * N + i) * 4, a.obs_dim + ((size_t)b * M * N + i) * 2);
+    for (int i = al; i < M * N; i += an) {  // obstacle table, I/Obstacle.cpp:41-62 (entry i = m·N + t)
+      const int m = i / N;
+      const ObsEntry e = obs_entry_at(kp, a, b, m, i - m * N);
       double* o = tab + (size_t)i * TABF;
       o[0] = e.ox; o[1] = e.oy; o[2] = e.co; o[3] = e.so; o[4] = e.ia2; o[5] = e.ib2;
     }
@@ -2204,6 +2210,10 @@ hipError_t launch_solve_wave(const SolveArgs& a, hipStream_t stream) {
   if (a.pair >= 2 && a.n_samples == 0 && solve_share_applies(a.N, a.M, a.kp.n_samples, a.tab_budget) && (a.flags & CILQR_FLAG_FAITHFUL_ITERS) == 0) {
     if (a.unc.layer) return a.diag ? launch_shared_L_by_shape<true, true>(a, tab_bytes, stream) : launch_shared_L_by_shape<false, true>(a, tab_bytes, stream);
     return a.diag ? launch_shared_L_by_shape<true, false>(a, tab_bytes, stream) : launch_shared_L_by_shape<false, false>(a, tab_bytes, stream);
+  }
+  if (!tab_lds && a.obs_shared) {  // one scene for the batch, table in the workspace: its one table, read by both kernels
+    const hipError_t e = launch_obstacle_table(a, stream);
+    if (e != hipSuccess) return e;
   }
   if (a.diag) return tab_lds ? launch_pair<true, 1>(a, extra, stream) : launch_pair<true, 0>(a, extra, stream);
   return tab_lds ? launch_pair<false, 1>(a, extra, stream) : launch_pair<false, 0>(a, extra, stream);

@@ -125,8 +125,11 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_fast(SolveArgs a, dou
   // column `grp` of this wavefront's block: element (row r) at ws[r * S]
   const double* wave_ws = ws_base + (size_t)blockIdx.x * L.rows() * S;
   double* ws = ws_base + (size_t)blockIdx.x * L.rows() * S + grp;
-  // obstacle table of this wavefront: entry (m, t, solve) = 6 contiguous doubles at ((m*N + t)*S + solve)*6
-  double* tab = a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)grp * TABF;
+  // obstacle table of this wavefront: entry (m, t, solve) = 6 contiguous doubles at ((m*N + t)*S + solve)*6; with one scene for the
+  // batch (a.obs_shared) the one table launch_obstacle_table built, entry (m, t) at (m*N + t)*6, read by every solve
+  const bool tab_shared = a.obs_shared != 0;
+  const int tab_rs = tab_shared ? TABF : S * TABF;  // doubles from row (m, t) to row (m, t + 1)
+  double* tab = tab_shared ? a.obs_tab : a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)grp * TABF;
 #define XF(base, t, f) ws[(size_t)((base) + (t) * XR + (f)) * S]  /* state arrays: (N+1) steps x 6 fields */
 #define UF(base, t, f) ws[(size_t)((base) + (t) * 2 + (f)) * S]   /* control arrays: N steps x 2 fields */
 #define KF(t, f) ws[(size_t)(L.kk() + (t) * KR + (f)) * S]        /* gains: N steps x 10 fields */
@@ -186,24 +189,30 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_fast(SolveArgs a, dou
     // reference node feeds static obstacles: one pose replicated over the horizon, I/ilqr_uncertainty_node.cpp:175-185) gets a
     // bit in `held`: phase L then reads its step-0 row for every step — the same values, but one cache-resident line per
     // field instead of a stream of N·6 doubles per obstacle, solve and iteration from HBM.
+    // Obstacles given constant over the horizon (step stride 0) are held without comparing their columns.  With one scene for
+    // the batch the table is already built: only the held bits are decided here.
     for (int m = 0; m < M; ++m) {
-      const double* pose0 = a.obs_pose + ((size_t)b * M + m) * N * 4;
-      const double* dim0 = a.obs_dim + ((size_t)b * M + m) * N * 2;
+      const long long e0 = obs_entry_index(a, b, m, 0);
+      const double* pose0 = a.obs_pose + 4 * e0;
+      const double* dim0 = a.obs_dim + 2 * e0;
       bool same = true;
-      for (int t = g; t < N; t += G) {
-        const double* pose = pose0 + (size_t)t * 4;
-        const double* dim = dim0 + (size_t)t * 2;
-        same = same && pose[0] == pose0[0] && pose[1] == pose0[1] && pose[2] == pose0[2] && pose[3] == pose0[3] &&
-               dim[0] == dim0[0] && dim[1] == dim0[1];
+      if (a.obs_ts != 0) {
+        for (int t = g; t < N; t += G) {
+          const double* pose = pose0 + 4 * (long long)t * a.obs_ts;
+          const double* dim = dim0 + 2 * (long long)t * a.obs_ts;
+          same = same && pose[0] == pose0[0] && pose[1] == pose0[1] && pose[2] == pose0[2] && pose[3] == pose0[3] &&
+                 dim[0] == dim0[0] && dim[1] == dim0[1];
+        }
       }
       int all = same ? 1 : 0;
 #pragma unroll
       for (int o = G / 2; o > 0; o >>= 1) all &= __shfl_xor(all, o, WAVE);
       const bool is_held = all && m < 64;
       if (is_held) held |= 1ull << m;
+      if (tab_shared) continue;
       // a held obstacle needs its step-0 row only (lane g == 0 of the group writes it); the others need every row
       for (int t = g; t < (is_held ? 1 : N); t += G) {
-        const ObsEntry e = make_obs_entry(kp, pose0 + (size_t)t * 4, dim0 + (size_t)t * 2);
+        const ObsEntry e = obs_entry_at(kp, a, b, m, t);
         double* o = tab + (size_t)(m * N + t) * S * TABF;
         o[0] = e.ox; o[1] = e.oy; o[2] = e.co; o[3] = e.so; o[4] = e.ia2; o[5] = e.ib2;
       }
@@ -296,8 +305,8 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_fast(SolveArgs a, dou
         const int xcs = reinterpret_cast<const int*>(q + P_BUF)[0], ucs = reinterpret_cast<const int*>(q + P_BUF)[1];
         const int bs = blockIdx.x * S + my_slot;
         const double* wss = wave_ws + my_slot;  // column my_slot of this wavefront's workspace block
-        const double* tabs = a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)my_slot * TABF;
-        const double* wtss = a.obs_weight ? a.obs_weight + (size_t)bs * M : nullptr;
+        const double* tabs = tab_shared ? a.obs_tab : a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)my_slot * TABF;
+        const double* wtss = obs_weights(a, bs);
         auto sample_s = [&](int s_, double& x, double& y) { sample_xy(gs, pcs, s_, x, y); };
         struct LIn { double px, py, v, ct, st, u0, u1, vn, cn, sn; };
         auto load_in = [&](LIn& o, int t) {
@@ -320,7 +329,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_fast(SolveArgs a, dou
           // one 48-byte entry = three 16-byte loads from one address; a held obstacle reads its step-0 entry
           auto obs = [&](int m, ObsEntry& e, double& w) {
             const int row = (m < 64 && ((held_s >> m) & 1)) ? 0 : t;
-            const double2* p = reinterpret_cast<const double2*>(tabs + ((size_t)m * N + row) * S * TABF);
+            const double2* p = reinterpret_cast<const double2*>(tabs + ((size_t)m * N + row) * tab_rs);
             const double2 q0 = p[0], q1 = p[1], q2 = p[2];
             e.ox = q0.x; e.oy = q0.y; e.co = q1.x; e.so = q1.y; e.ia2 = q2.x; e.ib2 = q2.y;
             w = wtss ? wtss[m] : kpl.w_obstacle;
@@ -589,7 +598,10 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_general(SolveArgs a, 
   const WsLayout L{N, M};
   double* ws = ws_base + (size_t)blockIdx.x * L.rows() * S + grp;
   double* rws = rec_base + (size_t)blockIdx.x * ((size_t)N * REC) * S + grp;
-  double* tab = a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)grp * TABF;
+  // (one scene for the batch: the one table launch_obstacle_table built, which no solve writes)
+  const bool tab_shared = a.obs_shared != 0;
+  const int tab_rs = tab_shared ? TABF : S * TABF;
+  double* tab = tab_shared ? a.obs_tab : a.obs_tab + (size_t)blockIdx.x * ((size_t)M * N * TABF) * S + (size_t)grp * TABF;
 #define XF(base, t, f) ws[(size_t)((base) + (t) * XR + (f)) * S]
 #define UF(base, t, f) ws[(size_t)((base) + (t) * 2 + (f)) * S]
 #define RF(t, f) rws[(size_t)((t) * REC + (f)) * S]
@@ -605,10 +617,10 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_general(SolveArgs a, 
     UF(L.ua(), t, 0) = Ug[2 * t];
     UF(L.ua(), t, 1) = Ug[2 * t + 1];
   }
-  const double* wts = a.obs_weight ? a.obs_weight + (size_t)b * M : nullptr;
-  for (int m = 0; m < M; ++m)  // the production kernel fills only the step-0 row of a horizon-constant obstacle: fill them all
+  const double* wts = obs_weights(a, b);
+  for (int m = 0; m < M && !tab_shared; ++m)  // the production kernel fills only the step-0 row of a horizon-constant obstacle: fill them all
     for (int t = g; t < N; t += G) {
-      const ObsEntry e = make_obs_entry(kp, a.obs_pose + (((size_t)b * M + m) * N + t) * 4, a.obs_dim + (((size_t)b * M + m) * N + t) * 2);
+      const ObsEntry e = obs_entry_at(kp, a, b, m, t);
       double* o = tab + (size_t)(m * N + t) * S * TABF;
       o[0] = e.ox; o[1] = e.oy; o[2] = e.co; o[3] = e.so; o[4] = e.ia2; o[5] = e.ib2;
     }
@@ -650,7 +662,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_solve_groups_general(SolveArgs a, 
       double cx, cy;
       sample_xy(grid, pc, cs, cx, cy);
       auto obs = [&](int m, ObsEntry& e, double& w) {
-        const double* p = tab + ((size_t)m * N + t) * S * TABF;
+        const double* p = tab + ((size_t)m * N + t) * tab_rs;
         e.ox = p[0]; e.oy = p[1]; e.co = p[2]; e.so = p[3]; e.ia2 = p[4]; e.ib2 = p[5];
         w = wts ? wts[m] : kp.w_obstacle;
         return true;
@@ -806,6 +818,10 @@ size_t solve_groups_ws_doubles(int B, int N) {
 
 hipError_t launch_solve_groups(const SolveArgs& a, int G, double* ws, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
+  if (a.obs_shared) {  // one scene for the batch: its one table, read by the production kernel and its GENERAL follower
+    const hipError_t e = launch_obstacle_table(a, stream);
+    if (e != hipSuccess) return e;
+  }
   switch (G) {
     case 1: launch_g<1>(a, ws, stream); break;
     case 2: launch_g<2>(a, ws, stream); break;

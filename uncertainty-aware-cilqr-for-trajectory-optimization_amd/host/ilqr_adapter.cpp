@@ -1,6 +1,8 @@
 // ilqr_adapter.cpp — see ilqr_adapter.h.  Pure host C++ over the C-ABI (no HIP here).
 #include "ilqr_adapter.h"
 
+#include <string.h>
+
 #include <stdexcept>
 #include <string>
 
@@ -35,14 +37,12 @@ void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
         o.relative_pos_array.cols < params.horizon)
       throw std::runtime_error("set_Obstacle: dimension must be 2×horizon and relative_pos_array 4×horizon");
   obstacles_ = obstacles;
-  obs_pose_.clear();
-  obs_dim_.clear();
+  pack_obstacles();
 }
 
 void iLQR::clear_Obstacle() {
   obstacles_.clear();
-  obs_pose_.clear();
-  obs_dim_.clear();
+  pack_obstacles();
 }
 
 void iLQR::set_uncertainty_map(const Uncertainty& u) {
@@ -64,19 +64,38 @@ void iLQR::set_global_plan(const Matrix& global_plan) {
   global_plan_ = global_plan;
 }
 
-void iLQR::pack_obstacles(int copies) {
-  const int N = params.horizon, M = (int)obstacles_.size();
-  if (obs_pose_.size() == (size_t)copies * M * 4 * N) return;
-  obs_pose_.resize((size_t)copies * M * 4 * N);
-  obs_dim_.resize((size_t)copies * M * 2 * N);
-  for (int c = 0; c < copies; ++c)
-    for (int m = 0; m < M; ++m) {
-      const Obstacle& o = obstacles_[m];
-      for (int t = 0; t < N; ++t) {
-        for (int r = 0; r < 4; ++r) obs_pose_[(((size_t)c * M + m) * N + t) * 4 + r] = o.relative_pos_array(r, t);
-        for (int r = 0; r < 2; ++r) obs_dim_[(((size_t)c * M + m) * N + t) * 2 + r] = o.dimension(r, t);
-      }
+void iLQR::pack_obstacles() {
+  // held: every column of every obstacle equals its first one, bit for bit (so that passing the first alone changes nothing)
+  const int N = params.horizon;
+  held_ = true;
+  for (const Obstacle& o : obstacles_)
+    for (int t = 1; t < N && held_; ++t)
+      held_ = memcmp(&o.relative_pos_array.a[(size_t)4 * t], &o.relative_pos_array.a[0], 4 * sizeof(double)) == 0 &&
+              memcmp(&o.dimension.a[(size_t)2 * t], &o.dimension.a[0], 2 * sizeof(double)) == 0;
+  packed_horizon_ = N;
+  const int M = (int)obstacles_.size(), T = held_ ? 1 : N;  // columns packed per obstacle
+  obs_pose_.resize((size_t)M * 4 * T);
+  obs_dim_.resize((size_t)M * 2 * T);
+  for (int m = 0; m < M; ++m) {
+    const Obstacle& o = obstacles_[m];
+    for (int t = 0; t < T; ++t) {
+      for (int r = 0; r < 4; ++r) obs_pose_[((size_t)m * T + t) * 4 + r] = o.relative_pos_array(r, t);
+      for (int r = 0; r < 2; ++r) obs_dim_[((size_t)m * T + t) * 2 + r] = o.dimension(r, t);
     }
+  }
+}
+
+cilqr_obstacles iLQR::obstacle_strides() {
+  if (packed_horizon_ != params.horizon) pack_obstacles();  // (params is public: the horizon may have changed since set_Obstacle)
+  cilqr_obstacles o{};
+  o.pose = obs_pose_.data();
+  o.dim = obs_dim_.data();
+  o.weight = nullptr;
+  o.batch_stride = 0;
+  o.obstacle_stride = held_ ? 1 : params.horizon;
+  o.step_stride = held_ ? 0 : 1;
+  o.weight_batch_stride = 0;
+  return o;
 }
 
 void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double poly_coeffs[6],
@@ -84,13 +103,13 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   const int N = params.horizon, M = (int)obstacles_.size();
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
-  pack_obstacles(1);
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
-  check(cilqr_solve_batch(h_, 1, N, M, x_0, U.a.data(), poly_coeffs, fl, M ? obs_pose_.data() : nullptr,
-                          M ? obs_dim_.data() : nullptr, nullptr, X_result.a.data(), &last_cost, &iters, &status, CILQR_FLAG_NONE),
-        "cilqr_solve_batch");
+  const cilqr_obstacles obs = obstacle_strides();
+  check(cilqr_solve_batch_obstacles(h_, 1, N, M, x_0, U.a.data(), poly_coeffs, fl, M ? &obs : nullptr, X_result.a.data(), &last_cost,
+                                    &iters, &status, CILQR_FLAG_NONE),
+        "cilqr_solve_batch_obstacles");
   last_iterations = iters;
   last_exit = status;
   U_result = U;  // I/iLQR.cpp:244
@@ -140,10 +159,10 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
                                ref.data(), n_ref.data()), "cilqr_local_plan_batch");
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
-  pack_obstacles(B);
-  check(cilqr_solve_batch(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? obs_pose_.data() : nullptr,
-                          M ? obs_dim_.data() : nullptr, nullptr, X.data(), J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
-        "cilqr_solve_batch");
+  const cilqr_obstacles obs = obstacle_strides();  // one obstacle set for every candidate
+  check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, X.data(),
+                                    J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
+        "cilqr_solve_batch_obstacles");
   int best = 0;  // strict-< first minimum, NaN never wins (the convention of cilqr_argmin_device)
   bool have = false;
   for (int b = 0; b < B; ++b)

@@ -5,7 +5,7 @@
 //     ilqrplanner.run_step(ego_state);           → X_result, U_result, ref_traj_result
 // (I/ilqr_uncertainty_node.cpp:113-130).  This class keeps those names, argument meanings and the persistent, un-shifted
 // warm start (`control_seq`, I/iLQR.cpp:9-15,253) so that call sequence is unchanged; every solve goes through
-// cilqr_solve_batch with B = 1 (or B = candidates, see run_candidates) on the HIP device.  There is no CPU path.
+// cilqr_solve_batch_obstacles with B = 1 (or B = candidates, see run_candidates) on the HIP device.  There is no CPU path.
 //
 // Differences from the reference interface, all forced by the boundary:
 //   * Eigen types are replaced by the column-major `Matrix` below (Eigen is not a dependency of this library);
@@ -89,7 +89,8 @@ class iLQR {
 
   // Batched form of run_step for sampled ego states (e.g. the node's Gaussian pose noise, I/ilqr_uncertainty_node.cpp:82-110):
   // solves every candidate from the current warm start in ONE launch, keeps the minimum-cost one (cilqr_argmin_device)
-  // as X_result/U_result/control_seq and returns its index.
+  // as X_result/U_result/control_seq and returns its index.  The obstacle set travels once for all candidates
+  // (cilqr_solve_batch_obstacles, batch stride 0).
   int run_candidates(const std::vector<double>& ego_states /* 4 per candidate */);
 
   Parameters params;
@@ -101,13 +102,18 @@ class iLQR {
   double last_cost = 0.0;
 
  private:
-  void pack_obstacles(int copies);
+  void pack_obstacles();
+  cilqr_obstacles obstacle_strides();  // the packed set, shared by every solve of a call (batch stride 0)
   cilqr_handle* h_ = nullptr;
   int device_, max_obstacles_, max_candidates_;
   Matrix control_seq_;  // I/iLQR.h:34
   Matrix global_plan_;
   std::vector<Obstacle> obstacles_;
-  std::vector<double> obs_pose_, obs_dim_;  // packed [copy][obstacle][4N] / [2N]
+  // set_Obstacle: every obstacle's columns are bit-identical over the horizon (how the reference node feeds static obstacles,
+  // I/ilqr_uncertainty_node.cpp:175-185): then one column per obstacle is packed and passed with step stride 0
+  bool held_ = false;
+  int packed_horizon_ = -1;  // the horizon obs_pose_ / obs_dim_ were packed for
+  std::vector<double> obs_pose_, obs_dim_;  // packed ONCE: [obstacle][4N] / [2N], or [obstacle][4] / [2] when held_
 };
 
 }  // namespace cilqr_host
