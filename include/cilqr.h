@@ -407,11 +407,16 @@ int cilqr_solve_family(const cilqr_handle* h, int B, int N, int M);
  * table in LDS — a solve's LDS share grows where fewer solves share a CU; with an uncertainty map set, whose term then goes to the
  * last of the further wavefronts: three up to half a solve per SIMD, two up to one; results bit-identical to the one-wavefront kernel; CILQR_NO_SHARE_KERNEL in the environment at create switches it
  * off, CILQR_SHARE_W = 2 or 3 fixes the number), else 1 (also for every shape cilqr_solve_family sends to the grouped family).
- * CILQR_FLAG_FAITHFUL_ITERS always runs on one.  Negative: error code. */
+ * CILQR_FLAG_FAITHFUL_ITERS always runs on one, and under CILQR_PAIR_KERNEL (the two-wavefront experiment) the answer
+ * is 1 at every batch size.  Together with cilqr_solve_family and cilqr_solve_sampled_wavefronts it reads the launch plan the solve
+ * entry points themselves follow (csrc/cilqr_wave_plan.h, plan_wave: one host-side function of the batch shape and the handle's
+ * environment knobs), for flags = 0 and the handle's current map.  Negative: error code. */
 int cilqr_solve_wavefronts(const cilqr_handle* h, int B, int N, int M);
 /* The same for cilqr_solve_batch_sampled(_device): how many wavefronts share a solve's phase L on this handle — 1 (one wavefront
  * per solve: horizons beyond 64, CILQR_NO_SPLIT_KERNEL), 2 or 4 (cilqr_solve_split_kernel, DESIGN.md
- * §4.1c).  CILQR_FLAG_FAITHFUL_ITERS always runs on one.  Negative: error code. */
+ * §4.1c).  CILQR_FLAG_FAITHFUL_ITERS always runs on one.  The answer is the rule by shape alone (there is no n_samples here to size
+ * the LDS with): a call whose sample records take the split kernel's LDS beyond 64 KiB runs on one wavefront all the same.
+ * Negative: error code. */
 int cilqr_solve_sampled_wavefronts(const cilqr_handle* h, int B, int N, int n_obs);
 
 /* Test hook: runs the kernels' own regularised Q_uu inverse (I/iLQR.cpp:155-175) on n column-major 2×2 matrices (host

@@ -417,7 +417,7 @@ def test_automatic_family_choice_large_batch(cilqr, oracle):
 @pytest.mark.parametrize("B,N,M", [(2048, 50, 4), (8192, 50, 4), (2048, 80, 16)])
 def test_several_wavefronts_per_simd(cilqr, oracle, monkeypatch, B, N, M):
     """Batches of two to eight solves per SIMD on the one-wavefront-per-solve family (forced here: the library keeps it for a
-    few solves per SIMD only while the solves are short, pick_group_lanes); N = 80 / M = 16 is the instantiation with the obstacle
+    few solves per SIMD only while the solves are short, plan_group_lanes); N = 80 / M = 16 is the instantiation with the obstacle
     table in global memory.  First, middle and last 64 solves against the oracle, the rest finite with a sane status."""
     from cilqr_amd import scenes
     monkeypatch.setenv("CILQR_FORCE_G", "64")
@@ -451,13 +451,15 @@ def _pair_vs_single(cilqr, monkeypatch, sc, N, M, B):
         one.close()
 
 
-@pytest.mark.parametrize("N,M,B", [(50, 4, 1024), (30, 2, 200), (2, 1, 9), (3, 0, 5), (17, 5, 64), (64, 4, 96), (72, 3, 40), (33, 9, 70)])
+@pytest.mark.parametrize("N,M,B", [(50, 4, 1024), (30, 2, 200), (2, 1, 9), (3, 0, 5), (17, 5, 64), (64, 4, 96), (72, 3, 40), (33, 9, 70), (50, 30, 160)])
 def test_pair_kernel_equals_single_wavefront_kernel(cilqr, oracle, monkeypatch, N, M, B):
     """CILQR_PAIR_KERNEL (opt-in experiment): up to one solve per SIMD every solve runs as a workgroup of two
     wavefronts — the linearisation of the new trajectory on the second one, behind the forward pass, four lanes per step.  Same
     statements, other order of a few sums: it must take the accept / reject path of the one-wavefront kernel on every solve and
     agree with it to rounding (1e-11) — on config 2 in full and on ragged shapes: horizons that are no multiple of its chunks,
-    obstacle counts that are no multiple of the quad, none at all, N > 64 — and both must agree with the oracle."""
+    obstacle counts that are no multiple of the quad, none at all, N > 64 — and both must agree with the oracle.  M = 30 at
+    B = 160: a table that takes the solve's LDS beyond 64 KiB, where the experiment hands the batch to the one-wavefront kernel
+    (plan_wave, tests/test_wave_plan.py)."""
     from cilqr_amd import scenes
     p = cilqr.default_params(N)
     sc = scenes.make_static(B, N, M, p, 7100 + N)
@@ -620,7 +622,7 @@ def test_lane_sharing_changes_no_bit(cilqr, oracle, monkeypatch, G, B, N, M):
 
 
 def test_family_rule_on_measured_shapes(cilqr, oracle):
-    """The family rule (pick_group_lanes, drawn from profiles/r03_family_shapes.txt) at shapes on either side of its lines, and
+    """The family rule (plan_group_lanes, drawn from profiles/r03_family_shapes.txt) at shapes on either side of its lines, and
     one long-horizon batch end to end: N = 120, B = 4096 takes the wavefront family (5.9 ms against 6.7 ms grouped) and agrees with
     the oracle on a sample."""
     from cilqr_amd import scenes

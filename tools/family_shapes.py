@@ -4,7 +4,7 @@ wavefront per solve (CILQR_FORCE_G=64) and G lanes per solve (CILQR_FORCE_G = th
 library's own rule picks (cilqr_solve_family) and what that pick loses against the faster family.  Each figure is the best of
 four launches of one batch WITHOUT the schedule hint (CILQR_NO_SCHEDULE_HINT): on a planner's tick sequence the hint changes
 nothing (profiles/r03_schedule_hint_ticks.txt), so the dispatch-in-index-order figure is the one that decides.  Its table is
-profiles/rNN_family_shapes.txt and the rule in cilqr_api.cpp (pick_group_lanes) is drawn from it."""
+profiles/rNN_family_shapes.txt and the rule in csrc/cilqr_wave_plan.h (plan_group_lanes) is drawn from it."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "uncertainty-aware-cilqr-for-trajectory-optimization_amd")]
@@ -57,7 +57,7 @@ for N, M in shapes:
         G = 32
         while G > 1 and G * B > 64 * 1024:
             G >>= 1
-        G = max(G, 4 if N > 64 else 2)  # (pick_group_lanes)
+        G = max(G, 4 if N > 64 else 2)  # (plan_group_lanes)
         _, _, fam = run(N, M, B, 0)
         w, iw, _ = run(N, M, B, 64)
         g, ig, _ = run(N, M, B, G)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Grouped family: kernel time for every lane grouping G at large batches (CILQR_FORCE_G), beside the library's own pick.
-The rule in cilqr_api.cpp (pick_group_lanes) is drawn from this table.   python tools/group_lanes_sweep.py"""
+The rule in csrc/cilqr_wave_plan.h (plan_group_lanes) is drawn from this table.   python tools/group_lanes_sweep.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "uncertainty-aware-cilqr-for-trajectory-optimization_amd")]

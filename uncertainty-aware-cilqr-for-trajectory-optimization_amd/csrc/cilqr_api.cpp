@@ -58,6 +58,29 @@ int check_sizes(const cilqr_handle* h, int B, int N, int M) {
   return CILQR_OK;
 }
 
+// The environment's A/B and test hooks, read once per handle (cilqr_wave_plan.h says what each does).
+cilqr::SolveKnobs read_knobs(int simds) {
+  const auto on = [](const char* name) { return getenv(name) != nullptr ? 1 : 0; };
+  const auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+  cilqr::SolveKnobs k = {};
+  k.simds = simds; k.force_g = num("CILQR_FORCE_G", 0);
+  k.hint_off = on("CILQR_NO_SCHEDULE_HINT"); k.pair_on = on("CILQR_PAIR_KERNEL"); k.steal_off = on("CILQR_NO_LANE_SHARING"); k.split_off = on("CILQR_NO_SPLIT_KERNEL");
+  k.share_off = on("CILQR_NO_SHARE_KERNEL"); k.tab_budget_kb = num("CILQR_LDS_TABLE_KB", 0);
+  k.split_w = num("CILQR_SPLIT_W", 0);  // (test hook: 2 or 4 wavefronts per solve)
+  if (on("CILQR_SHARE_W")) k.share_w = num("CILQR_SHARE_W", 0) == 3 ? 3 : 2;  // (A/B hook: two or three wavefronts wherever the kernel applies)
+  k.share_max = num("CILQR_SHARE_MAX_B", -1);  // (A/B hook: largest batch on the shared-phase-L kernel; -1: by horizon, share_wavefronts)
+  return k;
+}
+
+// What every solve call takes from its handle and its sizes; the pointers of the call and its obstacle fields are the caller's.
+cilqr::SolveArgs handle_args(const cilqr_handle* h, int B, int N, int M, uint32_t flags) {
+  cilqr::SolveArgs a = {};
+  a.obs_tab = h->d_obs_tab; a.fwd = h->d_ws;  // (fwd: the grouped family's workspace: 42·N + 12 doubles per solve ≥ the 16·(N + 1) needed here; never both at once)
+  a.redo = h->d_redo; a.diag = h->diag; a.passes = h->passes; a.unc = h->unc; a.kp = h->kp;
+  a.B = B; a.N = N; a.M = M; a.flags = flags;
+  return a;
+}
+
 template <typename T>
 hipError_t dmalloc(T** p, size_t n) {
   *p = nullptr;
@@ -67,84 +90,6 @@ hipError_t dmalloc(T** p, size_t n) {
 
 }  // namespace
 
-// Kernel family by batch shape: lanes per solve, 64 = the one-wavefront-per-solve family (cilqr_solve.hip), less =
-// the grouped family (cilqr_solve_groups.hip).  Drawn from tools/family_shapes.py (profiles/r03_family_shapes.txt: both families
-// at N = 30 … 160, M = 0 … 16, B = 2048 … 16384, first calls, i.e. WITHOUT the schedule hint — on a planner's tick sequence
-// the hint changes nothing, profiles/r03_schedule_hint_ticks.txt) and tools/group_lanes_sweep.py.  Up to one solve per SIMD the
-// wavefront family always (its backward pass on the matrix cores and scalar-path forward pass give it the shorter serial chain);
-// beyond, it keeps batches of a few solves per SIMD while a solve is short — the shorter the horizon and the fewer the
-// obstacles, the longer — and the grouped family, whose phase L shares the lanes of finished solves since round 3, takes the
-// rest.  Very long horizons (N > 110: the records no longer fit the grouped family's LDS chunks well) stay on the wavefront
-// family at every size measured.
-static int pick_group_lanes(const cilqr_handle* h, int B, int N, int M) {
-  const int f = h->force_g;
-  if (f == 1 || f == 2 || f == 4 || f == 8 || f == 16 || f == 32 || f == 64) return f;
-  // (with hundreds of obstacle entries per step the solve is a stream over its obstacle table: the wavefront-per-solve
-  // family reads it as whole 400-640 B rows per instruction and measures ≈2x faster there — BASELINE config 3)
-  if (M > 32 || N > 110) return 64;
-  // largest batch that stays on the wavefront family, in half solves per SIMD
-  int cap2;
-  // (redrawn at the end of round 3, when the family had got its shared-phase-L kernel up to two solves per SIMD and N = 127:
-  // profiles/r03_family_shapes.txt)
-  if (N <= 32) cap2 = 16;
-  else if (N <= 56) cap2 = 8;
-  else if (N <= 92) cap2 = 4;
-  else cap2 = 8;
-  if (2L * B <= (long)cap2 * h->simds) return 64;
-  int G = 32;
-  while (G > 1 && (long)G * B > 64L * h->simds) G >>= 1;
-  // not below 2 lanes per solve (4 for horizons beyond one round of lanes): with the lanes of finished solves helping in phase L
-  // twice as many, smaller wavefronts — started as the first ones end — beat one wavefront per SIMD with 64 solves and 3-step
-  // hand-over chunks each (profiles/r03_group_lanes_sweep.txt: B = 65536, N = 50: G = 2 5.7 ms against 7.1 at G = 1; N = 80:
-  // G = 4 16.4-19.6 ms against 20.5-24.6)
-  const int g_min = N > 64 ? 4 : 2;
-  if (G < g_min) G = g_min;
-  return G;
-}
-
-// Sampled obstacles: wavefronts per solve that share phase L (0: the one-wavefront kernel); the launcher falls back to one where
-// the split kernel does not apply (N > 64, fewer obstacles than wavefronts, a map set, the reference-loop mode).
-static int pick_split_wavefronts(const cilqr_handle* h, int B) {
-  if (h->split_off) return 0;
-  if (h->split_w) return h->split_w;
-  return B <= h->simds ? 4 : 2;
-}
-
-// Static obstacles on the one-wavefront family: further wavefronts per solve for phase L (cilqr_solve_share_kernel) up to about two solves
-// per SIMD — tools/share_ab.py, profiles/r03_share_kernel.txt: config-2 scenes 0.372 against 0.404 ms at B = 256, 0.390 / 0.415 at 1024,
-// 0.406 / 0.433 at 2048, level at 3072, slower at 4096 (0.547 / 0.476: the second wavefronts cost residency there).
-// Up to THREE QUARTERS of a solve per SIMD three: the obstacle terms on two of them (even / odd entries: obstacle_loop's own two chains),
-// Jacobians and control barrier on the last — the solves that decide such a launch are the ones with every obstacle close (B = 256: 0.356
-// against 0.362 ms).  Not at one solve per SIMD: three wavefronts of 153 registers fill a SIMD, so a CU holds exactly its four workgroups
-// and every unevenness of the dispatch makes one wait for a whole solve (rocprofv3, 61 launches at B = 1024: 395 µs average, 538 µs
-// maximum with three; 391 / 418 with two).  0: one wavefront.
-static int pick_share(const cilqr_handle* h, int B, int N, int M) {
-  // how far beyond one solve per SIMD the further wavefronts pay depends on how many workgroups a CU still holds, i.e. on the horizon
-  // (tools/share_ab.py with CILQR_SHARE_MAX_B open, profiles/r03_share_kernel.txt, last section: N = 30 still 6 % ahead at four solves
-  // per SIMD, N = 40 8 % at three, N = 50 8 % at two and level at three, N = 56 / 60 5 / 3 % at 1.5 and behind at two, N = 64 ahead at
-  // 1.25 and behind at 1.5, N = 80 2 % at one) — in quarters of a solve per SIMD:
-  const int q = N <= 32 ? 16 : N <= 44 ? 12 : N <= 52 ? 8 : N <= 60 ? 6 : N <= 64 ? 5 : 4;
-  const long cap = h->share_max >= 0 ? (long)h->share_max : (long)q * h->simds / 4;
-  if (h->share_off || B > cap) return 0;
-  const int w = h->share_w ? h->share_w : (4 * B <= 3 * h->simds ? 3 : 2);
-  if (h->unc.layer)  // a map set: its term on the last aux wavefront; two wavefronts per SIMD, so three per solve up to half a solve per SIMD
-    return N > 64 ? 2 : h->share_w ? h->share_w : (2 * B <= h->simds ? 3 : (B <= h->simds ? 2 : 0));
-  return w == 3 && (M < 2 || N > 64) ? 2 : w;  // (horizons 65 … 127: two steps per lane, built for two wavefronts)
-}
-
-// LDS a solve of the one-wavefront family may take with its obstacle table inside.  32 KiB keeps five solves per CU resident — what a
-// batch beyond one solve per SIMD needs; a batch of at most k ≤ 4 solves per CU cannot use that residency, and each of its solves may
-// as well have 1/k of the CU's 160 KiB (beyond 64 KiB the launcher raises the kernels' limit): the table of up to ≈ 20 obstacles at two
-// solves per CU, ≈ 45 at one, then lies in LDS instead of being streamed from the workspace by every pass, and the shape can take the
-// shared-phase-L kernel (tools/share_ab.py, N = 50: M = 12 at B = 256 0.485 → 0.370 ms, M = 8 at B = 1024 0.503 → 0.435 ms).
-static int lds_table_budget(const cilqr_handle* h, int B) {
-  if (h->tab_budget_kb > 0) return h->tab_budget_kb * 1024;  // (environment CILQR_LDS_TABLE_KB at create: A/B hook)
-  const int cus = h->simds / 4, k = (B + cus - 1) / cus;
-  if (k < 1 || k > 4) return 32 * 1024;
-  const int share = (160 * 1024) / k - 2048;
-  return share < 32 * 1024 ? 32 * 1024 : share;
-}
-
 // The one-wavefront-per-solve family with a schedule hint.  A batch of more solves than SIMDs is dispatched in workgroup order,
 // and its launch ends when the last workgroup does: a 20-pass solve that starts among the last costs its full length on top of
 // everything else (config-2 scenes at B = 4096: 0.91 ms as given, 0.53 ms with the longest solves first; config 3: 3.8 → 2.4 ms,
@@ -152,21 +97,11 @@ static int lds_table_budget(const cilqr_handle* h, int B) {
 // so each call records its solves' pass counts and a small kernel sorts them into the NEXT call's dispatch order (same batch
 // size, same stream; otherwise, and in a first call, the order is the identity).  Any order gives the same results: a solve
 // depends on nothing but its own inputs.  CILQR_NO_SCHEDULE_HINT in the environment at create switches it off.
-static int launch_wave_scheduled(cilqr_handle* h, cilqr::SolveArgs& a, void* stream) {
-  const bool hinted = !h->hint_off && a.B > h->simds;
-  a.order = hinted && h->hint_B == a.B && h->hint_stream == stream ? h->d_order : nullptr;
-  a.hint_passes = hinted ? h->d_hint_passes : nullptr;
-  // CILQR_PAIR_KERNEL: up to one solve per SIMD every solve gets a second wavefront on another SIMD of its CU that linearises the
-  // new trajectory behind the forward pass (cilqr_solve_pair_kernel).  Measured slower at every batch size (the
-  // second wavefront's work is paid for by the main wavefronts that share its SIMD): an experiment, not the default.
-  a.pair = h->pair_on && a.B <= h->simds ? 1 : 0;
-  // Default up to two solves per SIMD (share_max solves): further wavefronts per solve take the obstacle, control-barrier and Jacobian
-  // terms of phase L while the first searches the closest samples (cilqr_solve_share_kernel; bit-identical results; the launcher
-  // falls back where it does not apply: table not in LDS, N > 127, a map set, the reference-loop mode).
-  if (!a.pair) a.pair = pick_share(h, a.B, a.N, a.M);
-  a.tab_budget = lds_table_budget(h, a.B);
-  HIP_TRY(cilqr::launch_solve_wave(a, (hipStream_t)stream));
-  if (hinted) {
+static int launch_wave_scheduled(cilqr_handle* h, cilqr::SolveArgs& a, const cilqr::WavePlan& plan, void* stream) {
+  a.order = plan.hinted && h->hint_B == a.B && h->hint_stream == stream ? h->d_order : nullptr;
+  a.hint_passes = plan.hinted ? h->d_hint_passes : nullptr;
+  HIP_TRY(cilqr::launch_solve_wave(a, plan, (hipStream_t)stream));
+  if (plan.hinted) {
     HIP_TRY(cilqr::launch_schedule_order(h->d_hint_passes, a.B, h->d_order, (hipStream_t)stream));
     h->hint_B = a.B; h->hint_stream = stream;
   }
@@ -198,31 +133,21 @@ int check_obstacles(int B, int N, int M, const cilqr_obstacles* o, size_t* span,
 int solve_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* x0, double* U, const double* poly,
                  const double* xplan_fl, const cilqr_obstacles& o, double* X_out, double* J_out, int32_t* iters_out,
                  int32_t* status_out, uint32_t flags) {
-  cilqr::SolveArgs a;
+  cilqr::SolveArgs a = handle_args(h, B, N, M, flags);
   a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
   a.obs_pose = o.pose; a.obs_dim = o.dim; a.obs_weight = M > 0 ? o.weight : nullptr;
   a.obs_bs = o.batch_stride; a.obs_ms = o.obstacle_stride; a.obs_ts = o.step_stride; a.obs_wbs = o.weight_batch_stride;
   // one scene for the batch: the kernels that keep their table in the workspace read one table built in front of them
   a.obs_shared = M > 0 && B > 1 && o.batch_stride == 0 && (!a.obs_weight || o.weight_batch_stride == 0) ? 1 : 0;
   a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
-  a.samp_off = nullptr; a.n_samples = 0; a.samp_w = 0.0;
-  a.obs_tab = h->d_obs_tab;
-  a.fwd = h->d_ws;  // (the grouped family's workspace: 42·N + 12 doubles per solve ≥ the 16·(N + 1) needed here; never both at once)
-  a.order = nullptr; a.hint_passes = nullptr; a.pair = 0; a.tab_budget = 0; a.steal = h->steal_off ? 0 : 1; a.split = 0;
-  a.redo = h->d_redo;
-  a.diag = h->diag;
-  a.passes = h->passes;
-  a.unc = h->unc;
-  a.B = B; a.N = N; a.M = M; a.flags = flags;
-  a.kp = h->kp;
+  a.steal = h->knobs.steal_off ? 0 : 1;
   HIP_TRY(hipSetDevice(h->device));
-  const int G = pick_group_lanes(h, B, N, M);
-  if (G == 64 && cilqr::solve_lds_bytes(N, h->kp.n_samples) > cilqr::SOLVE_LDS_MAX)
-    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch: horizon %d needs %zu bytes of LDS per solve (limit %zu)", N,
-                cilqr::solve_lds_bytes(N, h->kp.n_samples), cilqr::SOLVE_LDS_MAX);
-  if (G == 64) return launch_wave_scheduled(h, a, stream);
-  HIP_TRY(cilqr::launch_solve_groups(a, G, h->d_ws, (hipStream_t)stream));
-  return CILQR_OK;
+  const int G = cilqr::plan_group_lanes(h->knobs, B, N, M);
+  if (G != 64) { HIP_TRY(cilqr::launch_solve_groups(a, G, h->d_ws, (hipStream_t)stream)); return CILQR_OK; }
+  const cilqr::WavePlan plan = cilqr::plan_wave(h->knobs, {B, N, M, 0, h->kp.n_samples, flags, h->unc.layer != nullptr, a.obs_shared != 0});
+  if (plan.too_large)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch: horizon %d needs %zu bytes of LDS per solve (limit %zu)", N, plan.lds_general, cilqr::SOLVE_LDS_MAX);
+  return launch_wave_scheduled(h, a, plan, stream);
 }
 
 }  // namespace
@@ -308,9 +233,8 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   h->params = *p;
   derive(*p, h->kp);
   h->device = device;
-  h->simds = prop.multiProcessorCount > 0 ? prop.multiProcessorCount * 4 : 1024;
+  h->knobs = read_knobs(prop.multiProcessorCount > 0 ? prop.multiProcessorCount * 4 : 1024);
   h->max_batch = max_batch; h->max_horizon = max_horizon; h->max_obstacles = max_obstacles;
-  if (const char* fg = getenv("CILQR_FORCE_G")) h->force_g = atoi(fg);
   const size_t B = max_batch, N = max_horizon, M = max_obstacles;
   hipError_t err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   {  // arena of the host-buffer entry points: the larger of the two layouts that can be asked for (cilqr_host_io.cpp)
@@ -327,16 +251,6 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   if (err == hipSuccess) err = dmalloc(&h->d_hint_passes, B);
   if (err == hipSuccess) err = dmalloc(&h->d_order, B);
   h->hint_B = 0; h->hint_stream = nullptr;
-  h->hint_off = getenv("CILQR_NO_SCHEDULE_HINT") != nullptr;
-  h->pair_on = getenv("CILQR_PAIR_KERNEL") != nullptr;
-  h->steal_off = getenv("CILQR_NO_LANE_SHARING") != nullptr;
-  h->split_off = getenv("CILQR_NO_SPLIT_KERNEL") != nullptr;
-  h->share_off = getenv("CILQR_NO_SHARE_KERNEL") != nullptr;
-  if (const char* kb = getenv("CILQR_LDS_TABLE_KB")) h->tab_budget_kb = atoi(kb);
-  h->share_max = -1;  // by horizon (pick_share)
-  if (const char* sw = getenv("CILQR_SHARE_W")) h->share_w = atoi(sw) == 3 ? 3 : 2;  // (A/B hook: two or three wavefronts wherever the kernel applies)
-  if (const char* sm = getenv("CILQR_SHARE_MAX_B")) h->share_max = atoi(sm);  // (A/B hook: largest batch on the shared-phase-L kernel)
-  if (const char* sw = getenv("CILQR_SPLIT_W")) h->split_w = atoi(sw);  // (test hook: 2 or 4 wavefronts per solve)
   if (err == hipSuccess) err = dmalloc(&h->d_pair, (size_t)2);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
@@ -528,21 +442,17 @@ int cilqr_wait(cilqr_handle* h) {
 
 int cilqr_solve_family(const cilqr_handle* h, int B, int N, int M) {
   if (!h || B < 0 || N < 1 || M < 0) return fail(CILQR_ERR_ARG, "cilqr_solve_family: bad argument");
-  return pick_group_lanes(h, B, N, M);
+  return cilqr::plan_group_lanes(h->knobs, B, N, M);
 }
 
 int cilqr_solve_wavefronts(const cilqr_handle* h, int B, int N, int M) {
   if (!h || B < 0 || N < 1 || M < 0) return fail(CILQR_ERR_ARG, "cilqr_solve_wavefronts: bad argument");
-  if (pick_group_lanes(h, B, N, M) != 64) return 1;
-  const int w = pick_share(h, B, N, M);
-  return w && !h->pair_on && cilqr::solve_share_applies(N, M, h->kp.n_samples, lds_table_budget(h, B)) ? w : 1;
+  return cilqr::query_wavefronts(h->knobs, B, N, M, h->kp.n_samples, h->unc.layer != nullptr);
 }
 
 int cilqr_solve_sampled_wavefronts(const cilqr_handle* h, int B, int N, int n_obs) {
   if (!h || B < 0 || N < 1 || n_obs < 1) return fail(CILQR_ERR_ARG, "cilqr_solve_sampled_wavefronts: bad argument");
-  const int w = pick_split_wavefronts(h, B);
-  if (w < 2 || N > 64 || n_obs < w) return 1;
-  return w >= 4 ? 4 : 2;
+  return cilqr::split_shape_wavefronts(h->knobs, B, N, n_obs);  // (the rule by shape alone: plan_wave's fall-back beyond 64 KiB of LDS is not in it)
 }
 
 int cilqr_solve_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* x0, double* U,
@@ -570,10 +480,6 @@ int cilqr_solve_batch_obstacles_device(cilqr_handle* h, void* stream, int B, int
   const cilqr_obstacles none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
   return solve_device(h, stream, B, N, M, x0, U, poly, xplan_fl, M > 0 ? *obs : none, X_out, J_out, iters_out, status_out, flags);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int cilqr_solve_batch(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly,
                       const double* xplan_fl, const double* obs_pose, const double* obs_dim, const double* obs_weight,
@@ -622,31 +528,19 @@ int cilqr_solve_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out || !nom_pose || !nom_dim || !sample_offset)
     return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: null required pointer");
-  if (cilqr::solve_lds_bytes(N, h->kp.n_samples) + cilqr::solve_sampled_lds_bytes(n_obs, n_samples) > cilqr::SOLVE_LDS_MAX)
+  const cilqr::WavePlan plan = cilqr::plan_wave(h->knobs, {B, N, n_obs, n_samples, h->kp.n_samples, flags, h->unc.layer != nullptr, false});
+  if (plan.too_large)
     return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch_sampled: n_obs * n_samples offset records do not fit LDS beside the solve");
-  if (cilqr::solve_sampled_tab_doubles(n_obs, N) > (size_t)h->max_obstacles * 6 * (size_t)h->max_horizon)
+  if (cilqr::sampled_tab_doubles(n_obs, N) > (size_t)h->max_obstacles * 6 * (size_t)h->max_horizon)
     return fail(CILQR_ERR_UNSUPPORTED, "cilqr_solve_batch_sampled: nominal records exceed the obstacle workspace reserved at create");
-  cilqr::SolveArgs a;
+  cilqr::SolveArgs a = handle_args(h, B, N, n_obs, flags);  // (obs_tab: n_obs·N·8 doubles per solve ≤ the n_obs·n_samples·N·6 reserved for the materialised form)
   a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
-  a.obs_pose = nom_pose; a.obs_dim = nom_dim; a.obs_weight = nullptr;
-  a.obs_bs = (long long)n_obs * N; a.obs_ms = N; a.obs_ts = 1; a.obs_wbs = 0; a.obs_shared = 0;  // (sampled_prologue reads them densely)
+  a.obs_pose = nom_pose; a.obs_dim = nom_dim;
+  a.obs_bs = (long long)n_obs * N; a.obs_ms = N; a.obs_ts = 1;  // (sampled_prologue reads them densely)
   a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
   a.samp_off = sample_offset; a.n_samples = n_samples; a.samp_w = sample_weight;
-  a.obs_tab = h->d_obs_tab;  // n_obs·N·8 doubles per solve ≤ the n_obs·n_samples·N·6 reserved for the materialised form
-  a.fwd = h->d_ws;
-  a.pair = 0; a.tab_budget = 0; a.steal = 0;
-  // wavefronts per solve sharing phase L (cilqr_solve_split_kernel): four up to one solve per SIMD, where a shorter pass is all that
-  // counts, two beyond (tools/split_ab.py, profiles/r03_split_kernel.txt: B = 256 0.88 / 1.35 / 2.08 ms with 4 / 2 / 1 wavefronts,
-  // B = 1024 1.47 / 1.55 / 2.11, B = 4096 3.86 / 3.27 / 3.97, B = 8192 6.81 / 5.48 / 5.68)
-  a.split = pick_split_wavefronts(h, B);
-  a.redo = h->d_redo;
-  a.diag = h->diag;
-  a.passes = h->passes;
-  a.unc = h->unc;
-  a.B = B; a.N = N; a.M = n_obs; a.flags = flags;
-  a.kp = h->kp;
   HIP_TRY(hipSetDevice(h->device));
-  return launch_wave_scheduled(h, a, stream);  // the LDS-resident family at every batch size
+  return launch_wave_scheduled(h, a, plan, stream);  // the LDS-resident family at every batch size
 }
 
 int cilqr_solve_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* x0, double* U,

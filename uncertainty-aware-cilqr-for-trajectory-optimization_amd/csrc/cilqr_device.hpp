@@ -10,15 +10,12 @@
 #include <float.h>
 
 #include "cilqr_internal.h"
+#include "cilqr_wave_plan.h"  // WAVE and the record widths XR, REC, TABF, …: one definition for the kernels and the host's LDS sizes
 
 namespace cilqr {
 namespace dev {
 
-constexpr int WAVE = 64;
-constexpr int XR = 6;    // doubles per state record {x, y, v, theta, cos theta, sin theta}
-constexpr int REC = 16;  // doubles per linearisation record
 constexpr int KR = 10;   // doubles per gain record {k(2), K(2x4)}
-constexpr int TABF = 6;  // fields per obstacle-table entry
 
 // ---- single-instruction helpers ------------------------------------------------------------------------------------
 // One wavefront per SIMD issues one instruction every ~5 shader ticks whatever its kind (tools/ubench_issue.hip), so the

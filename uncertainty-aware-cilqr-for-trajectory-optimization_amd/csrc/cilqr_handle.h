@@ -56,7 +56,7 @@ struct cilqr_handle {
   cilqr_params params;
   cilqr::KParams kp;
   int device;
-  int simds;         // SIMDs of the device (4 per CU): 1024 on an MI355X
+  cilqr::SolveKnobs knobs;  // SIMDs of the device and the environment's A/B and test hooks, read once at create (cilqr_wave_plan.h)
   int max_batch, max_horizon, max_obstacles;
   hipStream_t stream;
   // host-buffer entry points (cilqr_host_io.cpp): device arena and pinned staging sized at create, the call in flight
@@ -78,17 +78,6 @@ struct cilqr_handle {
   int32_t* d_order;
   int hint_B;          // batch size the order is valid for (0: none)
   void* hint_stream;   // stream it was built on (a call on another stream does not use it)
-  int hint_off;        // environment CILQR_NO_SCHEDULE_HINT at create
-  int steal_off;       // environment CILQR_NO_LANE_SHARING at create: the grouped family without phase L's lane sharing (A/B, bit-equality test)
-  int split_w;         // 0 = automatic; else 2 or 4 (test hook: environment CILQR_SPLIT_W at create)
-  int split_off;       // environment CILQR_NO_SPLIT_KERNEL at create: sampled obstacles on one wavefront per solve (A/B, tests)
-  int share_off;       // environment CILQR_NO_SHARE_KERNEL at create: static obstacles on one wavefront per solve at every batch size (A/B, tests)
-  int tab_budget_kb;   // 0 = automatic (cilqr_api.cpp, lds_table_budget); else KiB (environment CILQR_LDS_TABLE_KB at create: A/B)
-  int share_w;         // 0 = automatic (three wavefronts up to one solve per SIMD, two beyond); else 2 or 3 (environment CILQR_SHARE_W at create)
-  int share_max;       // -1: the largest batch on the shared-phase-L kernel follows the horizon (cilqr_api.cpp, pick_share); CILQR_SHARE_MAX_B overrides
-  int pair_on;         // environment CILQR_PAIR_KERNEL at create: the two-wavefront kernel for batches up to one solve per SIMD
-                       // (a measured negative result, DESIGN.md §5: kept for the A/B of tools/pair_ab.py and its tests, off by default)
-  int force_g;       // 0 = automatic; else 1,2,4,8,16,32 or 64 (test hook: environment CILQR_FORCE_G at create)
   double* d_pair;
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;

@@ -1,6 +1,6 @@
 // cilqr_solve.hip — batched constrained-iLQR solve for gfx950 (MI355X), ONE WAVEFRONT PER SOLVE, LDS-resident.
 // This is the kernel family for batches up to about one solve per SIMD (B ≤ 1024 on the 1024 SIMDs of an MI355X, e.g.
-// BASELINE config 2); larger batches go to the G-lanes-per-solve family in cilqr_solve_groups.hip (launch_solve picks).
+// BASELINE config 2); larger batches go to the G-lanes-per-solve family in cilqr_solve_groups.hip (plan_group_lanes, cilqr_wave_plan.h, picks).
 //
 // Hot path of the reference planner: iLQR::get_optimal_control_seq (I/iLQR.cpp:201-245) with everything it
 // calls — nominal rollout (:51-62), Constraints::get_state_cost / get_control_cost / get_J
@@ -25,6 +25,8 @@
 //      across the lanes, operands fetched from the records by per-lane LDS addresses (riccati_mfma); the GENERAL kernel
 //      evaluates the same recursion entry by entry on the vector ALU (riccati);
 //   F  forward pass, sequential in t, every lane computing the same values.
+#include <type_traits>
+
 #include "cilqr_device.hpp"
 
 namespace cilqr {
@@ -33,7 +35,6 @@ using namespace dev;
 
 namespace {
 
-constexpr int RECF = REC - 2;  // record width of the production kernel: p and q are not stored (they are (dt/2)·al, (dt/2)·be)
 // Forward-pass record of the production kernel, in GLOBAL memory (SolveArgs::fwd, [N + 1][FREC] per solve, the last one a dump):
 // {k(2), K(2x4)} written by phase R, {x, y, v, theta, u0, u1} of the old trajectory written by phase L; phase F reads a step's
 // record with two s_load_dwordx16 (forward_smem).
@@ -164,8 +165,6 @@ struct TabSource {  // every obstacle has its own table row; STREAMED: the table
 // re-streamed from HBM by every iteration (measured ≈ 20 GB per launch of 4096 solves).  The nominal records (8 doubles per
 // (o, t)) stay in global memory and are read once per obstacle and iteration; the offset records live in LDS and are read
 // at a wave-uniform address.  cos/sin of the sample heading come from the angle-addition formulas.
-constexpr int NOMF = 8;  // x, y, cos, sin, v·t_safe, half-length + margins, half-width + margins, pad
-constexpr int OFFF = 6;  // dx, dy, then (cos, sin of the SAMPLE's heading, 1/a², 1/b²) for an obstacle of constant shape, else (cos dtheta, sin dtheta, -, -)
 struct SampledObstacles {
   const double* nom;  // this lane's step: record of obstacle 0; obstacle stride N·NOMF
   const double* off;  // LDS [o][s][OFFF]
@@ -499,11 +498,6 @@ __device__ __forceinline__ bool riccati(const KParams& kp, int N, const double* 
 // multiply-adds over k per entry, structural zeros included), so results agree with it to rounding, like the other identities
 // of the production kernel; a non-finite or non-PSD Q_uu hands the solve to the GENERAL kernel exactly as before.
 #define CILQR_MFMA(xa, xb, xc) __builtin_amdgcn_mfma_f64_4x4x4f64(xa, xb, xc, 0, 0, 0)
-// Constant table behind the records: {0, 1, dt, 2·w_vel, 2} twice, RECF doubles apart — a lane that reads a constant keeps its
-// address while the others step through the records, and the two steps of one loop trip are read at immediate offsets 0 and RECF.
-// (Records of 16 doubles would hold p and q, but a lane stride of 128 bytes puts phase L's record stores on two banks only:
-// measured +17 % on phase L; 112 bytes spread a quarter-wave's 16-byte stores over all 64 banks.)
-constexpr int RCST = REC + 6;
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   int lo = __double2loint(v), hi = __double2hiint(v);
@@ -1078,7 +1072,6 @@ __global__ __launch_bounds__(WAVE, UNC ? 1 : 2) void cilqr_solve_kernel(SolveArg
 // summed in the order of wave_sum_uniform — agreement with the one-wavefront kernel to rounding (observed ≤ 4e-13 on config 2;
 // the compiler contracts a few sums differently in the two mappings), accept / reject paths equal on every solve tested.
 constexpr unsigned long long THETA_PENDING = 0x7FF00000DEADBEEFull;
-constexpr int PAIR_CTL = 4;       // doubles: {J of the trajectory in LDS, command | abort (two int32), -, -}
 constexpr int PAIR_SPIN = 1 << 16;  // polls (≈ 150 ticks each) before the aux wavefront gives up on a state: ≫ any phase
 constexpr int CMD_GO = 1, CMD_EXIT = 2;
 constexpr int PAIR_LAST = 10;  // steps of the last chunk of a linearisation (linearize_quads)
@@ -1655,7 +1648,7 @@ __global__ __launch_bounds__(W * WAVE, 2) void cilqr_solve_split_kernel(SolveArg
 // two meet at two barriers per pass.  While every SIMD still holds a main wavefront the aux wavefronts take issue slots from the
 // main wavefronts of OTHER solves (work-conserving: no gain, no loss to speak of); once the short solves have ended — the larger
 // part of the launch — the long ones have their SIMDs' partners to themselves and a pass is ≈ 4.5 k ticks shorter.
-// W = 3 (up to three quarters of a solve per SIMD: cilqr_api.cpp, pick_share): the obstacle terms are split once more — wavefront 1 sums the entries of EVEN index, wavefront 2
+// W = 3 (up to three quarters of a solve per SIMD: cilqr_wave_plan.h, share_wavefronts): the obstacle terms are split once more — wavefront 1 sums the entries of EVEN index, wavefront 2
 // those of odd index, each in one chain, in order, which is obstacle_loop's own order of summation (cilqr_device.hpp, SPLIT); wavefront
 // 2 also takes the Jacobian slots and the control barrier, and main adds odd sums to even sums as obstacle_loop does.  The solves that
 // decide a launch are the ones with every obstacle close (their aux wavefront took 6.1 k ticks per call where the mean took 4.3 k).
@@ -2043,87 +2036,17 @@ __global__ void unc_cost_kernel(UncArgs u, int n, const double* states, double* 
   mx[3 * i] = h00 * inv; mx[3 * i + 1] = h01 * inv; mx[3 * i + 2] = h11 * inv;
 }
 
-// Bytes of the per-solve arrays: `compact` = the production kernel without CILQR_FLAG_FAITHFUL_ITERS (forward pass in place,
-// no candidate buffers); otherwise with candidate buffers.
-size_t core_lds_bytes(int N, int n_samples, bool compact) {
-  const size_t traj = (size_t)(N + 1) * XR + (size_t)2 * N;
-  const size_t doubles = (((size_t)n_samples + 1) & ~(size_t)1) + (compact ? 1 : 2) * traj + (size_t)N * (compact ? RECF : REC) + RCST;  // gains overlay the records
-  return doubles * sizeof(double);
+// Run-time bools as template arguments: f(std::bool_constant<b>{}, …).
+template <typename F>
+hipError_t with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
-
-// `extra`: bytes behind the per-solve arrays (obstacle table or sample records), the same for both kernels of the pair.
-template <bool DIAG, int TAB, bool UNC>
-hipError_t launch_pair_unc(const SolveArgs& a, size_t extra, hipStream_t stream) {
-  const bool faithful = (a.flags & CILQR_FLAG_FAITHFUL_ITERS) != 0;
-  const size_t lds_fast = core_lds_bytes(a.N, a.kp.n_samples, !faithful) + extra;
-  const size_t lds_general = core_lds_bytes(a.N, a.kp.n_samples, false) + extra;
-  if (lds_general > 64 * 1024) {  // long horizons: opt in to more than the default 64 KiB of dynamic LDS (the CU has 160 KiB)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cilqr_solve_kernel<DIAG, TAB, false, UNC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_general);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cilqr_solve_kernel<DIAG, TAB, true, UNC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_general);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((cilqr_solve_kernel<DIAG, TAB, false, UNC>), dim3(a.B), dim3(WAVE), lds_fast, stream, a);
-  hipLaunchKernelGGL((cilqr_solve_kernel<DIAG, TAB, true, UNC>), dim3(a.B), dim3(WAVE), lds_general, stream, a);
-  return hipGetLastError();
-}
-// The two-wavefront kernel (table in LDS, no map, early exit) with the GENERAL kernel of the one-wavefront family behind it.
-template <bool DIAG>
-hipError_t launch_two_wavefronts(const SolveArgs& a, size_t tab_bytes, hipStream_t stream) {
-  const size_t lds_fast = core_lds_bytes(a.N, a.kp.n_samples, true) + tab_bytes + ((((size_t)a.N + 1) & ~(size_t)1) + PAIR_CTL) * sizeof(double);
-  const size_t lds_general = core_lds_bytes(a.N, a.kp.n_samples, false) + tab_bytes;
-  hipLaunchKernelGGL((cilqr_solve_pair_kernel<DIAG>), dim3(a.B), dim3(2 * WAVE), lds_fast, stream, a);
-  hipLaunchKernelGGL((cilqr_solve_kernel<DIAG, 1, true, false>), dim3(a.B), dim3(WAVE), lds_general, stream, a);
-  return hipGetLastError();
-}
-// The shared-phase-L kernel (table in LDS, early exit, N ≤ 127; with or without an uncertainty map) with the GENERAL kernel of the
-// one-wavefront family behind it.
-template <int W, bool LONG, bool DIAG, bool UNC>
-hipError_t launch_shared_L(const SolveArgs& a, size_t tab_bytes, hipStream_t stream) {
-  const size_t lds_fast = core_lds_bytes(a.N, a.kp.n_samples, true) + tab_bytes +
-                          ((((size_t)((W - 1) + (UNC ? 1 : 0)) * 5 * a.N + 1) & ~(size_t)1) + 4) * sizeof(double);
-  const size_t lds_general = core_lds_bytes(a.N, a.kp.n_samples, false) + tab_bytes;
-  if (lds_fast > 64 * 1024 || lds_general > 64 * 1024) {  // few solves per CU with large tables: more than the default 64 KiB of dynamic LDS
-    const int want = (int)(lds_fast > lds_general ? lds_fast : lds_general);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cilqr_solve_share_kernel<W, LONG, DIAG, UNC>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cilqr_solve_kernel<DIAG, 1, true, UNC>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((cilqr_solve_share_kernel<W, LONG, DIAG, UNC>), dim3(a.B), dim3(W * WAVE), lds_fast, stream, a);
-  hipLaunchKernelGGL((cilqr_solve_kernel<DIAG, 1, true, UNC>), dim3(a.B), dim3(WAVE), lds_general, stream, a);
-  return hipGetLastError();
-}
-template <bool DIAG, bool UNC>
-hipError_t launch_shared_L_by_shape(const SolveArgs& a, size_t tab_bytes, hipStream_t stream) {
-  if (a.N > WAVE) return launch_shared_L<2, true, DIAG, UNC>(a, tab_bytes, stream);
-  if (a.pair == 3 && (UNC || a.M >= 2)) return launch_shared_L<3, false, DIAG, UNC>(a, tab_bytes, stream);
-  return launch_shared_L<2, false, DIAG, UNC>(a, tab_bytes, stream);
-}
-template <bool DIAG, int TAB>
-hipError_t launch_pair(const SolveArgs& a, size_t extra, hipStream_t stream) {
-  return a.unc.layer ? launch_pair_unc<DIAG, TAB, true>(a, extra, stream) : launch_pair_unc<DIAG, TAB, false>(a, extra, stream);
+template <typename F>
+hipError_t with_bools(bool b1, bool b2, F&& f) {
+  return with_bool(b1, [&](auto c1) { return with_bool(b2, [&](auto c2) { return f(c1, c2); }); });
 }
 
 }  // namespace
-
-size_t solve_lds_bytes(int N, int n_samples) { return core_lds_bytes(N, n_samples, false); }  // the larger of the two layouts
-// Static obstacles: the table stays in LDS while a workgroup stays within 32 KiB (≥ 5 solves resident per CU of 160 KiB).  (M = 0: an empty table fits)
-// `budget` (bytes; 0: those 32 KiB): what a workgroup may take where fewer solves than that share a CU — a batch of at most four solves
-// per CU leaves each of them a quarter of the CU's LDS, and the table in LDS is worth more than the residency nobody uses
-// (cilqr_api.cpp, lds_table_budget).
-bool solve_table_in_lds(int N, int M, int n_samples, int budget) {
-  return solve_lds_bytes(N, n_samples) + (size_t)M * TABF * N * sizeof(double) <= (size_t)(budget > 0 ? budget : 32 * 1024);
-}
-// … and whether a solve of this shape can take the shared-phase-L kernel (cilqr_solve_share_kernel): table in LDS, at most two steps per lane
-bool solve_share_applies(int N, int M, int n_samples, int budget) { return N < 2 * WAVE && solve_table_in_lds(N, M, n_samples, budget); }
-
-size_t solve_sampled_lds_bytes(int n_obs, int n_samples) {
-  return ((size_t)n_obs * n_samples * OFFF + (size_t)2 * n_obs) * sizeof(double);  // offset records + rmax + constant-shape flags
-}
-size_t solve_sampled_tab_doubles(int n_obs, int N) { return (size_t)n_obs * NOMF * N; }
 
 // Dispatch order for the next call: solve indices sorted by pass count, descending (counting sort, one workgroup; ties in any
 // order — every permutation gives the same results, the order only decides which solves start first).
@@ -2172,51 +2095,46 @@ hipError_t launch_quu_inverse(int n, const double* q, const double* lamb, double
   return hipGetLastError();
 }
 
-hipError_t launch_solve_wave(const SolveArgs& a, hipStream_t stream) {
+// Carries out a plan (cilqr_wave_plan.h) and decides nothing: kernel, W, long_form, tab, map set, diagnostic buffer set name the two
+// instantiations; only the combinations a plan can hold are spelled out, so no others are built.  First the plan's kernel with W wavefronts
+// per solve, then the GENERAL kernel; beyond the default 64 KiB of dynamic LDS (long horizons, or few solves per CU with large tables:
+// the CU has 160 KiB) both have their limit raised first.
+hipError_t launch_solve_wave(const SolveArgs& a, const WavePlan& p, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
-  const size_t lds = solve_lds_bytes(a.N, a.kp.n_samples);  // the larger layout: limits and the table decision hold for both kernels
-  const size_t tab_bytes = (size_t)a.M * TABF * a.N * sizeof(double);
-  const bool tab_lds = a.n_samples == 0 && solve_table_in_lds(a.N, a.M, a.kp.n_samples, a.tab_budget);
-  if (a.n_samples > 0) {  // sampled obstacles: offset records in LDS, nominal records in the global workspace
-    const size_t extra = solve_sampled_lds_bytes(a.M, a.n_samples);
-    if (lds + extra > SOLVE_LDS_MAX) return hipErrorInvalidValue;  // checked by the caller
-    if (a.split >= 2 && a.N <= WAVE && a.M >= a.split && (a.flags & CILQR_FLAG_FAITHFUL_ITERS) == 0) {
-      // a.split wavefronts per solve share phase L (cilqr_solve_split_kernel); the GENERAL kernel of the one-wavefront family behind
-      const int W = a.split >= 4 ? 4 : 2;
-      const bool unc = a.unc.layer != nullptr;
-      const size_t lds_fast = core_lds_bytes(a.N, a.kp.n_samples, true) + extra + ((((size_t)((W - 1) + (unc ? 1 : 0)) * 5 * a.N + 1) & ~(size_t)1) + 2) * sizeof(double);
-      const size_t lds_general = core_lds_bytes(a.N, a.kp.n_samples, false) + extra;
-      if (lds_fast <= 64 * 1024 && lds_general <= 64 * 1024) {
-#define CILQR_SPLIT_LAUNCH(WW, DD, UU)                                                                                          \
-  hipLaunchKernelGGL((cilqr_solve_split_kernel<WW, DD, UU>), dim3(a.B), dim3(WW * WAVE), lds_fast, stream, a);                 \
-  hipLaunchKernelGGL((cilqr_solve_kernel<DD, 2, true, UU>), dim3(a.B), dim3(WAVE), lds_general, stream, a);
-        if (a.diag) {
-          if (unc) { if (W == 4) { CILQR_SPLIT_LAUNCH(4, true, true) } else { CILQR_SPLIT_LAUNCH(2, true, true) } }
-          else { if (W == 4) { CILQR_SPLIT_LAUNCH(4, true, false) } else { CILQR_SPLIT_LAUNCH(2, true, false) } }
-        } else {
-          if (unc) { if (W == 4) { CILQR_SPLIT_LAUNCH(4, false, true) } else { CILQR_SPLIT_LAUNCH(2, false, true) } }
-          else { if (W == 4) { CILQR_SPLIT_LAUNCH(4, false, false) } else { CILQR_SPLIT_LAUNCH(2, false, false) } }
-        }
-#undef CILQR_SPLIT_LAUNCH
-        return hipGetLastError();
-      }
-    }
-    return a.diag ? launch_pair<true, 2>(a, extra, stream) : launch_pair<false, 2>(a, extra, stream);
-  }
-  if (lds > SOLVE_LDS_MAX) return hipErrorInvalidValue;  // checked by the caller
-  const size_t extra = tab_lds ? tab_bytes : 0;
-  if (tab_lds && a.pair == 1 && !a.unc.layer && (a.flags & CILQR_FLAG_FAITHFUL_ITERS) == 0)
-    return a.diag ? launch_two_wavefronts<true>(a, tab_bytes, stream) : launch_two_wavefronts<false>(a, tab_bytes, stream);
-  if (a.pair >= 2 && a.n_samples == 0 && solve_share_applies(a.N, a.M, a.kp.n_samples, a.tab_budget) && (a.flags & CILQR_FLAG_FAITHFUL_ITERS) == 0) {
-    if (a.unc.layer) return a.diag ? launch_shared_L_by_shape<true, true>(a, tab_bytes, stream) : launch_shared_L_by_shape<false, true>(a, tab_bytes, stream);
-    return a.diag ? launch_shared_L_by_shape<true, false>(a, tab_bytes, stream) : launch_shared_L_by_shape<false, false>(a, tab_bytes, stream);
-  }
-  if (!tab_lds && a.obs_shared) {  // one scene for the batch, table in the workspace: its one table, read by both kernels
-    const hipError_t e = launch_obstacle_table(a, stream);
-    if (e != hipSuccess) return e;
-  }
-  if (a.diag) return tab_lds ? launch_pair<true, 1>(a, extra, stream) : launch_pair<true, 0>(a, extra, stream);
-  return tab_lds ? launch_pair<false, 1>(a, extra, stream) : launch_pair<false, 0>(a, extra, stream);
+  if (p.too_large) return hipErrorInvalidValue;  // checked by the caller
+  if (p.shared_table)  // one scene for the batch, table in the workspace: its one table, read by both kernels
+    if (const hipError_t e = launch_obstacle_table(a, stream)) return e;
+  using Kernel = void (*)(SolveArgs);
+  const auto go = [&](Kernel fast, Kernel general) {
+    const size_t want = p.lds_fast > p.lds_general ? p.lds_fast : p.lds_general;
+    hipError_t e = hipSuccess;
+    for (Kernel k : {fast, general})
+      if (want > SOLVE_LDS_DEFAULT && e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+    void* args[] = {const_cast<SolveArgs*>(&a)};
+    if (e == hipSuccess) e = hipLaunchKernel(reinterpret_cast<const void*>(fast), dim3(a.B), dim3(p.W * WAVE), args, p.lds_fast, stream);
+    if (e == hipSuccess) e = hipLaunchKernel(reinterpret_cast<const void*>(general), dim3(a.B), dim3(WAVE), args, p.lds_general, stream);
+    return e;
+  };
+  const bool diag = a.diag != nullptr, unc = a.unc.layer != nullptr;
+  if (p.kernel == WavePlan::SPLIT)
+    return with_bools(diag, unc, [&](auto d, auto u) {
+      return p.W == 4 ? go(cilqr_solve_split_kernel<4, d.value, u.value>, cilqr_solve_kernel<d.value, 2, true, u.value>)
+                      : go(cilqr_solve_split_kernel<2, d.value, u.value>, cilqr_solve_kernel<d.value, 2, true, u.value>);
+    });
+  if (p.tab == 2)  // sampled obstacles on one wavefront
+    return with_bools(diag, unc, [&](auto d, auto u) { return go(cilqr_solve_kernel<d.value, 2, false, u.value>, cilqr_solve_kernel<d.value, 2, true, u.value>); });
+  if (p.kernel == WavePlan::PAIR)  // (never with a map)
+    return with_bool(diag, [&](auto d) { return go(cilqr_solve_pair_kernel<d.value>, cilqr_solve_kernel<d.value, 1, true, false>); });
+  if (p.kernel == WavePlan::SHARE)
+    return with_bools(unc, diag, [&](auto u, auto d) {
+      if (p.long_form) return go(cilqr_solve_share_kernel<2, true, d.value, u.value>, cilqr_solve_kernel<d.value, 1, true, u.value>);
+      return p.W == 3 ? go(cilqr_solve_share_kernel<3, false, d.value, u.value>, cilqr_solve_kernel<d.value, 1, true, u.value>)
+                      : go(cilqr_solve_share_kernel<2, false, d.value, u.value>, cilqr_solve_kernel<d.value, 1, true, u.value>);
+    });
+  return with_bool(diag, [&](auto d) {  // static obstacles on one wavefront
+    return p.tab == 1 ? with_bool(unc, [&](auto u) { return go(cilqr_solve_kernel<d.value, 1, false, u.value>, cilqr_solve_kernel<d.value, 1, true, u.value>); })
+                      : with_bool(unc, [&](auto u) { return go(cilqr_solve_kernel<d.value, 0, false, u.value>, cilqr_solve_kernel<d.value, 0, true, u.value>); });
+  });
 }
 
 }  // namespace cilqr
