@@ -23,6 +23,10 @@
  *   LocalPlanner::get_local_plan(_coeffs) I/LocalPlanner.cpp:25-117 cilqr_local_plan (host pre-step),
  *                                                                cilqr_local_plan_batch(_device) (B candidates on the device)
  *   LocalCostmap::odomCallback warp loop M/src/local_costmap.cpp:242-264 cilqr_warp_costmap(_device)
+ *   LocalCostmap::bondingBoxHandle      M/src/local_costmap.cpp:860-922  cilqr_boxes_to_polygons (corner arithmetic, host) +
+ *                                                                cilqr_rasterize_polygons(_device); fused into the warp and the
+ *                                                                frame: cilqr_warp_costmap_polygons_device,
+ *                                                                cilqr_costmap_frame_polygons_device
  *   thrust_propagateUncertainty     M/src/arbitrary_transformation.cu:8-157  cilqr_blur_costmap(_device)
  *   (none: batch min-cost selection is new)      cilqr_argmin_device, cilqr_argmin_global_device (RCCL),
  *                                                                cilqr_create_multi / cilqr_multi_solve_batch
@@ -59,6 +63,8 @@ extern "C" {
 #define CILQR_MAX_HORIZON 384  /* per-solve arrays of the LDS-resident family at the default sample count: 98 KiB of 160 */
 #define CILQR_ABI_VERSION 2
 #define CILQR_COMM_ID_BYTES 128 /* an RCCL ncclUniqueId, carried opaquely */
+#define CILQR_MAX_POLYGONS 1024        /* obstacle polygons per rasterisation call */
+#define CILQR_MAX_POLYGON_VERTICES 16  /* vertices per polygon (at least 3) */
 
 /* Field-for-field POD mirror of class Parameters (I/Parameters.h:5-91) — only the fields the
  * constructor initialises (I/Parameters.cpp:6-74) — plus the two constants iLQR::iLQR sets
@@ -496,6 +502,46 @@ int cilqr_costmap_frame_device(cilqr_handle* h, void* stream, const float* globa
                                const cilqr_map_geom* vehicle_geom, double vx, double vy, double vtheta, const float* bbox,
                                double sigma_x, double sigma_y, double sigma_theta, float* vehicle_layer,
                                float* uncertainty_layer, int8_t* occupancy_out, int64_t* n_out_of_range_dev);
+
+/* --- obstacle bounding boxes (LocalCostmap::bondingBoxHandle, M/src/local_costmap.cpp:860-922) ------------------------- */
+/* The corner arithmetic of bondingBoxHandle (:866-913), on the host (host libm, no fused multiply-add), expression for
+ * expression: a box is kept iff sqrt(dx^2 + dy^2) <= max_distance from (own_x, own_y) (:870-875; reference 100.0); its sizes
+ * grow by `inflate` (:880-881; reference 0.2) and are halved (:885-886); the corners (+,+) (+,-) (-,-) (-,+) (:889-893) are turned
+ * by the box's yaw and moved to its position (:899-900), then taken into the vehicle frame (own_x, own_y, own_yaw) (:903-904).
+ * boxes: [n][5] = (x, y, yaw, size_x, size_y) in the planning frame — the caller applies the message's sign flips (posY =
+ * -pose.position.y, yaw = -pose.orientation.z, :867,:882).  vertices: [n][4][2] out, the kept boxes packed in order, WITHOUT
+ * the repeated closing vertex the reference adds (:913; it changes no cell).  *n_kept: number of boxes kept.  Needs no device. */
+int cilqr_boxes_to_polygons(int n, const double* boxes, double own_x, double own_y, double own_yaw, double inflate,
+                            double max_distance, double* vertices, int32_t* n_kept);
+/* The PolygonIterator loop of bondingBoxHandle (:916-919, called at :232) for n_polygons polygons of n_vertices vertices each: a cell takes
+ * `value` iff Polygon::isInside(cell centre) (G/grid_map_core/src/Polygon.cpp:32-44) holds for at least one polygon — for
+ * i = 0..V-1, j = i-1 (mod V) a crossing counts when (y_i > p_y) != (y_j > p_y) && p_x < (x_j - x_i) * (p_y - y_i) / (y_j - y_i) + x_i,
+ * inside when the count is odd; fp64 in that order, IEEE division, no contraction, on the centre the warp computes.
+ * clear != 0: every other cell becomes NaN (the layer setGeometry has just cleared, :213); clear == 0: every other
+ * cell is left untouched, so calls accumulate.  vertices: HOST [n_polygons][n_vertices][2] in the layer's frame, read before the
+ * call returns; a repeated closing vertex is allowed and changes nothing.  0 <= n_polygons <= CILQR_MAX_POLYGONS,
+ * 3 <= n_vertices <= CILQR_MAX_POLYGON_VERTICES, every vertex finite — otherwise CILQR_ERR_ARG (checked before the handle is
+ * touched).  layer: g.rows*g.cols float32 column-major.
+ * One difference from the iterator is possible in principle and was not seen in 40 359 cells compared against it: the iterator
+ * walks the submap of the polygon's vertex bounding box, so a centre inside the polygon but within rounding of that box's edge
+ * could fall outside the submap and stay unmarked there; here it is marked. */
+int cilqr_rasterize_polygons_device(cilqr_handle* h, void* stream, const cilqr_map_geom* g, int n_polygons, int n_vertices,
+                                    const double* vertices, float value, int clear, float* layer);
+int cilqr_rasterize_polygons(cilqr_handle* h, const cilqr_map_geom* g, int n_polygons, int n_vertices, const double* vertices,
+                             float value, int clear, float* layer);
+/* cilqr_warp_costmap_device with bbox = cilqr_rasterize_polygons_device(dst_geom, ..., value 100, clear 1), bit for bit and
+ * including the out-of-range counter (counted before the override) — but no bbox layer is written or read: the
+ * warp kernel tests the polygons itself.  vertices: HOST, read before the call returns. */
+int cilqr_warp_costmap_polygons_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* src_geom, float* dst,
+                                       const cilqr_map_geom* dst_geom, double vx, double vy, double vtheta, int n_polygons,
+                                       int n_vertices, const double* vertices, int64_t* n_out_of_range_dev);
+/* cilqr_costmap_frame_device with the polygons in place of the bbox layer (the warp above, then blur and OccupancyGrid): the
+ * whole of odomCallback from the odometry message and the tracked vehicles to the published grid. */
+int cilqr_costmap_frame_polygons_device(cilqr_handle* h, void* stream, const float* global_layer, const cilqr_map_geom* global_geom,
+                                        const cilqr_map_geom* vehicle_geom, double vx, double vy, double vtheta, int n_polygons,
+                                        int n_vertices, const double* vertices, double sigma_x, double sigma_y, double sigma_theta,
+                                        float* vehicle_layer, float* uncertainty_layer, int8_t* occupancy_out,
+                                        int64_t* n_out_of_range_dev);
 
 /* setGeometry(Length(lx,ly), res, Position(px,py)) size/length rule (G/grid_map_core/src/GridMap.cpp:45-62). */
 int cilqr_map_geom_set(cilqr_map_geom* g, double len_x, double len_y, double res, double pos_x, double pos_y);

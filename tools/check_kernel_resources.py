@@ -5,6 +5,10 @@ registers — and the production instantiations must not spill vector registers 
 one-wavefront sampled kernel to 257 + 1 registers unnoticed: −7 % at B = 4096, −20 % at B = 8192.
 
     python tools/check_kernel_resources.py [path/to/cilqr_solve.o]      exit code 1 and a listing on any violation
+    python tools/check_kernel_resources.py --map OBJECT...              the costmap kernels' rules (check_map) instead
+
+The costmap kernels (warp, polygon rasteriser) are latency chains of a few microseconds: they use no scratch memory, spill
+nothing, and stay within 128 vector registers so that a SIMD holds at least four of their wavefronts.
 """
 import os
 import re
@@ -59,7 +63,33 @@ def check(notes):
     return bad
 
 
+def check_map(notes):
+    """Violations among the costmap kernels of one object: scratch memory, spills, more than 128 vector registers."""
+    bad = []
+    for name, r in sorted(notes.items()):
+        if r["scratch"] or r["vgpr_spill"] or r["sgpr_spill"]:
+            bad.append((name, r, "uses scratch memory or spills registers"))
+        if r["vgpr"] + r["agpr"] > 128:
+            bad.append((name, r, "more than 128 vector registers: fewer than four wavefronts per SIMD"))
+    return bad
+
+
+def main_map(objs):
+    rc = 0
+    for obj in objs:
+        notes = kernel_notes(obj)
+        bad = check_map(notes)
+        print("%d map kernels checked in %s: %d violation(s)" % (len(notes), os.path.relpath(obj, ROOT), len(bad)))
+        for name, r, why in bad:
+            print("  %s\n    %s\n    %s" % (name, r, why))
+        if bad or not notes:
+            rc = 1
+    return rc
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--map":
+        return main_map(sys.argv[2:])
     obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "uncertainty-aware-cilqr-for-trajectory-optimization_amd", "build", "cilqr_solve.o")
     notes = kernel_notes(obj)
     bad = check(notes)

@@ -24,6 +24,8 @@ ABI_SYMBOLS = (
     "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_map_geom_set",
     "cilqr_occupancy_to_layer", "cilqr_occupancy_to_layer_device", "cilqr_layer_to_occupancy", "cilqr_layer_to_occupancy_device",
     "cilqr_costmap_frame_device",
+    "cilqr_boxes_to_polygons", "cilqr_rasterize_polygons", "cilqr_rasterize_polygons_device", "cilqr_warp_costmap_polygons_device",
+    "cilqr_costmap_frame_polygons_device",
     "cilqr_set_uncertainty_map", "cilqr_set_uncertainty_map_device", "cilqr_clear_uncertainty_map", "cilqr_debug_uncertainty_cost",
     "cilqr_comm_unique_id", "cilqr_comm_init_rank", "cilqr_comm_destroy", "cilqr_comm_size", "cilqr_argmin_global_device", "cilqr_debug_select",
     "cilqr_create_multi", "cilqr_multi_destroy", "cilqr_multi_device_count", "cilqr_multi_handle", "cilqr_multi_solve_batch",
@@ -204,6 +206,30 @@ def map_geom(len_x, len_y, res, pos_x, pos_y):
     _check(lib().cilqr_map_geom_set(C.byref(g), C.c_double(len_x), C.c_double(len_y), C.c_double(res),
                                     C.c_double(pos_x), C.c_double(pos_y)))
     return g
+
+
+def boxes_to_polygons(boxes, own_x, own_y, own_yaw, inflate=0.2, max_distance=100.0):
+    """`cilqr_boxes_to_polygons` (bondingBoxHandle's corner arithmetic, host only).  boxes: (n, 5) = (x, y, yaw, size_x, size_y) in the
+    planning frame.  Returns the (n_kept, 4, 2) corners of the boxes within max_distance, in the vehicle frame."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 5)
+    out = np.zeros((boxes.shape[0], 4, 2))
+    kept = C.c_int32(0)
+    _check(lib().cilqr_boxes_to_polygons(int(boxes.shape[0]), boxes.ctypes.data_as(_dp), C.c_double(own_x), C.c_double(own_y),
+                                         C.c_double(own_yaw), C.c_double(inflate), C.c_double(max_distance), out.ctypes.data_as(_dp),
+                                         C.byref(kept)))
+    return out[:kept.value].copy()
+
+
+def _polygons(vertices):
+    """(n, V, 2) float64 C-contiguous vertices -> (array, n, V); an empty list of polygons is (0, V, 2) or just empty (V = 4)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    if v.ndim != 3:
+        if v.size:
+            raise CilqrError("polygons must have shape (n, V, 2), not %s" % (v.shape,))
+        v = v.reshape(0, 4, 2)
+    if v.shape[2] != 2:
+        raise CilqrError("polygons must have shape (n, V, 2), not %s" % (v.shape,))
+    return v, int(v.shape[0]), int(v.shape[1])
 
 
 def _np64(a):
@@ -490,6 +516,41 @@ class Solver:
                                                C.byref(dst_geom), C.c_double(vx), C.c_double(vy), C.c_double(vtheta),
                                                _vp(bbox), _vp(n_oob)))
 
+
+    # ---- obstacle polygons ----
+    def rasterize_polygons(self, geom, vertices, value=100.0, layer=None):
+        """vertices: (n, V, 2) in the layer's frame.  layer None: a fresh layer, NaN outside the polygons (clear); otherwise the
+        (rows, cols) float32 layer to accumulate into (its other cells are kept).  Returns the F-ordered layer."""
+        v, n, V = _polygons(vertices)
+        clear = layer is None
+        out = np.zeros((geom.rows, geom.cols), dtype=np.float32, order="F") if clear else np.array(layer, dtype=np.float32, order="F")
+        assert out.shape == (geom.rows, geom.cols)
+        _check(lib().cilqr_rasterize_polygons(self._h, C.byref(geom), n, V, v.ctypes.data_as(_dp), C.c_float(value), int(clear),
+                                              out.ctypes.data_as(_fp)))
+        return out
+
+    def rasterize_polygons_device(self, stream, geom, vertices, layer, value=100.0, clear=True):
+        """layer: device address of rows*cols float32 (column-major)."""
+        v, n, V = _polygons(vertices)
+        _check(lib().cilqr_rasterize_polygons_device(self._h, _vp(stream), C.byref(geom), n, V, v.ctypes.data_as(_dp), C.c_float(value),
+                                                     int(bool(clear)), _vp(layer)))
+
+    def warp_costmap_polygons_device(self, stream, src, src_geom, dst, dst_geom, vx, vy, vtheta, vertices, n_oob=0):
+        """`warp_costmap_device` whose override comes from the polygons ((n, V, 2), destination frame) instead of a bbox layer."""
+        v, n, V = _polygons(vertices)
+        _check(lib().cilqr_warp_costmap_polygons_device(self._h, _vp(stream), _vp(src), C.byref(src_geom), _vp(dst), C.byref(dst_geom),
+                                                        C.c_double(vx), C.c_double(vy), C.c_double(vtheta), n, V, v.ctypes.data_as(_dp),
+                                                        _vp(n_oob)))
+
+    def costmap_frame_polygons_device(self, stream, global_layer, global_geom, vehicle_geom, vx, vy, vtheta, vertices, sigma_x, sigma_y,
+                                      sigma_theta, vehicle_layer, uncertainty_layer, occupancy_out=0, n_oob=0):
+        """`costmap_frame_device` with the obstacle polygons ((n, V, 2), vehicle frame) in place of the bbox layer."""
+        v, n, V = _polygons(vertices)
+        _check(lib().cilqr_costmap_frame_polygons_device(self._h, _vp(stream), _vp(global_layer), C.byref(global_geom),
+                                                         C.byref(vehicle_geom), C.c_double(vx), C.c_double(vy), C.c_double(vtheta), n, V,
+                                                         v.ctypes.data_as(_dp), C.c_double(sigma_x), C.c_double(sigma_y),
+                                                         C.c_double(sigma_theta), _vp(vehicle_layer), _vp(uncertainty_layer),
+                                                         _vp(occupancy_out), _vp(n_oob)))
 
     def warp_costmap_batch_device(self, stream, src, src_geom, dst, dst_geom, poses, bbox=0, n_oob=0):
         """poses: (K, 3) host array of (vx, vy, vtheta); dst: device address of K destination layers back to back."""

@@ -8,6 +8,7 @@
 
 #include <new>
 #include <string>
+#include <vector>
 
 #include "cilqr_internal.h"
 
@@ -257,6 +258,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   h->comm_ranks = 1;
   if (err == hipSuccess) err = dmalloc(&h->d_oob, (size_t)1);
   if (err == hipSuccess) err = dmalloc(&h->d_poses, (size_t)8 * 1024 * 4);
+  if (err == hipSuccess) err = dmalloc(&h->d_polys, (size_t)8 * cilqr::POLYGON_TABLE_DOUBLES);
   if (err == hipSuccess) err = dmalloc(&h->d_occ_steps, (size_t)8 * 128);
   if (err == hipSuccess) {  // scratch of cilqr_local_plan_batch for max_batch candidates and a 1024-waypoint path
     void* unused = nullptr;
@@ -282,7 +284,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -732,6 +734,171 @@ int cilqr_costmap_frame_device(cilqr_handle* h, void* stream, const float* globa
   cilqr::BlurArgs a;
   a.src = vehicle_layer; a.out = uncertainty_layer; a.count_out = nullptr;
   a.occ_out = occupancy_out; a.occ_min = 0.0f; a.occ_den = 100.0f - 0.0f;  // toOccupancyGrid(..., 0, 100, ...) (M/src/local_costmap.cpp:298)
+  a.g = *vehicle_geom; a.index = 0;
+  a.sin_t = sin(vtheta); a.cos_t = cos(vtheta);
+  a.sigma_x = sigma_x; a.sigma_y = sigma_y; a.sigma_theta = sigma_theta;
+  HIP_TRY(cilqr::launch_blur(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+namespace {
+// The argument rules the polygon entry points share; they need no handle and no device.
+int check_polygons(const char* who, const cilqr_map_geom* g, int n, int V, const double* vertices) {
+  if (!g) return fail(CILQR_ERR_ARG, "%s: null geometry", who);
+  if (n < 0 || n > CILQR_MAX_POLYGONS) return fail(CILQR_ERR_ARG, "%s: n_polygons=%d outside [0,%d]", who, n, CILQR_MAX_POLYGONS);
+  if (V < 3 || V > CILQR_MAX_POLYGON_VERTICES) return fail(CILQR_ERR_ARG, "%s: n_vertices=%d outside [3,%d]", who, V, CILQR_MAX_POLYGON_VERTICES);
+  if (n > 0 && !vertices) return fail(CILQR_ERR_ARG, "%s: null vertices", who);
+  for (size_t k = 0; k < (size_t)n * V * 2; ++k)
+    if (!__builtin_isfinite(vertices[k])) return fail(CILQR_ERR_ARG, "%s: vertex %zu of polygon %zu is not finite", who, (k / 2) % V, k / (2 * (size_t)V));
+  if (g->rows < 1 || g->cols < 1 || !(g->res > 0.0)) return fail(CILQR_ERR_ARG, "%s: bad geometry", who);
+  return CILQR_OK;
+}
+
+// Cells of one axis whose centres c0 - res*i can lie in [lo, hi], widened by one cell and clamped to [0, cells): false if none.
+bool cell_range(double c0, double res, int cells, double lo, double hi, int32_t& first, int32_t& last) {
+  const double a = floor((c0 - hi) / res) - 1.0, b = ceil((c0 - lo) / res) + 1.0;
+  if (!(a <= (double)(cells - 1)) || !(b >= 0.0)) return false;
+  first = (int32_t)fmax(a, 0.0);
+  last = (int32_t)fmin(b, (double)(cells - 1));
+  return true;
+}
+
+// The device table of costmap_polygons.hpp for the polygons whose vertex bounding box can touch the map, into the next of the
+// handle's slots on stream s.  The ranges are a cull and nothing else: dropping a polygon here is the same cull, made once.
+int upload_polygons(cilqr_handle* h, hipStream_t s, const cilqr_map_geom& g, int n, int V, const double* vertices, cilqr::PolygonTable& t) {
+  std::vector<int32_t> ranges;
+  std::vector<int> kept;
+  const double cx0 = g.pos_x + (0.5 * g.len_x - 0.5 * g.res), cy0 = g.pos_y + (0.5 * g.len_y - 0.5 * g.res);
+  for (int p = 0; p < n; ++p) {
+    const double* v = vertices + (size_t)p * V * 2;
+    double xlo = v[0], xhi = v[0], ylo = v[1], yhi = v[1];
+    for (int k = 1; k < V; ++k) {
+      xlo = fmin(xlo, v[2 * k]); xhi = fmax(xhi, v[2 * k]);
+      ylo = fmin(ylo, v[2 * k + 1]); yhi = fmax(yhi, v[2 * k + 1]);
+    }
+    int32_t r[4];
+    if (!cell_range(cx0, g.res, g.rows, xlo, xhi, r[0], r[1]) || !cell_range(cy0, g.res, g.cols, ylo, yhi, r[2], r[3])) continue;
+    ranges.insert(ranges.end(), r, r + 4);
+    kept.push_back(p);
+  }
+  t.n = (int32_t)kept.size();
+  t.V = V;
+  double* d_table = h->d_polys + cilqr::POLYGON_TABLE_DOUBLES * (h->poly_slot++ & 7);
+  t.table = d_table;
+  if (t.n == 0) return CILQR_OK;
+  std::vector<double> table((size_t)t.n * (2 + 2 * V));
+  memcpy(table.data(), ranges.data(), ranges.size() * sizeof(int32_t));
+  for (int q = 0; q < t.n; ++q) memcpy(&table[2 * (size_t)t.n + (size_t)q * 2 * V], vertices + (size_t)kept[q] * V * 2, sizeof(double) * 2 * V);
+  // (pageable source: the runtime has staged the copy by the time the call returns, as with the pose tables below)
+  HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  return CILQR_OK;
+}
+
+int grow(float** p, size_t* cap, size_t n) {
+  if (n <= *cap) return CILQR_OK;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr; *cap = 0;
+  HIP_TRY(dmalloc(p, n));
+  *cap = n;
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_boxes_to_polygons(int n, const double* boxes, double own_x, double own_y, double own_yaw, double inflate, double max_distance,
+                            double* vertices, int32_t* n_kept) {
+#pragma clang fp contract(off)
+  if (n < 0 || !n_kept || (n > 0 && (!boxes || !vertices))) return fail(CILQR_ERR_ARG, "cilqr_boxes_to_polygons: bad argument");
+  int32_t kept = 0;
+  for (int b = 0; b < n; ++b) {
+    const double posX = boxes[5 * b], posY = boxes[5 * b + 1], yaw = boxes[5 * b + 2];
+    const double dx = posX - own_x, dy = posY - own_y;
+    const double distance = sqrt(dx * dx + dy * dy);  // M/src/local_costmap.cpp:870 (std::pow(d, 2) is d*d)
+    if (!(distance <= max_distance)) continue;         // :875
+    const double half_x = (boxes[5 * b + 3] + inflate) / 2.0, half_y = (boxes[5 * b + 4] + inflate) / 2.0;  // :880-886
+    const double corners[4][2] = {{half_x, half_y}, {half_x, -half_y}, {-half_x, -half_y}, {-half_x, half_y}};  // :889-893
+    double* out = vertices + (size_t)kept * 8;
+    for (int c = 0; c < 4; ++c) {  // :897-910
+      const double global_x = cos(yaw) * corners[c][0] - sin(yaw) * corners[c][1] + posX;
+      const double global_y = sin(yaw) * corners[c][0] + cos(yaw) * corners[c][1] + posY;
+      out[2 * c] = cos(own_yaw) * (global_x - own_x) + sin(own_yaw) * (global_y - own_y);
+      out[2 * c + 1] = -sin(own_yaw) * (global_x - own_x) + cos(own_yaw) * (global_y - own_y);
+    }
+    ++kept;
+  }
+  *n_kept = kept;
+  return CILQR_OK;
+}
+
+int cilqr_rasterize_polygons_device(cilqr_handle* h, void* stream, const cilqr_map_geom* g, int n_polygons, int n_vertices,
+                                    const double* vertices, float value, int clear, float* layer) {
+  int rc = check_polygons("cilqr_rasterize_polygons", g, n_polygons, n_vertices, vertices);
+  if (rc) return rc;
+  if (!h || !layer) return fail(CILQR_ERR_ARG, "cilqr_rasterize_polygons: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->device));
+  cilqr::PolygonTable t;
+  rc = upload_polygons(h, s, *g, n_polygons, n_vertices, vertices, t);
+  if (rc) return rc;
+  HIP_TRY(cilqr::launch_rasterize_polygons(t, *g, value, clear != 0, layer, s));
+  return CILQR_OK;
+}
+
+int cilqr_rasterize_polygons(cilqr_handle* h, const cilqr_map_geom* g, int n_polygons, int n_vertices, const double* vertices,
+                             float value, int clear, float* layer) {
+  int rc = check_polygons("cilqr_rasterize_polygons", g, n_polygons, n_vertices, vertices);
+  if (rc) return rc;
+  if (!h || !layer) return fail(CILQR_ERR_ARG, "cilqr_rasterize_polygons: null argument");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t cells = (size_t)g->rows * g->cols;
+  rc = grow(&h->d_dst, &h->dst_cap, cells);
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+  if (!clear) HIP_TRY(hipMemcpyAsync(h->d_dst, layer, cells * sizeof(float), hipMemcpyHostToDevice, s));
+  rc = cilqr_rasterize_polygons_device(h, s, g, n_polygons, n_vertices, vertices, value, clear, h->d_dst);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(layer, h->d_dst, cells * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return CILQR_OK;
+}
+
+int cilqr_warp_costmap_polygons_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* sg, float* dst,
+                                       const cilqr_map_geom* dg, double vx, double vy, double vtheta, int n_polygons, int n_vertices,
+                                       const double* vertices, int64_t* n_oob_dev) {
+  int rc = check_polygons("cilqr_warp_costmap_polygons", dg, n_polygons, n_vertices, vertices);
+  if (rc) return rc;
+  if (!h || !src || !sg || !dst) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_polygons: null argument");
+  if (sg->rows < 1 || sg->cols < 1 || !(sg->res > 0.0)) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_polygons: bad geometry");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->device));
+  cilqr::PolygonTable t;
+  rc = upload_polygons(h, s, *dg, n_polygons, n_vertices, vertices, t);
+  if (rc) return rc;
+  cilqr::WarpArgs a;
+  a.src = src; a.dst = dst; a.bbox = nullptr;
+  a.n_oob = (unsigned long long*)n_oob_dev;
+  a.sg = *sg; a.dg = *dg;
+  a.vx = vx; a.vy = vy;
+  a.sin_t = sin(vtheta);  // host libm, as the reference (M/src/local_costmap.cpp:201-202)
+  a.cos_t = cos(vtheta);
+  if (n_oob_dev) HIP_TRY(hipMemsetAsync(n_oob_dev, 0, sizeof(int64_t), s));
+  HIP_TRY(cilqr::launch_warp_polygons(a, t, s));
+  return CILQR_OK;
+}
+
+int cilqr_costmap_frame_polygons_device(cilqr_handle* h, void* stream, const float* global_layer, const cilqr_map_geom* global_geom,
+                                        const cilqr_map_geom* vehicle_geom, double vx, double vy, double vtheta, int n_polygons,
+                                        int n_vertices, const double* vertices, double sigma_x, double sigma_y, double sigma_theta,
+                                        float* vehicle_layer, float* uncertainty_layer, int8_t* occupancy_out, int64_t* n_out_of_range_dev) {
+  int rc = check_polygons("cilqr_costmap_frame_polygons", vehicle_geom, n_polygons, n_vertices, vertices);
+  if (rc) return rc;
+  if (!h || !global_layer || !global_geom || !vehicle_layer || !uncertainty_layer)
+    return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_polygons: null argument");
+  rc = cilqr_warp_costmap_polygons_device(h, stream, global_layer, global_geom, vehicle_layer, vehicle_geom, vx, vy, vtheta, n_polygons,
+                                          n_vertices, vertices, n_out_of_range_dev);
+  if (rc) return rc;
+  cilqr::BlurArgs a;  // as cilqr_costmap_frame_device
+  a.src = vehicle_layer; a.out = uncertainty_layer; a.count_out = nullptr;
+  a.occ_out = occupancy_out; a.occ_min = 0.0f; a.occ_den = 100.0f - 0.0f;
   a.g = *vehicle_geom; a.index = 0;
   a.sin_t = sin(vtheta); a.cos_t = cos(vtheta);
   a.sigma_x = sigma_x; a.sigma_y = sigma_y; a.sigma_theta = sigma_theta;

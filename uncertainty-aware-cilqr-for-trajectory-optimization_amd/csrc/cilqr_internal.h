@@ -134,6 +134,18 @@ struct WarpBatchArgs {
 };
 hipError_t launch_warp_batch(const WarpBatchArgs& a, int K, hipStream_t stream);
 
+// Obstacle polygons on the device (layout: costmap_polygons.hpp): n polygons of V vertices that can touch the map.
+struct PolygonTable {
+  const double* table;
+  int32_t n, V;
+};
+constexpr size_t POLYGON_TABLE_DOUBLES = (size_t)CILQR_MAX_POLYGONS * (2 + 2 * CILQR_MAX_POLYGON_VERTICES);  // one full table
+// Polygon::isInside of every cell centre (costmap_polygons.hip): value inside any polygon; elsewhere NaN (clear) or untouched.
+hipError_t launch_rasterize_polygons(const PolygonTable& t, const cilqr_map_geom& g, float value, bool clear, float* layer, hipStream_t stream);
+// launch_warp with the override decided by the polygons themselves (a.bbox is ignored): a covered cell takes 100, as if a.bbox
+// were launch_rasterize_polygons(t, a.dg, 100, clear) — no such layer is written or read.
+hipError_t launch_warp_polygons(const WarpArgs& a, const PolygonTable& t, hipStream_t stream);
+
 struct BlurArgs {
   const float* src;
   float* out;

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "cilqr_internal.h"
+#include "costmap_polygons.hpp"
 
 namespace cilqr {
 
@@ -78,7 +79,13 @@ __device__ __forceinline__ double estimate_guard(const cilqr_map_geom& sg, const
   return mag * 0x1p-40 + 0x1p-1000;
 }
 
-__global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i, int n_tiles) {
+// what bondingBoxHandle writes into bounding_box_map (M/src/local_costmap.cpp:918): above the 90 of the override test (:260)
+constexpr float POLYGON_VALUE = 100.0f;
+
+// POLY: the override is the polygon test itself (costmap_polygons.hpp) on the destination cell's centre instead of a read of the
+// bbox layer; the other instantiation does not look at the table and is the kernel as it was before there were polygons.
+template <bool POLY>
+__global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i, int n_tiles, const double* __restrict__ table, int n_polygons, int V) {
 #pragma clang fp contract(off)
   // XCD-aware remap: workgroup ids are dealt round-robin over the 8 XCDs (speed only, never correctness).
   int bid = blockIdx.x;
@@ -102,6 +109,14 @@ __global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i,
   const double step_x = 4.0 * a.dg.res * a.sin_t, step_y = -4.0 * a.dg.res * a.cos_t;
   double t0x = 0.0, t0y = 0.0;
   unsigned long long oob = 0;
+  unsigned hit[TILE_J / 4];
+  if constexpr (POLY) {  // before any lane leaves: the cull ballots over the whole wavefront
+    const double px[1] = {Cx};
+    double py[TILE_J / 4];
+#pragma unroll
+    for (int jj = 0; jj < TILE_J / 4; ++jj) py[jj] = (a.dg.pos_y + off_dy) + a.dg.res * (double)(-(tj * TILE_J + wave + 4 * jj));
+    polygons_cover<1, TILE_J / 4>(table, n_polygons, V, ti * TILE_I, ti * TILE_I + TILE_I - 1, tj * TILE_J, tj * TILE_J + TILE_J - 1, px, py, hit);
+  }
 #pragma unroll
   for (int jj = 0; jj < TILE_J / 4; ++jj) {
     const int j = tj * TILE_J + wave + 4 * jj;
@@ -126,7 +141,9 @@ __global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i,
       v = __builtin_nanf("");
       ++oob;
     }
-    if (a.bbox) {
+    if constexpr (POLY) {
+      if (hit[jj]) v = POLYGON_VALUE;
+    } else if (a.bbox) {
       const float bb = a.bbox[lin];
       if (bb > 90.0f) v = bb;
     }
@@ -153,8 +170,9 @@ constexpr int VT_J = 8;    // columns per tile: wave w handles j = w, w + 4
 // the rotation) takes its value without another gather.
 // REUSE: that reuse — worth 6-8 % where frames are many (K ≥ 4); for ONE frame, which is a latency chain and not work, the
 // comparison in front of every gather costs 1.5 µs of 6 (rocprofv3: 7.7 against 6.2 µs), so single frames run without it.
-template <int ROWS, bool REUSE>
-__global__ __launch_bounds__(NTHREADS) void warp_batch_kernel(WarpBatchArgs a, int tiles_i) {
+// POLY: as warp_kernel's.
+template <int ROWS, bool REUSE, bool POLY>
+__global__ __launch_bounds__(NTHREADS) void warp_batch_kernel(WarpBatchArgs a, int tiles_i, const double* __restrict__ table, int n_polygons, int V) {
 #pragma clang fp contract(off)
   constexpr int VT_I = 64 * ROWS;  // rows per tile
   const int frame = blockIdx.y;
@@ -174,6 +192,15 @@ __global__ __launch_bounds__(NTHREADS) void warp_batch_kernel(WarpBatchArgs a, i
   const double step_x = -a.dg.res * cos_t, step_y = -a.dg.res * sin_t;
   unsigned long long oob = 0;
   const bool in_i = i0 < drows;  // drows is a multiple of ROWS on this path: a lane's rows are all inside or all outside
+  unsigned hit[VT_J / 4];
+  if constexpr (POLY) {  // before any lane leaves: the cull ballots over the whole wavefront
+    double px[ROWS], py[VT_J / 4];
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) px[k] = (a.dg.pos_x + off_dx) + a.dg.res * (double)(-(i0 + k));
+#pragma unroll
+    for (int jj = 0; jj < VT_J / 4; ++jj) py[jj] = (a.dg.pos_y + off_dy) + a.dg.res * (double)(-(tj * VT_J + wave + 4 * jj));
+    polygons_cover<ROWS, VT_J / 4>(table, n_polygons, V, ti * VT_I, ti * VT_I + VT_I - 1, tj * VT_J, tj * VT_J + VT_J - 1, px, py, hit);
+  }
 #pragma unroll
   for (int jj = 0; jj < VT_J / 4; ++jj) {
     const int j = tj * VT_J + wave + 4 * jj;
@@ -211,7 +238,11 @@ __global__ __launch_bounds__(NTHREADS) void warp_batch_kernel(WarpBatchArgs a, i
     const size_t lin = (size_t)j * drows + i0;
 #pragma unroll
     for (int q = 0; q < ROWS / 4; ++q) {
-      if (a.bbox) {
+      if constexpr (POLY) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if ((hit[jj] >> (4 * q + k)) & 1) v[4 * q + k] = POLYGON_VALUE;
+      } else if (a.bbox) {
         const float4 bb = *reinterpret_cast<const float4*>(a.bbox + lin + 4 * q);
         if (bb.x > 90.0f) v[4 * q] = bb.x;
         if (bb.y > 90.0f) v[4 * q + 1] = bb.y;
@@ -355,14 +386,15 @@ hipError_t launch_warp_batch(const WarpBatchArgs& a, int K, hipStream_t stream) 
   // Four rows per lane.  Eight (CILQR_WARP_ROWS=8: one exact cell in eight) measured slower at every K — 2.83 against 2.41 µs per
   // frame at K = 16, 10.6 against 8.4 µs for one frame (profiles/r03_warp.txt): half the workgroups, and the arithmetic was not
   // what bounds the kernel.
+  const double* no_table = nullptr;
   const int rows8 = getenv("CILQR_WARP_ROWS") ? atoi(getenv("CILQR_WARP_ROWS")) : 4;
   if (a.dg.rows % 8 == 0 && rows8 == 8) {
     const int tiles_i = (a.dg.rows + 511) / 512;
-    hipLaunchKernelGGL((warp_batch_kernel<8, true>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i);
+    hipLaunchKernelGGL((warp_batch_kernel<8, true, false>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i, no_table, 0, 0);
   } else {
     const int tiles_i = (a.dg.rows + 255) / 256;
-    if (K >= 4) hipLaunchKernelGGL((warp_batch_kernel<4, true>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i);
-    else hipLaunchKernelGGL((warp_batch_kernel<4, false>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i);
+    if (K >= 4) hipLaunchKernelGGL((warp_batch_kernel<4, true, false>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i, no_table, 0, 0);
+    else hipLaunchKernelGGL((warp_batch_kernel<4, false, false>), dim3(tiles_i * tiles_j, K), dim3(NTHREADS), 0, stream, a, tiles_i, no_table, 0, 0);
   }
   return hipGetLastError();
 }
@@ -378,7 +410,24 @@ hipError_t launch_warp(const WarpArgs& a, hipStream_t stream) {
   const int tiles_i = (a.dg.rows + TILE_I - 1) / TILE_I, tiles_j = (a.dg.cols + TILE_J - 1) / TILE_J;
   const int n_tiles = tiles_i * tiles_j;
   if (n_tiles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(warp_kernel, dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles);
+  hipLaunchKernelGGL(warp_kernel<false>, dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, (const double*)nullptr, 0, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_warp_polygons(const WarpArgs& a, const PolygonTable& t, hipStream_t stream) {
+  if (a.dg.rows % 4 == 0) {  // as launch_warp: one frame of the four-rows-per-lane kernel, its pose in the arguments
+    WarpBatchArgs b;
+    b.src = a.src; b.dst = a.dst; b.bbox = nullptr; b.n_oob = a.n_oob; b.poses = nullptr;
+    b.pose0[0] = a.vx; b.pose0[1] = a.vy; b.pose0[2] = a.sin_t; b.pose0[3] = a.cos_t;
+    b.sg = a.sg; b.dg = a.dg;
+    const int tiles_i = (a.dg.rows + 255) / 256, tiles_j = (a.dg.cols + VT_J - 1) / VT_J;
+    hipLaunchKernelGGL((warp_batch_kernel<4, false, true>), dim3(tiles_i * tiles_j, 1), dim3(NTHREADS), 0, stream, b, tiles_i, t.table, t.n, t.V);
+    return hipGetLastError();
+  }
+  const int tiles_i = (a.dg.rows + TILE_I - 1) / TILE_I, tiles_j = (a.dg.cols + TILE_J - 1) / TILE_J;
+  const int n_tiles = tiles_i * tiles_j;
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(warp_kernel<true>, dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, t.table, t.n, t.V);
   return hipGetLastError();
 }
 
