@@ -20,6 +20,8 @@
  *   GridMapRosConverter::from/toOccupancyGrid G/grid_map_ros/src/GridMapRosConverter.cpp:225-307
  *                                                                cilqr_occupancy_to_layer / cilqr_layer_to_occupancy(_device)
  *   LocalCostmap::odomCallback (one frame) M/src/local_costmap.cpp:172-305 cilqr_costmap_frame_device
+ *   odomCallback for the node's K pose-noise candidates I/ilqr_uncertainty_node.cpp:82-113
+ *                                                                cilqr_costmap_frame_batch_device (K frames, two launches)
  *   LocalPlanner::get_local_plan(_coeffs) I/LocalPlanner.cpp:25-117 cilqr_local_plan (host pre-step),
  *                                                                cilqr_local_plan_batch(_device) (B candidates on the device)
  *   LocalCostmap::odomCallback warp loop M/src/local_costmap.cpp:242-264 cilqr_warp_costmap(_device)
@@ -27,7 +29,8 @@
  *                                                                cilqr_rasterize_polygons(_device); fused into the warp and the
  *                                                                frame: cilqr_warp_costmap_polygons_device,
  *                                                                cilqr_costmap_frame_polygons_device
- *   thrust_propagateUncertainty     M/src/arbitrary_transformation.cu:8-157  cilqr_blur_costmap(_device)
+ *   thrust_propagateUncertainty     M/src/arbitrary_transformation.cu:8-157  cilqr_blur_costmap(_device),
+ *                                                                cilqr_blur_costmap_batch_device (K headings per launch)
  *   (none: batch min-cost selection is new)      cilqr_argmin_device, cilqr_argmin_global_device (RCCL),
  *                                                                cilqr_create_multi / cilqr_multi_solve_batch
  *
@@ -478,6 +481,14 @@ int cilqr_blur_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* 
                        double sigma_y, double sigma_theta, float* out, int32_t* count_out);
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
                               double sigma_x, double sigma_y, double sigma_theta, float* out, int32_t* count_out);
+/* K blurs in one launch.  Frame k = cilqr_blur_costmap_device(src + k*src_stride, g, index, vthetas[k], sigmas) written to
+ * out + k*rows*cols (count_out likewise, may be NULL), bit for bit.  src_stride in floats: 0 = one layer under K headings, else
+ * >= rows*cols.  vthetas: HOST [K], read before the call returns.  1 <= K <= 1024.  A null handle or pointer, K outside that
+ * range, a bad geometry, index < 0 or a src_stride that is negative or between 1 and rows*cols - 1: CILQR_ERR_ARG, checked before
+ * the handle or the device is touched.  K = 1 is the single-frame call. */
+int cilqr_blur_costmap_batch_device(cilqr_handle* h, void* stream, const float* src, int64_t src_stride, const cilqr_map_geom* g,
+                                    int index, int K, const double* vthetas, double sigma_x, double sigma_y, double sigma_theta,
+                                    float* out, int32_t* count_out);
 
 /* --- wire formats either side of the costmap path --------------------------------- */
 /* GridMapRosConverter::fromOccupancyGrid's data loop (G/grid_map_ros/src/GridMapRosConverter.cpp:259-266, called at
@@ -502,6 +513,17 @@ int cilqr_costmap_frame_device(cilqr_handle* h, void* stream, const float* globa
                                const cilqr_map_geom* vehicle_geom, double vx, double vy, double vtheta, const float* bbox,
                                double sigma_x, double sigma_y, double sigma_theta, float* vehicle_layer,
                                float* uncertainty_layer, int8_t* occupancy_out, int64_t* n_out_of_range_dev);
+/* K odometry-callback frames in two launches (one warp, one blur with the OccupancyGrid), for vehicle maps of any size: the node's
+ * pose-noise candidates (I/ilqr_uncertainty_node.cpp:82-113).  Frame k = cilqr_costmap_frame_device for poses[k] = (vx, vy,
+ * vtheta), bit for bit in all outputs.  vehicle_layers, uncertainty_layers: [K][rows*cols] floats.  occupancy_out: [K][rows*cols]
+ * int8 or NULL.  n_out_of_range_dev: K int64 (zeroed by the call) or NULL.  bbox: one layer shared by the frames, or NULL.
+ * poses: HOST [K][3], read before the call returns.  1 <= K <= 1024; arguments are checked as cilqr_blur_costmap_batch_device's,
+ * before the handle or the device is touched; K = 1 is the single-frame call.  uncertainty_layers is what
+ * cilqr_set_uncertainty_map_device takes with layer_stride = rows*cols and poses = the same K poses on the device. */
+int cilqr_costmap_frame_batch_device(cilqr_handle* h, void* stream, const float* global_layer, const cilqr_map_geom* global_geom,
+                                     const cilqr_map_geom* vehicle_geom, int K, const double* poses, const float* bbox,
+                                     double sigma_x, double sigma_y, double sigma_theta, float* vehicle_layers,
+                                     float* uncertainty_layers, int8_t* occupancy_out, int64_t* n_out_of_range_dev);
 
 /* --- obstacle bounding boxes (LocalCostmap::bondingBoxHandle, M/src/local_costmap.cpp:860-922) ------------------------- */
 /* The corner arithmetic of bondingBoxHandle (:866-913), on the host (host libm, no fused multiply-add), expression for

@@ -21,9 +21,9 @@ EXIT_TOLERANCE, EXIT_LAMBDA_MAX, EXIT_MAX_ITER, EXIT_NUMERIC = 0, 1, 2, 3
 ABI_SYMBOLS = (
     "cilqr_params_default", "cilqr_abi_version", "cilqr_device_count", "cilqr_last_error", "cilqr_default_control_seq",
     "cilqr_local_plan", "cilqr_local_plan_batch", "cilqr_local_plan_batch_device", "cilqr_create", "cilqr_destroy", "cilqr_host_alloc", "cilqr_host_free", "cilqr_solve_batch", "cilqr_solve_batch_device", "cilqr_solve_batch_obstacles", "cilqr_solve_batch_obstacles_device", "cilqr_solve_batch_sampled", "cilqr_solve_batch_sampled_device",
-    "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_map_geom_set",
+    "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_blur_costmap_batch_device", "cilqr_map_geom_set",
     "cilqr_occupancy_to_layer", "cilqr_occupancy_to_layer_device", "cilqr_layer_to_occupancy", "cilqr_layer_to_occupancy_device",
-    "cilqr_costmap_frame_device",
+    "cilqr_costmap_frame_device", "cilqr_costmap_frame_batch_device",
     "cilqr_boxes_to_polygons", "cilqr_rasterize_polygons", "cilqr_rasterize_polygons_device", "cilqr_warp_costmap_polygons_device",
     "cilqr_costmap_frame_polygons_device",
     "cilqr_set_uncertainty_map", "cilqr_set_uncertainty_map_device", "cilqr_clear_uncertainty_map", "cilqr_debug_uncertainty_cost",
@@ -601,3 +601,21 @@ class Solver:
         _check(lib().cilqr_blur_costmap_device(self._h, _vp(stream), _vp(src), C.byref(geom), int(index), C.c_double(vtheta),
                                                C.c_double(sigma_x), C.c_double(sigma_y), C.c_double(sigma_theta), _vp(out),
                                                _vp(count_out)))
+
+    def blur_costmap_batch_device(self, stream, src, geom, vthetas, sigma_x, sigma_y, sigma_theta, out, index=0, count_out=0, src_stride=0):
+        """vthetas: (K,) host array; src: device address of one layer (src_stride 0) or of K layers src_stride floats apart; out (and
+        count_out): device addresses of K layers back to back."""
+        vthetas = _np64(vthetas).reshape(-1)
+        _check(lib().cilqr_blur_costmap_batch_device(self._h, _vp(stream), _vp(src), C.c_int64(src_stride), C.byref(geom), int(index),
+                                                     int(vthetas.shape[0]), _p(vthetas), C.c_double(sigma_x), C.c_double(sigma_y),
+                                                     C.c_double(sigma_theta), _vp(out), _vp(count_out)))
+
+    def costmap_frame_batch_device(self, stream, global_layer, global_geom, vehicle_geom, poses, sigma_x, sigma_y, sigma_theta,
+                                   vehicle_layers, uncertainty_layers, occupancy_out=0, bbox=0, n_oob=0):
+        """poses: (K, 3) host array of (vx, vy, vtheta); vehicle_layers, uncertainty_layers (and occupancy_out, n_oob): device
+        addresses of K layers (K counters) back to back; bbox: one device layer shared by the frames."""
+        poses = _np64(poses).reshape(-1, 3)
+        _check(lib().cilqr_costmap_frame_batch_device(self._h, _vp(stream), _vp(global_layer), C.byref(global_geom), C.byref(vehicle_geom),
+                                                      int(poses.shape[0]), _p(poses), _vp(bbox), C.c_double(sigma_x), C.c_double(sigma_y),
+                                                      C.c_double(sigma_theta), _vp(vehicle_layers), _vp(uncertainty_layers),
+                                                      _vp(occupancy_out), _vp(n_oob)))

@@ -939,6 +939,29 @@ int cilqr_warp_costmap_device(cilqr_handle* h, void* stream, const float* src, c
   return CILQR_OK;
 }
 
+namespace {
+// The [K][4] device table (vx, vy, sin theta, cos theta) of the batched warp and blur kernels, into the next of the handle's slots
+// on stream s.  Frame k's vx, vy and theta are rows[k*stride + ix / iy / it] (ix < 0: no translation, zeros).
+int upload_pose_table(cilqr_handle* h, hipStream_t s, int K, const double* rows, int stride, int ix, int iy, int it, double** d_out) {
+  double table[1024 * 4];
+  for (int k = 0; k < K; ++k) {
+    const double* r = rows + (size_t)stride * k;
+    table[4 * k] = ix < 0 ? 0.0 : r[ix];
+    table[4 * k + 1] = ix < 0 ? 0.0 : r[iy];
+    table[4 * k + 2] = sin(r[it]);  // host libm, as the reference (M/src/local_costmap.cpp:201-202)
+    table[4 * k + 3] = cos(r[it]);
+  }
+  // eight device slots in rotation keep the tables of calls still in flight (on other streams) apart; the copy itself is
+  // staged by the runtime before this call returns (pageable source)
+  double* d_table = h->d_poses + (size_t)1024 * 4 * (h->pose_slot++ & 7);
+  HIP_TRY(hipMemcpyAsync(d_table, table, sizeof(double) * 4 * K, hipMemcpyHostToDevice, s));
+  *d_out = d_table;
+  return CILQR_OK;
+}
+
+bool good_geom(const cilqr_map_geom* g) { return g->rows >= 1 && g->cols >= 1 && g->res > 0.0; }
+}  // namespace
+
 int cilqr_warp_costmap_batch_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* sg, float* dst,
                                     const cilqr_map_geom* dg, int K, const double* poses, const float* bbox, int64_t* n_oob_dev) {
   if (!h || !src || !sg || !dst || !dg || !poses) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_batch: null argument");
@@ -947,26 +970,11 @@ int cilqr_warp_costmap_batch_device(cilqr_handle* h, void* stream, const float* 
     return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_batch: bad geometry");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->device));
-  if (dg->rows % 4 != 0) {  // the 16-byte-store kernel needs rows in fours: frame by frame with the single-frame kernel
-    const size_t cells = (size_t)dg->rows * dg->cols;
-    for (int k = 0; k < K; ++k) {
-      int rc = cilqr_warp_costmap_device(h, stream, src, sg, dst + (size_t)k * cells, dg, poses[3 * k], poses[3 * k + 1], poses[3 * k + 2], bbox,
-                                         n_oob_dev ? n_oob_dev + k : nullptr);
-      if (rc) return rc;
-    }
-    return CILQR_OK;
-  }
-  double table[1024 * 4];
-  for (int k = 0; k < K; ++k) {
-    table[4 * k] = poses[3 * k];
-    table[4 * k + 1] = poses[3 * k + 1];
-    table[4 * k + 2] = sin(poses[3 * k + 2]);  // host libm, as the reference (M/src/local_costmap.cpp:201-202)
-    table[4 * k + 3] = cos(poses[3 * k + 2]);
-  }
-  // eight device slots in rotation keep the tables of calls still in flight (on other streams) apart; the copy itself is
-  // staged by the runtime before this call returns (pageable source)
-  double* d_table = h->d_poses + (size_t)1024 * 4 * (h->pose_slot++ & 7);
-  HIP_TRY(hipMemcpyAsync(d_table, table, sizeof(double) * 4 * K, hipMemcpyHostToDevice, s));
+  if (dg->rows % 4 != 0 && K == 1)  // rows not in fours: one frame is the single-frame kernel's, its pose in the arguments
+    return cilqr_warp_costmap_device(h, stream, src, sg, dst, dg, poses[0], poses[1], poses[2], bbox, n_oob_dev);
+  double* d_table = nullptr;
+  int rc = upload_pose_table(h, s, K, poses, 3, 0, 1, 2, &d_table);
+  if (rc) return rc;
   if (n_oob_dev) HIP_TRY(hipMemsetAsync(n_oob_dev, 0, sizeof(int64_t) * K, s));
   cilqr::WarpBatchArgs a;
   a.src = src; a.dst = dst; a.bbox = bbox;
@@ -974,6 +982,64 @@ int cilqr_warp_costmap_batch_device(cilqr_handle* h, void* stream, const float* 
   a.poses = d_table;
   a.sg = *sg; a.dg = *dg;
   HIP_TRY(cilqr::launch_warp_batch(a, K, s));
+  return CILQR_OK;
+}
+
+int cilqr_blur_costmap_batch_device(cilqr_handle* h, void* stream, const float* src, int64_t src_stride, const cilqr_map_geom* g,
+                                    int index, int K, const double* vthetas, double sigma_x, double sigma_y, double sigma_theta,
+                                    float* out, int32_t* count_out) {
+  if (!h || !src || !g || !vthetas || !out) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap_batch: null argument");
+  if (K < 1 || K > 1024) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap_batch: K=%d outside [1,1024]", K);
+  if (!good_geom(g) || index < 0) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap_batch: bad geometry");
+  const int64_t cells = (int64_t)g->rows * g->cols;
+  if (src_stride < 0 || (src_stride > 0 && src_stride < cells))
+    return fail(CILQR_ERR_ARG, "cilqr_blur_costmap_batch: src_stride=%lld is neither 0 nor >= rows*cols=%lld", (long long)src_stride, (long long)cells);
+  if (K == 1) return cilqr_blur_costmap_device(h, stream, src, g, index, vthetas[0], sigma_x, sigma_y, sigma_theta, out, count_out);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->device));
+  double* d_table = nullptr;
+  int rc = upload_pose_table(h, s, K, vthetas, 1, -1, -1, 0, &d_table);
+  if (rc) return rc;
+  cilqr::BlurArgs a;  // as cilqr_blur_costmap_device; sine and cosine come from the table
+  a.src = src; a.out = out; a.count_out = count_out;
+  a.occ_out = nullptr; a.occ_min = 0.0f; a.occ_den = 100.0f;
+  a.g = *g; a.index = index;
+  a.sin_t = 0.0; a.cos_t = 0.0;
+  a.sigma_x = sigma_x; a.sigma_y = sigma_y; a.sigma_theta = sigma_theta;
+  HIP_TRY(cilqr::launch_blur_batch(a, K, d_table, (long)src_stride, s));
+  return CILQR_OK;
+}
+
+int cilqr_costmap_frame_batch_device(cilqr_handle* h, void* stream, const float* global_layer, const cilqr_map_geom* global_geom,
+                                     const cilqr_map_geom* vehicle_geom, int K, const double* poses, const float* bbox,
+                                     double sigma_x, double sigma_y, double sigma_theta, float* vehicle_layers,
+                                     float* uncertainty_layers, int8_t* occupancy_out, int64_t* n_out_of_range_dev) {
+  if (!h || !global_layer || !global_geom || !vehicle_geom || !poses || !vehicle_layers || !uncertainty_layers)
+    return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: null argument");
+  if (K < 1 || K > 1024) return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: K=%d outside [1,1024]", K);
+  if (!good_geom(global_geom) || !good_geom(vehicle_geom)) return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: bad geometry");
+  if (K == 1)
+    return cilqr_costmap_frame_device(h, stream, global_layer, global_geom, vehicle_geom, poses[0], poses[1], poses[2], bbox, sigma_x, sigma_y,
+                                      sigma_theta, vehicle_layers, uncertainty_layers, occupancy_out, n_out_of_range_dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->device));
+  double* d_table = nullptr;  // one table for both launches: the warp reads all four entries of a row, the blur its sine and cosine
+  int rc = upload_pose_table(h, s, K, poses, 3, 0, 1, 2, &d_table);
+  if (rc) return rc;
+  if (n_out_of_range_dev) HIP_TRY(hipMemsetAsync(n_out_of_range_dev, 0, sizeof(int64_t) * K, s));
+  cilqr::WarpBatchArgs w;
+  w.src = global_layer; w.dst = vehicle_layers; w.bbox = bbox;
+  w.n_oob = (unsigned long long*)n_out_of_range_dev;
+  w.poses = d_table;
+  w.sg = *global_geom; w.dg = *vehicle_geom;
+  HIP_TRY(cilqr::launch_warp_batch(w, K, s));
+  cilqr::BlurArgs a;  // as cilqr_costmap_frame_device, frame k blurring the vehicle layer the warp has just written for it
+  a.src = vehicle_layers; a.out = uncertainty_layers; a.count_out = nullptr;
+  a.occ_out = occupancy_out; a.occ_min = 0.0f; a.occ_den = 100.0f - 0.0f;
+  a.g = *vehicle_geom; a.index = 0;
+  a.sin_t = 0.0; a.cos_t = 0.0;
+  a.sigma_x = sigma_x; a.sigma_y = sigma_y; a.sigma_theta = sigma_theta;
+  HIP_TRY(cilqr::launch_blur_batch(a, K, d_table, (long)vehicle_geom->rows * vehicle_geom->cols, s));
   return CILQR_OK;
 }
 

@@ -83,7 +83,7 @@ struct cilqr_handle {
   float *d_src, *d_dst, *d_bbox;
   size_t src_cap, dst_cap, bbox_cap;
   unsigned long long* d_oob;
-  double* d_poses;       // 8 slots x 1024 poses x 4 doubles: pose tables of cilqr_warp_costmap_batch_device calls in flight
+  double* d_poses;       // 8 slots x 1024 poses x 4 doubles: pose tables of the batched warp / blur / frame calls in flight
   unsigned pose_slot;
   double* d_polys;       // 8 slots x one full polygon table (costmap_polygons.hpp): tables of the polygon calls in flight
   unsigned poly_slot;

@@ -121,8 +121,8 @@ struct WarpArgs {
   double vx, vy, sin_t, cos_t;
 };
 hipError_t launch_warp(const WarpArgs& a, hipStream_t stream);
-// K frames per launch (dst rows must be a multiple of 4): poses [K][4] = (vx, vy, sin theta, cos theta) on the device,
-// destination frames back to back, n_oob [K] or null.
+// K frames per launch: poses [K][4] = (vx, vy, sin theta, cos theta) on the device, destination frames back to back, n_oob [K] or
+// null.  Rows in fours take the 16-byte-store kernel, any other row count the cell-by-cell kernel with a frame dimension.
 struct WarpBatchArgs {
   const float* src;
   float* dst;
@@ -157,6 +157,20 @@ struct BlurArgs {
   double sin_t, cos_t, sigma_x, sigma_y, sigma_theta;
 };
 hipError_t launch_blur(const BlurArgs& a, hipStream_t stream);
+// the argument block of a batched blur launch, and the kernel's argument type by instantiation (named at namespace scope so that
+// the kernels' demangled names carry no nested parentheses: tools/compare_kernel_isa.py cuts them at the parameter list)
+struct BlurBatchArgs {
+  BlurArgs a;
+  const double* poses;
+  long src_stride;
+};
+template <bool FRAMES>
+struct BlurKernelArgs { using type = BlurArgs; };
+template <>
+struct BlurKernelArgs<true> { using type = BlurBatchArgs; };
+// K frames per launch: frame k reads a.src + k*src_stride (floats), takes (sin, cos) from poses[4k+2], poses[4k+3] (device table,
+// the layout of WarpBatchArgs::poses; a.sin_t / a.cos_t are ignored) and writes a.out / a.occ_out / a.count_out + k*rows*cols.
+hipError_t launch_blur_batch(const BlurArgs& a, int K, const double* poses, long src_stride, hipStream_t stream);
 // OccupancyGrid <-> layer (costmap_occupancy.hip)
 hipError_t launch_occ_to_layer(const int8_t* occ, float* layer, long n, hipStream_t stream);
 // steps_ws: 102 floats of device workspace for the step table of large conversions (null: always the per-cell division)

@@ -157,10 +157,28 @@ __device__ __forceinline__ double inside_value_exact(double x_first, double y_fi
 // LPC lanes per destination cell.  One lane per cell fills the chip from ≈ 65 k cells; the node's own map has 15 000, which
 // leaves three quarters of the SIMDs idle while each lane walks its ellipse alone — there four adjacent lanes share a cell
 // (rows of the ellipse's box dealt round-robin, the three sums combined by two shuffles; summation order changes by that).
-template <int LPC>
-__global__ __launch_bounds__(256) void blur_kernel(BlurArgs a) {
+// FRAMES: K frames per launch, blockIdx.y = frame, as warp_batch_kernel: frame k reads src + k*src_stride, takes (sin, cos) from
+// entries 2 and 3 of row k of the [K][4] pose table (the warp's own table serves) and writes out / occ_out / count_out + k*cells.
+// LPC follows the PER-FRAME cell count (launch_blur_batch), so a frame's lanes, their rows and the order of its sums are the
+// single-frame launch's: every bit of every frame is.  The other instantiation takes BlurArgs alone and is the kernel as it was
+// before there were frames, its argument block included (the table and the stride travel behind the BlurArgs of a batch only).
+template <int LPC, bool FRAMES>
+__global__ __launch_bounds__(256) void blur_kernel(typename BlurKernelArgs<FRAMES>::type args) {
 #pragma clang fp contract(off)  // cell centres, ellipse box and row offsets as the reference's compiler forms them: no fma
+  BlurArgs& a = [&]() -> BlurArgs& {
+    if constexpr (FRAMES) return args.a;
+    else return args;
+  }();
   const long n = (long)a.g.rows * a.g.cols;
+  if constexpr (FRAMES) {
+    const long frame = blockIdx.y;
+    a.src += frame * args.src_stride;
+    a.out += frame * n;
+    if (a.occ_out) a.occ_out += frame * n;
+    if (a.count_out) a.count_out += frame * n;
+    a.sin_t = args.poses[4 * frame + 2];
+    a.cos_t = args.poses[4 * frame + 3];
+  }
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long lin = tid / LPC;
   const int sub = (int)(tid % LPC);
@@ -260,15 +278,33 @@ hipError_t launch_blur_ellipse(int n, const double* abc, double* out, hipStream_
   return hipGetLastError();
 }
 
+// lanes per cell by the cell count of ONE frame.  Measured on MI355X: 150×100 cells 55 µs with one lane per cell, 20.7 / 16.4 /
+// 17.4 µs with 4 / 8 / 16; 256² cells 101 µs against 58 µs with 4; from about a million cells one lane per cell already fills the chip
+static int blur_lanes_per_cell(long n) { return n <= 20000 ? 8 : n <= 300000 ? 4 : 1; }
+
 hipError_t launch_blur(const BlurArgs& a, hipStream_t stream) {
   const long n = (long)a.g.rows * a.g.cols;
   if (n <= 0) return hipSuccess;
-  // measured on MI355X: 150×100 cells 55 µs with one lane per cell, 20.7 / 16.4 / 17.4 µs with 4 / 8 / 16; 256² cells 101 µs
-  // against 58 µs with 4; from about a million cells one lane per cell already fills the chip
-  const int lpc = n <= 20000 ? 8 : n <= 300000 ? 4 : 1;
-  if (lpc == 8) hipLaunchKernelGGL(blur_kernel<8>, dim3((unsigned)((8 * n + 255) / 256)), dim3(256), 0, stream, a);
-  else if (lpc == 4) hipLaunchKernelGGL(blur_kernel<4>, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(blur_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  const int lpc = blur_lanes_per_cell(n);
+  if (lpc == 8) hipLaunchKernelGGL((blur_kernel<8, false>), dim3((unsigned)((8 * n + 255) / 256)), dim3(256), 0, stream, a);
+  else if (lpc == 4) hipLaunchKernelGGL((blur_kernel<4, false>), dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((blur_kernel<1, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// K frames in one launch (blur_kernel<LPC, true>).  The lanes-per-cell rule sees one frame's cells, not K times as many: a batch
+// of small frames fills the chip by itself, but fewer lanes per cell would change the order of the sums, and with it the last bit
+// of some cells, against the single-frame call.
+hipError_t launch_blur_batch(const BlurArgs& a, int K, const double* poses, long src_stride, hipStream_t stream) {
+  const long n = (long)a.g.rows * a.g.cols;
+  if (n <= 0 || K <= 0) return hipSuccess;
+  if (K > 65535 || !poses) return hipErrorInvalidValue;
+  const int lpc = blur_lanes_per_cell(n);
+  const dim3 grid((unsigned)((lpc * n + 255) / 256), (unsigned)K);
+  const BlurBatchArgs b{a, poses, src_stride};
+  if (lpc == 8) hipLaunchKernelGGL((blur_kernel<8, true>), grid, dim3(256), 0, stream, b);
+  else if (lpc == 4) hipLaunchKernelGGL((blur_kernel<4, true>), grid, dim3(256), 0, stream, b);
+  else hipLaunchKernelGGL((blur_kernel<1, true>), grid, dim3(256), 0, stream, b);
   return hipGetLastError();
 }
 

@@ -84,9 +84,20 @@ constexpr float POLYGON_VALUE = 100.0f;
 
 // POLY: the override is the polygon test itself (costmap_polygons.hpp) on the destination cell's centre instead of a read of the
 // bbox layer; the other instantiation does not look at the table and is the kernel as it was before there were polygons.
-template <bool POLY>
-__global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i, int n_tiles, const double* __restrict__ table, int n_polygons, int V) {
+// FRAMES: K frames per launch for destination maps of ANY row count (warp_batch_kernel needs rows in fours): blockIdx.y = frame,
+// its pose row k of the [K][4] device table (vx, vy, sin, cos), its cells at dst + k*cells, its counter n_oob + k; tiles, lanes
+// and per-cell arithmetic are the single frame's, so results and counters are too.  Without it `poses` is not looked at.
+template <bool POLY, bool FRAMES>
+__global__ __launch_bounds__(NTHREADS) void warp_kernel(WarpArgs a, int tiles_i, int n_tiles, const double* __restrict__ table, int n_polygons, int V,
+                                                        const double* __restrict__ poses) {
 #pragma clang fp contract(off)
+  if constexpr (FRAMES) {
+    const size_t frame = blockIdx.y;
+    const double* pose = poses + 4 * frame;  // (wave-uniform)
+    a.vx = pose[0]; a.vy = pose[1]; a.sin_t = pose[2]; a.cos_t = pose[3];
+    a.dst += frame * ((size_t)a.dg.rows * a.dg.cols);
+    if (a.n_oob) a.n_oob += frame;
+  }
   // XCD-aware remap: workgroup ids are dealt round-robin over the 8 XCDs (speed only, never correctness).
   int bid = blockIdx.x;
   {
@@ -367,7 +378,18 @@ __global__ __launch_bounds__(NTHREADS) void warp_tile_kernel(WarpBatchArgs a, in
 
 hipError_t launch_warp_batch(const WarpBatchArgs& a, int K, hipStream_t stream) {
   if (K <= 0) return hipSuccess;
-  if (a.dg.rows % 4 != 0) return hipErrorInvalidValue;  // the caller falls back to per-frame launches
+  if (a.dg.rows % 4 != 0) {  // no 16-byte stores: the cell-by-cell kernel with a frame dimension
+    if (!a.poses || K > 65535) return hipErrorInvalidValue;
+    WarpArgs w;
+    w.src = a.src; w.dst = a.dst; w.bbox = a.bbox; w.n_oob = a.n_oob;
+    w.sg = a.sg; w.dg = a.dg;
+    w.vx = w.vy = w.sin_t = w.cos_t = 0.0;  // (the kernel takes them from the table)
+    const int tiles_i = (a.dg.rows + TILE_I - 1) / TILE_I, tiles_j = (a.dg.cols + TILE_J - 1) / TILE_J;
+    const int n_tiles = tiles_i * tiles_j;
+    if (n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL((warp_kernel<false, true>), dim3(n_tiles, K), dim3(NTHREADS), 0, stream, w, tiles_i, n_tiles, (const double*)nullptr, 0, 0, a.poses);
+    return hipGetLastError();
+  }
   // The LDS-tiled kernel is an experiment, OFF unless CILQR_WARP_LDS=1: bit-exact, but slower than the gather kernel below at every
   // K (profiles/r03_warp.txt: 3.4 against 2.4 µs per frame at K = 16, 2.7 against 1.9 at K = 64) — the texture path's gathers from an
   // L2-resident patch were not what bounds the kernel, and the staging (box, loads, barrier, four workgroups' worth of LDS) is not free.
@@ -410,7 +432,7 @@ hipError_t launch_warp(const WarpArgs& a, hipStream_t stream) {
   const int tiles_i = (a.dg.rows + TILE_I - 1) / TILE_I, tiles_j = (a.dg.cols + TILE_J - 1) / TILE_J;
   const int n_tiles = tiles_i * tiles_j;
   if (n_tiles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(warp_kernel<false>, dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, (const double*)nullptr, 0, 0);
+  hipLaunchKernelGGL((warp_kernel<false, false>), dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, (const double*)nullptr, 0, 0, (const double*)nullptr);
   return hipGetLastError();
 }
 
@@ -427,7 +449,7 @@ hipError_t launch_warp_polygons(const WarpArgs& a, const PolygonTable& t, hipStr
   const int tiles_i = (a.dg.rows + TILE_I - 1) / TILE_I, tiles_j = (a.dg.cols + TILE_J - 1) / TILE_J;
   const int n_tiles = tiles_i * tiles_j;
   if (n_tiles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(warp_kernel<true>, dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, t.table, t.n, t.V);
+  hipLaunchKernelGGL((warp_kernel<true, false>), dim3(n_tiles), dim3(NTHREADS), 0, stream, a, tiles_i, n_tiles, t.table, t.n, t.V, (const double*)nullptr);
   return hipGetLastError();
 }
 
