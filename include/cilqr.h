@@ -33,6 +33,8 @@
  *                                                                cilqr_blur_costmap_batch_device (K headings per launch)
  *   (none: batch min-cost selection is new)      cilqr_argmin_device, cilqr_argmin_global_device (RCCL),
  *                                                                cilqr_create_multi / cilqr_multi_solve_batch
+ *   (none: the reference never compares candidates)          cilqr_score_batch(_device), cilqr_score_batch_sampled(_device):
+ *                                                                full cost, worst constraint, collision share of solved candidates
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -334,6 +336,61 @@ int cilqr_solve_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N
  * I/Constraints.cpp:50): writes {J_min, (double)index} to out_pair (device, 2 doubles).  The cross-GPU step
  * is cilqr_argmin_global_device below. */
 int cilqr_argmin_device(cilqr_handle* h, void* stream, int B, const double* J, double* out_pair);
+
+/* --- scoring solved candidates (new: the reference never compares candidates) --------------------------------------------
+ * J_out, the cost the pick above ranks by, is Constraints::get_J: tracking and control effort only.  The control barriers, the
+ * obstacle barriers and the uncertainty-map cost the solve descends along are not in it (the reference's get_J has them commented
+ * out, I/Constraints.cpp:553-557), so the cheapest J may belong to a trajectory that drives through an obstacle: the barriers are
+ * soft.  One launch after the solve evaluates, per solve, every term once and the constraint values themselves: */
+#define CILQR_SCORE_FIELDS 8
+typedef enum cilqr_score_field {
+  CILQR_SCORE_TRACK = 0,        /* Constraints::get_J(X, U), I/Constraints.cpp:534-561 */
+  CILQR_SCORE_CONTROL = 1,      /* sum over t < N of the four control barriers' VALUES q1*exp(q2*c), I/Constraints.cpp:67-78, 86-137 */
+  CILQR_SCORE_OBSTACLE = 2,     /* sum over t < N, m < M of weight_m * (front + rear barrier value), I/Obstacle.cpp:21-32, 39-112 */
+  CILQR_SCORE_UNCERTAINTY = 3,  /* w_uncertainty * sum over t < N of the map cost (the mean barrier value defined at
+                                   cilqr_set_uncertainty_map); exactly 0.0 with no map set */
+  CILQR_SCORE_MAX_C = 4,        /* max over t, m, both circles of c = 1 - d'Pd;  -HUGE_VAL when M == 0 */
+  CILQR_SCORE_MAX_C_ENTRY = 5,  /* (double)(m*N + t) of that maximum, the lowest such index on equal values; -1 when M == 0 */
+  CILQR_SCORE_MAX_CTRL = 6,     /* max over t of the four control constraint values (> 0: a bound is exceeded) */
+  CILQR_SCORE_COLLISION = 7     /* ordinary obstacles: 1.0 if MAX_C > 0 else 0.0;  sampled: max over (t, o) of the share of samples s
+                                   with c > 0 on either circle, a count / n_samples */
+} cilqr_score_field;
+/* cilqr_score_batch_device: device pointers, asynchronous on `stream`, like cilqr_solve_batch_obstacles_device (*obs is a host
+ * struct, read before the call returns; NULL only when M == 0).  X [B][4*(N+1)], U [B][2*N], poly [B][6], xplan_fl [B][2] as the
+ * solve takes and returns them; score [B][CILQR_SCORE_FIELDS]; total [B] or NULL.  cilqr_score_batch: host buffers, synchronous.
+ *   - States X[:, t], t = 0 … N-1, pair with obstacle column t: the steps Constraints::get_state_cost visits.  x_N carries no
+ *     cost, as in the reference.  No term depends on a heading error (the reference's state cost has no theta weight).
+ *   - Obstacle weights apply as in l_x: weight[b][m] through the strides of *obs, or p.w_obstacle when NULL; sample_weight for the
+ *     sampled call.
+ *   - The closest path point is the strict-< first minimum of the squared distance over all num_of_local_wpts*10 samples
+ *     (I/Constraints.cpp:43-56), found by a full scan.
+ *   - UNCERTAINTY is added while a map is set on the handle, with the layer and pose of the solve's index, as in the solve.
+ *   - total[b] = ((TRACK + CONTROL) + OBSTACLE) + UNCERTAINTY, summed in that order; NaN when COLLISION > max_collision or when any
+ *     of the four terms is not finite.  A NaN never wins cilqr_argmin_device / cilqr_argmin_global_device, which return index -1
+ *     when every candidate is rejected: hand them `total` in place of J_out to pick among the safe.  max_collision = 1.0 rejects
+ *     nothing on collision grounds, 0.0 rejects any contact (c > 0: an ego circle centre inside the inflated ellipse).
+ *   - The score of a solve is a function of that solve's inputs alone: bit-identical whatever B is, whatever the solve's index in
+ *     the batch and whatever strides address the same obstacle values.  (Sums run over a reduction tree fixed by (N, M); the
+ *     (max c, entry) reduction is lexicographic.)
+ *   - cilqr_score_batch_sampled(_device) takes the compact form of cilqr_solve_batch_sampled and equals the ordinary call on the
+ *     materialised obstacles m = o*n_samples + s, pose (x + dx, y + dy, v, theta + dtheta), weight sample_weight, BIT FOR BIT in
+ *     fields 0-6 (the sample pose is formed by those plain additions, not by the solve kernels' angle-addition shortcut).  Field 7
+ *     differs by definition: a share there, 0 or 1 for the ordinary call.
+ *   - Limits are those of cilqr_create: B <= max_batch, N <= max_horizon, M or n_obs*n_samples <= max_obstacles; beyond them, for
+ *     a negative stride or a NULL X, U, poly, xplan_fl or score: CILQR_ERR_ARG.  Nothing is allocated per call.  The sampled call
+ *     keeps one 4-byte counter per (t, o) on chip beside the path samples: where 16*num_of_local_wpts*10 + 16*N + 4*n_obs*N + 272
+ *     bytes exceed 64 KiB it returns CILQR_ERR_UNSUPPORTED (n_obs*N beyond about 15 000 at the default sample count). */
+int cilqr_score_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* poly,
+                             const double* xplan_fl, const cilqr_obstacles* obs, double max_collision, double* score, double* total);
+int cilqr_score_batch(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* poly,
+                      const double* xplan_fl, const cilqr_obstacles* obs, double max_collision, double* score, double* total);
+int cilqr_score_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
+                                     const double* nom_dim, const double* sample_offset, double sample_weight, double max_collision,
+                                     double* score, double* total);
+int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
+                              const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
+                              const double* sample_offset, double sample_weight, double max_collision, double* score, double* total);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

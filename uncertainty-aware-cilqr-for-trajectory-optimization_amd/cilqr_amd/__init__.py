@@ -16,6 +16,10 @@ NX, NU, POLY = 4, 2, 6
 FLAG_FAITHFUL_ITERS = 1
 FLAG_GENERAL_ONLY = 2
 EXIT_TOLERANCE, EXIT_LAMBDA_MAX, EXIT_MAX_ITER, EXIT_NUMERIC = 0, 1, 2, 3
+# `cilqr_score_field`: the columns of a score row
+SCORE_FIELDS = 8
+(SCORE_TRACK, SCORE_CONTROL, SCORE_OBSTACLE, SCORE_UNCERTAINTY, SCORE_MAX_C, SCORE_MAX_C_ENTRY, SCORE_MAX_CTRL,
+ SCORE_COLLISION) = range(SCORE_FIELDS)
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -30,6 +34,7 @@ ABI_SYMBOLS = (
     "cilqr_comm_unique_id", "cilqr_comm_init_rank", "cilqr_comm_destroy", "cilqr_comm_size", "cilqr_argmin_global_device", "cilqr_debug_select",
     "cilqr_create_multi", "cilqr_multi_destroy", "cilqr_multi_device_count", "cilqr_multi_handle", "cilqr_multi_solve_batch",
     "cilqr_shard_range", "cilqr_multi_uses_rccl", "cilqr_debug_fail_enqueue",
+    "cilqr_score_batch", "cilqr_score_batch_device", "cilqr_score_batch_sampled", "cilqr_score_batch_sampled_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -362,6 +367,62 @@ class Solver:
         _check(lib().cilqr_solve_batch_obstacles_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(x0), _vp(U), _vp(poly),
                                                         _vp(xplan_fl), C.byref(obs), _vp(X_out), _vp(J_out), _vp(iters_out),
                                                         _vp(status_out), C.c_uint32(flags)))
+
+    # ---- scoring solved candidates ----
+    def score_batch(self, N, X, U, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, max_collision=1.0):
+        """`cilqr_score_batch`: X (B, 4(N+1)), U (B, 2N) as a solve returns them, the obstacles in any of the shapes of
+        `obstacle_strides`.  Returns dict(score (B, SCORE_FIELDS), total (B,)); total is NaN where the collision share
+        exceeds max_collision or a term is not finite — hand it to `argmin_device` in place of J."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U = _np64(U).reshape(B, 2 * N)
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        M, obs = 0, None
+        if obs_pose is not None:
+            obs_pose, obs_dim, obs_weight = _np64(obs_pose), _np64(obs_dim), _np64(obs_weight)
+            M, bs, ms, ts, wbs = obstacle_strides(obs_pose.shape, obs_dim.shape, None if obs_weight is None else obs_weight.shape, B, N)
+            obs = Obstacles(obs_pose.ctypes.data, obs_dim.ctypes.data, None if obs_weight is None else obs_weight.ctypes.data,
+                            bs, ms, ts, wbs)
+        score, total = np.zeros((B, SCORE_FIELDS)), np.zeros(B)
+        _check(lib().cilqr_score_batch(self._h, B, int(N), int(M), _p(X), _p(U), _p(poly), _p(xplan_fl),
+                                       None if obs is None else C.byref(obs), C.c_double(max_collision), _p(score), _p(total)))
+        return dict(score=score, total=total)
+
+    def score_batch_device(self, stream, B, N, M, X, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, strides, score, total=0,
+                           max_collision=1.0):
+        """`cilqr_score_batch_device`: device addresses and strides as `solve_batch_obstacles_device`; score: B*8 doubles,
+        total: B doubles or 0."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None,
+                        int(obs_weight) if obs_weight else None, bs, ms, ts, wbs)
+        _check(lib().cilqr_score_batch_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(U), _vp(poly), _vp(xplan_fl),
+                                              C.byref(obs) if M else None, C.c_double(max_collision), _vp(score), _vp(total)))
+
+    def score_batch_sampled(self, N, X, U, poly, xplan_fl, nom_pose, nom_dim, offsets, weight, max_collision=1.0):
+        """`cilqr_score_batch_sampled`: the compact form of `solve_batch_sampled`; COLLISION is the largest share of an obstacle's
+        pose samples hit at one step."""
+        offsets = _np64(offsets)
+        B, n_obs, S = offsets.shape[0], offsets.shape[1], offsets.shape[2]
+        X = _np64(X).reshape(B, 4 * (N + 1))
+        U = _np64(U).reshape(B, 2 * N)
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        nom_pose = _np64(nom_pose).reshape(B, n_obs, 4 * N)
+        nom_dim = _np64(nom_dim).reshape(B, n_obs, 2 * N)
+        offsets = offsets.reshape(B, n_obs, S, 3)
+        score, total = np.zeros((B, SCORE_FIELDS)), np.zeros(B)
+        _check(lib().cilqr_score_batch_sampled(self._h, B, int(N), int(n_obs), int(S), _p(X), _p(U), _p(poly), _p(xplan_fl),
+                                               _p(nom_pose), _p(nom_dim), _p(offsets), C.c_double(weight), C.c_double(max_collision),
+                                               _p(score), _p(total)))
+        return dict(score=score, total=total)
+
+    def score_batch_sampled_device(self, stream, B, N, n_obs, n_samples, X, U, poly, xplan_fl, nom_pose, nom_dim, offsets, weight,
+                                   score, total=0, max_collision=1.0):
+        _check(lib().cilqr_score_batch_sampled_device(self._h, _vp(stream), int(B), int(N), int(n_obs), int(n_samples), _vp(X), _vp(U),
+                                                      _vp(poly), _vp(xplan_fl), _vp(nom_pose), _vp(nom_dim), _vp(offsets),
+                                                      C.c_double(weight), C.c_double(max_collision), _vp(score), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

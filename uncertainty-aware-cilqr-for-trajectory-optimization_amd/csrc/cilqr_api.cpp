@@ -241,6 +241,10 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   {  // arena of the host-buffer entry points: the larger of the two layouts that can be asked for (cilqr_host_io.cpp)
     const cilqr::IoLayout plain = cilqr::io_layout(B, N, B * M * N, B * M, 0), sampled = cilqr::io_layout(B, N, B * M * N, 0, B * M);
     h->arena_cap = plain.end > sampled.end ? plain.end : sampled.end;
+    // (the score calls carry X beside U and 9 doubles per solve back: a few doubles per solve more than a solve call)
+    const size_t score_plain = cilqr::score_layout(B, N, B * M * N, B * M, 0).end, score_sampled = cilqr::score_layout(B, N, B * M * N, 0, B * M).end;
+    if (score_plain > h->arena_cap) h->arena_cap = score_plain;
+    if (score_sampled > h->arena_cap) h->arena_cap = score_sampled;
     if (err == hipSuccess) err = hipMalloc((void**)&h->d_arena, h->arena_cap);
     h->stage_cap = h->arena_cap < ((size_t)1 << 20) ? h->arena_cap : ((size_t)1 << 20);  // pinned: calls up to 1 MiB travel packed
     if (err == hipSuccess) err = hipHostMalloc((void**)&h->stage, h->stage_cap, hipHostMallocDefault);
@@ -568,6 +572,99 @@ int cilqr_argmin_device(cilqr_handle* h, void* stream, int B, const double* J, d
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(cilqr::launch_argmin(J, B, out_pair, nullptr, 0.0, (hipStream_t)stream));
   return CILQR_OK;
+}
+
+// ---- scoring of solved trajectories (cilqr_score.hip) --------------------------------------------------------------------
+namespace {
+// What both score calls share: the solve-side fields of the launch, the on-chip budget, the launch.  `a.s` arrives with its
+// obstacle fields set by the caller.
+int score_device(cilqr_handle* h, void* stream, cilqr::ScoreArgs& a, const double* X, const double* U, const double* poly,
+                 const double* xplan_fl, double max_collision, double* score, double* total, int n_counters) {
+  cilqr::SolveArgs& s = a.s;
+  s.X_out = const_cast<double*>(X);  // read only (cilqr_internal.h, ScoreArgs)
+  s.U = const_cast<double*>(U);
+  s.poly = poly; s.xplan_fl = xplan_fl;
+  a.score = score; a.total = total; a.max_collision = max_collision; a.w_uncertainty = h->params.w_uncertainty;
+  if (cilqr::score_lds_bytes(s.N, h->kp.n_samples, n_counters) > cilqr::SCORE_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_score_batch: %d path samples, horizon %d and %d sample counters do not fit 64 KiB of LDS",
+                h->kp.n_samples, s.N, n_counters);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_score(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_score_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* poly,
+                             const double* xplan_fl, const cilqr_obstacles* obs, double max_collision, double* score, double* total) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, nullptr, nullptr);
+  if (rc) return rc;
+  if (!X || !U || !poly || !xplan_fl || !score) return fail(CILQR_ERR_ARG, "cilqr_score_batch: null required pointer");
+  if ((int64_t)M * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_score_batch: M * N beyond 2^31 entries");
+  if (B == 0) return CILQR_OK;
+  cilqr::ScoreArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  if (M > 0) {
+    a.s.obs_pose = obs->pose; a.s.obs_dim = obs->dim; a.s.obs_weight = obs->weight;
+    a.s.obs_bs = obs->batch_stride; a.s.obs_ms = obs->obstacle_stride; a.s.obs_ts = obs->step_stride; a.s.obs_wbs = obs->weight_batch_stride;
+  }
+  return score_device(h, stream, a, X, U, poly, xplan_fl, max_collision, score, total, 0);
+}
+
+int cilqr_score_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
+                                     const double* nom_dim, const double* sample_offset, double sample_weight, double max_collision,
+                                     double* score, double* total) {
+  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
+  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: n_obs * n_samples too large");
+  int rc = check_sizes(h, B, N, n_obs * n_samples);  // the equivalent materialised obstacle count
+  if (rc) return rc;
+  if (!X || !U || !poly || !xplan_fl || !score || !nom_pose || !nom_dim || !sample_offset)
+    return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: null required pointer");
+  if ((int64_t)n_obs * n_samples * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: n_obs * n_samples * N beyond 2^31 entries");
+  if (B == 0) return CILQR_OK;
+  cilqr::ScoreArgs a = {};
+  a.s = handle_args(h, B, N, n_obs, 0);
+  a.s.obs_pose = nom_pose; a.s.obs_dim = nom_dim;
+  a.s.samp_off = sample_offset; a.s.n_samples = n_samples; a.s.samp_w = sample_weight;
+  return score_device(h, stream, a, X, U, poly, xplan_fl, max_collision, score, total, n_obs * N);
+}
+
+int cilqr_score_batch(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* poly,
+                      const double* xplan_fl, const cilqr_obstacles* obs, double max_collision, double* score, double* total) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  size_t span = 0, w_span = 0;
+  rc = check_obstacles(B, N, M, obs, &span, &w_span);
+  if (rc) return rc;
+  if (!X || !U || !poly || !xplan_fl || !score) return fail(CILQR_ERR_ARG, "cilqr_score_batch: null required pointer");
+  if (B == 0) return CILQR_OK;
+  cilqr::HostScore q = {};
+  q.B = B; q.N = N; q.M = M;
+  q.X = X; q.U = U; q.poly = poly; q.xplan_fl = xplan_fl;
+  if (M > 0) { q.obs = *obs; q.obs_span = span; q.w_span = w_span; }
+  q.max_collision = max_collision; q.score = score; q.total = total;
+  return cilqr::host_score(h, q);
+}
+
+int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
+                              const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
+                              const double* sample_offset, double sample_weight, double max_collision, double* score, double* total) {
+  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
+  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: n_obs * n_samples too large");
+  int rc = check_sizes(h, B, N, n_obs * n_samples);
+  if (rc) return rc;
+  if (!X || !U || !poly || !xplan_fl || !score || !nom_pose || !nom_dim || !sample_offset)
+    return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: null required pointer");
+  if (B == 0) return CILQR_OK;
+  cilqr::HostScore q = {};
+  q.B = B; q.N = N; q.M = n_obs; q.n_samples = n_samples;
+  q.X = X; q.U = U; q.poly = poly; q.xplan_fl = xplan_fl;
+  q.obs.pose = nom_pose; q.obs.dim = nom_dim; q.obs_span = (size_t)B * n_obs * N;
+  q.samp_off = sample_offset; q.samp_w = sample_weight;
+  q.max_collision = max_collision; q.score = score; q.total = total;
+  return cilqr::host_score(h, q);
 }
 
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,

@@ -39,6 +39,22 @@ struct PendingOut {
 };
 int host_solve_enqueue(cilqr_handle* h, const HostBatch& q);  // copies in, kernels, copies out: all enqueued on h->stream
 int host_solve_finish(cilqr_handle* h);                       // waits; unpacks the staging buffer of a small call
+// One host-buffer score call (cilqr_score_batch, cilqr_score_batch_sampled): synchronous, through the solve's arena and pinned
+// staging buffer with a layout of its own (X and U both travel in; the scores and totals come back).
+struct HostScore {
+  int B, N, M, n_samples;  // M: obstacles, or nominal obstacles of the sampled form (n_samples > 0)
+  const double *X, *U, *poly, *xplan_fl;
+  cilqr_obstacles obs;     // host pointers; sampled: pose / dim are the dense nominal tables, strides unused
+  size_t obs_span, w_span; // entries and weights that travel
+  const double* samp_off;
+  double samp_w, max_collision;
+  double *score, *total;   // total may be null
+};
+struct ScoreLayout {
+  size_t poly, xplan, obs_w, samp_off, obs_pose, obs_dim, U, X, score, total, end;  // inputs poly … X, outputs score, total
+};
+ScoreLayout score_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries);
+int host_score(cilqr_handle* h, const HostScore& q);
 enum { SCR_PLAN_PATH, SCR_PLAN_IO, SCR_COUNT, SCR_CONV_IN, SCR_CONV_OUT, SCR_DEBUG, SCR_SLOTS };
 int scratch_bytes(cilqr_handle* h, int slot, size_t bytes, void** out);
 

@@ -164,6 +164,95 @@ int host_solve_finish(cilqr_handle* h) {
   return CILQR_OK;
 }
 
+// ---- cilqr_score_batch, cilqr_score_batch_sampled: the same two ways of travelling, for
+//     [ poly | xplan | obs_weight | sample_offset | obs_pose | obs_dim | U | X ][ score | total ]
+ScoreLayout score_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries) {
+  ScoreLayout L;
+  size_t o = 0;
+  L.poly = o; o = up16(o + B * CILQR_POLY_COEFFS * sizeof(double));
+  L.xplan = o; o = up16(o + B * 2 * sizeof(double));
+  L.obs_w = o; o = up16(o + w_entries * sizeof(double));
+  L.samp_off = o; o = up16(o + samp_entries * 3 * sizeof(double));
+  L.obs_pose = o; o = up16(o + obs_entries * 4 * sizeof(double));
+  L.obs_dim = o; o = up16(o + obs_entries * 2 * sizeof(double));
+  L.U = o; o = up16(o + B * 2 * N * sizeof(double));
+  L.X = o; o = up16(o + B * 4 * (N + 1) * sizeof(double));
+  L.score = o; o = up16(o + B * CILQR_SCORE_FIELDS * sizeof(double));
+  L.total = o; o = up16(o + B * sizeof(double));
+  L.end = o;
+  return L;
+}
+
+namespace {
+int score_steps(cilqr_handle* h, const HostScore& q) {
+  const bool sampled = q.n_samples > 0;
+  const size_t B = q.B, N = q.N, M = q.M;
+  const size_t n_went = !sampled && q.obs.weight && M > 0 ? q.w_span : 0, n_samp = sampled ? B * M * (size_t)q.n_samples : 0;
+  const size_t n_ent = M > 0 ? q.obs_span : 0;
+  const ScoreLayout L = score_layout(B, N, n_ent, n_went, n_samp);
+  if (L.end > h->arena_cap) return fail(CILQR_ERR_ARG, "batch does not fit the device buffers reserved at create");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  char* dv = h->d_arena;
+  const bool packed = L.end <= h->stage_cap;
+  char* up = packed ? h->stage : nullptr;  // packed: the arrays are gathered in pinned memory and travel as one copy
+  const auto put = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
+    if (!bytes) return hipSuccess;
+    if (up) { memcpy(up + at, src, bytes); return hipSuccess; }
+    return hipMemcpyAsync(dv + at, src, bytes, hipMemcpyHostToDevice, s);
+  };
+  HIP_TRY(put(L.poly, q.poly, B * CILQR_POLY_COEFFS * sizeof(double)));
+  HIP_TRY(put(L.xplan, q.xplan_fl, B * 2 * sizeof(double)));
+  HIP_TRY(put(L.obs_w, q.obs.weight, n_went * sizeof(double)));
+  HIP_TRY(put(L.samp_off, q.samp_off, n_samp * 3 * sizeof(double)));
+  HIP_TRY(put(L.obs_pose, q.obs.pose, n_ent * 4 * sizeof(double)));
+  HIP_TRY(put(L.obs_dim, q.obs.dim, n_ent * 2 * sizeof(double)));
+  HIP_TRY(put(L.U, q.U, B * 2 * N * sizeof(double)));
+  HIP_TRY(put(L.X, q.X, B * 4 * (N + 1) * sizeof(double)));
+  if (up) HIP_TRY(hipMemcpyAsync(dv, up, L.score, hipMemcpyHostToDevice, s));
+  const auto at = [&](size_t off) { return (const double*)(dv + off); };
+  double* d_score = (double*)(dv + L.score);
+  double* d_total = q.total ? (double*)(dv + L.total) : nullptr;
+  int rc;
+  if (sampled)
+    rc = cilqr_score_batch_sampled_device(h, s, q.B, q.N, q.M, q.n_samples, at(L.X), at(L.U), at(L.poly), at(L.xplan), at(L.obs_pose),
+                                          at(L.obs_dim), at(L.samp_off), q.samp_w, q.max_collision, d_score, d_total);
+  else {
+    const cilqr_obstacles o{at(L.obs_pose), at(L.obs_dim), n_went ? at(L.obs_w) : nullptr, q.obs.batch_stride, q.obs.obstacle_stride,
+                            q.obs.step_stride, q.obs.weight_batch_stride};
+    rc = cilqr_score_batch_device(h, s, q.B, q.N, q.M, at(L.X), at(L.U), at(L.poly), at(L.xplan), M > 0 ? &o : nullptr, q.max_collision,
+                                  d_score, d_total);
+  }
+  if (rc) return rc;
+  const size_t n_score = B * CILQR_SCORE_FIELDS * sizeof(double);
+  if (up) {
+    HIP_TRY(hipMemcpyAsync(up + L.score, dv + L.score, L.end - L.score, hipMemcpyDeviceToHost, s));
+  } else {
+    HIP_TRY(hipMemcpyAsync(q.score, d_score, n_score, hipMemcpyDeviceToHost, s));
+    if (q.total) HIP_TRY(hipMemcpyAsync(q.total, d_total, B * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (up) {
+    memcpy(q.score, up + L.score, n_score);
+    if (q.total) memcpy(q.total, up + L.total, B * sizeof(double));
+  }
+  return CILQR_OK;
+}
+}  // namespace
+
+// As host_solve_enqueue: on a failure the stream is drained before the error returns — no copy to or from the caller's memory
+// stays in flight.
+int host_score(cilqr_handle* h, const HostScore& q) {
+  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
+  const int rc = score_steps(h, q);
+  if (rc != CILQR_OK) {
+    const std::string msg = g_last_error;
+    (void)hipStreamSynchronize(h->stream);
+    g_last_error = msg;
+  }
+  return rc;
+}
+
 // Device scratch of the convenience entry points that take host pointers (local plan, blur counts, conversions, test hooks):
 // slots owned by the handle, grown when a call needs more than any before it — never allocated and freed per call.
 int scratch_bytes(cilqr_handle* h, int slot, size_t bytes, void** out) {

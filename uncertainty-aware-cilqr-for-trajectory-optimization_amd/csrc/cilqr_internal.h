@@ -93,6 +93,21 @@ hipError_t launch_unc_cost(const UncArgs& u, int n, const double* states, double
 hipError_t launch_quu_inverse(int n, const double* q, const double* lamb, double* out, int general, hipStream_t stream);
 hipError_t launch_closest_sample(int n, int S, const double* in, int32_t* out, hipStream_t stream);  // test hook (cilqr_debug_closest_sample)
 
+// Scoring of solved trajectories (cilqr_score.hip; cilqr_score_batch*, include/cilqr.h): one workgroup of SCORE_THREADS lanes per
+// solve.  `s` carries what the launch shares with a solve — U, poly, xplan_fl, the obstacle fields (strided, or the compact sampled
+// form with M = nominal obstacles and n_samples > 0), B, N, M, kp, unc — and the trajectories to score in X_out (read only).
+constexpr int SCORE_THREADS = 256;
+constexpr size_t SCORE_LDS_MAX = 64 * 1024;  // dynamic LDS a launch gets without opting in to more
+struct ScoreArgs {
+  SolveArgs s;
+  double* score;         // [B][CILQR_SCORE_FIELDS]
+  double* total;         // [B] or null
+  double max_collision;
+  double w_uncertainty;  // Parameters::w_uncertainty (UncArgs::scale holds it divided by the probe count only)
+};
+hipError_t launch_score(const ScoreArgs& a, hipStream_t stream);
+size_t score_lds_bytes(int N, int S, int n_counters);  // n_counters: n_obs·N per-(t, o) sample counters of the sampled form, else 0
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

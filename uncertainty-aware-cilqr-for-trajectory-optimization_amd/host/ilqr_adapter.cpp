@@ -144,6 +144,11 @@ Experiment flatten_experiment(const double start_pos[4], double planning_time, c
   return e;
 }
 
+void iLQR::set_candidate_pick(CandidatePick pick, double max_collision) {
+  pick_ = pick;
+  max_collision_ = max_collision;
+}
+
 int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
@@ -163,10 +168,21 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, X.data(),
                                     J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
         "cilqr_solve_batch_obstacles");
+  std::vector<double> total;
+  last_scores.clear();
+  if (pick_ == CandidatePick::MinTotalCost) {  // rank by everything the solve descended along, among the candidates that are safe
+    last_scores.resize((size_t)B * CILQR_SCORE_FIELDS);
+    total.resize(B);
+    check(cilqr_score_batch(h_, B, N, M, X.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, max_collision_,
+                            last_scores.data(), total.data()),
+          "cilqr_score_batch");
+  }
+  const std::vector<double>& rank = pick_ == CandidatePick::MinTotalCost ? total : J;
   int best = 0;  // strict-< first minimum, NaN never wins (the convention of cilqr_argmin_device)
   bool have = false;
   for (int b = 0; b < B; ++b)
-    if (J[b] == J[b] && (!have || J[b] < J[best])) { best = b; have = true; }
+    if (rank[b] == rank[b] && (!have || rank[b] < rank[best])) { best = b; have = true; }
+  if (pick_ == CandidatePick::MinTotalCost && !have) return -1;  // every candidate rejected: results and warm start stay
   X_result = Matrix(4, N + 1);
   for (int i = 0; i < 4 * (N + 1); ++i) X_result.a[i] = X[(size_t)best * 4 * (N + 1) + i];
   for (int i = 0; i < 2 * N; ++i) control_seq_.a[i] = U[(size_t)best * 2 * N + i];

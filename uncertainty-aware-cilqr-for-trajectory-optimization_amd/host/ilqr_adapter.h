@@ -67,6 +67,11 @@ struct Experiment {
 };
 Experiment flatten_experiment(const double start_pos[4], double planning_time, const Matrix& X, const Matrix& U);
 
+// What run_candidates ranks the solved candidates by.  MinTrackingCost: J = Constraints::get_J, tracking and control effort only
+// (the default).  MinTotalCost: the `total` column of cilqr_score_batch — J plus the control-barrier, obstacle-barrier and
+// uncertainty-map costs, NaN (never picked) for a candidate whose collision share exceeds max_collision.
+enum class CandidatePick { MinTrackingCost, MinTotalCost };
+
 class iLQR {
  public:
   // max_candidates > 1 reserves device buffers for run_candidates().
@@ -91,7 +96,13 @@ class iLQR {
   // solves every candidate from the current warm start in ONE launch, keeps the minimum-cost one (cilqr_argmin_device)
   // as X_result/U_result/control_seq and returns its index.  The obstacle set travels once for all candidates
   // (cilqr_solve_batch_obstacles, batch stride 0).
+  // With set_candidate_pick(CandidatePick::MinTotalCost, max_collision) the solved batch is scored on the device against the same
+  // shared obstacle set (cilqr_score_batch, batch stride 0) and the pick is the strict-< first minimum of `total`, a NaN never
+  // winning (the convention of cilqr_argmin_device): the cheapest among the safe.  last_scores then holds the B × 8 score rows
+  // (cilqr_score_field).  If every candidate is rejected the call returns -1 and X_result, U_result, the warm start and the
+  // last_* fields stay as they were.  max_collision = 0 rejects any contact, 1 rejects nothing on collision grounds.
   int run_candidates(const std::vector<double>& ego_states /* 4 per candidate */);
+  void set_candidate_pick(CandidatePick pick, double max_collision = 0.0);
 
   Parameters params;
   Matrix X_result;         // 4 × (horizon + 1)
@@ -100,12 +111,15 @@ class iLQR {
   int last_iterations = 0;
   int last_exit = 0;  // cilqr_exit
   double last_cost = 0.0;
+  std::vector<double> last_scores;  // run_candidates under MinTotalCost: CILQR_SCORE_FIELDS per candidate; empty otherwise
 
  private:
   void pack_obstacles();
   cilqr_obstacles obstacle_strides();  // the packed set, shared by every solve of a call (batch stride 0)
   cilqr_handle* h_ = nullptr;
   int device_, max_obstacles_, max_candidates_;
+  CandidatePick pick_ = CandidatePick::MinTrackingCost;
+  double max_collision_ = 0.0;
   Matrix control_seq_;  // I/iLQR.h:34
   Matrix global_plan_;
   std::vector<Obstacle> obstacles_;
