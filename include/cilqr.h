@@ -35,6 +35,9 @@
  *                                                                cilqr_create_multi / cilqr_multi_solve_batch
  *   (none: the reference never compares candidates)          cilqr_score_batch(_device), cilqr_score_batch_sampled(_device):
  *                                                                full cost, worst constraint, collision share of solved candidates
+ *   iLQR::backward_pass's k, K (computed, never handed out)   cilqr_gains_batch(_device): the gains of one backward pass
+ *   iLQR::forward_pass's control law from other starts (none)  cilqr_rollout_batch(_device), cilqr_score_rollouts(_device):
+ *                                                                closed-loop rollouts from offset starts, collision risk per solve
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -391,6 +394,66 @@ int cilqr_score_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N
 int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
                               const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
                               const double* sample_offset, double sample_weight, double max_collision, double* score, double* total);
+
+/* --- feedback gains, closed-loop rollouts from offset starts, collision risk per solve (new) ---------------------------------
+ * A solve returns U alone; the time-varying policy u = U_t + k_t + K_t (x - X_t) every backward pass computes (I/iLQR.cpp:177-178)
+ * is what tracks the plan from a start other than the one it was solved for.  Three additive groups of calls, each with a
+ * host-buffer form (synchronous) and a `_device` form (device pointers, asynchronous on `stream`), with the conventions of
+ * cilqr_score_batch(_device).  Ordinary obstacles only: the compact sampled form is not taken here.  Nothing is allocated per
+ * call: the host forms travel through buffers sized at create from max_batch, so their ROW counts are bounded by max_batch.
+ *
+ * cilqr_gains_batch(_device): ONE backward pass, iLQR::backward_pass(X, U, coeffs, x_plan, lamb) (I/iLQR.cpp:91-195), at the given
+ * trajectory X [B][4*(N+1)], U [B][2*N]: linearised at X[:, t], U[:, t] for t < N with A and B evaluated at the NEXT state, as the
+ * reference does; closest path point = strict-< first minimum; obstacle weights as in the solve; the uncertainty-map term added
+ * while a map is set on the handle, with the layer and pose of the solve's index.  k_out [B][2*N]; K_out [B][8*N], the 2x4 block
+ * of step t column-major: K[8*t + r + 2*c]; ok_out [B] int32 or NULL: 1 where backward_pass would return true, 0 where a step's
+ * Q_uu is not finite — that solve's gains are then zero from the failing step down to step 0, as in the reference.
+ *   `lamb` is the regularisation of that pass.  A solve does not export its last lambda, so the caller chooses: 1.0 is the
+ *   reference's starting value (I/iLQR.cpp:205); the gains of the reference's own last pass belong to the lambda of that pass.
+ *   B <= max_batch, N <= max_horizon, M <= max_obstacles; NULL X, U, poly, xplan_fl, k_out or K_out, a negative stride or a lamb
+ *   that is not finite: CILQR_ERR_ARG.  CILQR_ERR_UNSUPPORTED where 16*num_of_local_wpts*10 + 144*N + 16 bytes exceed 64 KiB.
+ *
+ * cilqr_rollout_batch(_device): S closed-loop rollouts per solve.  Nominal X, U and gains k, K in the layouts above; delta holds
+ * the start offsets (dx, dy, dv, dtheta), delta[b][s] at delta + 4*(b*delta_batch_stride*S + s): delta_batch_stride is in units of
+ * [S][4] blocks, 0 = one offset set shared by all solves (1 = dense).  Row b*S + s of X_roll [B*S][4*(N+1)], U_roll [B*S][2*N] —
+ * the layout the score calls read — is, with x'_0 = X[:, 0] + delta:
+ *     u_t = (U_t + k_scale*k_t) + K_t (x'_t - X_t)   (iLQR::forward_pass, I/iLQR.cpp:68-86; the heading difference is not wrapped)
+ *     x'_{t+1} = Model::forward_simulate(x'_t, u_t)  (the clamps act on a copy: u_t is stored unclamped)
+ *   k_scale = 1 with delta = 0 IS the reference's forward pass; k_scale = 0 tracks the nominal plan.  A row depends on its own
+ *   inputs alone: bit-identical whatever B, S and its position are.  S < 1, a negative delta_batch_stride, a NULL pointer or a
+ *   k_scale that is not finite: CILQR_ERR_ARG; so is B > max_batch and, for the host-buffer form, B*S > max_batch.  The host-buffer
+ *   form takes delta_batch_stride 0 or 1.  CILQR_ERR_UNSUPPORTED where 112*N + 25632 bytes exceed 64 KiB (N above 356).
+ *
+ * cilqr_score_rollouts(_device): scores B*S trajectory rows (row r belongs to solve r / S: its poly, xplan_fl, obstacle entries,
+ * weights and map index) as cilqr_score_batch scores a solve, into row_score [B*S][CILQR_SCORE_FIELDS]: S = 1 gives that call's rows
+ * bit for bit; for S > 1 the closest path sample is found by the solve kernels' windowed search, which returns the full scan's
+ * index.  It then reduces each solve's S rows to risk [B][CILQR_RISK_FIELDS] and total [B] (NULL: not written):
+ *   total[b] = RISK_MEAN_TOTAL, or NaN when RISK_COLLISION > max_risk or the mean is not finite: hand it to cilqr_argmin_device /
+ *   cilqr_argmin_global_device in place of J_out.  B <= max_batch; host-buffer form: B*S <= max_batch; row_score and risk are
+ *   required; violations are CILQR_ERR_ARG. */
+#define CILQR_RISK_FIELDS 4
+typedef enum cilqr_risk_field {
+  CILQR_RISK_COLLISION = 0,   /* (rows with SCORE_MAX_C > 0 or a term that is not finite) / S */
+  CILQR_RISK_WORST_C = 1,     /* max over the rows of SCORE_MAX_C */
+  CILQR_RISK_WORST_ROW = 2,   /* (double) row index s of that maximum, the lowest on equal values */
+  CILQR_RISK_MEAN_TOTAL = 3   /* mean over the rows of ((TRACK + CONTROL) + OBSTACLE) + UNCERTAINTY, summed over a tree fixed by S */
+} cilqr_risk_field;
+int cilqr_gains_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* poly,
+                             const double* xplan_fl, const cilqr_obstacles* obs, double lamb, double* k_out, double* K_out,
+                             int32_t* ok_out);
+int cilqr_gains_batch(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* poly,
+                      const double* xplan_fl, const cilqr_obstacles* obs, double lamb, double* k_out, double* K_out, int32_t* ok_out);
+int cilqr_rollout_batch_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, const double* U, const double* k,
+                               const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, double* X_roll,
+                               double* U_roll);
+int cilqr_rollout_batch(cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                        const double* delta, int64_t delta_batch_stride, double k_scale, double* X_roll, double* U_roll);
+int cilqr_score_rollouts_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X_roll, const double* U_roll,
+                                const double* poly, const double* xplan_fl, const cilqr_obstacles* obs, double max_risk,
+                                double* row_score, double* risk, double* total);
+int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const double* X_roll, const double* U_roll, const double* poly,
+                         const double* xplan_fl, const cilqr_obstacles* obs, double max_risk, double* row_score, double* risk,
+                         double* total);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

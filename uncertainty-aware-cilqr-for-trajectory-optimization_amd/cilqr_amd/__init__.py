@@ -20,6 +20,9 @@ EXIT_TOLERANCE, EXIT_LAMBDA_MAX, EXIT_MAX_ITER, EXIT_NUMERIC = 0, 1, 2, 3
 SCORE_FIELDS = 8
 (SCORE_TRACK, SCORE_CONTROL, SCORE_OBSTACLE, SCORE_UNCERTAINTY, SCORE_MAX_C, SCORE_MAX_C_ENTRY, SCORE_MAX_CTRL,
  SCORE_COLLISION) = range(SCORE_FIELDS)
+# `cilqr_risk_field`: the columns of a risk row (`Solver.score_rollouts`)
+RISK_FIELDS = 4
+RISK_COLLISION, RISK_WORST_C, RISK_WORST_ROW, RISK_MEAN_TOTAL = range(RISK_FIELDS)
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -35,6 +38,8 @@ ABI_SYMBOLS = (
     "cilqr_create_multi", "cilqr_multi_destroy", "cilqr_multi_device_count", "cilqr_multi_handle", "cilqr_multi_solve_batch",
     "cilqr_shard_range", "cilqr_multi_uses_rccl", "cilqr_debug_fail_enqueue",
     "cilqr_score_batch", "cilqr_score_batch_device", "cilqr_score_batch_sampled", "cilqr_score_batch_sampled_device",
+    "cilqr_gains_batch", "cilqr_gains_batch_device", "cilqr_rollout_batch", "cilqr_rollout_batch_device",
+    "cilqr_score_rollouts", "cilqr_score_rollouts_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -423,6 +428,91 @@ class Solver:
         _check(lib().cilqr_score_batch_sampled_device(self._h, _vp(stream), int(B), int(N), int(n_obs), int(n_samples), _vp(X), _vp(U),
                                                       _vp(poly), _vp(xplan_fl), _vp(nom_pose), _vp(nom_dim), _vp(offsets),
                                                       C.c_double(weight), C.c_double(max_collision), _vp(score), _vp(total)))
+
+    # ---- feedback gains, closed-loop rollouts from offset starts, collision risk ----
+    def _obstacles(self, obs_pose, obs_dim, obs_weight, B, N):
+        """(M, Obstacles or None, keepalive) from host arrays in any of the shapes of `obstacle_strides`."""
+        if obs_pose is None:
+            return 0, None, ()
+        obs_pose, obs_dim, obs_weight = _np64(obs_pose), _np64(obs_dim), _np64(obs_weight)
+        M, bs, ms, ts, wbs = obstacle_strides(obs_pose.shape, obs_dim.shape, None if obs_weight is None else obs_weight.shape, B, N)
+        obs = Obstacles(obs_pose.ctypes.data, obs_dim.ctypes.data, None if obs_weight is None else obs_weight.ctypes.data, bs, ms, ts, wbs)
+        return M, obs, (obs_pose, obs_dim, obs_weight)
+
+    def gains_batch(self, N, X, U, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, lamb=1.0):
+        """`cilqr_gains_batch`: one backward pass at X (B, 4(N+1)), U (B, 2N) with regularisation lamb (1.0: the reference's starting
+        value).  Returns dict(k (B, 2N), K (B, 8N) with K[8t + r + 2c], ok (B,) int32)."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U = _np64(U).reshape(B, 2 * N)
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, obs_weight, B, N)
+        k, K, ok = np.zeros((B, 2 * N)), np.zeros((B, 8 * N)), np.zeros(B, dtype=np.int32)
+        _check(lib().cilqr_gains_batch(self._h, B, int(N), int(M), _p(X), _p(U), _p(poly), _p(xplan_fl),
+                                       None if obs is None else C.byref(obs), C.c_double(lamb), _p(k), _p(K), _p(ok, _ip)))
+        return dict(k=k, K=K, ok=ok)
+
+    def gains_batch_device(self, stream, B, N, M, X, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, strides, k_out, K_out, ok_out=0,
+                           lamb=1.0):
+        """`cilqr_gains_batch_device`: device addresses and strides as `score_batch_device`."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None,
+                        int(obs_weight) if obs_weight else None, bs, ms, ts, wbs)
+        _check(lib().cilqr_gains_batch_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(U), _vp(poly), _vp(xplan_fl),
+                                              C.byref(obs) if M else None, C.c_double(lamb), _vp(k_out), _vp(K_out), _vp(ok_out)))
+
+    def rollout_batch(self, N, X, U, k, K, delta, k_scale=0.0):
+        """`cilqr_rollout_batch`: S closed-loop rollouts per solve.  delta: (S, 4) offsets (dx, dy, dv, dtheta) shared by all solves, or
+        (B, S, 4) one set per solve.  Returns dict(X (B, S, 4(N+1)), U (B, S, 2N)); B*S must not exceed max_batch."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U, k, K = _np64(U).reshape(B, 2 * N), _np64(k).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        delta = _np64(delta)
+        if delta.ndim == 3:
+            if delta.shape[0] != B or delta.shape[2] != 4:
+                raise CilqrError("rollout_batch: delta %s is neither (S, 4) nor (%d, S, 4)" % (delta.shape, B))
+            S, stride = delta.shape[1], 1
+        else:
+            delta = delta.reshape(-1, 4)
+            S, stride = delta.shape[0], 0
+        Xr, Ur = np.zeros((B, S, 4 * (N + 1))), np.zeros((B, S, 2 * N))
+        _check(lib().cilqr_rollout_batch(self._h, B, int(N), int(S), _p(X), _p(U), _p(k), _p(K), _p(delta), C.c_int64(stride),
+                                         C.c_double(k_scale), _p(Xr), _p(Ur)))
+        return dict(X=Xr, U=Ur)
+
+    def rollout_batch_device(self, stream, B, N, S, X, U, k, K, delta, delta_batch_stride, X_roll, U_roll, k_scale=0.0):
+        _check(lib().cilqr_rollout_batch_device(self._h, _vp(stream), int(B), int(N), int(S), _vp(X), _vp(U), _vp(k), _vp(K), _vp(delta),
+                                                C.c_int64(delta_batch_stride), C.c_double(k_scale), _vp(X_roll), _vp(U_roll)))
+
+    def score_rollouts(self, N, X_roll, U_roll, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, max_risk=1.0):
+        """`cilqr_score_rollouts`: X_roll (B, S, 4(N+1)), U_roll (B, S, 2N) as `rollout_batch` returns them, everything else per solve.
+        Returns dict(row_score (B, S, SCORE_FIELDS), risk (B, RISK_FIELDS), total (B,)); total is NaN where the share of colliding
+        rows exceeds max_risk — hand it to `argmin_device` in place of J."""
+        X_roll = _np64(X_roll)
+        if X_roll.ndim != 3 or X_roll.shape[2] != 4 * (N + 1):
+            raise CilqrError("score_rollouts: X_roll %s is not (B, S, %d)" % (X_roll.shape, 4 * (N + 1)))
+        B, S = X_roll.shape[0], X_roll.shape[1]
+        U_roll = _np64(U_roll).reshape(B, S, 2 * N)
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, obs_weight, B, N)
+        rows, risk, total = np.zeros((B, S, SCORE_FIELDS)), np.zeros((B, RISK_FIELDS)), np.zeros(B)
+        _check(lib().cilqr_score_rollouts(self._h, B, int(N), int(M), int(S), _p(X_roll), _p(U_roll), _p(poly), _p(xplan_fl),
+                                          None if obs is None else C.byref(obs), C.c_double(max_risk), _p(rows), _p(risk), _p(total)))
+        return dict(row_score=rows, risk=risk, total=total)
+
+    def score_rollouts_device(self, stream, B, N, M, S, X_roll, U_roll, poly, xplan_fl, obs_pose, obs_dim, obs_weight, strides, row_score,
+                              risk, total=0, max_risk=1.0):
+        """`cilqr_score_rollouts_device`: device addresses; strides as `score_batch_device` (per SOLVE, not per row)."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None,
+                        int(obs_weight) if obs_weight else None, bs, ms, ts, wbs)
+        _check(lib().cilqr_score_rollouts_device(self._h, _vp(stream), int(B), int(N), int(M), int(S), _vp(X_roll), _vp(U_roll), _vp(poly),
+                                                 _vp(xplan_fl), C.byref(obs) if M else None, C.c_double(max_risk), _vp(row_score),
+                                                 _vp(risk), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

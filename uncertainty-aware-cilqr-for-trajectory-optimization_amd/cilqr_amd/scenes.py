@@ -219,6 +219,17 @@ class TickSequence:
         self.tick += 1
 
 
+def pose_offsets(S, sigma_x, sigma_y, sigma_theta, seed):
+    """S start offsets (dx, dy, dv, dtheta) for `Solver.rollout_batch`: the node's Gaussian ego-pose noise (sigma from its launch
+    file), drawn once.  PCG64(seed) draws x (S), then y (S), then theta (S); the speed offset is 0.  Returns (S, 4)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = np.zeros((S, 4))
+    out[:, 0] = rng.normal(0.0, sigma_x, S)
+    out[:, 1] = rng.normal(0.0, sigma_y, S)
+    out[:, 3] = rng.normal(0.0, sigma_theta, S)
+    return out
+
+
 def make_c4(seed=SEED0 + 4, size=1024):
     """C4: source occupancy `size`×`size` float32 ({0,100} blobs + 2 % NaN) at 0.2 m; destination `size`×`size` at 0.1 m
     centred on the vehicle; 300-frame pose stream (theta 0→2π, position on a 20 m circle about the source centre)."""

@@ -82,6 +82,15 @@ cilqr::SolveArgs handle_args(const cilqr_handle* h, int B, int N, int M, uint32_
   return a;
 }
 
+// Upper bound of what a host-buffer gains, rollout or rollout-score call of at most B solves AND at most B rows places in the arena
+// (HostIo below: every array rounded up to 16 bytes): the obstacle tables, X, U, k, K, the offsets, the rollout rows, the score
+// rows, risk, total, ok.
+size_t risk_io_bytes(size_t B, size_t N, size_t M) {
+  const size_t doubles = B * (CILQR_POLY_COEFFS + 2 + M + 6 * M * N + 2 * (4 * (N + 1) + 2 * N) + 2 * N + 8 * N + 4 + CILQR_SCORE_FIELDS +
+                              CILQR_RISK_FIELDS + 1 + 1);
+  return doubles * sizeof(double) + 32 * 16;
+}
+
 template <typename T>
 hipError_t dmalloc(T** p, size_t n) {
   *p = nullptr;
@@ -245,6 +254,9 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
     const size_t score_plain = cilqr::score_layout(B, N, B * M * N, B * M, 0).end, score_sampled = cilqr::score_layout(B, N, B * M * N, 0, B * M).end;
     if (score_plain > h->arena_cap) h->arena_cap = score_plain;
     if (score_sampled > h->arena_cap) h->arena_cap = score_sampled;
+    // (the host forms of the gains / rollout / rollout-score calls: at most max_batch solves or rows, cilqr_gains_batch below)
+    const size_t risk_io = risk_io_bytes(B, N, M);
+    if (risk_io > h->arena_cap) h->arena_cap = risk_io;
     if (err == hipSuccess) err = hipMalloc((void**)&h->d_arena, h->arena_cap);
     h->stage_cap = h->arena_cap < ((size_t)1 << 20) ? h->arena_cap : ((size_t)1 << 20);  // pinned: calls up to 1 MiB travel packed
     if (err == hipSuccess) err = hipHostMalloc((void**)&h->stage, h->stage_cap, hipHostMallocDefault);
@@ -585,6 +597,7 @@ int score_device(cilqr_handle* h, void* stream, cilqr::ScoreArgs& a, const doubl
   s.U = const_cast<double*>(U);
   s.poly = poly; s.xplan_fl = xplan_fl;
   a.score = score; a.total = total; a.max_collision = max_collision; a.w_uncertainty = h->params.w_uncertainty;
+  if (a.rows < 1) a.rows = 1;  // (the score calls: one row per solve)
   if (cilqr::score_lds_bytes(s.N, h->kp.n_samples, n_counters) > cilqr::SCORE_LDS_MAX)
     return fail(CILQR_ERR_UNSUPPORTED, "cilqr_score_batch: %d path samples, horizon %d and %d sample counters do not fit 64 KiB of LDS",
                 h->kp.n_samples, s.N, n_counters);
@@ -665,6 +678,246 @@ int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_sa
   q.samp_off = sample_offset; q.samp_w = sample_weight;
   q.max_collision = max_collision; q.score = score; q.total = total;
   return cilqr::host_score(h, q);
+}
+
+// ---- feedback gains, closed-loop rollouts, collision risk (cilqr_gains.hip, cilqr_rollout.hip, cilqr_score.hip) -----------------
+namespace {
+bool is_finite(double v) { return v - v == 0.0; }
+
+// Argument checks that need no handle come first, so that they hold without a device.
+int gains_check(const cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* poly, const double* xplan_fl,
+                const cilqr_obstacles* obs, double lamb, const double* k_out, const double* K_out, size_t* span, size_t* w_span) {
+  if (!X || !U || !poly || !xplan_fl || !k_out || !K_out) return fail(CILQR_ERR_ARG, "cilqr_gains_batch: null required pointer");
+  if (!is_finite(lamb)) return fail(CILQR_ERR_ARG, "cilqr_gains_batch: lamb is not finite");
+  if (M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_gains_batch: negative stride");
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  return check_obstacles(B, N, M, obs, span, w_span);
+}
+int rollout_check(const cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                  const double* delta, int64_t delta_batch_stride, double k_scale, const double* X_roll, const double* U_roll, bool host) {
+  if (!X || !U || !k || !K || !delta || !X_roll || !U_roll) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: null required pointer");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: S = %d, needs S >= 1", S);
+  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30)) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: negative stride (or one beyond 2^30)");
+  if (!is_finite(k_scale)) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: k_scale is not finite");
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  if ((int64_t)B * ((S + 63) / 64) > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: B * S beyond 2^31 wavefronts");
+  if (host && (int64_t)B * S > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: B * S = %lld rows above max_batch = %d (host-buffer form)", (long long)B * S, h->max_batch);
+  return CILQR_OK;
+}
+int score_rollouts_check(const cilqr_handle* h, int B, int N, int M, int S, const double* X_roll, const double* U_roll, const double* poly,
+                         const double* xplan_fl, const cilqr_obstacles* obs, const double* row_score, const double* risk, bool host,
+                         size_t* span, size_t* w_span) {
+  if (!X_roll || !U_roll || !poly || !xplan_fl || !row_score || !risk) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: null required pointer");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: S = %d, needs S >= 1", S);
+  if (M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: negative stride");
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, w_span);
+  if (rc) return rc;
+  if ((int64_t)M * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: M * N beyond 2^31 entries");
+  if ((int64_t)B * S > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: B * S beyond 2^31 rows");
+  if (host && (int64_t)B * S > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: B * S = %lld rows above max_batch = %d (host-buffer form)", (long long)B * S, h->max_batch);
+  return CILQR_OK;
+}
+void set_obstacles(cilqr::SolveArgs& s, int M, const cilqr_obstacles* obs) {
+  if (M <= 0) return;
+  s.obs_pose = obs->pose; s.obs_dim = obs->dim; s.obs_weight = obs->weight;
+  s.obs_bs = obs->batch_stride; s.obs_ms = obs->obstacle_stride; s.obs_ts = obs->step_stride; s.obs_wbs = obs->weight_batch_stride;
+}
+
+// A host-buffer call's arrays in the handle's arena, in the order they are asked for (sized at create: risk_io_bytes); copies are
+// enqueued on the handle's stream.  The first failure is kept and reported by rc().
+struct HostIo {
+  cilqr_handle* h;
+  size_t off = 0;
+  bool over = false;
+  hipError_t err = hipSuccess;
+  explicit HostIo(cilqr_handle* h) : h(h) {}
+  void* take(size_t bytes) {
+    const size_t at = off;
+    off = (off + bytes + 15) & ~(size_t)15;
+    if (off > h->arena_cap) { over = true; return nullptr; }
+    return h->d_arena + at;
+  }
+  const double* in(const double* src, size_t n) {
+    void* d = take(n * sizeof(double));
+    if (d && n && src && err == hipSuccess) err = hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    return (const double*)d;
+  }
+  double* out(size_t n) { return (double*)take(n * sizeof(double)); }
+  void back(void* dst, const void* src, size_t bytes) {
+    if (dst && src && bytes && err == hipSuccess) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  }
+  cilqr_obstacles obstacles(int M, const cilqr_obstacles* obs, size_t span, size_t w_span) {
+    cilqr_obstacles o = {};
+    if (M <= 0) return o;
+    o = *obs;
+    o.pose = in(obs->pose, span * 4);
+    o.dim = in(obs->dim, span * 2);
+    o.weight = obs->weight ? in(obs->weight, w_span) : nullptr;
+    return o;
+  }
+  int rc(const char* what) {
+    if (over) return fail(CILQR_ERR_ARG, "%s: batch does not fit the device buffers reserved at create", what);
+    if (err != hipSuccess) return fail(CILQR_ERR_HIP, "%s: copy failed: %s", what, hipGetErrorString(err));
+    return CILQR_OK;
+  }
+};
+// Ends a host-buffer call: waits for the stream whatever happened, so that no copy to or from the caller's memory stays in flight.
+int host_io_finish(cilqr_handle* h, int rc) {
+  const std::string msg = cilqr::g_last_error;
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  if (rc != CILQR_OK) { cilqr::g_last_error = msg; return rc; }
+  if (e != hipSuccess) return fail(CILQR_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_gains_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* poly,
+                             const double* xplan_fl, const cilqr_obstacles* obs, double lamb, double* k_out, double* K_out,
+                             int32_t* ok_out) {
+  int rc = gains_check(h, B, N, M, X, U, poly, xplan_fl, obs, lamb, k_out, K_out, nullptr, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::gains_lds_bytes(N, h->kp.n_samples) > cilqr::GAINS_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_gains_batch: %d path samples and horizon %d do not fit 64 KiB of LDS", h->kp.n_samples, N);
+  cilqr::GainsArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.s.X_out = const_cast<double*>(X);  // read only (cilqr_internal.h, GainsArgs)
+  a.s.U = const_cast<double*>(U);
+  a.s.poly = poly; a.s.xplan_fl = xplan_fl;
+  a.k_out = k_out; a.K_out = K_out; a.ok_out = ok_out; a.lamb = lamb;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_gains(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_gains_batch(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* poly,
+                      const double* xplan_fl, const cilqr_obstacles* obs, double lamb, double* k_out, double* K_out, int32_t* ok_out) {
+  size_t span = 0, w_span = 0;
+  int rc = gains_check(h, B, N, M, X, U, poly, xplan_fl, obs, lamb, k_out, K_out, &span, &w_span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t b = B, n = N;
+  HostIo io(h);
+  const double* dX = io.in(X, b * 4 * (n + 1));
+  const double* dU = io.in(U, b * 2 * n);
+  const double* dpoly = io.in(poly, b * CILQR_POLY_COEFFS);
+  const double* dfl = io.in(xplan_fl, b * 2);
+  const cilqr_obstacles o = io.obstacles(M, obs, span, w_span);
+  double* dk = io.out(b * 2 * n);
+  double* dK = io.out(b * 8 * n);
+  int32_t* dok = ok_out ? (int32_t*)io.take(b * sizeof(int32_t)) : nullptr;
+  rc = io.rc("cilqr_gains_batch");
+  if (!rc) rc = cilqr_gains_batch_device(h, h->stream, B, N, M, dX, dU, dpoly, dfl, M > 0 ? &o : nullptr, lamb, dk, dK, dok);
+  if (!rc) {
+    io.back(k_out, dk, b * 2 * n * sizeof(double));
+    io.back(K_out, dK, b * 8 * n * sizeof(double));
+    io.back(ok_out, dok, b * sizeof(int32_t));
+    rc = io.rc("cilqr_gains_batch");
+  }
+  return host_io_finish(h, rc);
+}
+
+int cilqr_rollout_batch_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, const double* U, const double* k,
+                               const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, double* X_roll,
+                               double* U_roll) {
+  int rc = rollout_check(h, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, X_roll, U_roll, false);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::rollout_lds_bytes(N) > cilqr::GAINS_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rollout_batch: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::RolloutArgs a = {};
+  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
+  a.delta_bs = (long long)delta_batch_stride * S * 4;
+  a.X_roll = X_roll; a.U_roll = U_roll; a.k_scale = k_scale;
+  a.B = B; a.N = N; a.S = S; a.kp = h->kp;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_rollout(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_rollout_batch(cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                        const double* delta, int64_t delta_batch_stride, double k_scale, double* X_roll, double* U_roll) {
+  int rc = rollout_check(h, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, X_roll, U_roll, true);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t b = B, n = N, rows = b * (size_t)S;
+  // (a stride above 1 would address blocks between the solves' sets)
+  if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: the host-buffer form takes delta_batch_stride 0 or 1");
+  const size_t n_delta = (delta_batch_stride == 0 ? 1 : b) * (size_t)S * 4;
+  HostIo io(h);
+  const double* dX = io.in(X, b * 4 * (n + 1));
+  const double* dU = io.in(U, b * 2 * n);
+  const double* dk = io.in(k, b * 2 * n);
+  const double* dK = io.in(K, b * 8 * n);
+  const double* dd = io.in(delta, n_delta);
+  double* dXr = io.out(rows * 4 * (n + 1));
+  double* dUr = io.out(rows * 2 * n);
+  rc = io.rc("cilqr_rollout_batch");
+  if (!rc) rc = cilqr_rollout_batch_device(h, h->stream, B, N, S, dX, dU, dk, dK, dd, delta_batch_stride, k_scale, dXr, dUr);
+  if (!rc) {
+    io.back(X_roll, dXr, rows * 4 * (n + 1) * sizeof(double));
+    io.back(U_roll, dUr, rows * 2 * n * sizeof(double));
+    rc = io.rc("cilqr_rollout_batch");
+  }
+  return host_io_finish(h, rc);
+}
+
+int cilqr_score_rollouts_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X_roll, const double* U_roll,
+                                const double* poly, const double* xplan_fl, const cilqr_obstacles* obs, double max_risk,
+                                double* row_score, double* risk, double* total) {
+  int rc = score_rollouts_check(h, B, N, M, S, X_roll, U_roll, poly, xplan_fl, obs, row_score, risk, false, nullptr, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::ScoreArgs a = {};
+  a.s = handle_args(h, B * S, N, M, 0);  // (B counts the rows of the launch)
+  set_obstacles(a.s, M, obs);
+  a.rows = S;
+  rc = score_device(h, stream, a, X_roll, U_roll, poly, xplan_fl, 1.0, row_score, nullptr, 0);
+  if (rc) return rc;
+  const cilqr::RiskArgs r{row_score, risk, total, max_risk, B, S};
+  HIP_TRY(cilqr::launch_risk(r, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const double* X_roll, const double* U_roll, const double* poly,
+                         const double* xplan_fl, const cilqr_obstacles* obs, double max_risk, double* row_score, double* risk,
+                         double* total) {
+  size_t span = 0, w_span = 0;
+  int rc = score_rollouts_check(h, B, N, M, S, X_roll, U_roll, poly, xplan_fl, obs, row_score, risk, true, &span, &w_span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t b = B, n = N, rows = b * (size_t)S;
+  HostIo io(h);
+  const double* dX = io.in(X_roll, rows * 4 * (n + 1));
+  const double* dU = io.in(U_roll, rows * 2 * n);
+  const double* dpoly = io.in(poly, b * CILQR_POLY_COEFFS);
+  const double* dfl = io.in(xplan_fl, b * 2);
+  const cilqr_obstacles o = io.obstacles(M, obs, span, w_span);
+  double* drow = io.out(rows * CILQR_SCORE_FIELDS);
+  double* drisk = io.out(b * CILQR_RISK_FIELDS);
+  double* dtot = total ? io.out(b) : nullptr;
+  rc = io.rc("cilqr_score_rollouts");
+  if (!rc) rc = cilqr_score_rollouts_device(h, h->stream, B, N, M, S, dX, dU, dpoly, dfl, M > 0 ? &o : nullptr, max_risk, drow, drisk, dtot);
+  if (!rc) {
+    io.back(row_score, drow, rows * CILQR_SCORE_FIELDS * sizeof(double));
+    io.back(risk, drisk, b * CILQR_RISK_FIELDS * sizeof(double));
+    io.back(total, dtot, b * sizeof(double));
+    rc = io.rc("cilqr_score_rollouts");
+  }
+  return host_io_finish(h, rc);
 }
 
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,

@@ -104,9 +104,49 @@ struct ScoreArgs {
   double* total;         // [B] or null
   double max_collision;
   double w_uncertainty;  // Parameters::w_uncertainty (UncArgs::scale holds it divided by the probe count only)
+  // rows per solve (cilqr_score_rollouts: s.B counts ROWS, row r reads X_out / U at r and everything else of solve r / rows); the
+  // score calls pass 1
+  int32_t rows;
 };
 hipError_t launch_score(const ScoreArgs& a, hipStream_t stream);
 size_t score_lds_bytes(int N, int S, int n_counters);  // n_counters: n_obs·N per-(t, o) sample counters of the sampled form, else 0
+// Each solve's S score rows → risk [B][CILQR_RISK_FIELDS], total [B] or null (cilqr_score.hip): one wavefront per solve.
+struct RiskArgs {
+  const double* row_score;  // [B·S][CILQR_SCORE_FIELDS]
+  double* risk;
+  double* total;
+  double max_risk;
+  int32_t B, S;
+};
+hipError_t launch_risk(const RiskArgs& a, hipStream_t stream);
+
+// One backward pass at a given trajectory (cilqr_gains.hip; cilqr_gains_batch*): one wavefront per solve.  `s` carries what the
+// launch shares with a solve — X_out = the trajectory (read only), U, poly, xplan_fl, the strided obstacle fields, B, N, M, kp, unc.
+struct GainsArgs {
+  SolveArgs s;
+  double* k_out;    // [B][2N]
+  double* K_out;    // [B][8N], K[8t + r + 2c]
+  int32_t* ok_out;  // [B] or null
+  double lamb;
+};
+hipError_t launch_gains(const GainsArgs& a, hipStream_t stream);
+size_t gains_lds_bytes(int N, int n_path_samples);
+constexpr size_t GAINS_LDS_MAX = 64 * 1024;
+
+// S closed-loop rollouts per solve (cilqr_rollout.hip; cilqr_rollout_batch*): lane = sample, a wavefront holds up to 64 samples of
+// one solve.
+struct RolloutArgs {
+  const double *X, *U, *k, *K;  // nominal trajectory and gains, [B][…]
+  const double* delta;          // [B or 1][S][4]
+  long long delta_bs;           // doubles between two solves' offset sets (0: shared)
+  double* X_roll;               // [B·S][4(N+1)]
+  double* U_roll;               // [B·S][2N]
+  double k_scale;
+  int32_t B, N, S;
+  KParams kp;
+};
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t stream);
+size_t rollout_lds_bytes(int N);
 
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {

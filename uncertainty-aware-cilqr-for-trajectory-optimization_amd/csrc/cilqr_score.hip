@@ -16,6 +16,9 @@
 //            samples with c > 0 on either circle in LDS integers (integer adds: any order gives the same count)
 // Every phase reads its arguments through phase_args / phase_params (cilqr_device.hpp): no scratch memory, no spilled register,
 // 128 vector registers at most (make check).
+// cilqr_score_rollouts launches the same kernel over B·S rows, `rows` = S of them per solve (instantiation ROWS; S = 1 launches the
+// score calls' own instantiation): row r is scored against solve r / S; cilqr_risk_kernel then reduces each solve's rows (one
+// wavefront per solve, the same butterflies).
 // x_N carries no cost, as in the reference (get_state_cost and get_J visit t < N).
 #include "cilqr_device.hpp"
 
@@ -84,11 +87,23 @@ __device__ __forceinline__ ObsEntry score_entry(const SolveArgs& a, const double
 
 // a.s: the solve's argument block (X_out = the trajectories to score; for SAMPLED, M = nominal obstacles); LDS (dynamic):
 // [sx S][sy S][cos N][sin N][RED_SLOTS per wavefront][entry index per wavefront][n_obs*N counters]
-template <bool SAMPLED>
+struct LdsPath {  // the path samples as closest_sample reads them
+  const double* sx;
+  const double* sy;
+  __device__ __forceinline__ void operator()(int s, double& x, double& y) const { x = sx[s]; y = sy[s]; }
+};
+
+// ROWS (cilqr_score_rollouts with more than one row per solve; never SAMPLED): row b is scored against solve b / rows, and the
+// closest path sample is found by closest_sample's window — built to return the full scan's index, ties included (cilqr_device.hpp;
+// its squared distances come from the shared helper, so only two samples equidistant to the last bit could be ordered differently),
+// hence the same bits — because the scan over all samples on N of 256 lanes is most of a workgroup's time and there are B·S workgroups.
+template <bool SAMPLED, bool ROWS = false>
 __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a) {
   extern __shared__ double lds[];
   // (every phase reads the argument block through phase_args: its scalar registers are live for that phase only)
+  // b: the row scored (X, U, the outputs); sb: the solve whose path, obstacles, weights and map it is scored against (rows == 1: b)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int sb = ROWS ? b / a.rows : b;
   const int N = a.s.N, S = a.s.kp.n_samples;
   double* sx = lds;
   double* sy = sx + S;
@@ -103,9 +118,9 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
   // ---- phase 0: the path samples; the collision counters
   {
     const SolveArgs& s = phase_args();
-    const double* pc = s.poly + (size_t)b * CILQR_POLY_COEFFS;
+    const double* pc = s.poly + (size_t)sb * CILQR_POLY_COEFFS;
     SampleGrid g;
-    make_sample_grid(g, s.xplan_fl[2 * b], s.xplan_fl[2 * b + 1], S);
+    make_sample_grid(g, s.xplan_fl[2 * (size_t)sb], s.xplan_fl[2 * (size_t)sb + 1], S);
     for (int i = tid; i < S; i += SCORE_THREADS) sample_xy(g, pc, i, sx[i], sy[i]);
     for (int i = tid; i < n_hits; i += SCORE_THREADS) hits[i] = 0;
   }
@@ -117,6 +132,8 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
 #pragma clang fp contract(off)  // the closest-point comparison decides an index
     const KParams& kp = phase_params();
     const double* U = phase_args().U + (size_t)b * 2 * N;
+    SampleGrid grid;
+    if (ROWS) make_sample_grid(grid, phase_args().xplan_fl[2 * (size_t)sb], phase_args().xplan_fl[2 * (size_t)sb + 1], S);
     for (int t = tid; t < N; t += SCORE_THREADS) {
       const double px = X[4 * t], py = X[4 * t + 1], v = X[4 * t + 2];
       const double u0 = U[2 * t], u1 = U[2 * t + 1];
@@ -125,11 +142,15 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
       ect[t] = ct;
       est[t] = st;
       // I/Constraints.cpp:43-56: strict-< first minimum over all S samples
-      double md = (sx[0] - px) * (sx[0] - px) + (sy[0] - py) * (sy[0] - py);
       int best = 0;
-      for (int i = 1; i < S; ++i) {
-        const double d = (sx[i] - px) * (sx[i] - px) + (sy[i] - py) * (sy[i] - py);
-        if (d < md) { md = d; best = i; }
+      if (ROWS) {
+        best = closest_sample<false>(S, grid, px, py, LdsPath{sx, sy});
+      } else {
+        double md = (sx[0] - px) * (sx[0] - px) + (sy[0] - py) * (sy[0] - py);
+        for (int i = 1; i < S; ++i) {
+          const double d = (sx[i] - px) * (sx[i] - px) + (sy[i] - py) * (sy[i] - py);
+          if (d < md) { md = d; best = i; }
+        }
       }
       track = track + stage_cost(kp, px - sx[best], py - sy[best], v - kp.desired_speed, u0, u1);
     }
@@ -153,10 +174,10 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
   // the map cost in a loop of its own, as in the solve kernels: its registers stay out of the other phases' allocation
   if (phase_args().unc.layer) {
     const UncArgs& u = phase_args().unc;
-    const UncPose po = unc_pose(u, b);
+    const UncPose po = unc_pose(u, sb);
     for (int t = tid; t < N; t += SCORE_THREADS) {
       double g0 = 0.0, g1 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0;  // (the derivatives are the solve's business)
-      unc = unc + unc_cost_add(u, po, b, X[4 * t], X[4 * t + 1], ect[t], est[t], g0, g1, h0, h1, h2);
+      unc = unc + unc_cost_add(u, po, sb, X[4 * t], X[4 * t + 1], ect[t], est[t], g0, g1, h0, h1, h2);
     }
   }
   // (their wavefront sums leave the registers before phase 2: butterflies, then lane 0 → this wavefront's slots)
@@ -180,12 +201,12 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
     const double* Xb = s.X_out + (size_t)b * 4 * (N + 1);
     const int M = SAMPLED ? s.M * s.n_samples : s.M;
     const int n_ent = M * N;
-    const double* wts = SAMPLED ? nullptr : obs_weights(s, b);
+    const double* wts = SAMPLED ? nullptr : obs_weights(s, sb);
     for (int e = tid; e < n_ent; e += SCORE_THREADS) {
       const int m = e / N, t = e - m * N;
       int o;
       double w;
-      const ObsEntry en = score_entry<SAMPLED>(s, wts, b, m, t, o, w);
+      const ObsEntry en = score_entry<SAMPLED>(s, wts, sb, m, t, o, w);
       const ObsConsts oc = make_obs_consts(kp, Xb[4 * t], Xb[4 * t + 1], ect[t], est[t]);
       double cf, cr;
       circle_constraints(oc, en, cf, cr);
@@ -244,6 +265,43 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
   }
 }
 
+// Each solve's S score rows → its risk fields (cilqr_risk_field) and the `total` the pick ranks by.  One wavefront per solve: lane
+// l takes rows l, l + 64, … in ascending order, the lanes are joined by the xor butterflies above — a tree fixed by S alone; the
+// hit count is an integer, (worst c, lowest row) lexicographic.
+__global__ __launch_bounds__(WAVE) void cilqr_risk_kernel(RiskArgs a) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
+  const double* rows = a.row_score + (size_t)b * (size_t)S * CILQR_SCORE_FIELDS;
+  const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
+  double sum = 0.0, max_c = -__builtin_huge_val();
+  int max_r = 0x7fffffff, hits = 0;
+  for (int r = lane; r < S; r += WAVE) {
+    const double* q = rows + (size_t)r * CILQR_SCORE_FIELDS;
+    const double track = q[CILQR_SCORE_TRACK], ctrl = q[CILQR_SCORE_CONTROL], obst = q[CILQR_SCORE_OBSTACLE], unc = q[CILQR_SCORE_UNCERTAINTY];
+    const double c = q[CILQR_SCORE_MAX_C];
+    const bool finite = fabs(track) < big && fabs(ctrl) < big && fabs(obst) < big && fabs(unc) < big;
+    hits += (c > 0.0 || !finite) ? 1 : 0;
+    cmax_merge(max_c, max_r, c, r);
+    sum = sum + (((track + ctrl) + obst) + unc);
+  }
+  sum = wave_sum(sum);
+  for (int o = 32; o > 0; o >>= 1) {
+    hits += __shfl_xor(hits, o, WAVE);
+    const double oc = __shfl_xor(max_c, o, WAVE);
+    const int orow = __shfl_xor(max_r, o, WAVE);
+    cmax_merge(max_c, max_r, oc, orow);
+  }
+  if (lane == 0) {
+    const double share = (double)hits / (double)S, mean = sum / (double)S;
+    double* out = a.risk + (size_t)b * CILQR_RISK_FIELDS;
+    out[CILQR_RISK_COLLISION] = share;
+    out[CILQR_RISK_WORST_C] = max_c;
+    out[CILQR_RISK_WORST_ROW] = max_r == 0x7fffffff ? -1.0 : (double)max_r;
+    out[CILQR_RISK_MEAN_TOTAL] = mean;
+    if (a.total) a.total[b] = fabs(mean) < big && !(share > a.max_risk) ? mean : __builtin_nan("");
+  }
+}
+
 }  // namespace
 
 size_t score_lds_bytes(int N, int S, int n_counters) {
@@ -257,7 +315,14 @@ hipError_t launch_score(const ScoreArgs& a, hipStream_t stream) {
   const bool sampled = s.n_samples > 0;
   const size_t lds = score_lds_bytes(s.N, s.kp.n_samples, sampled ? s.M * s.N : 0);
   if (sampled) hipLaunchKernelGGL(cilqr_score_kernel<true>, dim3(s.B), dim3(SCORE_THREADS), lds, stream, a);
+  else if (a.rows > 1) hipLaunchKernelGGL((cilqr_score_kernel<false, true>), dim3(s.B), dim3(SCORE_THREADS), lds, stream, a);
   else hipLaunchKernelGGL(cilqr_score_kernel<false>, dim3(s.B), dim3(SCORE_THREADS), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_risk(const RiskArgs& a, hipStream_t stream) {
+  if (a.B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cilqr_risk_kernel, dim3(a.B), dim3(WAVE), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -1,5 +1,8 @@
-// ilqr_adapter.cpp — see ilqr_adapter.h.  Pure host C++ over the C-ABI (no HIP here).
+// ilqr_adapter.cpp — see ilqr_adapter.h.  Host C++ over the C-ABI; the HIP runtime is used for one thing only: the device block
+// and the stream of the pose-noise check (set_pose_noise_check), whose pipeline stays on the device between the C-ABI's _device calls.
 #include "ilqr_adapter.h"
+
+#include <hip/hip_runtime.h>
 
 #include <string.h>
 
@@ -28,7 +31,12 @@ iLQR::iLQR(const Parameters& params, int device, int max_obstacles, int max_cand
   check(cilqr_default_control_seq(N, control_seq_.a.data()), "cilqr_default_control_seq");
 }
 
-iLQR::~iLQR() { cilqr_destroy(h_); }
+iLQR::~iLQR() {
+  if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);
+  if (noise_dev_) (void)hipFree(noise_dev_);
+  if (noise_stream_) (void)hipStreamDestroy((hipStream_t)noise_stream_);
+  cilqr_destroy(h_);
+}
 
 void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
   if ((int)obstacles.size() > max_obstacles_) throw std::runtime_error("set_Obstacle: more obstacles than max_obstacles");
@@ -153,6 +161,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
+  if (!noise_.empty()) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
@@ -192,6 +201,121 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   last_iterations = iters[best];
   last_exit = status[best];
   last_cost = J[best];
+  return best;
+}
+
+namespace {
+void hip_check(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+}  // namespace
+
+void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb) {
+  if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check: offsets must hold 4 doubles per sample");
+  noise_ = offsets;
+  max_risk_ = max_risk;
+  noise_lamb_ = lamb;
+  last_risk.clear();
+  if (!noise_.empty()) reserve_noise_buffers();
+}
+
+// One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.
+void iLQR::reserve_noise_buffers() {
+  const size_t B = max_candidates_, S = noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = B * S;
+  size_t o = 0;
+  const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
+  NoiseLayout& L = nl_;
+  L.x0 = take(B * 4); L.U = take(B * 2 * N); L.poly = take(B * CILQR_POLY_COEFFS); L.fl = take(B * 2);
+  L.pose = take(M * 4 * N); L.dim = take(M * 2 * N);
+  L.X = take(B * 4 * (N + 1)); L.J = take(B); L.iters = take(B); L.status = take(B);
+  L.k = take(B * 2 * N); L.K = take(B * 8 * N); L.ok = take(B);
+  L.delta = take(S * 4);
+  L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
+  L.risk = take(B * CILQR_RISK_FIELDS); L.total = take(B); L.pair = take(2);
+  L.end = o;
+  hip_check(hipSetDevice(device_), "hipSetDevice");
+  if (!noise_stream_) {
+    hipStream_t st;
+    hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+    noise_stream_ = st;
+  }
+  hip_check(hipStreamSynchronize((hipStream_t)noise_stream_), "hipStreamSynchronize");
+  if (noise_dev_) hip_check(hipFree(noise_dev_), "hipFree");
+  noise_dev_ = nullptr;
+  hip_check(hipMalloc(&noise_dev_, L.end * sizeof(double)), "hipMalloc");
+  hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  noise_horizon_ = params.horizon;
+}
+
+int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_states) {
+  const int N = params.horizon, M = (int)obstacles_.size(), S = (int)(noise_.size() / 4);
+  if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
+  std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
+  const int W = params.num_of_local_wpts;
+  std::vector<double> ref((size_t)B * 2 * W);
+  std::vector<int32_t> n_ref(B);
+  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), poly.data(), fl.data(),
+                               ref.data(), n_ref.data()), "cilqr_local_plan_batch");
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
+  const cilqr_obstacles host_obs = obstacle_strides();
+  hip_check(hipSetDevice(device_), "hipSetDevice");
+  hipStream_t st = (hipStream_t)noise_stream_;
+  double* d = (double*)noise_dev_;
+  const NoiseLayout& L = nl_;
+  const auto up = [&](size_t at, const void* src, size_t doubles) {
+    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  };
+  const auto down = [&](void* dst, size_t at, size_t bytes) {
+    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  };
+  up(L.x0, ego_states.data(), (size_t)B * 4);
+  up(L.U, U.data(), U.size());
+  up(L.poly, poly.data(), poly.size());
+  up(L.fl, fl.data(), fl.size());
+  up(L.pose, obs_pose_.data(), obs_pose_.size());
+  up(L.dim, obs_dim_.data(), obs_dim_.size());
+  cilqr_obstacles obs = host_obs;  // the same strides over the device copies
+  obs.pose = d + L.pose;
+  obs.dim = d + L.dim;
+  const cilqr_obstacles* po = M ? &obs : nullptr;
+  int rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+                                              (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+  if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+  if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
+  if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
+  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + L.total, d + L.pair);
+  if (rc) {
+    const std::string msg = cilqr_last_error();
+    (void)hipStreamSynchronize(st);
+    throw std::runtime_error("run_candidates (pose-noise check): " + msg);
+  }
+  double pair[2] = {0.0, -1.0};
+  last_scores.clear();
+  last_risk.assign((size_t)B * CILQR_RISK_FIELDS, 0.0);
+  down(pair, L.pair, sizeof(pair));
+  down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  const int best = (int)pair[1];
+  if (best < 0) return -1;  // every candidate rejected: results and warm start stay
+  Matrix Xb(4, N + 1);
+  int32_t iters = 0, status = 0;
+  double J = 0.0;
+  down(Xb.a.data(), L.X + (size_t)best * 4 * (N + 1), Xb.a.size() * sizeof(double));
+  std::vector<double> Ub((size_t)2 * N);
+  down(Ub.data(), L.U + (size_t)best * 2 * N, Ub.size() * sizeof(double));
+  down(&J, L.J + (size_t)best, sizeof(double));
+  hip_check(hipMemcpyAsync(&iters, (int32_t*)(d + L.iters) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  hip_check(hipMemcpyAsync(&status, (int32_t*)(d + L.status) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  X_result = Xb;
+  control_seq_.a = Ub;
+  U_result = control_seq_;
+  ref_traj_result = Matrix(2, n_ref[best]);
+  for (int i = 0; i < 2 * n_ref[best]; ++i) ref_traj_result.a[i] = ref[(size_t)best * 2 * W + i];
+  last_iterations = iters;
+  last_exit = status;
+  last_cost = J;
   return best;
 }
 

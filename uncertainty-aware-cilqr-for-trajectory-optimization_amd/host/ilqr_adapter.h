@@ -103,6 +103,18 @@ class iLQR {
   // last_* fields stay as they were.  max_collision = 0 rejects any contact, 1 rejects nothing on collision grounds.
   int run_candidates(const std::vector<double>& ego_states /* 4 per candidate */);
   void set_candidate_pick(CandidatePick pick, double max_collision = 0.0);
+  // Pose-noise check.  The node plans from a pose it knows to be wrong: it adds Gaussian noise to the ego pose before run_step.
+  // `offsets` are S draws of that noise, (dx, dy, dv, dtheta) each, made ONCE by the node with its own sigmas.  With a non-empty set,
+  // run_candidates judges every solved candidate by where the vehicle may really be: solve -> cilqr_gains_batch_device(lamb) ->
+  // cilqr_rollout_batch_device (k_scale 0: the plan is tracked by the feedback gains from each offset start) ->
+  // cilqr_score_rollouts_device(max_risk) -> cilqr_argmin_device on its `total`, one after the other on one stream with nothing but
+  // the pick, the risk rows and the picked candidate's results coming back.  last_risk then holds CILQR_RISK_FIELDS per candidate.
+  // The pick is the cheapest mean total among the candidates whose share of colliding rollouts is at most max_risk; when every
+  // candidate is rejected the call returns -1 and X_result, U_result, the warm start and the last_* result fields stay as they were
+  // (the contract of set_candidate_pick, which this check takes precedence over; last_scores is then empty).  lamb: the
+  // regularisation of the gains' backward pass (1.0: the reference's starting value).  Device buffers are sized here, from
+  // max_candidates x offsets / 4 and the current horizon, not per call.  An empty `offsets` switches the check off (the default).
+  void set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb = 1.0);
 
   Parameters params;
   Matrix X_result;         // 4 × (horizon + 1)
@@ -112,6 +124,7 @@ class iLQR {
   int last_exit = 0;  // cilqr_exit
   double last_cost = 0.0;
   std::vector<double> last_scores;  // run_candidates under MinTotalCost: CILQR_SCORE_FIELDS per candidate; empty otherwise
+  std::vector<double> last_risk;  // run_candidates under set_pose_noise_check: CILQR_RISK_FIELDS per candidate; empty otherwise
 
  private:
   void pack_obstacles();
@@ -128,6 +141,19 @@ class iLQR {
   bool held_ = false;
   int packed_horizon_ = -1;  // the horizon obs_pose_ / obs_dim_ were packed for
   std::vector<double> obs_pose_, obs_dim_;  // packed ONCE: [obstacle][4N] / [2N], or [obstacle][4] / [2] when held_
+  // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
+  // so that this header needs no HIP
+  struct NoiseLayout {
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, end;
+  };
+  int run_candidates_noise_checked(int B, const std::vector<double>& ego_states);
+  void reserve_noise_buffers();
+  std::vector<double> noise_;
+  double max_risk_ = 1.0, noise_lamb_ = 1.0;
+  NoiseLayout nl_{};
+  int noise_horizon_ = -1;
+  void* noise_dev_ = nullptr;
+  void* noise_stream_ = nullptr;
 };
 
 }  // namespace cilqr_host
