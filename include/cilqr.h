@@ -38,6 +38,7 @@
  *   iLQR::backward_pass's k, K (computed, never handed out)   cilqr_gains_batch(_device): the gains of one backward pass
  *   iLQR::forward_pass's control law from other starts (none)  cilqr_rollout_batch(_device), cilqr_score_rollouts(_device):
  *                                                                closed-loop rollouts from offset starts, collision risk per solve
+ *                                                                cilqr_rollout_risk(_device): that risk in one launch, no rollout stored
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -454,6 +455,50 @@ int cilqr_score_rollouts_device(cilqr_handle* h, void* stream, int B, int N, int
 int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const double* X_roll, const double* U_roll, const double* poly,
                          const double* xplan_fl, const cilqr_obstacles* obs, double max_risk, double* row_score, double* risk,
                          double* total);
+
+/* --- fused rollout risk: the collision share per solve with no rollout stored (new) -------------------------------------------
+ * cilqr_rollout_risk(_device) runs the rollouts of cilqr_rollout_batch (same X, U, k, K, delta, delta_batch_stride, k_scale, same
+ * arithmetic) and evaluates, at every state x'_t with t < N (x'_N is not visited, as in the score calls), the obstacle constraints
+ * c = 1 - d'Pd of both ego circles against every obstacle entry (m, t) — the c of cilqr_score_batch — keeping only what a
+ * risk-bounded pick needs.  No X_roll, U_roll or row scores exist: the three-call path's 4*(N+1) + 2*N + 8 doubles per row are
+ * never written.  Ordinary obstacles only (cilqr_obstacles, strides as in cilqr_solve_batch_obstacles; weights are not read).
+ * Nothing here depends on the path (poly, xplan_fl) or on the uncertainty map: neither is an argument, and a map set on the
+ * handle is ignored.
+ *   A row HITS at step t when max(c_front, c_rear) > 0 for some obstacle m, or when one of x', y', v', theta' of x'_t or of the two
+ *   controls u_t is not finite.  A c that is NaN never wins a maximum.
+ * risk [B][CILQR_ROLLOUT_RISK_FIELDS] (required), see the enum; step_hits [B][N] int32 or NULL: the rows that hit AT step t;
+ * total [B] or NULL: total[b] = base[b] when RR_COLLISION <= max_risk and base[b] is finite, else NaN — hand it to
+ * cilqr_argmin_device / cilqr_argmin_global_device.  base [B] is any per-solve cost the caller ranks by (J_out, or the `total` of
+ * cilqr_score_batch); total without base is CILQR_ERR_ARG.
+ *   Counts are integers and (max c, lowest row, lowest entry) is lexicographic, so every field is independent of the evaluation
+ *   order: a solve's results depend on its own inputs and offsets alone — the same bits whatever B is and wherever the solve sits
+ *   in the batch.  Fed the same inputs, RR_COLLISION, RR_WORST_C and RR_WORST_ROW equal RISK_COLLISION, RISK_WORST_C (bit for bit)
+ *   and RISK_WORST_ROW of cilqr_rollout_batch + cilqr_score_rollouts whenever every row's cost terms are finite exactly when its
+ *   states and controls are, and RR_WORST_ENTRY is that row's SCORE_MAX_C_ENTRY.
+ * Mapping: lane = row; solve b takes ceil(S/256) workgroups, each leaving one partial record (8 doubles + max_horizon int32) in a
+ * buffer the handle allocates at create for max_batch records; nothing is allocated per call.
+ * CILQR_ERR_ARG: NULL X, U, k, K, delta or risk; S < 1; a negative stride; a k_scale or max_risk that is NaN; B, N or M beyond the
+ * cilqr_create limits; B*ceil(S/256) > max_batch.  The host-buffer form additionally takes delta_batch_stride 0 or 1, and its
+ * arrays — X, U, k, K, the obstacle span, (delta_batch_stride ? B : 1)*S*4 offsets, base, and the outputs — must fit the device
+ * arena reserved at create: (delta_batch_stride ? B : 1)*S <= max_batch*max_horizon always fits (no rollout rows travel).
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(14*N + 4) + 48*M*N + 4*N + 112 bytes (nominal records, obstacle entries, step
+ * counters, reduction slots), exceeds 64 KiB. */
+#define CILQR_ROLLOUT_RISK_FIELDS 6
+typedef enum cilqr_rollout_risk_field {
+  CILQR_RR_COLLISION = 0,    /* rows that hit at any step / S */
+  CILQR_RR_WORST_C = 1,      /* max over rows, t < N, m, both circles of c;  -HUGE_VAL when M == 0 */
+  CILQR_RR_WORST_ROW = 2,    /* row s of that maximum, lowest on equal values;  -1 when M == 0 */
+  CILQR_RR_WORST_ENTRY = 3,  /* m*N + t of that maximum within that row, lowest on equal values;  -1 when M == 0 */
+  CILQR_RR_FIRST_STEP = 4,   /* lowest t at which any row hits;  -1 when none does */
+  CILQR_RR_STEP_SHARE = 5    /* max over t of (rows that hit AT step t) / S */
+} cilqr_rollout_risk_field;
+int cilqr_rollout_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X, const double* U,
+                              const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                              const cilqr_obstacles* obs, double max_risk, const double* base, double* risk, int32_t* step_hits,
+                              double* total);
+int cilqr_rollout_risk(cilqr_handle* h, int B, int N, int M, int S, const double* X, const double* U, const double* k,
+                       const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, const cilqr_obstacles* obs,
+                       double max_risk, const double* base, double* risk, int32_t* step_hits, double* total);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

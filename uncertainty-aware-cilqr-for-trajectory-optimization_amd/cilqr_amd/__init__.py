@@ -23,6 +23,9 @@ SCORE_FIELDS = 8
 # `cilqr_risk_field`: the columns of a risk row (`Solver.score_rollouts`)
 RISK_FIELDS = 4
 RISK_COLLISION, RISK_WORST_C, RISK_WORST_ROW, RISK_MEAN_TOTAL = range(RISK_FIELDS)
+# `cilqr_rollout_risk_field`: the columns of a fused risk row (`Solver.rollout_risk`)
+ROLLOUT_RISK_FIELDS = 6
+RR_COLLISION, RR_WORST_C, RR_WORST_ROW, RR_WORST_ENTRY, RR_FIRST_STEP, RR_STEP_SHARE = range(ROLLOUT_RISK_FIELDS)
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -40,6 +43,7 @@ ABI_SYMBOLS = (
     "cilqr_score_batch", "cilqr_score_batch_device", "cilqr_score_batch_sampled", "cilqr_score_batch_sampled_device",
     "cilqr_gains_batch", "cilqr_gains_batch_device", "cilqr_rollout_batch", "cilqr_rollout_batch_device",
     "cilqr_score_rollouts", "cilqr_score_rollouts_device",
+    "cilqr_rollout_risk", "cilqr_rollout_risk_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -513,6 +517,42 @@ class Solver:
         _check(lib().cilqr_score_rollouts_device(self._h, _vp(stream), int(B), int(N), int(M), int(S), _vp(X_roll), _vp(U_roll), _vp(poly),
                                                  _vp(xplan_fl), C.byref(obs) if M else None, C.c_double(max_risk), _vp(row_score),
                                                  _vp(risk), _vp(total)))
+
+    def rollout_risk(self, N, X, U, k, K, delta, obs_pose=None, obs_dim=None, obs_weight=None, k_scale=0.0, max_risk=1.0, base=None):
+        """`cilqr_rollout_risk`: the collision risk of S closed-loop rollouts per solve in one launch, no rollout stored.  X, U, k, K,
+        delta and k_scale as `rollout_batch`; obstacles in any shape of `obstacle_strides` (weights are accepted and not read).
+        Returns (risk (B, ROLLOUT_RISK_FIELDS), step_hits (B, N) int32, total): total[b] is base[b], NaN where RR_COLLISION exceeds
+        max_risk or base[b] is not finite — hand it to `argmin_device`; None without `base`."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U, k, K = _np64(U).reshape(B, 2 * N), _np64(k).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        delta = _np64(delta)
+        if delta.ndim == 3:
+            if delta.shape[0] != B or delta.shape[2] != 4:
+                raise CilqrError("rollout_risk: delta %s is neither (S, 4) nor (%d, S, 4)" % (delta.shape, B))
+            S, stride = delta.shape[1], 1
+        else:
+            delta = delta.reshape(-1, 4)
+            S, stride = delta.shape[0], 0
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, obs_weight, B, N)
+        base = None if base is None else _np64(base).reshape(B)
+        risk, step_hits = np.zeros((B, ROLLOUT_RISK_FIELDS)), np.zeros((B, N), dtype=np.int32)
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_rollout_risk(self._h, B, int(N), int(M), int(S), _p(X), _p(U), _p(k), _p(K), _p(delta), C.c_int64(stride),
+                                        C.c_double(k_scale), None if obs is None else C.byref(obs), C.c_double(max_risk), _p(base),
+                                        _p(risk), _p(step_hits, _ip), _p(total)))
+        return risk, step_hits, total
+
+    def rollout_risk_device(self, stream, B, N, M, S, X, U, k, K, delta, delta_batch_stride, obs_pose, obs_dim, strides, risk,
+                            step_hits=0, total=0, base=0, k_scale=0.0, max_risk=1.0):
+        """`cilqr_rollout_risk_device`: device addresses; strides (batch, obstacle, step, weight batch) as `score_batch_device`."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_rollout_risk_device(self._h, _vp(stream), int(B), int(N), int(M), int(S), _vp(X), _vp(U), _vp(k), _vp(K),
+                                               _vp(delta), C.c_int64(delta_batch_stride), C.c_double(k_scale),
+                                               C.byref(obs) if M else None, C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_hits),
+                                               _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

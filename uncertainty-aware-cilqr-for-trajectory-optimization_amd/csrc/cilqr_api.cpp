@@ -269,6 +269,9 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   if (err == hipSuccess) err = dmalloc(&h->d_order, B);
   h->hint_B = 0; h->hint_stream = nullptr;
   if (err == hipSuccess) err = dmalloc(&h->d_pair, (size_t)2);
+  // partial records of cilqr_rollout_risk: max_batch of 8 doubles + max_horizon int32 each
+  h->risk_part_stride = cilqr::RISK_PART_DOUBLES + (N + 1) / 2;
+  if (err == hipSuccess) err = dmalloc(&h->d_risk_part, B * h->risk_part_stride);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
   h->comm_ranks = 1;
@@ -300,7 +303,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -916,6 +919,95 @@ int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const doub
     io.back(risk, drisk, b * CILQR_RISK_FIELDS * sizeof(double));
     io.back(total, dtot, b * sizeof(double));
     rc = io.rc("cilqr_score_rollouts");
+  }
+  return host_io_finish(h, rc);
+}
+
+// ---- fused rollout risk (cilqr_risk.hip) -------------------------------------------------------------------------------------------
+namespace {
+int rollout_risk_check(const cilqr_handle* h, int B, int N, int M, int S, const double* X, const double* U, const double* k,
+                       const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, const cilqr_obstacles* obs,
+                       double max_risk, const double* base, const double* risk, const double* total, size_t* span, size_t* w_span) {
+  if (!X || !U || !k || !K || !delta || !risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: total needs base");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: S = %d, needs S >= 1", S);
+  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30)) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: negative stride (or one beyond 2^30)");
+  if (M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: negative stride");
+  if (k_scale != k_scale || max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: k_scale or max_risk is NaN");
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, w_span);
+  if (rc) return rc;
+  const int64_t G = ((int64_t)S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  if ((int64_t)B * G > h->max_batch)
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: B * ceil(S/%d) = %lld partial records above max_batch = %d", cilqr::RISK_THREADS,
+                (long long)((int64_t)B * G), h->max_batch);
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_rollout_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X, const double* U,
+                              const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                              const cilqr_obstacles* obs, double max_risk, const double* base, double* risk, int32_t* step_hits,
+                              double* total) {
+  int rc = rollout_risk_check(h, B, N, M, S, X, U, k, K, delta, delta_batch_stride, k_scale, obs, max_risk, base, risk, total, nullptr, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::rollout_risk_lds_bytes(N, M) > cilqr::RISK_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rollout_risk: horizon %d with %d obstacles does not fit 64 KiB of LDS", N, M);
+  cilqr::RolloutRiskArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
+  a.delta_bs = (long long)delta_batch_stride * S * 4;
+  a.k_scale = k_scale; a.max_risk = max_risk;
+  a.base = base; a.risk = risk; a.step_hits = step_hits; a.total = total;
+  a.partials = h->d_risk_part; a.part_stride = (long long)h->risk_part_stride;
+  a.S = S; a.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_rollout_risk(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_rollout_risk(cilqr_handle* h, int B, int N, int M, int S, const double* X, const double* U, const double* k,
+                       const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, const cilqr_obstacles* obs,
+                       double max_risk, const double* base, double* risk, int32_t* step_hits, double* total) {
+  size_t span = 0, w_span = 0;
+  int rc = rollout_risk_check(h, B, N, M, S, X, U, k, K, delta, delta_batch_stride, k_scale, obs, max_risk, base, risk, total, &span, &w_span);
+  if (rc) return rc;
+  // (a stride above 1 would address blocks between the solves' sets)
+  if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: the host-buffer form takes delta_batch_stride 0 or 1");
+  if (B == 0) return CILQR_OK;
+  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t b = B, n = N;
+  const size_t n_delta = (delta_batch_stride == 0 ? 1 : b) * (size_t)S * 4;
+  HostIo io(h);
+  const double* dX = io.in(X, b * 4 * (n + 1));
+  const double* dU = io.in(U, b * 2 * n);
+  const double* dk = io.in(k, b * 2 * n);
+  const double* dK = io.in(K, b * 8 * n);
+  const double* dd = io.in(delta, n_delta);
+  cilqr_obstacles o = {};
+  if (M > 0) {  // (the weights are not read: they do not travel)
+    o = *obs;
+    o.pose = io.in(obs->pose, span * 4);
+    o.dim = io.in(obs->dim, span * 2);
+    o.weight = nullptr;
+  }
+  const double* dbase = base ? io.in(base, b) : nullptr;
+  double* drisk = io.out(b * CILQR_ROLLOUT_RISK_FIELDS);
+  int32_t* dhits = step_hits ? (int32_t*)io.take(b * n * sizeof(int32_t)) : nullptr;
+  double* dtot = total ? io.out(b) : nullptr;
+  rc = io.rc("cilqr_rollout_risk");
+  if (!rc) rc = cilqr_rollout_risk_device(h, h->stream, B, N, M, S, dX, dU, dk, dK, dd, delta_batch_stride, k_scale, M > 0 ? &o : nullptr,
+                                          max_risk, dbase, drisk, dhits, dtot);
+  if (!rc) {
+    io.back(risk, drisk, b * CILQR_ROLLOUT_RISK_FIELDS * sizeof(double));
+    io.back(step_hits, dhits, b * n * sizeof(int32_t));
+    io.back(total, dtot, b * sizeof(double));
+    rc = io.rc("cilqr_rollout_risk");
   }
   return host_io_finish(h, rc);
 }

@@ -95,6 +95,8 @@ struct cilqr_handle {
   int hint_B;          // batch size the order is valid for (0: none)
   void* hint_stream;   // stream it was built on (a call on another stream does not use it)
   double* d_pair;
+  double* d_risk_part;      // partial records of cilqr_rollout_risk: max_batch x risk_part_stride doubles (cilqr_risk.hip)
+  size_t risk_part_stride;  // 8 + ceil(max_horizon / 2)
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;
   size_t src_cap, dst_cap, bbox_cap;

@@ -148,6 +148,31 @@ struct RolloutArgs {
 hipError_t launch_rollout(const RolloutArgs& a, hipStream_t stream);
 size_t rollout_lds_bytes(int N);
 
+// Collision risk of S closed-loop rollouts per solve with no rollout stored (cilqr_risk.hip; cilqr_rollout_risk*): lane = rollout
+// row, a workgroup holds up to RISK_THREADS rows of one solve, solve b has G = ceil(S / RISK_THREADS) workgroups.  `s` carries what
+// the launch shares with a solve — the strided obstacle fields, B, N, M, kp — and comes first, so that phase_args / phase_params
+// of cilqr_device.hpp read it.
+constexpr int RISK_THREADS = 256;
+constexpr int RISK_WAVES = RISK_THREADS / 64;
+constexpr int RISK_PART_DOUBLES = 8;  // doubles at the head of a partial record; N int32 step counts follow
+constexpr size_t RISK_LDS_MAX = 64 * 1024;
+struct RolloutRiskArgs {
+  SolveArgs s;
+  const double *X, *U, *k, *K;  // nominal trajectory and gains, [B][…]
+  const double* delta;          // [B or 1][S][4]
+  long long delta_bs;           // doubles between two solves' offset sets (0: shared)
+  double k_scale, max_risk;
+  const double* base;           // [B] or null (then total is null)
+  double* risk;                 // [B][CILQR_ROLLOUT_RISK_FIELDS]
+  int32_t* step_hits;           // [B][N] or null
+  double* total;                // [B] or null
+  double* partials;             // the handle's: B·G records, part_stride doubles apart (read and written for G > 1 only)
+  long long part_stride;
+  int32_t S, G;
+};
+hipError_t launch_rollout_risk(const RolloutRiskArgs& a, hipStream_t stream);
+size_t rollout_risk_lds_bytes(int N, int M);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

@@ -215,13 +215,27 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
+  noise_fused_ = false;
   last_risk.clear();
+  last_step_hits.clear();
   if (!noise_.empty()) reserve_noise_buffers();
 }
 
-// One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.
+void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
+  if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check_fused: offsets must hold 4 doubles per sample");
+  noise_ = offsets;
+  max_risk_ = max_risk;
+  noise_lamb_ = lamb;
+  noise_fused_ = true;
+  last_risk.clear();
+  last_step_hits.clear();
+  if (!noise_.empty()) reserve_noise_buffers();
+}
+
+// One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.  The fused
+// check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
 void iLQR::reserve_noise_buffers() {
-  const size_t B = max_candidates_, S = noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = B * S;
+  const size_t B = max_candidates_, S = noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = noise_fused_ ? 0 : B * S;
   size_t o = 0;
   const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
   NoiseLayout& L = nl_;
@@ -231,7 +245,8 @@ void iLQR::reserve_noise_buffers() {
   L.k = take(B * 2 * N); L.K = take(B * 8 * N); L.ok = take(B);
   L.delta = take(S * 4);
   L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
-  L.risk = take(B * CILQR_RISK_FIELDS); L.total = take(B); L.pair = take(2);
+  L.risk = take(B * (noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
+  L.score = take(noise_fused_ ? B * CILQR_SCORE_FIELDS : 0); L.base = take(noise_fused_ ? B : 0); L.hits = take(noise_fused_ ? (B * N + 1) / 2 : 0);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -282,8 +297,14 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   int rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
                                               (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
   if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-  if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
-  if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
+  if (noise_fused_) {
+    if (!rc) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
+    if (!rc) rc = cilqr_rollout_risk_device(h_, st, B, N, M, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, po, max_risk_,
+                                            d + L.base, d + L.risk, (int32_t*)(d + L.hits), d + L.total);
+  } else {
+    if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
+    if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
+  }
   if (!rc) rc = cilqr_argmin_device(h_, st, B, d + L.total, d + L.pair);
   if (rc) {
     const std::string msg = cilqr_last_error();
@@ -292,9 +313,16 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   }
   double pair[2] = {0.0, -1.0};
   last_scores.clear();
-  last_risk.assign((size_t)B * CILQR_RISK_FIELDS, 0.0);
+  last_step_hits.clear();
+  last_risk.assign((size_t)B * (noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS), 0.0);
   down(pair, L.pair, sizeof(pair));
   down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
+  if (noise_fused_) {
+    last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
+    last_step_hits.assign((size_t)B * N, 0);
+    down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
+    down(last_step_hits.data(), L.hits, last_step_hits.size() * sizeof(int32_t));
+  }
   hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
   const int best = (int)pair[1];
   if (best < 0) return -1;  // every candidate rejected: results and warm start stay

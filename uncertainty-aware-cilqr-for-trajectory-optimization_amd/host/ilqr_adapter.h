@@ -115,6 +115,15 @@ class iLQR {
   // regularisation of the gains' backward pass (1.0: the reference's starting value).  Device buffers are sized here, from
   // max_candidates x offsets / 4 and the current horizon, not per call.  An empty `offsets` switches the check off (the default).
   void set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb = 1.0);
+  // The same check without stored rollouts: solve -> cilqr_gains_batch_device(lamb) -> cilqr_score_batch_device (the nominal
+  // `total` of every candidate, max_collision 1: nothing is rejected there) -> cilqr_rollout_risk_device(k_scale 0, max_risk, base =
+  // those totals) -> cilqr_argmin_device on its `total`.  The pick is the cheapest NOMINAL total among the candidates whose share of
+  // colliding rollouts is at most max_risk (the stored-rows check ranks by the mean total over the rollouts).  last_risk then holds
+  // CILQR_ROLLOUT_RISK_FIELDS per candidate (cilqr_rollout_risk_field), last_step_hits the rollouts that hit at each step, horizon
+  // per candidate, last_scores the nominal score rows.  Rejection, the -1 return and an empty `offsets` as above.  More than 256
+  // offsets take ceil(S/256) partial records per candidate of the max_candidates the handle holds: run_candidates then takes at most
+  // max_candidates / ceil(S/256) candidates.  Whichever of the two setters was called last applies.
+  void set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb = 1.0);
 
   Parameters params;
   Matrix X_result;         // 4 × (horizon + 1)
@@ -125,6 +134,8 @@ class iLQR {
   double last_cost = 0.0;
   std::vector<double> last_scores;  // run_candidates under MinTotalCost: CILQR_SCORE_FIELDS per candidate; empty otherwise
   std::vector<double> last_risk;  // run_candidates under set_pose_noise_check: CILQR_RISK_FIELDS per candidate; empty otherwise
+                                  // (under set_pose_noise_check_fused: CILQR_ROLLOUT_RISK_FIELDS per candidate)
+  std::vector<int32_t> last_step_hits;  // run_candidates under set_pose_noise_check_fused: horizon per candidate; empty otherwise
 
  private:
   void pack_obstacles();
@@ -144,9 +155,10 @@ class iLQR {
   // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
   // so that this header needs no HIP
   struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, end;
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, end;
   };
   int run_candidates_noise_checked(int B, const std::vector<double>& ego_states);
+  bool noise_fused_ = false;  // set_pose_noise_check_fused was the last setter
   void reserve_noise_buffers();
   std::vector<double> noise_;
   double max_risk_ = 1.0, noise_lamb_ = 1.0;
