@@ -82,20 +82,34 @@ cilqr::SolveArgs handle_args(const cilqr_handle* h, int B, int N, int M, uint32_
   return a;
 }
 
-// Upper bound of what a host-buffer gains, rollout or rollout-score call of at most B solves AND at most B rows places in the arena
-// (HostIo below: every array rounded up to 16 bytes): the obstacle tables, X, U, k, K, the offsets, the rollout rows, the score
-// rows, risk, total, ok.
-size_t risk_io_bytes(size_t B, size_t N, size_t M) {
-  const size_t doubles = B * (CILQR_POLY_COEFFS + 2 + M + 6 * M * N + 2 * (4 * (N + 1) + 2 * N) + 2 * N + 8 * N + 4 + CILQR_SCORE_FIELDS +
-                              CILQR_RISK_FIELDS + 1 + 1);
-  return doubles * sizeof(double) + 32 * 16;
-}
-
 template <typename T>
 hipError_t dmalloc(T** p, size_t n) {
   *p = nullptr;
   if (n == 0) return hipSuccess;
   return hipMalloc((void**)p, n * sizeof(T));
+}
+
+// Staging of the host-pointer costmap calls: grown when a call needs more than any before it.
+int grow(float** p, size_t* cap, size_t n) {
+  if (n <= *cap) return CILQR_OK;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr; *cap = 0;
+  HIP_TRY(dmalloc(p, n));
+  *cap = n;
+  return CILQR_OK;
+}
+
+void set_obstacles(cilqr::SolveArgs& s, int M, const cilqr_obstacles* obs) {
+  if (M <= 0) return;
+  s.obs_pose = obs->pose; s.obs_dim = obs->dim; s.obs_weight = obs->weight;
+  s.obs_bs = obs->batch_stride; s.obs_ms = obs->obstacle_stride; s.obs_ts = obs->step_stride; s.obs_wbs = obs->weight_batch_stride;
+}
+
+// What the four sampled forms check first; `name` is the call's, without its _device suffix.
+int check_sampled(const cilqr_handle* h, const char* name, int B, int N, int n_obs, int n_samples) {
+  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "%s: needs n_obs >= 1 and n_samples >= 2", name);
+  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "%s: n_obs * n_samples too large", name);
+  return check_sizes(h, B, N, n_obs * n_samples);  // the equivalent materialised obstacle count
 }
 
 }  // namespace
@@ -145,8 +159,7 @@ int solve_device(cilqr_handle* h, void* stream, int B, int N, int M, const doubl
                  int32_t* status_out, uint32_t flags) {
   cilqr::SolveArgs a = handle_args(h, B, N, M, flags);
   a.x0 = x0; a.U = U; a.poly = poly; a.xplan_fl = xplan_fl;
-  a.obs_pose = o.pose; a.obs_dim = o.dim; a.obs_weight = M > 0 ? o.weight : nullptr;
-  a.obs_bs = o.batch_stride; a.obs_ms = o.obstacle_stride; a.obs_ts = o.step_stride; a.obs_wbs = o.weight_batch_stride;
+  set_obstacles(a, M, &o);
   // one scene for the batch: the kernels that keep their table in the workspace read one table built in front of them
   a.obs_shared = M > 0 && B > 1 && o.batch_stride == 0 && (!a.obs_weight || o.weight_batch_stride == 0) ? 1 : 0;
   a.X_out = X_out; a.J_out = J_out; a.iters_out = iters_out; a.status_out = status_out;
@@ -247,20 +260,11 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   h->max_batch = max_batch; h->max_horizon = max_horizon; h->max_obstacles = max_obstacles;
   const size_t B = max_batch, N = max_horizon, M = max_obstacles;
   hipError_t err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  {  // arena of the host-buffer entry points: the larger of the two layouts that can be asked for (cilqr_host_io.cpp)
-    const cilqr::IoLayout plain = cilqr::io_layout(B, N, B * M * N, B * M, 0), sampled = cilqr::io_layout(B, N, B * M * N, 0, B * M);
-    h->arena_cap = plain.end > sampled.end ? plain.end : sampled.end;
-    // (the score calls carry X beside U and 9 doubles per solve back: a few doubles per solve more than a solve call)
-    const size_t score_plain = cilqr::score_layout(B, N, B * M * N, B * M, 0).end, score_sampled = cilqr::score_layout(B, N, B * M * N, 0, B * M).end;
-    if (score_plain > h->arena_cap) h->arena_cap = score_plain;
-    if (score_sampled > h->arena_cap) h->arena_cap = score_sampled;
-    // (the host forms of the gains / rollout / rollout-score calls: at most max_batch solves or rows, cilqr_gains_batch below)
-    const size_t risk_io = risk_io_bytes(B, N, M);
-    if (risk_io > h->arena_cap) h->arena_cap = risk_io;
-    if (err == hipSuccess) err = hipMalloc((void**)&h->d_arena, h->arena_cap);
-    h->stage_cap = h->arena_cap < ((size_t)1 << 20) ? h->arena_cap : ((size_t)1 << 20);  // pinned: calls up to 1 MiB travel packed
-    if (err == hipSuccess) err = hipHostMalloc((void**)&h->stage, h->stage_cap, hipHostMallocDefault);
-  }
+  // arena and pinned staging of the host-buffer entry points (cilqr_host_io.cpp): calls up to 1 MiB travel packed
+  h->arena_cap = cilqr::host_arena_bytes(B, N, M);
+  if (err == hipSuccess) err = hipMalloc((void**)&h->d_arena, h->arena_cap);
+  h->stage_cap = h->arena_cap < ((size_t)1 << 20) ? h->arena_cap : ((size_t)1 << 20);
+  if (err == hipSuccess) err = hipHostMalloc((void**)&h->stage, h->stage_cap, hipHostMallocDefault);
   const size_t Bpad = (B + 63) / 64 * 64;  // the grouped kernels pad the batch to whole wavefronts
   if (err == hipSuccess) err = dmalloc(&h->d_obs_tab, Bpad * M * N * 6);
   if (err == hipSuccess) err = dmalloc(&h->d_ws, cilqr::solve_groups_ws_doubles(max_batch, max_horizon));
@@ -502,6 +506,27 @@ int cilqr_solve_batch_obstacles_device(cilqr_handle* h, void* stream, int B, int
   return solve_device(h, stream, B, N, M, x0, U, poly, xplan_fl, M > 0 ? *obs : none, X_out, J_out, iters_out, status_out, flags);
 }
 
+}  // extern "C"
+
+// The host-buffer solve with ordinary obstacles, enqueued (cilqr_handle.h).  The kernels get device J, iters and status arrays
+// whether or not the caller asked for them, and h->d_J points at the costs: the exchange step of cilqr_multi_solve_batch reads them.
+int cilqr::host_solve_enqueue(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly, const double* xplan_fl,
+                              const cilqr_obstacles* obs, size_t span, size_t w_span, double* X_out, double* J_out, int32_t* iters_out,
+                              int32_t* status_out, uint32_t flags) {
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  const double* no_samples = nullptr;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_solve(p, B, N, M, 0, x0, U, poly, xplan_fl, o, span, w_span, no_samples, X_out, J_out, iters_out, status_out);
+  return cilqr::host_enqueue(h, p, [&] {
+    const int rc = cilqr_solve_batch_obstacles_device(h, h->stream, B, N, M, x0, U, poly, xplan_fl, M > 0 ? &o : nullptr, X_out, J_out,
+                                                      iters_out, status_out, flags);
+    if (rc == CILQR_OK) h->d_J = J_out;
+    return rc;
+  }, true);
+}
+
+extern "C" {
+
 int cilqr_solve_batch(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly,
                       const double* xplan_fl, const double* obs_pose, const double* obs_dim, const double* obs_weight,
                       double* X_out, double* J_out, int32_t* iters_out, int32_t* status_out, uint32_t flags) {
@@ -510,10 +535,9 @@ int cilqr_solve_batch(cilqr_handle* h, int B, int N, int M, const double* x0, do
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: null required pointer");
   if (M > 0 && (!obs_pose || !obs_dim)) return fail(CILQR_ERR_ARG, "cilqr_solve_batch: M > 0 but obstacle tables are null");
-  cilqr::HostBatch q{B, N, M, 0, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, nullptr, 0.0, X_out, J_out, iters_out, status_out, flags};
-  rc = cilqr::host_solve_enqueue(h, q);  // (on failure: stream drained, handle free again)
-  if (rc) return rc;
-  return cilqr::host_solve_finish(h);
+  const cilqr_obstacles o{obs_pose, obs_dim, obs_weight, (int64_t)M * N, N, 1, M};  // the dense layout
+  rc = cilqr::host_solve_enqueue(h, B, N, M, x0, U, poly, xplan_fl, &o, (size_t)B * M * N, (size_t)B * M, X_out, J_out, iters_out, status_out, flags);
+  return rc ? rc : cilqr::host_finish(h);
 }
 
 int cilqr_solve_batch_obstacles(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly,
@@ -526,25 +550,15 @@ int cilqr_solve_batch_obstacles(cilqr_handle* h, int B, int N, int M, const doub
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_obstacles: null required pointer");
-  cilqr::HostBatch q{B, N, M, 0, x0, U, poly, xplan_fl, nullptr, nullptr, nullptr, nullptr, 0.0, X_out, J_out, iters_out, status_out, flags};
-  if (M > 0) {  // only the span the strides address travels (cilqr_host_io.cpp)
-    q.obs_pose = obs->pose; q.obs_dim = obs->dim; q.obs_weight = obs->weight;
-    q.strided = true;
-    q.obs_bs = obs->batch_stride; q.obs_ms = obs->obstacle_stride; q.obs_ts = obs->step_stride; q.obs_wbs = obs->weight_batch_stride;
-    q.obs_span = span; q.w_span = w_span;
-  }
-  rc = cilqr::host_solve_enqueue(h, q);  // (on failure: stream drained, handle free again)
-  if (rc) return rc;
-  return cilqr::host_solve_finish(h);
+  rc = cilqr::host_solve_enqueue(h, B, N, M, x0, U, poly, xplan_fl, obs, span, w_span, X_out, J_out, iters_out, status_out, flags);
+  return rc ? rc : cilqr::host_finish(h);
 }
 
 int cilqr_solve_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* x0,
                                      double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
                                      const double* nom_dim, const double* sample_offset, double sample_weight, double* X_out,
                                      double* J_out, int32_t* iters_out, int32_t* status_out, uint32_t flags) {
-  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
-  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: n_obs * n_samples too large");
-  int rc = check_sizes(h, B, N, n_obs * n_samples);  // the equivalent materialised obstacle count
+  int rc = check_sampled(h, "cilqr_solve_batch_sampled", B, N, n_obs, n_samples);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out || !nom_pose || !nom_dim || !sample_offset)
@@ -568,18 +582,20 @@ int cilqr_solve_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_sa
                               const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
                               const double* sample_offset, double sample_weight, double* X_out, double* J_out,
                               int32_t* iters_out, int32_t* status_out, uint32_t flags) {
-  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
-  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: n_obs * n_samples too large");
-  int rc = check_sizes(h, B, N, n_obs * n_samples);
+  int rc = check_sampled(h, "cilqr_solve_batch_sampled", B, N, n_obs, n_samples);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
   if (!x0 || !U || !poly || !xplan_fl || !X_out || !nom_pose || !nom_dim || !sample_offset)
     return fail(CILQR_ERR_ARG, "cilqr_solve_batch_sampled: null required pointer");
-  cilqr::HostBatch q{B, N, n_obs, n_samples, x0, U, poly, xplan_fl, nom_pose, nom_dim, nullptr, sample_offset, sample_weight, X_out, J_out,
-                     iters_out, status_out, flags};
-  rc = cilqr::host_solve_enqueue(h, q);  // (on failure: stream drained, handle free again)
-  if (rc) return rc;
-  return cilqr::host_solve_finish(h);
+  cilqr_obstacles o{nom_pose, nom_dim, nullptr, 0, 0, 0, 0};  // the dense nominal tables
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_solve(p, B, N, n_obs, n_samples, x0, U, poly, xplan_fl, o, (size_t)B * n_obs * N, 0, sample_offset, X_out, J_out, iters_out, status_out);
+  return cilqr::host_call(h, p, [&] {
+    const int rc = cilqr_solve_batch_sampled_device(h, h->stream, B, N, n_obs, n_samples, x0, U, poly, xplan_fl, o.pose, o.dim, sample_offset,
+                                                    sample_weight, X_out, J_out, iters_out, status_out, flags);
+    if (rc == CILQR_OK) h->d_J = J_out;  // where this call's costs lie
+    return rc;
+  }, true);
 }
 
 int cilqr_argmin_device(cilqr_handle* h, void* stream, int B, const double* J, double* out_pair) {
@@ -621,10 +637,7 @@ int cilqr_score_batch_device(cilqr_handle* h, void* stream, int B, int N, int M,
   if (B == 0) return CILQR_OK;
   cilqr::ScoreArgs a = {};
   a.s = handle_args(h, B, N, M, 0);
-  if (M > 0) {
-    a.s.obs_pose = obs->pose; a.s.obs_dim = obs->dim; a.s.obs_weight = obs->weight;
-    a.s.obs_bs = obs->batch_stride; a.s.obs_ms = obs->obstacle_stride; a.s.obs_ts = obs->step_stride; a.s.obs_wbs = obs->weight_batch_stride;
-  }
+  set_obstacles(a.s, M, obs);
   return score_device(h, stream, a, X, U, poly, xplan_fl, max_collision, score, total, 0);
 }
 
@@ -632,9 +645,7 @@ int cilqr_score_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N
                                      const double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
                                      const double* nom_dim, const double* sample_offset, double sample_weight, double max_collision,
                                      double* score, double* total) {
-  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
-  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: n_obs * n_samples too large");
-  int rc = check_sizes(h, B, N, n_obs * n_samples);  // the equivalent materialised obstacle count
+  int rc = check_sampled(h, "cilqr_score_batch_sampled", B, N, n_obs, n_samples);
   if (rc) return rc;
   if (!X || !U || !poly || !xplan_fl || !score || !nom_pose || !nom_dim || !sample_offset)
     return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: null required pointer");
@@ -656,31 +667,30 @@ int cilqr_score_batch(cilqr_handle* h, int B, int N, int M, const double* X, con
   if (rc) return rc;
   if (!X || !U || !poly || !xplan_fl || !score) return fail(CILQR_ERR_ARG, "cilqr_score_batch: null required pointer");
   if (B == 0) return CILQR_OK;
-  cilqr::HostScore q = {};
-  q.B = B; q.N = N; q.M = M;
-  q.X = X; q.U = U; q.poly = poly; q.xplan_fl = xplan_fl;
-  if (M > 0) { q.obs = *obs; q.obs_span = span; q.w_span = w_span; }
-  q.max_collision = max_collision; q.score = score; q.total = total;
-  return cilqr::host_score(h, q);
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  const double* no_samples = nullptr;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_score(p, B, N, M, 0, X, U, poly, xplan_fl, o, span, w_span, no_samples, score, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_score_batch_device(h, h->stream, B, N, M, X, U, poly, xplan_fl, M > 0 ? &o : nullptr, max_collision, score, total);
+  });
 }
 
 int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
                               const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
                               const double* sample_offset, double sample_weight, double max_collision, double* score, double* total) {
-  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: needs n_obs >= 1 and n_samples >= 2");
-  if ((long)n_obs * n_samples > 1 << 20) return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: n_obs * n_samples too large");
-  int rc = check_sizes(h, B, N, n_obs * n_samples);
+  int rc = check_sampled(h, "cilqr_score_batch_sampled", B, N, n_obs, n_samples);
   if (rc) return rc;
   if (!X || !U || !poly || !xplan_fl || !score || !nom_pose || !nom_dim || !sample_offset)
     return fail(CILQR_ERR_ARG, "cilqr_score_batch_sampled: null required pointer");
   if (B == 0) return CILQR_OK;
-  cilqr::HostScore q = {};
-  q.B = B; q.N = N; q.M = n_obs; q.n_samples = n_samples;
-  q.X = X; q.U = U; q.poly = poly; q.xplan_fl = xplan_fl;
-  q.obs.pose = nom_pose; q.obs.dim = nom_dim; q.obs_span = (size_t)B * n_obs * N;
-  q.samp_off = sample_offset; q.samp_w = sample_weight;
-  q.max_collision = max_collision; q.score = score; q.total = total;
-  return cilqr::host_score(h, q);
+  cilqr_obstacles o{nom_pose, nom_dim, nullptr, 0, 0, 0, 0};  // the dense nominal tables
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_score(p, B, N, n_obs, n_samples, X, U, poly, xplan_fl, o, (size_t)B * n_obs * N, 0, sample_offset, score, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_score_batch_sampled_device(h, h->stream, B, N, n_obs, n_samples, X, U, poly, xplan_fl, o.pose, o.dim, sample_offset,
+                                            sample_weight, max_collision, score, total);
+  });
 }
 
 // ---- feedback gains, closed-loop rollouts, collision risk (cilqr_gains.hip, cilqr_rollout.hip, cilqr_score.hip) -----------------
@@ -726,58 +736,6 @@ int score_rollouts_check(const cilqr_handle* h, int B, int N, int M, int S, cons
   if (host && (int64_t)B * S > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_score_rollouts: B * S = %lld rows above max_batch = %d (host-buffer form)", (long long)B * S, h->max_batch);
   return CILQR_OK;
 }
-void set_obstacles(cilqr::SolveArgs& s, int M, const cilqr_obstacles* obs) {
-  if (M <= 0) return;
-  s.obs_pose = obs->pose; s.obs_dim = obs->dim; s.obs_weight = obs->weight;
-  s.obs_bs = obs->batch_stride; s.obs_ms = obs->obstacle_stride; s.obs_ts = obs->step_stride; s.obs_wbs = obs->weight_batch_stride;
-}
-
-// A host-buffer call's arrays in the handle's arena, in the order they are asked for (sized at create: risk_io_bytes); copies are
-// enqueued on the handle's stream.  The first failure is kept and reported by rc().
-struct HostIo {
-  cilqr_handle* h;
-  size_t off = 0;
-  bool over = false;
-  hipError_t err = hipSuccess;
-  explicit HostIo(cilqr_handle* h) : h(h) {}
-  void* take(size_t bytes) {
-    const size_t at = off;
-    off = (off + bytes + 15) & ~(size_t)15;
-    if (off > h->arena_cap) { over = true; return nullptr; }
-    return h->d_arena + at;
-  }
-  const double* in(const double* src, size_t n) {
-    void* d = take(n * sizeof(double));
-    if (d && n && src && err == hipSuccess) err = hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    return (const double*)d;
-  }
-  double* out(size_t n) { return (double*)take(n * sizeof(double)); }
-  void back(void* dst, const void* src, size_t bytes) {
-    if (dst && src && bytes && err == hipSuccess) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
-  }
-  cilqr_obstacles obstacles(int M, const cilqr_obstacles* obs, size_t span, size_t w_span) {
-    cilqr_obstacles o = {};
-    if (M <= 0) return o;
-    o = *obs;
-    o.pose = in(obs->pose, span * 4);
-    o.dim = in(obs->dim, span * 2);
-    o.weight = obs->weight ? in(obs->weight, w_span) : nullptr;
-    return o;
-  }
-  int rc(const char* what) {
-    if (over) return fail(CILQR_ERR_ARG, "%s: batch does not fit the device buffers reserved at create", what);
-    if (err != hipSuccess) return fail(CILQR_ERR_HIP, "%s: copy failed: %s", what, hipGetErrorString(err));
-    return CILQR_OK;
-  }
-};
-// Ends a host-buffer call: waits for the stream whatever happened, so that no copy to or from the caller's memory stays in flight.
-int host_io_finish(cilqr_handle* h, int rc) {
-  const std::string msg = cilqr::g_last_error;
-  const hipError_t e = hipStreamSynchronize(h->stream);
-  if (rc != CILQR_OK) { cilqr::g_last_error = msg; return rc; }
-  if (e != hipSuccess) return fail(CILQR_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-  return CILQR_OK;
-}
 }  // namespace
 
 int cilqr_gains_batch_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* poly,
@@ -806,27 +764,12 @@ int cilqr_gains_batch(cilqr_handle* h, int B, int N, int M, const double* X, con
   int rc = gains_check(h, B, N, M, X, U, poly, xplan_fl, obs, lamb, k_out, K_out, &span, &w_span);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
-  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t b = B, n = N;
-  HostIo io(h);
-  const double* dX = io.in(X, b * 4 * (n + 1));
-  const double* dU = io.in(U, b * 2 * n);
-  const double* dpoly = io.in(poly, b * CILQR_POLY_COEFFS);
-  const double* dfl = io.in(xplan_fl, b * 2);
-  const cilqr_obstacles o = io.obstacles(M, obs, span, w_span);
-  double* dk = io.out(b * 2 * n);
-  double* dK = io.out(b * 8 * n);
-  int32_t* dok = ok_out ? (int32_t*)io.take(b * sizeof(int32_t)) : nullptr;
-  rc = io.rc("cilqr_gains_batch");
-  if (!rc) rc = cilqr_gains_batch_device(h, h->stream, B, N, M, dX, dU, dpoly, dfl, M > 0 ? &o : nullptr, lamb, dk, dK, dok);
-  if (!rc) {
-    io.back(k_out, dk, b * 2 * n * sizeof(double));
-    io.back(K_out, dK, b * 8 * n * sizeof(double));
-    io.back(ok_out, dok, b * sizeof(int32_t));
-    rc = io.rc("cilqr_gains_batch");
-  }
-  return host_io_finish(h, rc);
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_gains(p, B, N, M, X, U, poly, xplan_fl, o, span, w_span, k_out, K_out, ok_out);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_gains_batch_device(h, h->stream, B, N, M, X, U, poly, xplan_fl, M > 0 ? &o : nullptr, lamb, k_out, K_out, ok_out);
+  });
 }
 
 int cilqr_rollout_batch_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, const double* U, const double* k,
@@ -852,28 +795,13 @@ int cilqr_rollout_batch(cilqr_handle* h, int B, int N, int S, const double* X, c
   int rc = rollout_check(h, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, X_roll, U_roll, true);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
-  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t b = B, n = N, rows = b * (size_t)S;
   // (a stride above 1 would address blocks between the solves' sets)
   if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_batch: the host-buffer form takes delta_batch_stride 0 or 1");
-  const size_t n_delta = (delta_batch_stride == 0 ? 1 : b) * (size_t)S * 4;
-  HostIo io(h);
-  const double* dX = io.in(X, b * 4 * (n + 1));
-  const double* dU = io.in(U, b * 2 * n);
-  const double* dk = io.in(k, b * 2 * n);
-  const double* dK = io.in(K, b * 8 * n);
-  const double* dd = io.in(delta, n_delta);
-  double* dXr = io.out(rows * 4 * (n + 1));
-  double* dUr = io.out(rows * 2 * n);
-  rc = io.rc("cilqr_rollout_batch");
-  if (!rc) rc = cilqr_rollout_batch_device(h, h->stream, B, N, S, dX, dU, dk, dK, dd, delta_batch_stride, k_scale, dXr, dUr);
-  if (!rc) {
-    io.back(X_roll, dXr, rows * 4 * (n + 1) * sizeof(double));
-    io.back(U_roll, dUr, rows * 2 * n * sizeof(double));
-    rc = io.rc("cilqr_rollout_batch");
-  }
-  return host_io_finish(h, rc);
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_rollout(p, B, N, S, delta_batch_stride == 0 ? 1 : B, X, U, k, K, delta, X_roll, U_roll);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_rollout_batch_device(h, h->stream, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, X_roll, U_roll);
+  });
 }
 
 int cilqr_score_rollouts_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X_roll, const double* U_roll,
@@ -900,27 +828,13 @@ int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const doub
   int rc = score_rollouts_check(h, B, N, M, S, X_roll, U_roll, poly, xplan_fl, obs, row_score, risk, true, &span, &w_span);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
-  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t b = B, n = N, rows = b * (size_t)S;
-  HostIo io(h);
-  const double* dX = io.in(X_roll, rows * 4 * (n + 1));
-  const double* dU = io.in(U_roll, rows * 2 * n);
-  const double* dpoly = io.in(poly, b * CILQR_POLY_COEFFS);
-  const double* dfl = io.in(xplan_fl, b * 2);
-  const cilqr_obstacles o = io.obstacles(M, obs, span, w_span);
-  double* drow = io.out(rows * CILQR_SCORE_FIELDS);
-  double* drisk = io.out(b * CILQR_RISK_FIELDS);
-  double* dtot = total ? io.out(b) : nullptr;
-  rc = io.rc("cilqr_score_rollouts");
-  if (!rc) rc = cilqr_score_rollouts_device(h, h->stream, B, N, M, S, dX, dU, dpoly, dfl, M > 0 ? &o : nullptr, max_risk, drow, drisk, dtot);
-  if (!rc) {
-    io.back(row_score, drow, rows * CILQR_SCORE_FIELDS * sizeof(double));
-    io.back(risk, drisk, b * CILQR_RISK_FIELDS * sizeof(double));
-    io.back(total, dtot, b * sizeof(double));
-    rc = io.rc("cilqr_score_rollouts");
-  }
-  return host_io_finish(h, rc);
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_score_rollouts(p, B, N, M, S, X_roll, U_roll, poly, xplan_fl, o, span, w_span, row_score, risk, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_score_rollouts_device(h, h->stream, B, N, M, S, X_roll, U_roll, poly, xplan_fl, M > 0 ? &o : nullptr, max_risk, row_score,
+                                       risk, total);
+  });
 }
 
 // ---- fused rollout risk (cilqr_risk.hip) -------------------------------------------------------------------------------------------
@@ -979,37 +893,13 @@ int cilqr_rollout_risk(cilqr_handle* h, int B, int N, int M, int S, const double
   // (a stride above 1 would address blocks between the solves' sets)
   if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: the host-buffer form takes delta_batch_stride 0 or 1");
   if (B == 0) return CILQR_OK;
-  if (h->pending.active) return fail(CILQR_ERR_ARG, "a host-buffer solve is in flight on this handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t b = B, n = N;
-  const size_t n_delta = (delta_batch_stride == 0 ? 1 : b) * (size_t)S * 4;
-  HostIo io(h);
-  const double* dX = io.in(X, b * 4 * (n + 1));
-  const double* dU = io.in(U, b * 2 * n);
-  const double* dk = io.in(k, b * 2 * n);
-  const double* dK = io.in(K, b * 8 * n);
-  const double* dd = io.in(delta, n_delta);
-  cilqr_obstacles o = {};
-  if (M > 0) {  // (the weights are not read: they do not travel)
-    o = *obs;
-    o.pose = io.in(obs->pose, span * 4);
-    o.dim = io.in(obs->dim, span * 2);
-    o.weight = nullptr;
-  }
-  const double* dbase = base ? io.in(base, b) : nullptr;
-  double* drisk = io.out(b * CILQR_ROLLOUT_RISK_FIELDS);
-  int32_t* dhits = step_hits ? (int32_t*)io.take(b * n * sizeof(int32_t)) : nullptr;
-  double* dtot = total ? io.out(b) : nullptr;
-  rc = io.rc("cilqr_rollout_risk");
-  if (!rc) rc = cilqr_rollout_risk_device(h, h->stream, B, N, M, S, dX, dU, dk, dK, dd, delta_batch_stride, k_scale, M > 0 ? &o : nullptr,
-                                          max_risk, dbase, drisk, dhits, dtot);
-  if (!rc) {
-    io.back(risk, drisk, b * CILQR_ROLLOUT_RISK_FIELDS * sizeof(double));
-    io.back(step_hits, dhits, b * n * sizeof(int32_t));
-    io.back(total, dtot, b * sizeof(double));
-    rc = io.rc("cilqr_rollout_risk");
-  }
-  return host_io_finish(h, rc);
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_rollout_risk(p, B, N, M, S, delta_batch_stride == 0 ? 1 : B, X, U, k, K, delta, o, span, base, risk, step_hits, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_rollout_risk_device(h, h->stream, B, N, M, S, X, U, k, K, delta, delta_batch_stride, k_scale, M > 0 ? &o : nullptr, max_risk,
+                                     base, risk, step_hits, total);
+  });
 }
 
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
@@ -1034,18 +924,9 @@ int cilqr_blur_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* 
   if (g->rows < 1 || g->cols < 1) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap: bad geometry");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)g->rows * g->cols;
-  if (n > h->src_cap) {
-    if (h->d_src) HIP_TRY(hipFree(h->d_src));
-    h->d_src = nullptr; h->src_cap = 0;
-    HIP_TRY(dmalloc(&h->d_src, n));
-    h->src_cap = n;
-  }
-  if (n > h->dst_cap) {
-    if (h->d_dst) HIP_TRY(hipFree(h->d_dst));
-    h->d_dst = nullptr; h->dst_cap = 0;
-    HIP_TRY(dmalloc(&h->d_dst, n));
-    h->dst_cap = n;
-  }
+  int rc = grow(&h->d_src, &h->src_cap, n);
+  if (rc == CILQR_OK) rc = grow(&h->d_dst, &h->dst_cap, n);
+  if (rc) return rc;
   void* v_cnt = nullptr;
   if (count_out) {
     int rcs = cilqr::scratch_bytes(h, cilqr::SCR_COUNT, n * sizeof(int32_t), &v_cnt);
@@ -1054,7 +935,7 @@ int cilqr_blur_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* 
   int32_t* d_cnt = (int32_t*)v_cnt;
   hipStream_t s = h->stream;
   HIP_TRY(hipMemcpyAsync(h->d_src, src, n * sizeof(float), hipMemcpyHostToDevice, s));
-  int rc = cilqr_blur_costmap_device(h, s, h->d_src, g, index, vtheta, sigma_x, sigma_y, sigma_theta, h->d_dst, d_cnt);
+  rc = cilqr_blur_costmap_device(h, s, h->d_src, g, index, vtheta, sigma_x, sigma_y, sigma_theta, h->d_dst, d_cnt);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, h->d_dst, n * sizeof(float), hipMemcpyDeviceToHost, s));
   if (count_out) HIP_TRY(hipMemcpyAsync(count_out, d_cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1233,15 +1114,6 @@ int upload_polygons(cilqr_handle* h, hipStream_t s, const cilqr_map_geom& g, int
   for (int q = 0; q < t.n; ++q) memcpy(&table[2 * (size_t)t.n + (size_t)q * 2 * V], vertices + (size_t)kept[q] * V * 2, sizeof(double) * 2 * V);
   // (pageable source: the runtime has staged the copy by the time the call returns, as with the pose tables below)
   HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  return CILQR_OK;
-}
-
-int grow(float** p, size_t* cap, size_t n) {
-  if (n <= *cap) return CILQR_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  HIP_TRY(dmalloc(p, n));
-  *cap = n;
   return CILQR_OK;
 }
 }  // namespace
@@ -1491,29 +1363,14 @@ int cilqr_warp_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* 
   if (sg->rows < 1 || sg->cols < 1 || dg->rows < 1 || dg->cols < 1) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap: bad geometry");
   HIP_TRY(hipSetDevice(h->device));
   const size_t ns = (size_t)sg->rows * sg->cols, nd = (size_t)dg->rows * dg->cols;
-  if (ns > h->src_cap) {
-    if (h->d_src) HIP_TRY(hipFree(h->d_src));
-    h->d_src = nullptr; h->src_cap = 0;
-    HIP_TRY(dmalloc(&h->d_src, ns));
-    h->src_cap = ns;
-  }
-  if (nd > h->dst_cap) {
-    if (h->d_dst) HIP_TRY(hipFree(h->d_dst));
-    h->d_dst = nullptr; h->dst_cap = 0;
-    HIP_TRY(dmalloc(&h->d_dst, nd));
-    h->dst_cap = nd;
-  }
-  if (bbox && nd > h->bbox_cap) {
-    if (h->d_bbox) HIP_TRY(hipFree(h->d_bbox));
-    h->d_bbox = nullptr; h->bbox_cap = 0;
-    HIP_TRY(dmalloc(&h->d_bbox, nd));
-    h->bbox_cap = nd;
-  }
+  int rc = grow(&h->d_src, &h->src_cap, ns);
+  if (rc == CILQR_OK) rc = grow(&h->d_dst, &h->dst_cap, nd);
+  if (rc == CILQR_OK && bbox) rc = grow(&h->d_bbox, &h->bbox_cap, nd);
+  if (rc) return rc;
   hipStream_t s = h->stream;
   HIP_TRY(hipMemcpyAsync(h->d_src, src, ns * sizeof(float), hipMemcpyHostToDevice, s));
   if (bbox) HIP_TRY(hipMemcpyAsync(h->d_bbox, bbox, nd * sizeof(float), hipMemcpyHostToDevice, s));
-  int rc = cilqr_warp_costmap_device(h, s, h->d_src, sg, h->d_dst, dg, vx, vy, vtheta, bbox ? h->d_bbox : nullptr,
-                                     (int64_t*)h->d_oob);
+  rc = cilqr_warp_costmap_device(h, s, h->d_src, sg, h->d_dst, dg, vx, vy, vtheta, bbox ? h->d_bbox : nullptr, (int64_t*)h->d_oob);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(dst, h->d_dst, nd * sizeof(float), hipMemcpyDeviceToHost, s));
   unsigned long long oob = 0;

@@ -254,11 +254,12 @@ int cilqr_multi_solve_batch(cilqr_multi* m, int B, int N, int M, const double* x
       HIP_TRY(hipSetDevice(h->device));
       if (cnt[d] > 0) {
         const size_t f = first[d];
-        cilqr::HostBatch q{cnt[d], N, M, 0, x0 + f * 4, U + f * 2 * sN, poly + f * CILQR_POLY_COEFFS, xplan_fl + f * 2,
-                           obs_pose ? obs_pose + f * sM * sN * 4 : nullptr, obs_dim ? obs_dim + f * sM * sN * 2 : nullptr,
-                           obs_weight ? obs_weight + f * sM : nullptr, nullptr, 0.0, X_out + f * 4 * (sN + 1), J_out ? J_out + f : nullptr,
-                           iters_out ? iters_out + f : nullptr, status_out ? status_out + f : nullptr, flags};
-        int rc = cilqr::host_solve_enqueue(h, q);
+        const cilqr_obstacles o{obs_pose ? obs_pose + f * sM * sN * 4 : nullptr, obs_dim ? obs_dim + f * sM * sN * 2 : nullptr,
+                                obs_weight ? obs_weight + f * sM : nullptr, (int64_t)M * N, N, 1, M};  // the shard's dense tables
+        const size_t c = cnt[d];
+        int rc = cilqr::host_solve_enqueue(h, cnt[d], N, M, x0 + f * 4, U + f * 2 * sN, poly + f * CILQR_POLY_COEFFS, xplan_fl + f * 2, &o,
+                                           c * sM * sN, c * sM, X_out + f * 4 * (sN + 1), J_out ? J_out + f : nullptr,
+                                           iters_out ? iters_out + f : nullptr, status_out ? status_out + f : nullptr, flags);
         if (rc) return rc;
         HIP_TRY(cilqr::launch_argmin(h->d_J, cnt[d], nullptr, h->d_triple, (double)first[d], h->stream));
       } else {  // a device without scenes takes part in the exchange with "no finite cost"
@@ -308,7 +309,7 @@ int cilqr_multi_solve_batch(cilqr_multi* m, int B, int N, int M, const double* x
     if (e != hipSuccess) return multi_abort(m, CILQR_ERR_HIP, std::string("min-cost pick failed: ") + hipGetErrorString(e));
   }
   for (int d = 0; d < n; ++d) {
-    int rc = cilqr::host_solve_finish(m->h[d]);  // waits for the device's stream; unpacks a small shard's staging buffer
+    int rc = cilqr::host_finish(m->h[d]);  // waits for the device's stream; unpacks a small shard's staging buffer
     if (rc == CILQR_OK && hipStreamSynchronize(m->h[d]->stream) != hipSuccess) rc = fail(CILQR_ERR_HIP, "hipStreamSynchronize failed");
     if (rc) return multi_abort(m, rc, cilqr::g_last_error);
   }

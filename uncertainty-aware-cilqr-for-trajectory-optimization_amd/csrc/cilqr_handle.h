@@ -4,6 +4,7 @@
 
 #include <string>
 
+#include "cilqr_host_plan.h"
 #include "cilqr_internal.h"
 
 struct ncclComm;  // RCCL communicator (rccl.h), only named here
@@ -11,50 +12,34 @@ struct ncclComm;  // RCCL communicator (rccl.h), only named here
 struct cilqr_handle;
 
 namespace cilqr {
-// Where a host-buffer call's arrays lie in the handle's device arena and pinned staging buffer (cilqr_host_io.cpp); bytes.
-struct IoLayout {
-  size_t x0, poly, xplan, obs_w, samp_off, obs_pose, obs_dim, U, X, J, iters, status, end;
-};
-// obs_entries: obstacle entries (4 pose + 2 dimension doubles each); w_entries: weights; samp_entries: sample-offset records (3 doubles)
-IoLayout io_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries);
-// One host-buffer solve call (M = obstacles, or nominal obstacles of the sampled form when n_samples > 0).
-struct HostBatch {
-  int B, N, M, n_samples;
-  const double *x0;
-  double* U;
-  const double *poly, *xplan_fl, *obs_pose, *obs_dim, *obs_weight, *samp_off;
-  double samp_w;
-  double *X_out, *J_out;
-  int32_t *iters_out, *status_out;
-  uint32_t flags;
-  // cilqr_solve_batch_obstacles: obstacles by strides (entries), of which only the span travels; false: the dense [B][M][N] layout
-  bool strided;
-  int64_t obs_bs, obs_ms, obs_ts, obs_wbs;
-  size_t obs_span, w_span;  // entries and weights the strides address
-};
+// The transport of every host-buffer call (cilqr_host_io.cpp): the arrays a HostPlan names are copied into the arena, `launch`
+// — the call's `_device` form on h->stream with the arena pointers the plan handed out — runs, the outputs are copied back.
+// All of it is enqueued by host_enqueue; host_finish waits and, for a call that travelled packed, unpacks the staging buffer.
+// What host_finish needs of a call in flight:
 struct PendingOut {
   bool active, packed;
-  IoLayout L;
-  HostBatch q;
+  int n;
+  HostPlan::Entry out[HostPlan::CAP];  // the entries with a host destination
 };
-int host_solve_enqueue(cilqr_handle* h, const HostBatch& q);  // copies in, kernels, copies out: all enqueued on h->stream
-int host_solve_finish(cilqr_handle* h);                       // waits; unpacks the staging buffer of a small call
-// One host-buffer score call (cilqr_score_batch, cilqr_score_batch_sampled): synchronous, through the solve's arena and pinned
-// staging buffer with a layout of its own (X and U both travel in; the scores and totals come back).
-struct HostScore {
-  int B, N, M, n_samples;  // M: obstacles, or nominal obstacles of the sampled form (n_samples > 0)
-  const double *X, *U, *poly, *xplan_fl;
-  cilqr_obstacles obs;     // host pointers; sampled: pose / dim are the dense nominal tables, strides unused
-  size_t obs_span, w_span; // entries and weights that travel
-  const double* samp_off;
-  double samp_w, max_collision;
-  double *score, *total;   // total may be null
-};
-struct ScoreLayout {
-  size_t poly, xplan, obs_w, samp_off, obs_pose, obs_dim, U, X, score, total, end;  // inputs poly … X, outputs score, total
-};
-ScoreLayout score_layout(size_t B, size_t N, size_t obs_entries, size_t w_entries, size_t samp_entries);
-int host_score(cilqr_handle* h, const HostScore& q);
+int host_copy_in(cilqr_handle* h, const HostPlan& p, bool solve);  // the two halves of host_enqueue, around the launch
+int host_copy_out(cilqr_handle* h, const HostPlan& p, int launch_rc);
+int host_finish(cilqr_handle* h);
+// `solve`: the call counts for cilqr_debug_fail_enqueue.  On failure the stream is drained and the handle is free again.
+template <typename Launch>
+int host_enqueue(cilqr_handle* h, const HostPlan& p, Launch&& launch, bool solve = false) {
+  const int rc = host_copy_in(h, p, solve);
+  return rc ? rc : host_copy_out(h, p, launch());
+}
+template <typename Launch>
+int host_call(cilqr_handle* h, const HostPlan& p, Launch&& launch, bool solve = false) {
+  const int rc = host_enqueue(h, p, launch, solve);
+  return rc ? rc : host_finish(h);
+}
+// cilqr_solve_batch, cilqr_solve_batch_obstacles and the shards of cilqr_multi_solve_batch (cilqr_api.cpp): arguments checked by
+// the caller, obs = host pointers and strides (null when M == 0) addressing `span` entries and `w_span` weights.  Enqueues only.
+int host_solve_enqueue(cilqr_handle* h, int B, int N, int M, const double* x0, double* U, const double* poly, const double* xplan_fl,
+                       const cilqr_obstacles* obs, size_t span, size_t w_span, double* X_out, double* J_out, int32_t* iters_out,
+                       int32_t* status_out, uint32_t flags);
 enum { SCR_PLAN_PATH, SCR_PLAN_IO, SCR_COUNT, SCR_CONV_IN, SCR_CONV_OUT, SCR_DEBUG, SCR_SLOTS };
 int scratch_bytes(cilqr_handle* h, int slot, size_t bytes, void** out);
 
@@ -81,7 +66,7 @@ struct cilqr_handle {
   char* stage;
   size_t stage_cap;
   cilqr::PendingOut pending;
-  int debug_fail_enqueue;  // test hook: the n-th host-buffer enqueue from now fails after its input copies (0: off)
+  int debug_fail_enqueue;  // test hook: the n-th host-buffer solve enqueued from now fails after its input copies (0: off)
   double* d_J;  // the costs of the last host-buffer call, inside the arena
   void* scratch[cilqr::SCR_SLOTS];
   size_t scratch_cap[cilqr::SCR_SLOTS];

@@ -1,0 +1,183 @@
+// cilqr_host_plan.h — where the arrays of a host-buffer call lie in the handle's device arena: plain C++, no HIP (checked
+// without a GPU by tests/test_host_plan.py through tests/cpp/host_plan_dump.cpp).  cilqr_host_io.cpp moves what a plan names.
+//
+// A call DECLARES its arrays in order — inputs, then arrays that travel both ways (the U of a solve), then outputs — and each
+// gets the next 16-byte-aligned place.  Declared in that order, what travels to the device is one contiguous prefix
+// [0, in_end) and what returns one contiguous suffix [out_begin, end): a call small enough for the pinned staging buffer moves
+// as ONE copy each way.  Declaring an array swaps the caller's HOST pointer for the array's place in the arena, so after its
+// plan_* function a host form holds exactly the pointers its `_device` form takes.  An input of no elements or with a null
+// pointer takes no place and becomes null; so does a null output, unless the call keeps its place (the solve's J, iters and
+// status, which the kernels and the multi-device argmin use whoever asked for them).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "cilqr.h"
+
+namespace cilqr {
+
+struct HostPlan {
+  enum { CAP = 16 };  // (the largest call, a solve with weighted obstacles, declares 11 arrays)
+  struct Entry {
+    const void* src;  // host source, null: nothing travels in
+    void* dst;        // host destination, null: nothing travels back
+    size_t off, bytes;
+  };
+  char* base;  // the arena
+  Entry e[CAP];
+  int n = 0, phase = 0;
+  size_t in_end = 0, out_begin = 0, end = 0;
+  bool ok = true;  // false: arrays declared out of order, or more than CAP of them (a mistake in a plan_* function)
+
+  explicit HostPlan(char* arena) : base(arena) {}
+
+  template <typename T> void in(const T*& p, size_t count) { p = (const T*)place(0, p, nullptr, p ? count * sizeof(T) : 0); }
+  template <typename T> void inout(T*& p, size_t count) { p = (T*)place(1, p, p, p ? count * sizeof(T) : 0); }
+  template <typename T> void out(T*& p, size_t count, bool keep_null = false) { p = (T*)place(2, nullptr, p, p || keep_null ? count * sizeof(T) : 0); }
+
+ private:
+  char* place(int ph, const void* src, void* dst, size_t bytes) {
+    if (bytes == 0) return nullptr;
+    if (ph < phase || n == CAP) { ok = false; return nullptr; }
+    phase = ph;
+    const size_t at = end;
+    e[n++] = Entry{src, dst, at, bytes};
+    end = (end + bytes + 15) & ~(size_t)15;
+    if (ph == 0) out_begin = end;
+    if (ph <= 1) in_end = end;
+    return base ? base + at : nullptr;  // (no arena: the plan only gives sizes and offsets)
+  }
+};
+
+// ---- what each host form declares (B solves, horizon N, M obstacles; every pointer is swapped for its place in the arena) ----
+
+// Obstacles travel as the span of entries their strides address (4 pose + 2 dimension doubles each) and w_span weights.
+inline void plan_obstacles(HostPlan& p, size_t M, cilqr_obstacles& o, size_t span, size_t w_span) {
+  if (M == 0) { o = cilqr_obstacles{}; return; }
+  p.in(o.weight, w_span);
+  p.in(o.pose, span * 4);
+  p.in(o.dim, span * 2);
+}
+
+// cilqr_solve_batch, cilqr_solve_batch_obstacles, cilqr_multi_solve_batch; cilqr_solve_batch_sampled with n_samples > 0, M its
+// n_obs and `o` its dense nominal tables without weights.
+inline void plan_solve(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, const double*& x0, double*& U, const double*& poly,
+                       const double*& xplan_fl, cilqr_obstacles& o, size_t span, size_t w_span, const double*& samp_off, double*& X_out,
+                       double*& J_out, int32_t*& iters_out, int32_t*& status_out) {
+  p.in(x0, B * 4);
+  p.in(poly, B * CILQR_POLY_COEFFS);
+  p.in(xplan_fl, B * 2);
+  plan_obstacles(p, M, o, span, w_span);
+  p.in(samp_off, B * M * n_samples * 3);
+  p.inout(U, B * 2 * N);
+  p.out(X_out, B * 4 * (N + 1));
+  p.out(J_out, B, true);
+  p.out(iters_out, B, true);
+  p.out(status_out, B, true);
+}
+
+// cilqr_score_batch; cilqr_score_batch_sampled as above.
+inline void plan_score(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, const double*& X, const double*& U, const double*& poly,
+                       const double*& xplan_fl, cilqr_obstacles& o, size_t span, size_t w_span, const double*& samp_off, double*& score,
+                       double*& total) {
+  p.in(poly, B * CILQR_POLY_COEFFS);
+  p.in(xplan_fl, B * 2);
+  plan_obstacles(p, M, o, span, w_span);
+  p.in(samp_off, B * M * n_samples * 3);
+  p.in(U, B * 2 * N);
+  p.in(X, B * 4 * (N + 1));
+  p.out(score, B * CILQR_SCORE_FIELDS);
+  p.out(total, B);
+}
+
+inline void plan_gains(HostPlan& p, size_t B, size_t N, size_t M, const double*& X, const double*& U, const double*& poly,
+                       const double*& xplan_fl, cilqr_obstacles& o, size_t span, size_t w_span, double*& k_out, double*& K_out,
+                       int32_t*& ok_out) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(poly, B * CILQR_POLY_COEFFS);
+  p.in(xplan_fl, B * 2);
+  plan_obstacles(p, M, o, span, w_span);
+  p.out(k_out, B * 2 * N);
+  p.out(K_out, B * 8 * N);
+  p.out(ok_out, B);
+}
+
+// delta_sets: B, or 1 for one offset set shared by the solves.
+inline void plan_rollout(HostPlan& p, size_t B, size_t N, size_t S, size_t delta_sets, const double*& X, const double*& U, const double*& k,
+                         const double*& K, const double*& delta, double*& X_roll, double*& U_roll) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(k, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(delta, delta_sets * S * 4);
+  p.out(X_roll, B * S * 4 * (N + 1));
+  p.out(U_roll, B * S * 2 * N);
+}
+
+inline void plan_score_rollouts(HostPlan& p, size_t B, size_t N, size_t M, size_t S, const double*& X_roll, const double*& U_roll,
+                                const double*& poly, const double*& xplan_fl, cilqr_obstacles& o, size_t span, size_t w_span,
+                                double*& row_score, double*& risk, double*& total) {
+  p.in(X_roll, B * S * 4 * (N + 1));
+  p.in(U_roll, B * S * 2 * N);
+  p.in(poly, B * CILQR_POLY_COEFFS);
+  p.in(xplan_fl, B * 2);
+  plan_obstacles(p, M, o, span, w_span);
+  p.out(row_score, B * S * CILQR_SCORE_FIELDS);
+  p.out(risk, B * CILQR_RISK_FIELDS);
+  p.out(total, B);
+}
+
+// The kernel does not read obstacle weights: they do not travel.
+inline void plan_rollout_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t S, size_t delta_sets, const double*& X, const double*& U,
+                              const double*& k, const double*& K, const double*& delta, cilqr_obstacles& o, size_t span, const double*& base,
+                              double*& risk, int32_t*& step_hits, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(k, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(delta, delta_sets * S * 4);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, span, 0);
+  p.in(base, B);
+  p.out(risk, B * CILQR_ROLLOUT_RISK_FIELDS);
+  p.out(step_hits, B * N);
+  p.out(total, B);
+}
+
+// Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
+// promises about "the buffers reserved at create" is a statement about this number: it does not change.
+inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {
+  // The solve and score forms: their own plans at the create sizes with dense obstacle tables — B·M·N entries with B·M weights,
+  // or with B·M sample-offset records in place of the weights (n_obs·n_samples <= M).  Serves "the span the strides address
+  // must fit the B·M·N reserved at create" of cilqr_solve_batch_obstacles and cilqr_score_batch.
+  static double host;  // (a non-null host pointer to declare with; never read)
+  size_t cap = 0;
+  // (`sampled`, 0 or 1, is passed as n_samples: B·M·1 records of 3 doubles are the B·M sample-offset records)
+  for (size_t sampled = 0; sampled < 2; ++sampled) {
+    for (int score = 0; score < 2; ++score) {
+      cilqr_obstacles o = {&host, &host, sampled ? nullptr : &host, 0, 0, 0, 0};
+      const double *a = &host, *b = &host, *c = &host, *d = &host, *off = &host;
+      double *u = &host, *x = &host, *j = &host;
+      int32_t *it = nullptr, *st = nullptr;
+      HostPlan p(nullptr);
+      if (score) plan_score(p, B, N, M, sampled, a, b, c, d, o, B * M * N, sampled ? 0 : B * M, off, x, j);
+      else plan_solve(p, B, N, M, sampled, a, u, c, d, o, B * M * N, sampled ? 0 : B * M, off, x, j, it, st);
+      if (p.end > cap) cap = p.end;
+    }
+  }
+  // The gains / rollout / rollout-score / rollout-risk forms, per unit of max_batch in doubles:
+  //   one SOLVE's arrays — path, obstacle weights and entries, nominal X and U, gains k and K, risk + total + ok — serving
+  //   "B <= max_batch", and
+  //   one ROW's arrays — a rollout's X and U, its 4 offsets, its score row — serving "host-buffer form: B*S <= max_batch";
+  //   cilqr_rollout_risk moves no rows, which leaves the row share to its offsets: 4 doubles each for up to
+  //   max_batch·max_horizon of them, "(delta_batch_stride ? B : 1)*S <= max_batch*max_horizon always fits";
+  //   and 32 roundings to 16 bytes.
+  const size_t per_solve = (CILQR_POLY_COEFFS + 2) + (M + 6 * M * N) + (4 * (N + 1) + 2 * N) + (2 * N + 8 * N) + (CILQR_RISK_FIELDS + 1 + 1);
+  const size_t per_row = (4 * (N + 1) + 2 * N) + 4 + CILQR_SCORE_FIELDS;
+  const size_t risk = B * (per_solve + per_row) * sizeof(double) + 32 * 16;
+  return risk > cap ? risk : cap;
+}
+
+}  // namespace cilqr
