@@ -39,6 +39,8 @@
  *   iLQR::forward_pass's control law from other starts (none)  cilqr_rollout_batch(_device), cilqr_score_rollouts(_device):
  *                                                                closed-loop rollouts from offset starts, collision risk per solve
  *                                                                cilqr_rollout_risk(_device): that risk in one launch, no rollout stored
+ *                                                                cilqr_gains_batch_sampled, cilqr_rollout_risk_sampled(_device): both
+ *                                                                for sampled obstacles in compact form
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -400,7 +402,8 @@ int cilqr_score_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_sa
  * A solve returns U alone; the time-varying policy u = U_t + k_t + K_t (x - X_t) every backward pass computes (I/iLQR.cpp:177-178)
  * is what tracks the plan from a start other than the one it was solved for.  Three additive groups of calls, each with a
  * host-buffer form (synchronous) and a `_device` form (device pointers, asynchronous on `stream`), with the conventions of
- * cilqr_score_batch(_device).  Ordinary obstacles only: the compact sampled form is not taken here.  Nothing is allocated per
+ * cilqr_score_batch(_device).  These take ordinary obstacles; the compact sampled form of cilqr_solve_batch_sampled is taken by
+ * cilqr_gains_batch_sampled and cilqr_rollout_risk_sampled below (the stored-rows pair has no sampled form).  Nothing is allocated per
  * call: the host forms travel through buffers sized at create from max_batch, so their ROW counts are bounded by max_batch.
  *
  * cilqr_gains_batch(_device): ONE backward pass, iLQR::backward_pass(X, U, coeffs, x_plan, lamb) (I/iLQR.cpp:91-195), at the given
@@ -499,6 +502,73 @@ int cilqr_rollout_risk_device(cilqr_handle* h, void* stream, int B, int N, int M
 int cilqr_rollout_risk(cilqr_handle* h, int B, int N, int M, int S, const double* X, const double* U, const double* k,
                        const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, const cilqr_obstacles* obs,
                        double max_risk, const double* base, double* risk, int32_t* step_hits, double* total);
+
+/* --- gains and fused rollout risk for SAMPLED obstacles in compact form (new) --------------------------------------------------
+ * The scene form of cilqr_solve_batch_sampled — nom_pose [B][n_obs][4*N], nom_dim [B][n_obs][2*N], sample_offset
+ * [B][n_obs][n_samples][3] = (dx, dy, dtheta), sample_weight — taken as it is: no materialised table of n_obs*n_samples obstacles
+ * is built, read or kept.  Materialised obstacle m = o*n_samples + s has pose (x + dx, y + dy, v, theta + dtheta), formed by those
+ * plain additions (not by the solve kernels' angle-addition shortcut), the nominal dimensions, and weight sample_weight.
+ *
+ * cilqr_gains_batch_sampled(_device) is cilqr_gains_batch on those materialised obstacles, BIT FOR BIT: k_out, K_out, ok_out, the
+ * zeroed gains below a failed step, the map term and lamb as there.  CILQR_ERR_ARG for a NULL X, U, poly, xplan_fl, nom_pose,
+ * nom_dim, sample_offset, k_out or K_out, a lamb that is not finite, n_obs < 1, n_samples < 2, B > max_batch, N > max_horizon or
+ * n_obs*n_samples > max_obstacles; CILQR_ERR_UNSUPPORTED where 16*num_of_local_wpts*10 + 144*N + 16 bytes exceed 64 KiB.
+ *
+ * cilqr_rollout_risk_sampled(_device) runs the rollouts of cilqr_rollout_risk (same X, U, k, K, delta, delta_batch_stride, k_scale,
+ * same arithmetic, lane = rollout row) and evaluates c of both ego circles against every sample of every obstacle at every state
+ * x'_t, t < N.  The HIT COUNT h(r, t, o) is the number of samples j of obstacle o with max(c_front, c_rear) > 0 at state x'_t of row
+ * r; it is n_samples for every o when one of x', y', v', theta' of x'_t or of the two controls u_t is not finite.  A c that is NaN is
+ * never > 0 and never wins a maximum.
+ * risk [B][CILQR_RRS_FIELDS] (required), see the enum; step_hits [B][N] int32 or NULL: the sum over rows of max_o h(r, t, o);
+ * total [B] or NULL: total[b] = base[b] when RRS_COLLISION <= max_risk and base[b] is finite, else NaN (the convention of
+ * cilqr_rollout_risk; total without base is CILQR_ERR_ARG).
+ *   Every count is an integer and (max c, lowest row, lowest entry) is lexicographic: a solve's results depend on its own inputs
+ *   alone — the same bits whatever B is and wherever the solve sits in the batch.  RRS_ANY_SHARE, RRS_WORST_ROW, RRS_WORST_ENTRY
+ *   and RRS_FIRST_STEP equal RR_COLLISION, RR_WORST_ROW, RR_WORST_ENTRY and RR_FIRST_STEP of cilqr_rollout_risk on the materialised
+ *   obstacles, and RRS_WORST_C equals its RR_WORST_C bit for bit.
+ * Mapping: solve b takes ceil(S/256) workgroups of 64*min(4, ceil(S/64)) lanes; each builds one step's n_obs*n_samples entries at a
+ * time into a double-buffered on-chip step buffer while it evaluates the step before.  cilqr_create reserves NOTHING further for
+ * this call and nothing is allocated per call: for S > 256 the workgroups' partial records (8 doubles + N*(1 + n_obs) int32 each)
+ * lie in the obstacle workspace the handle holds for the solve kernels (max_batch padded to 64, x max_obstacles x max_horizon x 6
+ * doubles), which no kernel of this call uses — a solve on ANOTHER stream of the same handle must not run beside it.
+ * CILQR_ERR_ARG: a NULL X, U, k, K, delta, nom_pose, nom_dim, sample_offset or risk; S < 1; a negative stride; a k_scale or max_risk
+ * that is NaN; n_obs < 1, n_samples < 2, B, N or n_obs*n_samples beyond the cilqr_create limits; S*n_samples, n_obs*n_samples*N or
+ * B*ceil(S/256) beyond 2^31 - 1; for S > 256, B*ceil(S/256) partial records beyond that workspace.  The host-buffer form takes
+ * delta_batch_stride 0 or 1, and its arrays — X, U, k, K, the offsets, the nominal tables, the sample offsets, base and the outputs —
+ * must fit the device arena reserved at create (CILQR_ERR_ARG otherwise).
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(14*N + 4) + 96*n_obs*n_samples + 4*N*(1 + n_obs) + 160 bytes (nominal records,
+ * the two halves of the step buffer, step and (t, o) counters, reduction slots), exceeds 64 KiB: 8 x 32 samples at N = 50 take
+ * 32 168 bytes. */
+#define CILQR_RRS_FIELDS 8
+typedef enum cilqr_rollout_risk_sampled_field {
+  CILQR_RRS_COLLISION = 0,    /* sum over rows of max over (t, o) of h / (S*n_samples): the mean over the rows of what
+                                 CILQR_SCORE_COLLISION of cilqr_score_batch_sampled would be for that row */
+  CILQR_RRS_WORST_C = 1,      /* max over rows, t < N, o, samples, both circles of c;  -HUGE_VAL when there is none */
+  CILQR_RRS_WORST_ROW = 2,    /* row of that maximum, lowest on equal values;  -1 when there is none */
+  CILQR_RRS_WORST_ENTRY = 3,  /* m*N + t of that maximum with m = o*n_samples + j, lowest within that row;  -1 when there is none */
+  CILQR_RRS_FIRST_STEP = 4,   /* lowest t with any h > 0;  -1 when none */
+  CILQR_RRS_STEP_SHARE = 5,   /* max over t of (sum over rows of max_o h) / (S*n_samples); step_hits[t] is that sum */
+  CILQR_RRS_ANY_SHARE = 6,    /* rows with some h > 0 / S */
+  CILQR_RRS_PAIR_SHARE = 7    /* max over (t, o) of (sum over rows of h) / (S*n_samples): the joint chance-constraint quantity
+                                 per obstacle and step */
+} cilqr_rollout_risk_sampled_field;
+int cilqr_gains_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
+                                     const double* nom_dim, const double* sample_offset, double sample_weight, double lamb,
+                                     double* k_out, double* K_out, int32_t* ok_out);
+int cilqr_gains_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
+                              const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
+                              const double* sample_offset, double sample_weight, double lamb, double* k_out, double* K_out,
+                              int32_t* ok_out);
+int cilqr_rollout_risk_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, int S, const double* X,
+                                      const double* U, const double* k, const double* K, const double* delta,
+                                      int64_t delta_batch_stride, double k_scale, const double* nom_pose, const double* nom_dim,
+                                      const double* sample_offset, double max_risk, const double* base, double* risk,
+                                      int32_t* step_hits, double* total);
+int cilqr_rollout_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, int S, const double* X, const double* U,
+                               const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                               const double* nom_pose, const double* nom_dim, const double* sample_offset, double max_risk,
+                               const double* base, double* risk, int32_t* step_hits, double* total);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

@@ -26,6 +26,10 @@ RISK_COLLISION, RISK_WORST_C, RISK_WORST_ROW, RISK_MEAN_TOTAL = range(RISK_FIELD
 # `cilqr_rollout_risk_field`: the columns of a fused risk row (`Solver.rollout_risk`)
 ROLLOUT_RISK_FIELDS = 6
 RR_COLLISION, RR_WORST_C, RR_WORST_ROW, RR_WORST_ENTRY, RR_FIRST_STEP, RR_STEP_SHARE = range(ROLLOUT_RISK_FIELDS)
+# `cilqr_rollout_risk_sampled_field`: the columns of a fused risk row against sampled obstacles (`Solver.rollout_risk_sampled`)
+RRS_FIELDS = 8
+(RRS_COLLISION, RRS_WORST_C, RRS_WORST_ROW, RRS_WORST_ENTRY, RRS_FIRST_STEP, RRS_STEP_SHARE, RRS_ANY_SHARE,
+ RRS_PAIR_SHARE) = range(RRS_FIELDS)
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -44,6 +48,7 @@ ABI_SYMBOLS = (
     "cilqr_gains_batch", "cilqr_gains_batch_device", "cilqr_rollout_batch", "cilqr_rollout_batch_device",
     "cilqr_score_rollouts", "cilqr_score_rollouts_device",
     "cilqr_rollout_risk", "cilqr_rollout_risk_device",
+    "cilqr_gains_batch_sampled", "cilqr_gains_batch_sampled_device", "cilqr_rollout_risk_sampled", "cilqr_rollout_risk_sampled_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -553,6 +558,66 @@ class Solver:
                                                _vp(delta), C.c_int64(delta_batch_stride), C.c_double(k_scale),
                                                C.byref(obs) if M else None, C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_hits),
                                                _vp(total)))
+
+    # ---- gains and fused rollout risk for sampled obstacles in compact form ----
+    def gains_batch_sampled(self, N, X, U, poly, xplan_fl, nom_pose, nom_dim, offsets, weight, lamb=1.0):
+        """`cilqr_gains_batch_sampled`: `gains_batch` on the compact form of `solve_batch_sampled` — nom_pose (B, n_obs, 4N), nom_dim
+        (B, n_obs, 2N), offsets (B, n_obs, n_samples, 3); the gains of `gains_batch` on the materialised obstacles, bit for bit."""
+        offsets = _np64(offsets)
+        B, n_obs, ns = offsets.shape[0], offsets.shape[1], offsets.shape[2]
+        X = _np64(X).reshape(B, 4 * (N + 1))
+        U = _np64(U).reshape(B, 2 * N)
+        poly = _np64(poly).reshape(B, POLY)
+        xplan_fl = _np64(xplan_fl).reshape(B, 2)
+        nom_pose = _np64(nom_pose).reshape(B, n_obs, 4 * N)
+        nom_dim = _np64(nom_dim).reshape(B, n_obs, 2 * N)
+        offsets = offsets.reshape(B, n_obs, ns, 3)
+        k, K, ok = np.zeros((B, 2 * N)), np.zeros((B, 8 * N)), np.zeros(B, dtype=np.int32)
+        _check(lib().cilqr_gains_batch_sampled(self._h, B, int(N), int(n_obs), int(ns), _p(X), _p(U), _p(poly), _p(xplan_fl), _p(nom_pose),
+                                               _p(nom_dim), _p(offsets), C.c_double(weight), C.c_double(lamb), _p(k), _p(K), _p(ok, _ip)))
+        return dict(k=k, K=K, ok=ok)
+
+    def gains_batch_sampled_device(self, stream, B, N, n_obs, n_samples, X, U, poly, xplan_fl, nom_pose, nom_dim, offsets, weight, k_out,
+                                   K_out, ok_out=0, lamb=1.0):
+        """`cilqr_gains_batch_sampled_device`: device addresses."""
+        _check(lib().cilqr_gains_batch_sampled_device(self._h, _vp(stream), int(B), int(N), int(n_obs), int(n_samples), _vp(X), _vp(U),
+                                                      _vp(poly), _vp(xplan_fl), _vp(nom_pose), _vp(nom_dim), _vp(offsets),
+                                                      C.c_double(weight), C.c_double(lamb), _vp(k_out), _vp(K_out), _vp(ok_out)))
+
+    def rollout_risk_sampled(self, N, X, U, k, K, delta, nom_pose, nom_dim, offsets, k_scale=0.0, max_risk=1.0, base=None):
+        """`cilqr_rollout_risk_sampled`: `rollout_risk` against sampled obstacles in compact form.  X, U, k, K, delta and k_scale as
+        `rollout_batch`; nom_pose, nom_dim, offsets as `solve_batch_sampled`.  Returns (risk (B, RRS_FIELDS), step_hits (B, N) int32,
+        total): total[b] is base[b], NaN where RRS_COLLISION exceeds max_risk or base[b] is not finite; None without `base`."""
+        offsets = _np64(offsets)
+        B, n_obs, ns = offsets.shape[0], offsets.shape[1], offsets.shape[2]
+        X = _np64(X).reshape(B, 4 * (N + 1))
+        U, k, K = _np64(U).reshape(B, 2 * N), _np64(k).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        delta = _np64(delta)
+        if delta.ndim == 3:
+            if delta.shape[0] != B or delta.shape[2] != 4:
+                raise CilqrError("rollout_risk_sampled: delta %s is neither (S, 4) nor (%d, S, 4)" % (delta.shape, B))
+            S, stride = delta.shape[1], 1
+        else:
+            delta = delta.reshape(-1, 4)
+            S, stride = delta.shape[0], 0
+        nom_pose = _np64(nom_pose).reshape(B, n_obs, 4 * N)
+        nom_dim = _np64(nom_dim).reshape(B, n_obs, 2 * N)
+        offsets = offsets.reshape(B, n_obs, ns, 3)
+        base = None if base is None else _np64(base).reshape(B)
+        risk, step_hits = np.zeros((B, RRS_FIELDS)), np.zeros((B, N), dtype=np.int32)
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_rollout_risk_sampled(self._h, B, int(N), int(n_obs), int(ns), int(S), _p(X), _p(U), _p(k), _p(K), _p(delta),
+                                                C.c_int64(stride), C.c_double(k_scale), _p(nom_pose), _p(nom_dim), _p(offsets),
+                                                C.c_double(max_risk), _p(base), _p(risk), _p(step_hits, _ip), _p(total)))
+        return risk, step_hits, total
+
+    def rollout_risk_sampled_device(self, stream, B, N, n_obs, n_samples, S, X, U, k, K, delta, delta_batch_stride, nom_pose, nom_dim,
+                                    offsets, risk, step_hits=0, total=0, base=0, k_scale=0.0, max_risk=1.0):
+        """`cilqr_rollout_risk_sampled_device`: device addresses."""
+        _check(lib().cilqr_rollout_risk_sampled_device(self._h, _vp(stream), int(B), int(N), int(n_obs), int(n_samples), int(S), _vp(X),
+                                                       _vp(U), _vp(k), _vp(K), _vp(delta), C.c_int64(delta_batch_stride),
+                                                       C.c_double(k_scale), _vp(nom_pose), _vp(nom_dim), _vp(offsets),
+                                                       C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_hits), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

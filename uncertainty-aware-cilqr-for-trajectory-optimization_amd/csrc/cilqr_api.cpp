@@ -902,6 +902,128 @@ int cilqr_rollout_risk(cilqr_handle* h, int B, int N, int M, int S, const double
   });
 }
 
+// ---- the compact sampled form of the gains and of the fused rollout risk (cilqr_gains.hip, cilqr_risk_sampled.hip) -------------------
+namespace {
+int gains_sampled_check(const cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U, const double* poly,
+                        const double* xplan_fl, const double* nom_pose, const double* nom_dim, const double* sample_offset, double lamb,
+                        const double* k_out, const double* K_out) {
+  if (!X || !U || !poly || !xplan_fl || !k_out || !K_out || !nom_pose || !nom_dim || !sample_offset)
+    return fail(CILQR_ERR_ARG, "cilqr_gains_batch_sampled: null required pointer");
+  if (!is_finite(lamb)) return fail(CILQR_ERR_ARG, "cilqr_gains_batch_sampled: lamb is not finite");
+  return check_sampled(h, "cilqr_gains_batch_sampled", B, N, n_obs, n_samples);
+}
+int rollout_risk_sampled_check(const cilqr_handle* h, int B, int N, int n_obs, int n_samples, int S, const double* X, const double* U,
+                               const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                               const double* nom_pose, const double* nom_dim, const double* sample_offset, double max_risk,
+                               const double* base, const double* risk, const double* total) {
+  if (!X || !U || !k || !K || !delta || !risk || !nom_pose || !nom_dim || !sample_offset)
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: total needs base");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: S = %d, needs S >= 1", S);
+  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30))
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: negative stride (or one beyond 2^30)");
+  if (k_scale != k_scale || max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: k_scale or max_risk is NaN");
+  int rc = check_sampled(h, "cilqr_rollout_risk_sampled", B, N, n_obs, n_samples);
+  if (rc) return rc;
+  // every count the kernels keep in 32 bits: the sum over a solve's rows of a sample count, an entry index m*N + t, the grid
+  if ((int64_t)S * n_samples > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: S * n_samples beyond 2^31 counts");
+  if ((int64_t)n_obs * n_samples * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: n_obs * n_samples * N beyond 2^31 entries");
+  const int64_t G = ((int64_t)S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  if ((int64_t)B * G > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: B * ceil(S/%d) beyond 2^31 workgroups", cilqr::RISK_THREADS);
+  // G > 1: the partial records lie in the obstacle workspace reserved at create (no solve kernel runs inside this call)
+  const size_t Bpad = ((size_t)h->max_batch + 63) / 64 * 64;
+  if (G > 1 && (size_t)B * (size_t)G * cilqr::rollout_risk_sampled_part_doubles(N, n_obs) > Bpad * h->max_obstacles * h->max_horizon * 6)
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: B * ceil(S/%d) = %lld partial records exceed the obstacle workspace reserved at create",
+                cilqr::RISK_THREADS, (long long)((int64_t)B * G));
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_gains_batch_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* U, const double* poly, const double* xplan_fl, const double* nom_pose,
+                                     const double* nom_dim, const double* sample_offset, double sample_weight, double lamb,
+                                     double* k_out, double* K_out, int32_t* ok_out) {
+  int rc = gains_sampled_check(h, B, N, n_obs, n_samples, X, U, poly, xplan_fl, nom_pose, nom_dim, sample_offset, lamb, k_out, K_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::gains_lds_bytes(N, h->kp.n_samples) > cilqr::GAINS_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_gains_batch_sampled: %d path samples and horizon %d do not fit 64 KiB of LDS", h->kp.n_samples, N);
+  cilqr::GainsArgs a = {};
+  a.s = handle_args(h, B, N, n_obs, 0);
+  a.s.obs_pose = nom_pose; a.s.obs_dim = nom_dim;
+  a.s.samp_off = sample_offset; a.s.n_samples = n_samples; a.s.samp_w = sample_weight;
+  a.s.X_out = const_cast<double*>(X);  // read only (cilqr_internal.h, GainsArgs)
+  a.s.U = const_cast<double*>(U);
+  a.s.poly = poly; a.s.xplan_fl = xplan_fl;
+  a.k_out = k_out; a.K_out = K_out; a.ok_out = ok_out; a.lamb = lamb;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_gains(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_gains_batch_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* U,
+                              const double* poly, const double* xplan_fl, const double* nom_pose, const double* nom_dim,
+                              const double* sample_offset, double sample_weight, double lamb, double* k_out, double* K_out,
+                              int32_t* ok_out) {
+  int rc = gains_sampled_check(h, B, N, n_obs, n_samples, X, U, poly, xplan_fl, nom_pose, nom_dim, sample_offset, lamb, k_out, K_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr_obstacles o{nom_pose, nom_dim, nullptr, 0, 0, 0, 0};  // the dense nominal tables
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_gains_sampled(p, B, N, n_obs, n_samples, X, U, poly, xplan_fl, o, sample_offset, k_out, K_out, ok_out);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_gains_batch_sampled_device(h, h->stream, B, N, n_obs, n_samples, X, U, poly, xplan_fl, o.pose, o.dim, sample_offset,
+                                            sample_weight, lamb, k_out, K_out, ok_out);
+  });
+}
+
+int cilqr_rollout_risk_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, int S, const double* X,
+                                      const double* U, const double* k, const double* K, const double* delta,
+                                      int64_t delta_batch_stride, double k_scale, const double* nom_pose, const double* nom_dim,
+                                      const double* sample_offset, double max_risk, const double* base, double* risk,
+                                      int32_t* step_hits, double* total) {
+  int rc = rollout_risk_sampled_check(h, B, N, n_obs, n_samples, S, X, U, k, K, delta, delta_batch_stride, k_scale, nom_pose, nom_dim,
+                                      sample_offset, max_risk, base, risk, total);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::rollout_risk_sampled_lds_bytes(N, n_obs, n_samples) > cilqr::RISK_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rollout_risk_sampled: horizon %d with %d x %d obstacle samples does not fit 64 KiB of LDS", N,
+                n_obs, n_samples);
+  cilqr::RolloutRiskArgs a = {};
+  a.s = handle_args(h, B, N, n_obs, 0);
+  a.s.obs_pose = nom_pose; a.s.obs_dim = nom_dim;
+  a.s.samp_off = sample_offset; a.s.n_samples = n_samples;
+  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
+  a.delta_bs = (long long)delta_batch_stride * S * 4;
+  a.k_scale = k_scale; a.max_risk = max_risk;
+  a.base = base; a.risk = risk; a.step_hits = step_hits; a.total = total;
+  a.partials = h->d_obs_tab; a.part_stride = (long long)cilqr::rollout_risk_sampled_part_doubles(N, n_obs);
+  a.S = S; a.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_rollout_risk_sampled(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_rollout_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, int S, const double* X, const double* U,
+                               const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                               const double* nom_pose, const double* nom_dim, const double* sample_offset, double max_risk,
+                               const double* base, double* risk, int32_t* step_hits, double* total) {
+  int rc = rollout_risk_sampled_check(h, B, N, n_obs, n_samples, S, X, U, k, K, delta, delta_batch_stride, k_scale, nom_pose, nom_dim,
+                                      sample_offset, max_risk, base, risk, total);
+  if (rc) return rc;
+  // (a stride above 1 would address blocks between the solves' sets)
+  if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: the host-buffer form takes delta_batch_stride 0 or 1");
+  if (B == 0) return CILQR_OK;
+  cilqr_obstacles o{nom_pose, nom_dim, nullptr, 0, 0, 0, 0};  // the dense nominal tables
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_rollout_risk_sampled(p, B, N, n_obs, n_samples, S, delta_batch_stride == 0 ? 1 : B, X, U, k, K, delta, o, sample_offset, base,
+                                   risk, step_hits, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_rollout_risk_sampled_device(h, h->stream, B, N, n_obs, n_samples, S, X, U, k, K, delta, delta_batch_stride, k_scale, o.pose,
+                                             o.dim, sample_offset, max_risk, base, risk, step_hits, total);
+  });
+}
+
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
                               double sigma_x, double sigma_y, double sigma_theta, float* out, int32_t* count_out) {
   if (!h || !src || !g || !out) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap: null argument");

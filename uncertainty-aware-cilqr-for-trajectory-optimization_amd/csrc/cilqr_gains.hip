@@ -5,7 +5,10 @@
 // Mapping: one wavefront per solve, the structure of one iteration of the one-wavefront solve family.
 //   phase 0  lanes over the path samples → LDS (sample_xy); lanes over the states t ≤ N: cos/sin of the heading → LDS
 //   phase L  lanes over the steps t < N: closest path sample (closest_sample: the strict-< first minimum), lin_step with the obstacle
-//            entries read through the strides (obs_entry_at), the map term (unc_cost_add) in a loop of its own; the record → LDS.
+//            entries read through the strides (obs_entry_at) — SAMPLED: entry m = o·n_samples + s made from nominal obstacle o and
+//            sample s's offset by the plain additions of score_entry<true> (cilqr_score.hip), in ascending m, so that the record
+//            carries the bits of the call on the materialised obstacles — the map term (unc_cost_add) in a loop of its own; the
+//            record → LDS.
 //            A and B are evaluated at state t + 1, as the reference does (I/iLQR.cpp:102-106).
 //   phase R  lane 0 runs the serial chain riccati_step<false> — the branching form, which clamps negative eigenvalues as the
 //            reference's EigenSolver path does, so that no solve is ever handed to another kernel — and stores each step's gains as
@@ -29,6 +32,7 @@ struct LdsPath {  // the path samples as closest_sample reads them
 // LDS (dynamic): [sx S][sy S][cos N+1][sin N+1][N records of REC_W doubles]
 constexpr int REC_W = 16;
 
+template <bool SAMPLED>
 __global__ __launch_bounds__(WAVE) void cilqr_gains_kernel(GainsArgs a) {
   extern __shared__ double lds[];
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -56,12 +60,22 @@ __global__ __launch_bounds__(WAVE) void cilqr_gains_kernel(GainsArgs a) {
   {
     const SolveArgs& s = phase_args();
     const KParams& kp = s.kp;
-    const double* wts = obs_weights(s, b);
-    const int M = s.M;
+    const double* wts = SAMPLED ? nullptr : obs_weights(s, b);
+    const int M = SAMPLED ? s.M * s.n_samples : s.M;  // (SAMPLED: s.M counts the nominal obstacles)
     for (int t = lane; t < N; t += WAVE) {
       const double px = X[4 * t], py = X[4 * t + 1];
       const int cs = closest_sample<false>(S, grid, px, py, LdsPath{sx, sy});
       auto obs = [&](int m, ObsEntry& e, double& w) {
+        if (SAMPLED) {  // the pose the materialised call is given: (x + dx, y + dy, v, theta + dtheta)
+          const int o = m / s.n_samples;
+          const long long ob = (long long)b * s.M + o, en = ob * N + t;
+          const double* np = s.obs_pose + 4 * en;
+          const double* off = s.samp_off + 3 * (ob * s.n_samples + (m - o * s.n_samples));
+          const double pose[4] = {np[0] + off[0], np[1] + off[1], np[2], np[3] + off[2]};
+          e = make_obs_entry(kp, pose, s.obs_dim + 2 * en);
+          w = s.samp_w;
+          return true;
+        }
         e = obs_entry_at(kp, s, b, m, t);
         w = wts ? wts[m] : kp.w_obstacle;
         return true;
@@ -130,7 +144,9 @@ size_t gains_lds_bytes(int N, int n_path_samples) {
 
 hipError_t launch_gains(const GainsArgs& a, hipStream_t stream) {
   if (a.s.B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(cilqr_gains_kernel, dim3(a.s.B), dim3(WAVE), gains_lds_bytes(a.s.N, a.s.kp.n_samples), stream, a);
+  const size_t lds = gains_lds_bytes(a.s.N, a.s.kp.n_samples);
+  if (a.s.n_samples > 0) hipLaunchKernelGGL(cilqr_gains_kernel<true>, dim3(a.s.B), dim3(WAVE), lds, stream, a);
+  else hipLaunchKernelGGL(cilqr_gains_kernel<false>, dim3(a.s.B), dim3(WAVE), lds, stream, a);
   return hipGetLastError();
 }
 

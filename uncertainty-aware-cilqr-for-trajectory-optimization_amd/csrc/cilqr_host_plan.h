@@ -18,7 +18,7 @@
 namespace cilqr {
 
 struct HostPlan {
-  enum { CAP = 16 };  // (the largest call, a solve with weighted obstacles, declares 11 arrays)
+  enum { CAP = 16 };  // (the largest call, the sampled rollout risk, declares 12 arrays)
   struct Entry {
     const void* src;  // host source, null: nothing travels in
     void* dst;        // host destination, null: nothing travels back
@@ -104,6 +104,22 @@ inline void plan_gains(HostPlan& p, size_t B, size_t N, size_t M, const double*&
   p.out(ok_out, B);
 }
 
+// cilqr_gains_batch_sampled: M its n_obs, `o` its dense nominal tables without weights.
+inline void plan_gains_sampled(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, const double*& X, const double*& U,
+                               const double*& poly, const double*& xplan_fl, cilqr_obstacles& o, const double*& samp_off, double*& k_out,
+                               double*& K_out, int32_t*& ok_out) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(poly, B * CILQR_POLY_COEFFS);
+  p.in(xplan_fl, B * 2);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, B * M * N, 0);
+  p.in(samp_off, B * M * n_samples * 3);
+  p.out(k_out, B * 2 * N);
+  p.out(K_out, B * 8 * N);
+  p.out(ok_out, B);
+}
+
 // delta_sets: B, or 1 for one offset set shared by the solves.
 inline void plan_rollout(HostPlan& p, size_t B, size_t N, size_t S, size_t delta_sets, const double*& X, const double*& U, const double*& k,
                          const double*& K, const double*& delta, double*& X_roll, double*& U_roll) {
@@ -142,6 +158,25 @@ inline void plan_rollout_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t 
   plan_obstacles(p, M, o, span, 0);
   p.in(base, B);
   p.out(risk, B * CILQR_ROLLOUT_RISK_FIELDS);
+  p.out(step_hits, B * N);
+  p.out(total, B);
+}
+
+// cilqr_rollout_risk_sampled: M its n_obs, `o` its dense nominal tables without weights (12 arrays, the most any call declares).
+inline void plan_rollout_risk_sampled(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, size_t S, size_t delta_sets,
+                                      const double*& X, const double*& U, const double*& k, const double*& K, const double*& delta,
+                                      cilqr_obstacles& o, const double*& samp_off, const double*& base, double*& risk,
+                                      int32_t*& step_hits, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(k, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(delta, delta_sets * S * 4);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, B * M * N, 0);
+  p.in(samp_off, B * M * n_samples * 3);
+  p.in(base, B);
+  p.out(risk, B * CILQR_RRS_FIELDS);
   p.out(step_hits, B * N);
   p.out(total, B);
 }

@@ -121,7 +121,8 @@ struct RiskArgs {
 hipError_t launch_risk(const RiskArgs& a, hipStream_t stream);
 
 // One backward pass at a given trajectory (cilqr_gains.hip; cilqr_gains_batch*): one wavefront per solve.  `s` carries what the
-// launch shares with a solve — X_out = the trajectory (read only), U, poly, xplan_fl, the strided obstacle fields, B, N, M, kp, unc.
+// launch shares with a solve — X_out = the trajectory (read only), U, poly, xplan_fl, the strided obstacle fields (or the compact
+// sampled form with M = nominal obstacles and n_samples > 0), B, N, M, kp, unc.
 struct GainsArgs {
   SolveArgs s;
   double* k_out;    // [B][2N]
@@ -172,6 +173,12 @@ struct RolloutRiskArgs {
 };
 hipError_t launch_rollout_risk(const RolloutRiskArgs& a, hipStream_t stream);
 size_t rollout_risk_lds_bytes(int N, int M);
+// The same against sampled obstacles in compact form (cilqr_risk_sampled.hip; cilqr_rollout_risk_sampled*): `s` carries the dense
+// nominal tables, M = n_obs, samp_off and n_samples > 0; risk has CILQR_RRS_FIELDS per solve.  For G > 1 `partials` holds B·G
+// records, part_stride = rollout_risk_sampled_part_doubles(N, n_obs) doubles apart: 8 doubles, then N + N·n_obs int32 counters.
+hipError_t launch_rollout_risk_sampled(const RolloutRiskArgs& a, hipStream_t stream);
+size_t rollout_risk_sampled_lds_bytes(int N, int n_obs, int n_samples);
+size_t rollout_risk_sampled_part_doubles(int N, int n_obs);
 
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {

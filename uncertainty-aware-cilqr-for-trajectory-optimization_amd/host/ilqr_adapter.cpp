@@ -114,6 +114,17 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
+  if (n_samples_) {
+    std::vector<double> pose, dim, off;
+    const int n_obs = pack_sampled(1, pose, dim, off);
+    check(cilqr_solve_batch_sampled(h_, 1, N, n_obs, n_samples_, x_0, U.a.data(), poly_coeffs, fl, pose.data(), dim.data(), off.data(),
+                                    sample_weight(), X_result.a.data(), &last_cost, &iters, &status, CILQR_FLAG_NONE),
+          "cilqr_solve_batch_sampled");
+    last_iterations = iters;
+    last_exit = status;
+    U_result = U;
+    return;
+  }
   const cilqr_obstacles obs = obstacle_strides();
   check(cilqr_solve_batch_obstacles(h_, 1, N, M, x_0, U.a.data(), poly_coeffs, fl, M ? &obs : nullptr, X_result.a.data(), &last_cost,
                                     &iters, &status, CILQR_FLAG_NONE),
@@ -174,17 +185,29 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
   const cilqr_obstacles obs = obstacle_strides();  // one obstacle set for every candidate
-  check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, X.data(),
-                                    J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
-        "cilqr_solve_batch_obstacles");
-  std::vector<double> total;
+  std::vector<double> total, nom_pose, nom_dim, samp_off;
+  const int n_obs = n_samples_ ? pack_sampled(B, nom_pose, nom_dim, samp_off) : 0;
+  if (n_samples_)
+    check(cilqr_solve_batch_sampled(h_, B, N, n_obs, n_samples_, ego_states.data(), U.data(), poly.data(), fl.data(), nom_pose.data(),
+                                    nom_dim.data(), samp_off.data(), sample_weight(), X.data(), J.data(), iters.data(), status.data(),
+                                    CILQR_FLAG_NONE),
+          "cilqr_solve_batch_sampled");
+  else
+    check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, X.data(),
+                                      J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
+          "cilqr_solve_batch_obstacles");
   last_scores.clear();
   if (pick_ == CandidatePick::MinTotalCost) {  // rank by everything the solve descended along, among the candidates that are safe
     last_scores.resize((size_t)B * CILQR_SCORE_FIELDS);
     total.resize(B);
-    check(cilqr_score_batch(h_, B, N, M, X.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, max_collision_,
-                            last_scores.data(), total.data()),
-          "cilqr_score_batch");
+    if (n_samples_)
+      check(cilqr_score_batch_sampled(h_, B, N, n_obs, n_samples_, X.data(), U.data(), poly.data(), fl.data(), nom_pose.data(),
+                                      nom_dim.data(), samp_off.data(), sample_weight(), max_collision_, last_scores.data(), total.data()),
+            "cilqr_score_batch_sampled");
+    else
+      check(cilqr_score_batch(h_, B, N, M, X.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, max_collision_,
+                              last_scores.data(), total.data()),
+            "cilqr_score_batch");
   }
   const std::vector<double>& rank = pick_ == CandidatePick::MinTotalCost ? total : J;
   int best = 0;  // strict-< first minimum, NaN never wins (the convention of cilqr_argmin_device)
@@ -210,8 +233,55 @@ void hip_check(hipError_t e, const char* what) {
 }
 }  // namespace
 
+namespace {
+const char* const kStoredRowsWithSamples =
+    "the stored-rows pose-noise check has no form for sampled obstacles (set_obstacle_samples): use set_pose_noise_check_fused";
+}  // namespace
+
+void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_samples) {
+  if (offsets.empty()) {
+    samples_.clear();
+    n_samples_ = 0;
+  } else {
+    if (n_samples < 2 || offsets.size() % ((size_t)3 * n_samples) != 0)
+      throw std::runtime_error("set_obstacle_samples: needs n_samples >= 2 and n_obs * n_samples * 3 offsets");
+    if (offsets.size() / 3 > (size_t)max_obstacles_) throw std::runtime_error("set_obstacle_samples: n_obs * n_samples above max_obstacles");
+    samples_ = offsets;
+    n_samples_ = n_samples;
+  }
+  last_risk.clear();
+  last_step_hits.clear();
+  if (!noise_.empty()) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+}
+
+int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
+  const size_t N = params.horizon, n_obs = obstacles_.size(), ns = n_samples_;
+  if (n_obs < 1 || n_obs * ns * 3 != samples_.size())
+    throw std::runtime_error("set_obstacle_samples: the offsets do not match the obstacles of set_Obstacle (n_obs * n_samples * 3)");
+  for (const Obstacle& o : obstacles_)
+    if ((size_t)o.dimension.cols < N || (size_t)o.relative_pos_array.cols < N)
+      throw std::runtime_error("set_Obstacle: dimension must be 2×horizon and relative_pos_array 4×horizon");
+  pose.resize((size_t)B * n_obs * 4 * N);
+  dim.resize((size_t)B * n_obs * 2 * N);
+  off.resize((size_t)B * samples_.size());
+  for (size_t m = 0; m < n_obs; ++m) {
+    const Obstacle& o = obstacles_[m];
+    for (size_t t = 0; t < N; ++t) {
+      for (int r = 0; r < 4; ++r) pose[(m * N + t) * 4 + r] = o.relative_pos_array(r, (int)t);
+      for (int r = 0; r < 2; ++r) dim[(m * N + t) * 2 + r] = o.dimension(r, (int)t);
+    }
+  }
+  for (int b = 1; b < B; ++b) {
+    memcpy(&pose[(size_t)b * n_obs * 4 * N], pose.data(), n_obs * 4 * N * sizeof(double));
+    memcpy(&dim[(size_t)b * n_obs * 2 * N], dim.data(), n_obs * 2 * N * sizeof(double));
+  }
+  for (int b = 0; b < B; ++b) memcpy(&off[(size_t)b * samples_.size()], samples_.data(), samples_.size() * sizeof(double));
+  return (int)n_obs;
+}
+
 void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check: offsets must hold 4 doubles per sample");
+  if (n_samples_ && !offsets.empty()) throw std::logic_error(kStoredRowsWithSamples);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
@@ -236,16 +306,19 @@ void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double
 // check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
 void iLQR::reserve_noise_buffers() {
   const size_t B = max_candidates_, S = noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = noise_fused_ ? 0 : B * S;
+  // with obstacle samples: per-candidate nominal tables and offsets in place of the one shared set (n_obs * n_samples <= M)
+  const size_t n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
   size_t o = 0;
   const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
   NoiseLayout& L = nl_;
   L.x0 = take(B * 4); L.U = take(B * 2 * N); L.poly = take(B * CILQR_POLY_COEFFS); L.fl = take(B * 2);
-  L.pose = take(M * 4 * N); L.dim = take(M * 2 * N);
+  L.pose = take(n_samples_ ? B * n_obs * 4 * N : M * 4 * N); L.dim = take(n_samples_ ? B * n_obs * 2 * N : M * 2 * N);
+  L.soff = take(B * samples_.size());
   L.X = take(B * 4 * (N + 1)); L.J = take(B); L.iters = take(B); L.status = take(B);
   L.k = take(B * 2 * N); L.K = take(B * 8 * N); L.ok = take(B);
   L.delta = take(S * 4);
   L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
-  L.risk = take(B * (noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
+  L.risk = take(B * (n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
   L.score = take(noise_fused_ ? B * CILQR_SCORE_FIELDS : 0); L.base = take(noise_fused_ ? B : 0); L.hits = take(noise_fused_ ? (B * N + 1) / 2 : 0);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -264,6 +337,7 @@ void iLQR::reserve_noise_buffers() {
 
 int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_states) {
   const int N = params.horizon, M = (int)obstacles_.size(), S = (int)(noise_.size() / 4);
+  if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   const int W = params.num_of_local_wpts;
@@ -288,22 +362,46 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   up(L.U, U.data(), U.size());
   up(L.poly, poly.data(), poly.size());
   up(L.fl, fl.data(), fl.size());
-  up(L.pose, obs_pose_.data(), obs_pose_.size());
-  up(L.dim, obs_dim_.data(), obs_dim_.size());
+  std::vector<double> nom_pose, nom_dim, samp_off;  // (alive until the stream has been waited for)
+  const int n_obs = n_samples_ ? pack_sampled(B, nom_pose, nom_dim, samp_off) : 0;
+  if (n_samples_) {
+    up(L.pose, nom_pose.data(), nom_pose.size());
+    up(L.dim, nom_dim.data(), nom_dim.size());
+    up(L.soff, samp_off.data(), samp_off.size());
+  } else {
+    up(L.pose, obs_pose_.data(), obs_pose_.size());
+    up(L.dim, obs_dim_.data(), obs_dim_.size());
+  }
   cilqr_obstacles obs = host_obs;  // the same strides over the device copies
   obs.pose = d + L.pose;
   obs.dim = d + L.dim;
   const cilqr_obstacles* po = M ? &obs : nullptr;
-  int rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
-                                              (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-  if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-  if (noise_fused_) {
-    if (!rc) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
-    if (!rc) rc = cilqr_rollout_risk_device(h_, st, B, N, M, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, po, max_risk_,
-                                            d + L.base, d + L.risk, (int32_t*)(d + L.hits), d + L.total);
+  const int risk_fields = n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS;
+  int rc = CILQR_OK;
+  if (n_samples_) {  // the same chain in the compact sampled form
+    const int ns = n_samples_;
+    const double w = sample_weight();
+    rc = cilqr_solve_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim, d + L.soff, w,
+                                          d + L.X, d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc) rc = cilqr_gains_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                   d + L.soff, w, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+    if (!rc) rc = cilqr_score_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                   d + L.soff, w, 1.0, d + L.score, d + L.base);
+    if (!rc) rc = cilqr_rollout_risk_sampled_device(h_, st, B, N, n_obs, ns, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0,
+                                                    d + L.pose, d + L.dim, d + L.soff, max_risk_, d + L.base, d + L.risk,
+                                                    (int32_t*)(d + L.hits), d + L.total);
   } else {
-    if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
-    if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+    if (noise_fused_) {
+      if (!rc) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
+      if (!rc) rc = cilqr_rollout_risk_device(h_, st, B, N, M, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, po, max_risk_,
+                                              d + L.base, d + L.risk, (int32_t*)(d + L.hits), d + L.total);
+    } else {
+      if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
+      if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
+    }
   }
   if (!rc) rc = cilqr_argmin_device(h_, st, B, d + L.total, d + L.pair);
   if (rc) {
@@ -314,7 +412,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   double pair[2] = {0.0, -1.0};
   last_scores.clear();
   last_step_hits.clear();
-  last_risk.assign((size_t)B * (noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS), 0.0);
+  last_risk.assign((size_t)B * risk_fields, 0.0);
   down(pair, L.pair, sizeof(pair));
   down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
   if (noise_fused_) {

@@ -125,6 +125,20 @@ class iLQR {
   // max_candidates / ceil(S/256) candidates.  Whichever of the two setters was called last applies.
   void set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb = 1.0);
 
+  // Sampled obstacles: the uncertainty-aware scene form.  `offsets` holds n_obs x n_samples x 3 doubles, (dx, dy, dtheta) per pose
+  // sample, drawn ONCE by the node with its own sigmas; the obstacles of set_Obstacle are then the NOMINAL ones (n_obs of them, in
+  // the same order, n_obs * n_samples <= max_obstacles), and every sample weighs params.w_obstacle / n_samples.  With a non-empty
+  // set, run_step and run_candidates solve with cilqr_solve_batch_sampled(_device), MinTotalCost scores with
+  // cilqr_score_batch_sampled (its collision share is the largest share of an obstacle's samples hit at one step), and under
+  // set_pose_noise_check_fused run_candidates runs, on one stream: cilqr_solve_batch_sampled_device ->
+  // cilqr_gains_batch_sampled_device(lamb) -> cilqr_score_batch_sampled_device (nominal totals, max_collision 1) ->
+  // cilqr_rollout_risk_sampled_device(k_scale 0, max_risk, base = those totals) -> cilqr_argmin_device.  last_risk then holds
+  // CILQR_RRS_FIELDS per candidate (cilqr_rollout_risk_sampled_field): a candidate is rejected when the mean over the ego-pose draws
+  // of its worst sample share exceeds max_risk.  The stored-rows check has no sampled form: with samples set,
+  // set_pose_noise_check (and a run_candidates under it) throws std::logic_error naming set_pose_noise_check_fused.  An empty
+  // `offsets` switches the samples off (the default): everything behaves as without this call.
+  void set_obstacle_samples(const std::vector<double>& offsets, int n_samples);
+
   Parameters params;
   Matrix X_result;         // 4 × (horizon + 1)
   Matrix U_result;         // 2 × horizon
@@ -134,7 +148,8 @@ class iLQR {
   double last_cost = 0.0;
   std::vector<double> last_scores;  // run_candidates under MinTotalCost: CILQR_SCORE_FIELDS per candidate; empty otherwise
   std::vector<double> last_risk;  // run_candidates under set_pose_noise_check: CILQR_RISK_FIELDS per candidate; empty otherwise
-                                  // (under set_pose_noise_check_fused: CILQR_ROLLOUT_RISK_FIELDS per candidate)
+                                  // (under set_pose_noise_check_fused: CILQR_ROLLOUT_RISK_FIELDS per candidate, CILQR_RRS_FIELDS with
+                                  // obstacle samples set)
   std::vector<int32_t> last_step_hits;  // run_candidates under set_pose_noise_check_fused: horizon per candidate; empty otherwise
 
  private:
@@ -155,8 +170,15 @@ class iLQR {
   // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
   // so that this header needs no HIP
   struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, end;
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, end;
   };
+  // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
+  std::vector<double> samples_;
+  int n_samples_ = 0;
+  // the compact form for B solves sharing the obstacle set: dense nominal tables [B][n_obs][4N] / [2N], offsets [B][n_obs][n_samples][3];
+  // returns n_obs
+  int pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const;
+  double sample_weight() const { return params.w_obstacle / n_samples_; }
   int run_candidates_noise_checked(int B, const std::vector<double>& ego_states);
   bool noise_fused_ = false;  // set_pose_noise_check_fused was the last setter
   void reserve_noise_buffers();
