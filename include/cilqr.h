@@ -570,6 +570,60 @@ int cilqr_rollout_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_s
                                const double* nom_pose, const double* nom_dim, const double* sample_offset, double max_risk,
                                const double* base, double* risk, int32_t* step_hits, double* total);
 
+/* --- map rollout risk: the share of rollouts that enter occupied cells of the uncertainty map (new) ----------------------------
+ * The map counterpart of cilqr_rollout_risk: in the reference's live node the ellipse channel is off and the blurred costmap given
+ * to set_uncertainty_map is the planner's only obstacle information (I/ilqr_uncertainty_node.cpp:111-113, 151-189).
+ * cilqr_rollout_risk_map(_device) runs the rollouts of cilqr_rollout_batch / cilqr_rollout_risk (same X, U, k, K, delta,
+ * delta_batch_stride, k_scale, same statements) and looks the map up under every state x'_t with t < N (x'_N is not visited):
+ *   probes   the probes_l x probes_w footprint probes and the bilinear lookup defined at cilqr_set_uncertainty_map — body offsets
+ *            a_k, b_l on safe_length x safe_width turned by the state's heading, a rigid transform into the map frame by the pose
+ *            of the solve's index, bilinear interpolation over four cell centres evaluated in double.  Layer
+ *            (layer + b*layer_stride) and pose (poses[b], or the shared one) are those of the map CURRENTLY SET on the handle,
+ *            indexed by the solve as the solve and score kernels index them.  Probe q = k*probes_w + l.
+ *   valid    a probe is valid when its four cells are all inside the map and finite — the map cost's own rule.
+ *   hit      a row HITS at step t when a valid probe's occupancy is > occ_threshold (strict), or one of x', y', v', theta' of
+ *            x'_t or of the two controls u_t is not finite (as in cilqr_rollout_risk), or CILQR_MAP_RISK_UNKNOWN_HITS is set and
+ *            a probe is invalid.
+ *   unknown  a row is UNKNOWN at step t when at least one probe is invalid; a state that is not finite makes all its probes invalid.
+ * risk [B][CILQR_MAP_RISK_FIELDS] (required), see the enum; step_hits [B][N] and unknown_hits [B][N] int32, each may be NULL: the
+ * rows that hit, or are unknown, AT step t; total [B] or NULL: total[b] = base[b] when MR_COLLISION <= max_risk and base[b] is
+ * finite, else NaN.  base [B] is any per-solve cost — typically the `total` of cilqr_rollout_risk or cilqr_rollout_risk_sampled,
+ * whose NaN (already rejected) stays NaN; hand total to cilqr_argmin_device / cilqr_argmin_global_device.  total without base is
+ * CILQR_ERR_ARG.
+ *   Nothing is a floating-point sum: counts are integers and (max occupancy, lowest row, lowest entry) is lexicographic, so a
+ *   solve's results are the same bits whatever B is and wherever the solve sits in the batch.  MR_WORST_OCC is the occupancy the
+ *   map cost interpolates at that probe (cilqr_debug_uncertainty_cost at probes 1 x 1 gives q1*exp(q2*(occ/100 - 1))).
+ * Mapping: lane = row; solve b takes ceil(S/256) workgroups of 64*min(4, ceil(S/64)) lanes.  cilqr_create reserves nothing new
+ * and nothing is allocated per call: for S > 256 the workgroups' partial records (8 doubles + N int32) lie in the buffer of
+ * cilqr_rollout_risk's records — a cilqr_rollout_risk with S > 256 on ANOTHER stream of the same handle must not run beside it.
+ * CILQR_ERR_ARG, decided before the handle is looked at where no handle is needed: NULL X, U, k, K, delta or risk; total without
+ * base; S < 1; a negative stride; a k_scale, occ_threshold or max_risk that is NaN; flag bits other than
+ * CILQR_MAP_RISK_UNKNOWN_HITS; then B or N beyond the cilqr_create limits; B*ceil(S/256) > max_batch; no uncertainty map set on the
+ * handle (the message says so).  The host-buffer form additionally takes delta_batch_stride 0 or 1, and its arrays — X, U, k, K,
+ * (delta_batch_stride ? B : 1)*S*4 offsets, base and the outputs — must fit the device arena reserved at create:
+ * (delta_batch_stride ? B : 1)*S <= max_batch*max_horizon always fits.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(14*N + 4) + 4*N + 160 bytes (nominal records, packed step counters, reduction
+ * slots), exceeds 64 KiB: N above 563, which CILQR_MAX_HORIZON = 384 keeps out of reach — every horizon a handle accepts runs. */
+#define CILQR_MAP_RISK_FIELDS 7
+typedef enum cilqr_map_risk_field {
+  CILQR_MR_COLLISION = 0,   /* rows that hit at any step / S */
+  CILQR_MR_WORST_OCC = 1,   /* max interpolated occupancy over rows, t < N, valid probes;  -HUGE_VAL when no probe is valid */
+  CILQR_MR_WORST_ROW = 2,   /* its row, lowest on equal values;  -1 when none */
+  CILQR_MR_WORST_ENTRY = 3, /* q*N + t of that maximum within that row, q = k*probes_w + l, lowest on equal values;  -1 when none */
+  CILQR_MR_FIRST_STEP = 4,  /* lowest t at which any row hits;  -1 when none does */
+  CILQR_MR_STEP_SHARE = 5,  /* max over t of (rows that hit AT step t) / S */
+  CILQR_MR_UNKNOWN = 6      /* rows with an invalid probe at any step / S */
+} cilqr_map_risk_field;
+#define CILQR_MAP_RISK_UNKNOWN_HITS 1u /* flags: an invalid probe counts as a hit */
+int cilqr_rollout_risk_map_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, const double* U,
+                                  const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
+                                  double occ_threshold, uint32_t flags, double max_risk, const double* base, double* risk,
+                                  int32_t* step_hits, int32_t* unknown_hits, double* total);
+int cilqr_rollout_risk_map(cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                           const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold, uint32_t flags,
+                           double max_risk, const double* base, double* risk, int32_t* step_hits, int32_t* unknown_hits,
+                           double* total);
+
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's
  * {J_min, local index, index offset} (24 bytes) through one ncclAllGather (RCCL over xGMI), then the lexicographic minimum

@@ -30,6 +30,10 @@ RR_COLLISION, RR_WORST_C, RR_WORST_ROW, RR_WORST_ENTRY, RR_FIRST_STEP, RR_STEP_S
 RRS_FIELDS = 8
 (RRS_COLLISION, RRS_WORST_C, RRS_WORST_ROW, RRS_WORST_ENTRY, RRS_FIRST_STEP, RRS_STEP_SHARE, RRS_ANY_SHARE,
  RRS_PAIR_SHARE) = range(RRS_FIELDS)
+# `cilqr_map_risk_field`: the columns of a map risk row (`Solver.rollout_risk_map`)
+MAP_RISK_FIELDS = 7
+MR_COLLISION, MR_WORST_OCC, MR_WORST_ROW, MR_WORST_ENTRY, MR_FIRST_STEP, MR_STEP_SHARE, MR_UNKNOWN = range(MAP_RISK_FIELDS)
+MAP_RISK_UNKNOWN_HITS = 1  # flags of `rollout_risk_map`: an invalid probe counts as a hit
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -49,6 +53,7 @@ ABI_SYMBOLS = (
     "cilqr_score_rollouts", "cilqr_score_rollouts_device",
     "cilqr_rollout_risk", "cilqr_rollout_risk_device",
     "cilqr_gains_batch_sampled", "cilqr_gains_batch_sampled_device", "cilqr_rollout_risk_sampled", "cilqr_rollout_risk_sampled_device",
+    "cilqr_rollout_risk_map", "cilqr_rollout_risk_map_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -618,6 +623,43 @@ class Solver:
                                                        _vp(U), _vp(k), _vp(K), _vp(delta), C.c_int64(delta_batch_stride),
                                                        C.c_double(k_scale), _vp(nom_pose), _vp(nom_dim), _vp(offsets),
                                                        C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_hits), _vp(total)))
+
+    # ---- map rollout risk: the rollouts against the uncertainty map set on the handle ----
+    def rollout_risk_map(self, N, X, U, k, K, delta, occ_threshold, k_scale=0.0, max_risk=1.0, base=None, unknown_hits=False):
+        """`cilqr_rollout_risk_map`: the share of S closed-loop rollouts per solve whose footprint probes enter cells of the
+        uncertainty map set on the handle above `occ_threshold`.  X, U, k, K, delta and k_scale as `rollout_batch`; unknown_hits:
+        a probe outside the map or on a cell that is not finite counts as a hit (MAP_RISK_UNKNOWN_HITS).  Returns (risk
+        (B, MAP_RISK_FIELDS), step_hits (B, N) int32, unknown_hits (B, N) int32, total): total[b] is base[b], NaN where MR_COLLISION
+        exceeds max_risk or base[b] is not finite — `base` is typically the total of `rollout_risk`; None without `base`."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U, k, K = _np64(U).reshape(B, 2 * N), _np64(k).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        delta = _np64(delta)
+        if delta.ndim == 3:
+            if delta.shape[0] != B or delta.shape[2] != 4:
+                raise CilqrError("rollout_risk_map: delta %s is neither (S, 4) nor (%d, S, 4)" % (delta.shape, B))
+            S, stride = delta.shape[1], 1
+        else:
+            delta = delta.reshape(-1, 4)
+            S, stride = delta.shape[0], 0
+        base = None if base is None else _np64(base).reshape(B)
+        risk = np.zeros((B, MAP_RISK_FIELDS))
+        step_hits, unknown = np.zeros((B, N), dtype=np.int32), np.zeros((B, N), dtype=np.int32)
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_rollout_risk_map(self._h, B, int(N), int(S), _p(X), _p(U), _p(k), _p(K), _p(delta), C.c_int64(stride),
+                                            C.c_double(k_scale), C.c_double(occ_threshold),
+                                            C.c_uint32(MAP_RISK_UNKNOWN_HITS if unknown_hits else 0), C.c_double(max_risk), _p(base),
+                                            _p(risk), _p(step_hits, _ip), _p(unknown, _ip), _p(total)))
+        return risk, step_hits, unknown, total
+
+    def rollout_risk_map_device(self, stream, B, N, S, X, U, k, K, delta, delta_batch_stride, occ_threshold, risk, step_hits=0,
+                                unknown_hits=0, total=0, base=0, k_scale=0.0, max_risk=1.0, flags=0):
+        """`cilqr_rollout_risk_map_device`: device addresses; the map is the one set by `set_uncertainty_map(_device)`."""
+        _check(lib().cilqr_rollout_risk_map_device(self._h, _vp(stream), int(B), int(N), int(S), _vp(X), _vp(U), _vp(k), _vp(K),
+                                                   _vp(delta), C.c_int64(delta_batch_stride), C.c_double(k_scale),
+                                                   C.c_double(occ_threshold), C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base),
+                                                   _vp(risk), _vp(step_hits), _vp(unknown_hits), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

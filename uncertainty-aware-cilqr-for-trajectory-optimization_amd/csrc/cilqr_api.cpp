@@ -1024,6 +1024,69 @@ int cilqr_rollout_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_s
   });
 }
 
+// ---- map rollout risk (cilqr_risk_map.hip) -------------------------------------------------------------------------------------------
+namespace {
+int rollout_risk_map_check(const cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                           const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold, uint32_t flags,
+                           double max_risk, const double* base, const double* risk, const double* total) {
+  if (!X || !U || !k || !K || !delta || !risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: total needs base");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: S = %d, needs S >= 1", S);
+  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30))
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: negative stride (or one beyond 2^30)");
+  if (k_scale != k_scale || occ_threshold != occ_threshold || max_risk != max_risk)
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: k_scale, occ_threshold or max_risk is NaN");
+  if (flags & ~CILQR_MAP_RISK_UNKNOWN_HITS) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: unknown flag bits 0x%x", flags);
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  const int64_t G = ((int64_t)S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  if ((int64_t)B * G > h->max_batch)
+    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: B * ceil(S/%d) = %lld partial records above max_batch = %d", cilqr::RISK_THREADS,
+                (long long)((int64_t)B * G), h->max_batch);
+  if (!h->unc.layer) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: no uncertainty map is set on the handle");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_rollout_risk_map_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, const double* U, const double* k,
+                                  const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold,
+                                  uint32_t flags, double max_risk, const double* base, double* risk, int32_t* step_hits,
+                                  int32_t* unknown_hits, double* total) {
+  int rc = rollout_risk_map_check(h, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, occ_threshold, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::rollout_risk_map_lds_bytes(N) > cilqr::RISK_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rollout_risk_map: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::MapRiskArgs a = {};
+  a.r.s = handle_args(h, B, N, 0, 0);
+  a.r.X = X; a.r.U = U; a.r.k = k; a.r.K = K; a.r.delta = delta;
+  a.r.delta_bs = (long long)delta_batch_stride * S * 4;
+  a.r.k_scale = k_scale; a.r.max_risk = max_risk;
+  a.r.base = base; a.r.risk = risk; a.r.step_hits = step_hits; a.r.total = total;
+  a.r.partials = h->d_risk_part; a.r.part_stride = (long long)h->risk_part_stride;
+  a.r.S = S; a.r.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+  a.occ_threshold = occ_threshold; a.unknown_hits = unknown_hits; a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_rollout_risk_map(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_rollout_risk_map(cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
+                           const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold, uint32_t flags,
+                           double max_risk, const double* base, double* risk, int32_t* step_hits, int32_t* unknown_hits, double* total) {
+  int rc = rollout_risk_map_check(h, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, occ_threshold, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  // (a stride above 1 would address blocks between the solves' sets)
+  if (delta_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: the host-buffer form takes delta_batch_stride 0 or 1");
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_rollout_risk_map(p, B, N, S, delta_batch_stride == 0 ? 1 : B, X, U, k, K, delta, base, risk, step_hits, unknown_hits, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_rollout_risk_map_device(h, h->stream, B, N, S, X, U, k, K, delta, delta_batch_stride, k_scale, occ_threshold, flags, max_risk,
+                                         base, risk, step_hits, unknown_hits, total);
+  });
+}
+
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
                               double sigma_x, double sigma_y, double sigma_theta, float* out, int32_t* count_out) {
   if (!h || !src || !g || !out) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap: null argument");

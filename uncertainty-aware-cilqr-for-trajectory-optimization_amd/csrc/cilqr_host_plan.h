@@ -181,6 +181,24 @@ inline void plan_rollout_risk_sampled(HostPlan& p, size_t B, size_t N, size_t M,
   p.out(total, B);
 }
 
+// cilqr_rollout_risk_map: no obstacle travels (the map is the handle's).  Per solve 17·N + 13 doubles and 4 per offset row: with
+// B <= max_batch, N <= max_horizon and delta_sets·S <= max_batch·max_horizon that is at most 21·N + 13 of the 22·N + 34 doubles
+// per unit of max_batch that host_arena_bytes reserves below, and the 10 arrays round up by less than its 32 x 16 bytes.
+inline void plan_rollout_risk_map(HostPlan& p, size_t B, size_t N, size_t S, size_t delta_sets, const double*& X, const double*& U,
+                                  const double*& k, const double*& K, const double*& delta, const double*& base, double*& risk,
+                                  int32_t*& step_hits, int32_t*& unknown_hits, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(k, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(delta, delta_sets * S * 4);
+  p.in(base, B);
+  p.out(risk, B * CILQR_MAP_RISK_FIELDS);
+  p.out(step_hits, B * N);
+  p.out(unknown_hits, B * N);
+  p.out(total, B);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

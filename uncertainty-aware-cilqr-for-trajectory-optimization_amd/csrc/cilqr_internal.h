@@ -179,6 +179,17 @@ size_t rollout_risk_lds_bytes(int N, int M);
 hipError_t launch_rollout_risk_sampled(const RolloutRiskArgs& a, hipStream_t stream);
 size_t rollout_risk_sampled_lds_bytes(int N, int n_obs, int n_samples);
 size_t rollout_risk_sampled_part_doubles(int N, int n_obs);
+// The same against the uncertainty map set on the handle (cilqr_risk_map.hip; cilqr_rollout_risk_map*): `r.s` carries B, N, kp and
+// unc (no obstacle field is read); risk has CILQR_MAP_RISK_FIELDS per solve.  For G > 1 `r.partials` holds B·G records of the
+// cilqr_rollout_risk shape — 8 doubles, then N int32 — whose counters pack the unknown rows above the hit rows (16 bits each).
+struct MapRiskArgs {
+  RolloutRiskArgs r;
+  double occ_threshold;
+  int32_t* unknown_hits;  // [B][N] or null
+  uint32_t flags;         // CILQR_MAP_RISK_*
+};
+hipError_t launch_rollout_risk_map(const MapRiskArgs& a, hipStream_t stream);
+size_t rollout_risk_map_lds_bytes(int N);
 
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {

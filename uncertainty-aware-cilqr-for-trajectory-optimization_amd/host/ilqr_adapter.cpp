@@ -63,9 +63,13 @@ void iLQR::set_uncertainty_map(const Uncertainty& u) {
   m.layer_stride = 0;
   m.probes_l = u.probes_l; m.probes_w = u.probes_w;
   check(cilqr_set_uncertainty_map(h_, &m), "cilqr_set_uncertainty_map");
+  map_set_ = true;
 }
 
-void iLQR::clear_uncertainty_map() { check(cilqr_clear_uncertainty_map(h_), "cilqr_clear_uncertainty_map"); }
+void iLQR::clear_uncertainty_map() {
+  check(cilqr_clear_uncertainty_map(h_), "cilqr_clear_uncertainty_map");
+  map_set_ = false;
+}
 
 void iLQR::set_global_plan(const Matrix& global_plan) {
   if (global_plan.rows != 2 || global_plan.cols < 1) throw std::runtime_error("set_global_plan: expected a 2×P matrix");
@@ -302,6 +306,17 @@ void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double
   if (!noise_.empty()) reserve_noise_buffers();
 }
 
+void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits) {
+  if (max_risk != max_risk) throw std::runtime_error("set_map_risk_check: max_risk is NaN");
+  map_check_ = occ_threshold == occ_threshold;  // NaN: off
+  map_threshold_ = occ_threshold;
+  map_max_risk_ = max_risk;
+  map_unknown_hits_ = unknown_hits;
+  last_map_risk.clear();
+  last_map_step_hits.clear();
+  last_map_unknown_hits.clear();
+}
+
 // One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.  The fused
 // check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
 void iLQR::reserve_noise_buffers() {
@@ -320,6 +335,9 @@ void iLQR::reserve_noise_buffers() {
   L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
   L.risk = take(B * (n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
   L.score = take(noise_fused_ ? B * CILQR_SCORE_FIELDS : 0); L.base = take(noise_fused_ ? B : 0); L.hits = take(noise_fused_ ? (B * N + 1) / 2 : 0);
+  // the map risk check's outputs (a few doubles per candidate: reserved with the fused check whether or not the check is on)
+  L.mrisk = take(noise_fused_ ? B * CILQR_MAP_RISK_FIELDS : 0); L.mtotal = take(noise_fused_ ? B : 0);
+  L.mhits = take(noise_fused_ ? (B * N + 1) / 2 : 0); L.munk = take(noise_fused_ ? (B * N + 1) / 2 : 0);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -403,7 +421,12 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
       if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
     }
   }
-  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + L.total, d + L.pair);
+  const bool map_checked = map_check_ && map_set_ && noise_fused_;
+  if (map_checked && !rc)  // the map's say on top of the obstacles': base = their total, NaN staying NaN
+    rc = cilqr_rollout_risk_map_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
+                                       map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + L.total, d + L.mrisk,
+                                       (int32_t*)(d + L.mhits), (int32_t*)(d + L.munk), d + L.mtotal);
+  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + (map_checked ? L.mtotal : L.total), d + L.pair);
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(st);
@@ -420,6 +443,17 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     last_step_hits.assign((size_t)B * N, 0);
     down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
     down(last_step_hits.data(), L.hits, last_step_hits.size() * sizeof(int32_t));
+  }
+  last_map_risk.clear();
+  last_map_step_hits.clear();
+  last_map_unknown_hits.clear();
+  if (map_checked) {
+    last_map_risk.assign((size_t)B * CILQR_MAP_RISK_FIELDS, 0.0);
+    last_map_step_hits.assign((size_t)B * N, 0);
+    last_map_unknown_hits.assign((size_t)B * N, 0);
+    down(last_map_risk.data(), L.mrisk, last_map_risk.size() * sizeof(double));
+    down(last_map_step_hits.data(), L.mhits, last_map_step_hits.size() * sizeof(int32_t));
+    down(last_map_unknown_hits.data(), L.munk, last_map_unknown_hits.size() * sizeof(int32_t));
   }
   hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
   const int best = (int)pair[1];

@@ -124,6 +124,17 @@ class iLQR {
   // offsets take ceil(S/256) partial records per candidate of the max_candidates the handle holds: run_candidates then takes at most
   // max_candidates / ceil(S/256) candidates.  Whichever of the two setters was called last applies.
   void set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb = 1.0);
+  // Map risk check: the fused check above looks at the obstacles of set_Obstacle only, and in the node that channel is switched off —
+  // the blurred costmap of set_uncertainty_map is all the planner knows of obstacles (I/ilqr_uncertainty_node.cpp:111-113, 151-189).
+  // It has effect under set_pose_noise_check_fused while an uncertainty map is set: run_candidates then enqueues, on the check's
+  // stream, ... -> cilqr_rollout_risk(_sampled)_device (its `total`) -> cilqr_rollout_risk_map_device(k_scale 0, occ_threshold,
+  // max_risk, base = that total) -> cilqr_argmin_device on the map call's `total`.  A candidate is then also rejected when the share
+  // of its rollouts whose footprint probes enter cells above occ_threshold exceeds max_risk (unknown_hits: a probe outside the map
+  // or on a cell that is not finite counts as entering one).  last_map_risk holds CILQR_MAP_RISK_FIELDS per candidate
+  // (cilqr_map_risk_field), last_map_step_hits and last_map_unknown_hits the rollouts that hit / are unknown at each step, horizon
+  // per candidate.  With no map set, or under any other pick, behaviour is what it is without this call and the three fields are
+  // empty.  An occ_threshold that is NaN switches the check off (the default).
+  void set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits = false);
 
   // Sampled obstacles: the uncertainty-aware scene form.  `offsets` holds n_obs x n_samples x 3 doubles, (dx, dy, dtheta) per pose
   // sample, drawn ONCE by the node with its own sigmas; the obstacles of set_Obstacle are then the NOMINAL ones (n_obs of them, in
@@ -151,6 +162,9 @@ class iLQR {
                                   // (under set_pose_noise_check_fused: CILQR_ROLLOUT_RISK_FIELDS per candidate, CILQR_RRS_FIELDS with
                                   // obstacle samples set)
   std::vector<int32_t> last_step_hits;  // run_candidates under set_pose_noise_check_fused: horizon per candidate; empty otherwise
+  // run_candidates with the map risk check in effect (set_map_risk_check); empty otherwise
+  std::vector<double> last_map_risk;               // CILQR_MAP_RISK_FIELDS per candidate
+  std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
 
  private:
   void pack_obstacles();
@@ -170,7 +184,7 @@ class iLQR {
   // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
   // so that this header needs no HIP
   struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, end;
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, end;
   };
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
@@ -188,6 +202,9 @@ class iLQR {
   int noise_horizon_ = -1;
   void* noise_dev_ = nullptr;
   void* noise_stream_ = nullptr;
+  // map risk check: in effect when map_check_ (set_map_risk_check), map_set_ (an uncertainty map is set) and noise_fused_
+  bool map_check_ = false, map_set_ = false, map_unknown_hits_ = false;
+  double map_threshold_ = 0.0, map_max_risk_ = 1.0;
 };
 
 }  // namespace cilqr_host
