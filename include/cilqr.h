@@ -41,6 +41,8 @@
  *                                                                cilqr_rollout_risk(_device): that risk in one launch, no rollout stored
  *                                                                cilqr_gains_batch_sampled, cilqr_rollout_risk_sampled(_device): both
  *                                                                for sampled obstacles in compact form
+ *   (none: the reference propagates no state covariance)     cilqr_chance_risk(_device): closed-loop covariance along the plan
+ *                                                                and Gaussian chance values per obstacle and step, no samples
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -623,6 +625,79 @@ int cilqr_rollout_risk_map(cilqr_handle* h, int B, int N, int S, const double* X
                            const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold, uint32_t flags,
                            double max_risk, const double* base, double* risk, int32_t* step_hits, int32_t* unknown_hits,
                            double* total);
+
+/* --- analytic pose-noise risk: closed-loop covariance chain and Gaussian chance values (new) -----------------------------------
+ * The rollout calls above judge a solve by S sampled starts: risk in steps of 1/S, dependent on the offsets' seed, and no state
+ * covariance along the plan.  cilqr_chance_risk(_device) propagates ONE 4x4 covariance per solve through the linear closed loop
+ * the gains define around the plan — no samples, no seed, the work of one rollout row — and turns it into a Gaussian chance value
+ * per (obstacle, step, ego circle).  X [B][4*(N+1)], U [B][2*N], K [B][8*N] in the layouts of cilqr_gains_batch (K[8*t + r + 2*c]).
+ * The feedforward k is not an argument: the model is the k_scale = 0 policy u = U_t + K_t (x - X_t), whose mean is the plan X.
+ * Ordinary obstacles through the strides of cilqr_obstacles (weights are not read).  Neither the path nor an uncertainty map set
+ * on the handle is read.
+ *
+ * Covariance chain.  Every 4x4 matrix is column-major, entry (r, c) at [r + 4*c], state order (x, y, v, theta).  For t < N
+ *     F_t = A_t + B_t K_t,      Sigma_{t+1} = F_t Sigma_t F_t' + W,
+ *   A_t, B_t the Jacobians of Model::forward_simulate (I/Model.cpp:100-155) at the step's OWN state and control,
+ *   v = X_t[2], theta = X_t[3], a = U_t[0], with adv = v*dt + a*dt^2/2:
+ *     A = I + { (0,2): dt*cos theta, (1,2): dt*sin theta, (0,3): -sin theta*adv, (1,3): cos theta*adv },
+ *     B = { (0,0): dt^2*cos theta/2, (1,0): dt^2*sin theta/2, (2,0): dt, (3,1): dt },  every other entry 0.
+ *   They are NOT evaluated at the next state (that shift is the backward pass's, see cilqr_gains_batch), and the model's clamps
+ *   (acceleration, yaw rate, speed) are treated as INACTIVE: a plan that rides a clamp has less closed-loop authority than this
+ *   chain assumes.  Entries with row <= column are computed and mirrored, so every Sigma_t is exactly symmetric; only the
+ *   row <= column entries of sigma0 and process_noise are read.  sigma0 [B or 1][16]: sigma0_batch_stride 1 = one per solve, 0 =
+ *   one shared by the batch.  process_noise [16] = W, shared by the batch, NULL = zero.  sigma_out[b][t] = Sigma_t, t = 0 ... N.
+ *
+ * Chance value.  For obstacle entry (m, t), t < N, and each ego circle, lever l = +ego_front (front) or -ego_rear (rear), centre
+ * (x + l cos theta, y + l sin theta) at X_t:
+ *     cbar  the c = 1 - d'Pd of cilqr_score_batch at X_t: the same inflated semi-axes a, b (the stray +1 on b included);
+ *     g     its gradient over (x, y, v, theta):  g_xy = -2 R(theta_o)' P d  (the first two components of the reference's c_dot,
+ *           I/Obstacle.cpp:82, 101),  g_v = 0,  g_theta = g_xy . (-l sin theta, l cos theta).  The reference leaves g_theta at 0
+ *           in its cost; the lever arm is kept here because heading noise moves the circles;
+ *     s     sqrt(max(g' Sigma_t g, 0))   (a quadratic form that is NaN counts as 0);
+ *     p     erfc(-cbar / (s*sqrt 2)) / 2, the Gaussian probability of c > 0;  with s = 0: 1 if cbar > 0, else 0.
+ *   entry_p[m*N + t] = max(p_front, p_rear), evaluated as erfc of the smaller of the two arguments (erfc decreases); a NaN never
+ *   wins a maximum.
+ * Per step:  r_t = min(1, sum over m of entry_p[m*N + t]) — Boole's bound over the obstacles, summed in ascending m (an order fixed by
+ *   M); a sum that is NaN gives 1; r_t = 1 when any of X_t, U_t, K_t or Sigma_t is not finite (the rollout calls' convention for a
+ *   lost row).  step_risk[b][t] = r_t.
+ * risk [B][CILQR_CHANCE_FIELDS] (required), see the enum; step_risk [B][N], entry_p [B][M*N], sigma_out [B][N+1][16], each may be
+ * NULL; total [B] or NULL: total[b] = base[b] when the bounded field — CR_STEP_RISK, or CR_SUM_RISK under CILQR_CHANCE_BOUND_SUM —
+ * is <= max_risk and base[b] is finite, else NaN: the convention of cilqr_rollout_risk, so the result composes with it and with
+ * cilqr_rollout_risk_map through `base` and feeds cilqr_argmin_device / cilqr_argmin_global_device.  total without base is
+ * CILQR_ERR_ARG.
+ *   A solve's outputs depend on its own inputs alone: the same bits whatever B is, wherever the solve sits in the batch and whatever
+ *   strides address the same obstacle values (sums run over trees fixed by (N, M); maxima are lexicographic, lowest index first).
+ * Mapping: one workgroup per solve, one launch, nothing allocated per call.  The steps' F_t are formed in parallel, ten lanes then
+ * run the serial chain (one per row <= column entry), every lane then takes obstacle entries.
+ * CILQR_ERR_ARG, decided before the handle is looked at where no handle is needed: NULL X, U, K, sigma0 or risk; total without base;
+ * obs NULL with M > 0; a negative stride; sigma0_batch_stride other than 0 or 1; a max_risk that is NaN; flag bits other than
+ * CILQR_CHANCE_BOUND_SUM; then B, N or M beyond the cilqr_create limits.  The host-buffer form's arrays — X, U, K, sigma0,
+ * process_noise, the obstacle span, base and the outputs — must fit the device arena reserved at create (CILQR_ERR_ARG otherwise).
+ * Per solve that is 15*N + 6*M*N + 28 doubles, N + 1 covariances of 16 with sigma_out and M*N more with entry_p: without these two
+ * outputs every B <= max_batch fits; with both, every B <= max_batch/2 does (the arena is the one the earlier calls sized: this
+ * call adds nothing to it).
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(33*N + M*N + 16) bytes (F_t and Sigma_t, 16 doubles each, r_t, entry_p), exceeds
+ * 64 KiB: N above 247 without obstacles, above 220 with M = 4. */
+#define CILQR_CHANCE_FIELDS 6
+typedef enum cilqr_chance_risk_field {
+  CILQR_CR_STEP_RISK = 0,     /* max over t of r_t: what max_risk bounds by default.  The counterpart of RR_STEP_SHARE; it tracks
+                                 RR_COLLISION because the steps are strongly correlated */
+  CILQR_CR_WORST_STEP = 1,    /* lowest t of that maximum;  -1 when M == 0 */
+  CILQR_CR_SUM_RISK = 2,      /* min(1, sum over t of r_t), over a tree fixed by N: Boole's bound over the horizon, an upper bound.
+                                 Bounded instead of CR_STEP_RISK under CILQR_CHANCE_BOUND_SUM */
+  CILQR_CR_MAX_P = 3,         /* max over entries of entry_p;  0 when M == 0 */
+  CILQR_CR_MAX_ENTRY = 4,     /* m*N + t of that maximum, lowest on equal values;  -1 when M == 0 */
+  CILQR_CR_MAX_POS_SIGMA = 5  /* max over t <= N of sqrt(lambda_max of Sigma_t's 2x2 position block), closed form */
+} cilqr_chance_risk_field;
+#define CILQR_CHANCE_BOUND_SUM 1u /* flags: max_risk bounds CR_SUM_RISK */
+int cilqr_chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                             const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
+                             const cilqr_obstacles* obs, uint32_t flags, double max_risk, const double* base, double* risk,
+                             double* step_risk, double* entry_p, double* sigma_out, double* total);
+int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                      int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, uint32_t flags,
+                      double max_risk, const double* base, double* risk, double* step_risk, double* entry_p, double* sigma_out,
+                      double* total);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

@@ -34,6 +34,10 @@ RRS_FIELDS = 8
 MAP_RISK_FIELDS = 7
 MR_COLLISION, MR_WORST_OCC, MR_WORST_ROW, MR_WORST_ENTRY, MR_FIRST_STEP, MR_STEP_SHARE, MR_UNKNOWN = range(MAP_RISK_FIELDS)
 MAP_RISK_UNKNOWN_HITS = 1  # flags of `rollout_risk_map`: an invalid probe counts as a hit
+# `cilqr_chance_risk_field`: the columns of an analytic risk row (`Solver.chance_risk`)
+CHANCE_FIELDS = 6
+CR_STEP_RISK, CR_WORST_STEP, CR_SUM_RISK, CR_MAX_P, CR_MAX_ENTRY, CR_MAX_POS_SIGMA = range(CHANCE_FIELDS)
+CHANCE_BOUND_SUM = 1  # flags of `chance_risk`: max_risk bounds CR_SUM_RISK instead of CR_STEP_RISK
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -54,6 +58,7 @@ ABI_SYMBOLS = (
     "cilqr_rollout_risk", "cilqr_rollout_risk_device",
     "cilqr_gains_batch_sampled", "cilqr_gains_batch_sampled_device", "cilqr_rollout_risk_sampled", "cilqr_rollout_risk_sampled_device",
     "cilqr_rollout_risk_map", "cilqr_rollout_risk_map_device",
+    "cilqr_chance_risk", "cilqr_chance_risk_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -660,6 +665,47 @@ class Solver:
                                                    _vp(delta), C.c_int64(delta_batch_stride), C.c_double(k_scale),
                                                    C.c_double(occ_threshold), C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base),
                                                    _vp(risk), _vp(step_hits), _vp(unknown_hits), _vp(total)))
+
+    # ---- analytic pose-noise risk: closed-loop covariance chain and Gaussian chance values ----
+    def chance_risk(self, N, X, U, K, sigma0, process_noise=None, obs_pose=None, obs_dim=None, max_risk=1.0, base=None, sum_bound=False,
+                    want_entry_p=True, want_sigma=True):
+        """`cilqr_chance_risk`: the state covariance along each plan under u = U_t + K_t (x - X_t), from sigma0 — (4, 4) or (16,)
+        shared by the solves, or (B, 4, 4) / (B, 16) one per solve, column-major, only row <= column read — and process noise W (4, 4)
+        or None, and from it the Gaussian chance of each obstacle entry; obstacles in any shape of `obstacle_strides`.  Returns
+        dict(risk (B, CHANCE_FIELDS), step_risk (B, N), entry_p (B, M*N) or None, sigma (B, N+1, 16) or None, total): total[b] is
+        base[b], NaN where CR_STEP_RISK (CR_SUM_RISK with sum_bound) exceeds max_risk or base[b] is not finite; None without `base`."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U, K = _np64(U).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        sigma0 = _np64(sigma0)
+        if sigma0.size == 16:
+            sigma0, stride = sigma0.reshape(16), 0
+        elif sigma0.size == 16 * B:
+            sigma0, stride = sigma0.reshape(B, 16), 1
+        else:
+            raise CilqrError("chance_risk: sigma0 %s holds neither 16 nor %d x 16 values" % (sigma0.shape, B))
+        W = None if process_noise is None else _np64(process_noise).reshape(16)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        base = None if base is None else _np64(base).reshape(B)
+        risk, step_risk = np.zeros((B, CHANCE_FIELDS)), np.zeros((B, N))
+        entry_p = np.zeros((B, M * N)) if want_entry_p else None
+        sigma = np.zeros((B, N + 1, 16)) if want_sigma else None
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_chance_risk(self._h, B, int(N), int(M), _p(X), _p(U), _p(K), _p(sigma0), C.c_int64(stride), _p(W),
+                                       None if obs is None else C.byref(obs), C.c_uint32(CHANCE_BOUND_SUM if sum_bound else 0),
+                                       C.c_double(max_risk), _p(base), _p(risk), _p(step_risk), _p(entry_p), _p(sigma), _p(total)))
+        return dict(risk=risk, step_risk=step_risk, entry_p=entry_p, sigma=sigma, total=total)
+
+    def chance_risk_device(self, stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs_pose, obs_dim, strides, risk,
+                           step_risk=0, entry_p=0, sigma_out=0, total=0, base=0, max_risk=1.0, flags=0):
+        """`cilqr_chance_risk_device`: device addresses; strides (batch, obstacle, step, weight batch) as `score_batch_device`."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_chance_risk_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(U), _vp(K), _vp(sigma0),
+                                              C.c_int64(sigma0_batch_stride), _vp(process_noise), C.byref(obs) if M else None,
+                                              C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_risk),
+                                              _vp(entry_p), _vp(sigma_out), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -1087,6 +1087,68 @@ int cilqr_rollout_risk_map(cilqr_handle* h, int B, int N, int S, const double* X
   });
 }
 
+// ---- analytic pose-noise risk (cilqr_chance.hip) --------------------------------------------------------------------------------------
+namespace {
+int chance_risk_check(const cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                      int64_t sigma0_batch_stride, const cilqr_obstacles* obs, uint32_t flags, double max_risk, const double* base,
+                      const double* risk, const double* total, size_t* span) {
+  if (!X || !U || !K || !sigma0 || !risk) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: total needs base");
+  if (M > 0 && !obs) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: M = %d but obs is null", M);
+  if (M > 0 && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk: negative stride");
+  if (sigma0_batch_stride < 0) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: negative stride");
+  if (sigma0_batch_stride > 1) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: sigma0_batch_stride is 0 (one shared) or 1 (one per solve)");
+  if (max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: max_risk is NaN");
+  if (flags & ~CILQR_CHANCE_BOUND_SUM) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: unknown flag bits 0x%x", flags);
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, nullptr);
+  if (rc) return rc;
+  if ((int64_t)M * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_chance_risk: M * N beyond 2^31 entries");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                             const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
+                             const cilqr_obstacles* obs, uint32_t flags, double max_risk, const double* base, double* risk,
+                             double* step_risk, double* entry_p, double* sigma_out, double* total) {
+  int rc = chance_risk_check(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, obs, flags, max_risk, base, risk, total, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::chance_risk_lds_bytes(N, M) > cilqr::CHANCE_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_chance_risk: horizon %d with %d obstacles does not fit 64 KiB of LDS", N, M);
+  cilqr::ChanceArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.X = X; a.U = U; a.K = K;
+  a.sigma0 = sigma0; a.sigma0_bs = (long long)sigma0_batch_stride * 16; a.W = process_noise;
+  a.max_risk = max_risk; a.base = base; a.risk = risk; a.step_risk = step_risk; a.entry_p = entry_p; a.sigma_out = sigma_out;
+  a.total = total; a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_chance_risk(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                      int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, uint32_t flags,
+                      double max_risk, const double* base, double* risk, double* step_risk, double* entry_p, double* sigma_out,
+                      double* total) {
+  size_t span = 0;
+  int rc = chance_risk_check(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, obs, flags, max_risk, base, risk, total, &span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_chance_risk(p, B, N, M, sigma0_batch_stride == 0 ? 1 : B, X, U, K, sigma0, process_noise, o, span, base, risk, step_risk,
+                          entry_p, sigma_out, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_chance_risk_device(h, h->stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, M > 0 ? &o : nullptr, flags,
+                                    max_risk, base, risk, step_risk, entry_p, sigma_out, total);
+  });
+}
+
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
                               double sigma_x, double sigma_y, double sigma_theta, float* out, int32_t* count_out) {
   if (!h || !src || !g || !out) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap: null argument");

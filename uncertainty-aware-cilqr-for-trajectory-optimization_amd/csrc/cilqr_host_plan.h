@@ -18,7 +18,7 @@
 namespace cilqr {
 
 struct HostPlan {
-  enum { CAP = 16 };  // (the largest call, the sampled rollout risk, declares 12 arrays)
+  enum { CAP = 16 };  // (the largest call, the chance risk, declares 13 arrays)
   struct Entry {
     const void* src;  // host source, null: nothing travels in
     void* dst;        // host destination, null: nothing travels back
@@ -162,7 +162,7 @@ inline void plan_rollout_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t 
   p.out(total, B);
 }
 
-// cilqr_rollout_risk_sampled: M its n_obs, `o` its dense nominal tables without weights (12 arrays, the most any call declares).
+// cilqr_rollout_risk_sampled: M its n_obs, `o` its dense nominal tables without weights (12 arrays).
 inline void plan_rollout_risk_sampled(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, size_t S, size_t delta_sets,
                                       const double*& X, const double*& U, const double*& k, const double*& K, const double*& delta,
                                       cilqr_obstacles& o, const double*& samp_off, const double*& base, double*& risk,
@@ -196,6 +196,29 @@ inline void plan_rollout_risk_map(HostPlan& p, size_t B, size_t N, size_t S, siz
   p.out(risk, B * CILQR_MAP_RISK_FIELDS);
   p.out(step_hits, B * N);
   p.out(unknown_hits, B * N);
+  p.out(total, B);
+}
+
+// cilqr_chance_risk: 13 arrays, the most any call declares; obstacle weights are not read and do not travel.  sigma_sets: B, or 1
+// for one Σ0 shared by the solves.  Per solve 15·N + 6·M·N + 28 doubles without sigma_out and entry_p — inside the 22·N + 6·M·N +
+// M + 34 per unit of max_batch that host_arena_bytes reserves below, for every B <= max_batch — and 31·N + 7·M·N + 44 with both,
+// which fits for every B <= max_batch / 2; the shared W and the 13 roundings stay within its 32 x 16 bytes and that margin.
+inline void plan_chance_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t sigma_sets, const double*& X, const double*& U,
+                             const double*& K, const double*& sigma0, const double*& W, cilqr_obstacles& o, size_t span,
+                             const double*& base, double*& risk, double*& step_risk, double*& entry_p, double*& sigma_out,
+                             double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(sigma0, sigma_sets * 16);
+  p.in(W, 16);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, span, 0);
+  p.in(base, B);
+  p.out(risk, B * CILQR_CHANCE_FIELDS);
+  p.out(step_risk, B * N);
+  p.out(entry_p, B * M * N);
+  p.out(sigma_out, B * (N + 1) * 16);
   p.out(total, B);
 }
 

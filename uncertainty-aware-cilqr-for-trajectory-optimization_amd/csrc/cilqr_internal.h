@@ -191,6 +191,29 @@ struct MapRiskArgs {
 hipError_t launch_rollout_risk_map(const MapRiskArgs& a, hipStream_t stream);
 size_t rollout_risk_map_lds_bytes(int N);
 
+// Closed-loop covariance chain and Gaussian chance values per solve (cilqr_chance.hip; cilqr_chance_risk*): one workgroup per
+// solve.  `s` carries what the launch shares with a solve — the strided obstacle fields, B, N, M, kp — and comes first, so that
+// phase_args / phase_params of cilqr_device.hpp read it.
+constexpr int CHANCE_THREADS = 256;
+constexpr size_t CHANCE_LDS_MAX = 64 * 1024;
+struct ChanceArgs {
+  SolveArgs s;
+  const double *X, *U, *K;   // the plan and its gains, [B][…]
+  const double* sigma0;      // [B or 1][16]
+  long long sigma0_bs;       // doubles between two solves' Σ0 (0: shared)
+  const double* W;           // [16] or null (zero)
+  double max_risk;
+  const double* base;        // [B] or null (then total is null)
+  double* risk;              // [B][CILQR_CHANCE_FIELDS]
+  double* step_risk;         // [B][N] or null
+  double* entry_p;           // [B][M·N] or null
+  double* sigma_out;         // [B][N + 1][16] or null
+  double* total;             // [B] or null
+  uint32_t flags;            // CILQR_CHANCE_*
+};
+hipError_t launch_chance_risk(const ChanceArgs& a, hipStream_t stream);
+size_t chance_risk_lds_bytes(int N, int M);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

@@ -176,7 +176,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
-  if (!noise_.empty()) return run_candidates_noise_checked(B, ego_states);
+  if (!noise_.empty() || cov_check_) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
@@ -240,6 +240,10 @@ void hip_check(hipError_t e, const char* what) {
 namespace {
 const char* const kStoredRowsWithSamples =
     "the stored-rows pose-noise check has no form for sampled obstacles (set_obstacle_samples): use set_pose_noise_check_fused";
+const char* const kCovarianceWithNoise =
+    "set_pose_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
+const char* const kCovarianceWithSamples =
+    "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples) yet: use set_pose_noise_check_fused";
 }  // namespace
 
 void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_samples) {
@@ -250,12 +254,13 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
     if (n_samples < 2 || offsets.size() % ((size_t)3 * n_samples) != 0)
       throw std::runtime_error("set_obstacle_samples: needs n_samples >= 2 and n_obs * n_samples * 3 offsets");
     if (offsets.size() / 3 > (size_t)max_obstacles_) throw std::runtime_error("set_obstacle_samples: n_obs * n_samples above max_obstacles");
+    if (cov_check_) throw std::logic_error(kCovarianceWithSamples);
     samples_ = offsets;
     n_samples_ = n_samples;
   }
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty()) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+  if (!noise_.empty() || cov_check_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
 }
 
 int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
@@ -286,6 +291,7 @@ int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& di
 void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check: offsets must hold 4 doubles per sample");
   if (n_samples_ && !offsets.empty()) throw std::logic_error(kStoredRowsWithSamples);
+  if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
@@ -297,6 +303,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
 
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check_fused: offsets must hold 4 doubles per sample");
+  if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
@@ -317,10 +324,28 @@ void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknow
   last_map_unknown_hits.clear();
 }
 
+void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
+  if (Sigma0 && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
+  if (Sigma0 && n_samples_) throw std::logic_error(kCovarianceWithSamples);
+  if (max_risk != max_risk) throw std::runtime_error("set_pose_covariance_check: max_risk is NaN");
+  cov_check_ = Sigma0 != nullptr;
+  cov_has_W_ = cov_check_ && W != nullptr;
+  if (cov_check_) memcpy(cov_sigma0_, Sigma0, sizeof(cov_sigma0_));
+  if (cov_has_W_) memcpy(cov_W_, W, sizeof(cov_W_));
+  cov_max_risk_ = max_risk;
+  cov_lamb_ = lamb;
+  cov_sum_ = sum_bound;
+  last_chance_risk.clear();
+  last_step_risk.clear();
+  if (cov_check_) reserve_noise_buffers();
+}
+
 // One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.  The fused
 // check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
 void iLQR::reserve_noise_buffers() {
-  const size_t B = max_candidates_, S = noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = noise_fused_ ? 0 : B * S;
+  // (the covariance check has no draws: it keeps ONE zero offset, the plan itself, for the map risk call, and the fused check's arrays)
+  const bool fused = noise_fused_ || cov_check_;
+  const size_t B = max_candidates_, S = cov_check_ ? 1 : noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = fused ? 0 : B * S;
   // with obstacle samples: per-candidate nominal tables and offsets in place of the one shared set (n_obs * n_samples <= M)
   const size_t n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
   size_t o = 0;
@@ -333,11 +358,14 @@ void iLQR::reserve_noise_buffers() {
   L.k = take(B * 2 * N); L.K = take(B * 8 * N); L.ok = take(B);
   L.delta = take(S * 4);
   L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
-  L.risk = take(B * (n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
-  L.score = take(noise_fused_ ? B * CILQR_SCORE_FIELDS : 0); L.base = take(noise_fused_ ? B : 0); L.hits = take(noise_fused_ ? (B * N + 1) / 2 : 0);
+  L.risk = take(B * (n_samples_ ? CILQR_RRS_FIELDS : fused ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
+  L.score = take(fused ? B * CILQR_SCORE_FIELDS : 0); L.base = take(fused ? B : 0); L.hits = take(fused ? (B * N + 1) / 2 : 0);
   // the map risk check's outputs (a few doubles per candidate: reserved with the fused check whether or not the check is on)
-  L.mrisk = take(noise_fused_ ? B * CILQR_MAP_RISK_FIELDS : 0); L.mtotal = take(noise_fused_ ? B : 0);
-  L.mhits = take(noise_fused_ ? (B * N + 1) / 2 : 0); L.munk = take(noise_fused_ ? (B * N + 1) / 2 : 0);
+  L.mrisk = take(fused ? B * CILQR_MAP_RISK_FIELDS : 0); L.mtotal = take(fused ? B : 0);
+  L.mhits = take(fused ? (B * N + 1) / 2 : 0); L.munk = take(fused ? (B * N + 1) / 2 : 0);
+  // the covariance check's inputs and outputs
+  L.s0 = take(cov_check_ ? 16 : 0); L.W = take(cov_check_ ? 16 : 0);
+  L.crisk = take(cov_check_ ? B * CILQR_CHANCE_FIELDS : 0); L.cstep = take(cov_check_ ? B * N : 0);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -349,12 +377,15 @@ void iLQR::reserve_noise_buffers() {
   if (noise_dev_) hip_check(hipFree(noise_dev_), "hipFree");
   noise_dev_ = nullptr;
   hip_check(hipMalloc(&noise_dev_, L.end * sizeof(double)), "hipMalloc");
-  hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  if (cov_check_) hip_check(hipMemset((double*)noise_dev_ + L.delta, 0, 4 * sizeof(double)), "hipMemset");
+  else hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
   noise_horizon_ = params.horizon;
 }
 
 int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_states) {
-  const int N = params.horizon, M = (int)obstacles_.size(), S = (int)(noise_.size() / 4);
+  const int N = params.horizon, M = (int)obstacles_.size(), S = cov_check_ ? 1 : (int)(noise_.size() / 4);
+  if (cov_check_ && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
+  if (cov_check_ && n_samples_) throw std::logic_error(kCovarianceWithSamples);
   if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
@@ -396,7 +427,18 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   const cilqr_obstacles* po = M ? &obs : nullptr;
   const int risk_fields = n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS;
   int rc = CILQR_OK;
-  if (n_samples_) {  // the same chain in the compact sampled form
+  const bool scored = cov_check_ ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
+  if (cov_check_) {  // the analytic check: covariance chain and chance values in place of rollouts
+    up(L.s0, cov_sigma0_, 16);
+    if (cov_has_W_) up(L.W, cov_W_, 16);
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
+    if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, cov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+    if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
+                                           cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
+                                           d + L.cstep, nullptr, nullptr, d + L.total);
+  } else if (n_samples_) {  // the same chain in the compact sampled form
     const int ns = n_samples_;
     const double w = sample_weight();
     rc = cilqr_solve_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim, d + L.soff, w,
@@ -421,7 +463,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
       if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
     }
   }
-  const bool map_checked = map_check_ && map_set_ && noise_fused_;
+  const bool map_checked = map_check_ && map_set_ && (noise_fused_ || cov_check_);
   if (map_checked && !rc)  // the map's say on top of the obstacles': base = their total, NaN staying NaN
     rc = cilqr_rollout_risk_map_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
                                        map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + L.total, d + L.mrisk,
@@ -435,13 +477,25 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   double pair[2] = {0.0, -1.0};
   last_scores.clear();
   last_step_hits.clear();
-  last_risk.assign((size_t)B * risk_fields, 0.0);
+  last_risk.clear();
+  last_chance_risk.clear();
+  last_step_risk.clear();
   down(pair, L.pair, sizeof(pair));
-  down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
-  if (noise_fused_) {
+  if (cov_check_) {
+    last_chance_risk.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0);
+    last_step_risk.assign((size_t)B * N, 0.0);
+    down(last_chance_risk.data(), L.crisk, last_chance_risk.size() * sizeof(double));
+    down(last_step_risk.data(), L.cstep, last_step_risk.size() * sizeof(double));
+  } else {
+    last_risk.assign((size_t)B * risk_fields, 0.0);
+    down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
+  }
+  if (scored) {
     last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
-    last_step_hits.assign((size_t)B * N, 0);
     down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
+  }
+  if (noise_fused_ && !cov_check_) {
+    last_step_hits.assign((size_t)B * N, 0);
     down(last_step_hits.data(), L.hits, last_step_hits.size() * sizeof(int32_t));
   }
   last_map_risk.clear();

@@ -135,6 +135,21 @@ class iLQR {
   // per candidate.  With no map set, or under any other pick, behaviour is what it is without this call and the three fields are
   // empty.  An occ_threshold that is NaN switches the check off (the default).
   void set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits = false);
+  // Pose-covariance check: the analytic counterpart of the fused pose-noise check.  Instead of S draws of the pose noise the node
+  // hands over its covariance: Sigma0, 4 x 4 column-major over (x, y, v, theta) (only row <= column is read), and the process noise
+  // W added per step (nullable: none).  run_candidates then enqueues, on the check's stream: solve -> (under MinTotalCost
+  // cilqr_score_batch_device, max_collision 1: the nominal totals) -> cilqr_gains_batch_device(lamb) -> cilqr_chance_risk_device
+  // (max_risk; base = those totals, or J under MinTrackingCost) -> cilqr_argmin_device on its `total`.  A candidate is rejected when
+  // CR_STEP_RISK — with sum_bound CR_SUM_RISK — exceeds max_risk: the largest per-step (the summed) Gaussian chance that an ego circle
+  // enters an obstacle of set_Obstacle under the closed-loop covariance along its plan.  No samples, no seed, and it orders candidates
+  // the sampled check calls 0 / S.  last_chance_risk holds CILQR_CHANCE_FIELDS per candidate (cilqr_chance_risk_field),
+  // last_step_risk the per-step bound r_t, horizon per candidate; last_scores the nominal score rows under MinTotalCost.  Rejection
+  // and the -1 return as under set_pose_noise_check.  set_map_risk_check composes after it through `base` while an uncertainty map
+  // is set: with no draws to roll out, the map call sees ONE rollout per candidate, from the zero offset — the plan itself — so a
+  // plan whose own footprint enters cells above occ_threshold is rejected whenever max_risk of set_map_risk_check is below 1.
+  // Together with set_pose_noise_check(_fused) offsets, or with set_obstacle_samples (the chance value has no sampled form yet),
+  // the setters throw std::logic_error naming the conflict.  Sigma0 == nullptr switches the check off (the default).
+  void set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb = 1.0, bool sum_bound = false);
 
   // Sampled obstacles: the uncertainty-aware scene form.  `offsets` holds n_obs x n_samples x 3 doubles, (dx, dy, dtheta) per pose
   // sample, drawn ONCE by the node with its own sigmas; the obstacles of set_Obstacle are then the NOMINAL ones (n_obs of them, in
@@ -165,6 +180,8 @@ class iLQR {
   // run_candidates with the map risk check in effect (set_map_risk_check); empty otherwise
   std::vector<double> last_map_risk;               // CILQR_MAP_RISK_FIELDS per candidate
   std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
+  // run_candidates under set_pose_covariance_check; empty otherwise
+  std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
 
  private:
   void pack_obstacles();
@@ -184,7 +201,7 @@ class iLQR {
   // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
   // so that this header needs no HIP
   struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, end;
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep, end;
   };
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
@@ -205,6 +222,9 @@ class iLQR {
   // map risk check: in effect when map_check_ (set_map_risk_check), map_set_ (an uncertainty map is set) and noise_fused_
   bool map_check_ = false, map_set_ = false, map_unknown_hits_ = false;
   double map_threshold_ = 0.0, map_max_risk_ = 1.0;
+  // pose-covariance check (set_pose_covariance_check): Sigma0 and W travel with every call (32 doubles)
+  bool cov_check_ = false, cov_has_W_ = false, cov_sum_ = false;
+  double cov_sigma0_[16] = {}, cov_W_[16] = {}, cov_max_risk_ = 1.0, cov_lamb_ = 1.0;
 };
 
 }  // namespace cilqr_host
