@@ -43,6 +43,8 @@
  *                                                                for sampled obstacles in compact form
  *   (none: the reference propagates no state covariance)     cilqr_chance_risk(_device): closed-loop covariance along the plan
  *                                                                and Gaussian chance values per obstacle and step, no samples
+ *                                                                cilqr_tighten_obstacles(_device): obstacles inflated by that
+ *                                                                covariance for a warm-started re-solve; cilqr_chance_kappa
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -698,6 +700,73 @@ int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, con
                       int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, uint32_t flags,
                       double max_risk, const double* base, double* risk, double* step_risk, double* entry_p, double* sigma_out,
                       double* total);
+
+/* --- chance-constraint tightening: obstacles inflated by Sigma_t for a re-solve (new) ---------------------------------------------
+ * Every call above JUDGES a solved plan under pose uncertainty; none feeds back into the solve.  cilqr_tighten_obstacles(_device)
+ * is that step: from the Sigma_t that cilqr_chance_risk left in sigma_out it grows every obstacle entry by kappa standard
+ * deviations of the relative position (ego circle minus obstacle) along the ellipse's own axes, and writes a dense obstacle table
+ * that cilqr_solve_batch_obstacles(_device) re-solves against, warm-started from the plan's U.  One round of the loop, all of it
+ * device-resident:  solve -> cilqr_gains_batch -> cilqr_chance_risk (sigma_out) -> cilqr_tighten_obstacles -> solve on (pose_out,
+ * dim_out).  Sigma is an INPUT: the chain has its kernel, and the loop wants the chance figures of the untightened plan anyway.
+ * X [B][4*(N+1)], the plan; sigma [B][N+1][16], exactly sigma_out of cilqr_chance_risk (column-major, entry (r, c) at [r + 4*c]).
+ * Of each Sigma_t, t < N, six entries are read: (0,0), (0,1), (0,3), (1,1), (1,3), (3,3) — row <= column, position and heading; the
+ * speed row and column do not move a circle centre.  Obstacles through the strides of cilqr_obstacles (weights are not read).
+ * obs_cov: NULL (zero), or the obstacle's own position covariance, 3 doubles (xx, xy, yy; world frame) at obs_cov + 3*e for the same
+ * entry index e = b*batch_stride + m*obstacle_stride + t*step_stride that addresses its pose: an obstacle whose predicted position
+ * is uncertain is then solved against as ONE inflated ellipse where the sampled form uses n_samples of them.
+ *
+ * Definition.  For entry (m, t), t < N, and each ego circle, lever l = +ego_front (front) or -ego_rear (rear), theta = X_t[3],
+ * j = (-l sin theta, l cos theta) the derivative of the circle centre over theta, S = Sigma_t:
+ *     Cxx = S00 + 2 jx S03 + jx^2 S33,    Cyy = S11 + 2 jy S13 + jy^2 S33,    Cxy = S01 + jx S13 + jy S03 + jx jy S33
+ *   is the centre's position covariance; obs_cov is added to it; and with co = cos theta_o, so = sin theta_o of the obstacle's pose
+ *     va = co^2 Cxx + 2 co so Cxy + so^2 Cyy,      vb = so^2 Cxx - 2 co so Cxy + co^2 Cyy
+ *   are the variances along the ellipse's axes.  Over the two circles the larger va and the larger vb are taken, a NaN losing to a
+ *   number; a negative result counts as 0; where both circles' values are NaN the result is NaN.  Then
+ *     da = kappa*sqrt(va),  db = kappa*sqrt(vb),   each replaced by max_inflate when it is not finite or exceeds max_inflate: such
+ *   an entry counts as CAPPED (a Sigma_t with a NaN among its six entries caps every entry of its step, kappa = 0 included);
+ *     dim_out[b][m][2*t ...] = (length + 2*da, width + 2*db).  The solver's semi-axes are dim/2 + ..., so a and b grow by exactly
+ *   da and db.  dim_out is dense [B][M][2*N], the layout of obs_dim and of nom_dim: it feeds both solve forms.
+ *   pose_out [B][M][4*N] or NULL: the bit copy of the addressed poses, so that obstacles shared by strides become the dense table
+ *   (strides M*N, N, 1) the re-solve needs beside dim_out.
+ * What this is: an AXIS-WISE MARGINAL tightening — the ellipse grows along its axes by the marginal standard deviations, the
+ * correlation between the two axes is dropped, and it agrees with the chance value of cilqr_chance_risk (one Gaussian of the
+ * linearised constraint) to first order only.  kappa for a per-entry chance eps: cilqr_chance_kappa(eps).  The barriers are soft:
+ * the loop guarantees nothing.  Where the plan has room to move it does what it should (an obstacle 12 m ahead and 1 to 3.8 m to
+ * the side, eps 0.05: one round turns a candidate in contact, CR_STEP_RISK 1, into max c <= -0.08 and CR_STEP_RISK <= 1.5e-7 for
+ * every candidate, both against the ORIGINAL obstacles).  Where it has none it does not help: with the ego starting beside the
+ * obstacle the first steps cannot leave the inflated ellipse, a warm-started re-solve drifts with or without tightening, and
+ * CR_STEP_RISK went 0.1015 -> 0.1044 re-solved without it and 0.1015 -> 0.131 with kappa 1.645.  Judge the final plan against the
+ * original obstacles, always.
+ * tighten [B][CILQR_TIGHTEN_FIELDS] (required), see the enum.  No floating sums: maxima are lexicographic, the count is an integer.
+ *   A solve's outputs depend on its own inputs alone: the same bits whatever B is, wherever the solve sits in the batch and whatever
+ *   strides address the same values.
+ * Mapping: one workgroup per solve, one launch, nothing allocated per call.  Per step the two circle centres' covariances (Cxx, Cxy,
+ * Cyy: what depends on the step alone) are staged in LDS, lanes then stride over the M*N entries.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X, sigma, dim_out or tighten; obs NULL with M > 0; a negative stride;
+ * a kappa or max_inflate that is negative or not finite; then B, N or M beyond the cilqr_create limits.  The host-buffer form's
+ * arrays — X, sigma, the obstacle span, 3 doubles of obs_cov per entry of the span, and the outputs — must fit the device arena
+ * reserved at create (CILQR_ERR_ARG otherwise; this call adds nothing to it).  With dense obstacles that is 20*N + 15*M*N + 24
+ * doubles per solve with obs_cov and pose_out, 20*N + 8*M*N + 24 without them: every B <= 2*max_batch/5 always fits with both, every
+ * B <= 3*max_batch/4 without; M = 0 fits for every B <= max_batch.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(6*N + 20) bytes (six doubles per step, five per wavefront for the reduction),
+ * exceeds 64 KiB: N above 1362, which CILQR_MAX_HORIZON = 384 keeps out of reach — every horizon a handle accepts runs. */
+#define CILQR_TIGHTEN_FIELDS 4
+typedef enum cilqr_tighten_field {
+  CILQR_TG_MAX_DA = 0,    /* max over entries of da;  0 when M == 0 */
+  CILQR_TG_MAX_DB = 1,    /* max over entries of db;  0 when M == 0 */
+  CILQR_TG_MAX_ENTRY = 2, /* m*N + t of the largest max(da, db), lowest index on equal values;  -1 when M == 0 */
+  CILQR_TG_CAPPED = 3     /* number of capped entries */
+} cilqr_tighten_field;
+int cilqr_tighten_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* sigma,
+                                   const cilqr_obstacles* obs, const double* obs_cov, double kappa, double max_inflate,
+                                   double* pose_out, double* dim_out, double* tighten);
+int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* X, const double* sigma, const cilqr_obstacles* obs,
+                            const double* obs_cov, double kappa, double max_inflate, double* pose_out, double* dim_out,
+                            double* tighten);
+/* Host only: the kappa with erfc(kappa/sqrt 2)/2 = eps, the one-sided Gaussian quantile of a per-entry chance eps, by Newton's
+ * iteration on (the logarithm of) erfc from the fixed start sqrt(-2 log eps) with a fixed number of steps: the same bits for the
+ * same eps.  NaN outside (0, 0.5]; exactly 0 at 0.5. */
+double cilqr_chance_kappa(double eps);
 
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's

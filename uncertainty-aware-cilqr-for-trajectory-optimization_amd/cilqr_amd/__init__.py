@@ -38,6 +38,9 @@ MAP_RISK_UNKNOWN_HITS = 1  # flags of `rollout_risk_map`: an invalid probe count
 CHANCE_FIELDS = 6
 CR_STEP_RISK, CR_WORST_STEP, CR_SUM_RISK, CR_MAX_P, CR_MAX_ENTRY, CR_MAX_POS_SIGMA = range(CHANCE_FIELDS)
 CHANCE_BOUND_SUM = 1  # flags of `chance_risk`: max_risk bounds CR_SUM_RISK instead of CR_STEP_RISK
+# `cilqr_tighten_field`: the columns of a tightening row (`Solver.tighten_obstacles`)
+TIGHTEN_FIELDS = 4
+TG_MAX_DA, TG_MAX_DB, TG_MAX_ENTRY, TG_CAPPED = range(TIGHTEN_FIELDS)
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -59,6 +62,7 @@ ABI_SYMBOLS = (
     "cilqr_gains_batch_sampled", "cilqr_gains_batch_sampled_device", "cilqr_rollout_risk_sampled", "cilqr_rollout_risk_sampled_device",
     "cilqr_rollout_risk_map", "cilqr_rollout_risk_map_device",
     "cilqr_chance_risk", "cilqr_chance_risk_device",
+    "cilqr_tighten_obstacles", "cilqr_tighten_obstacles_device", "cilqr_chance_kappa",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -156,6 +160,8 @@ def lib():
             raise CilqrError("%s not built — run __graft_entry__.build() (hipcc --offload-arch=gfx950)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         L.cilqr_last_error.restype = C.c_char_p
+        L.cilqr_chance_kappa.restype = C.c_double
+        L.cilqr_chance_kappa.argtypes = [C.c_double]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
         _lib = L
@@ -202,6 +208,11 @@ def pinned_copy(a):
 def _check(rc):
     if rc != 0:
         raise CilqrError("cilqr error %d: %s" % (rc, lib().cilqr_last_error().decode()))
+
+
+def chance_kappa(eps):
+    """`cilqr_chance_kappa`: the kappa with erfc(kappa / sqrt 2) / 2 = eps; NaN outside (0, 0.5], exactly 0 at 0.5."""
+    return float(lib().cilqr_chance_kappa(float(eps)))
 
 
 def default_params(horizon=None):
@@ -706,6 +717,34 @@ class Solver:
                                               C.c_int64(sigma0_batch_stride), _vp(process_noise), C.byref(obs) if M else None,
                                               C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_risk),
                                               _vp(entry_p), _vp(sigma_out), _vp(total)))
+
+    # ---- chance-constraint tightening: obstacles inflated by Sigma_t for a warm-started re-solve ----
+    def tighten_obstacles(self, N, X, sigma, obs_pose=None, obs_dim=None, obs_cov=None, kappa=0.0, max_inflate=2.0, want_pose=True):
+        """`cilqr_tighten_obstacles`: sigma (B, N+1, 16) as `chance_risk` returns it; obstacles in any shape of `obstacle_strides`;
+        obs_cov None or (xx, xy, yy) per obstacle entry in the obstacles' own shape with 3 (or 3N) columns.  Returns dict(dim (B, M, 2N),
+        pose (B, M, 4N) or None, tighten (B, TIGHTEN_FIELDS)): the dense table `solve_batch` re-solves against."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        sigma = _np64(sigma).reshape(B, N + 1, 16)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        obs_cov = None if obs_cov is None or M == 0 else _np64(obs_cov)
+        if obs_cov is not None and obs_cov.size * 4 != keep[0].size * 3:
+            raise CilqrError("tighten_obstacles: obs_cov %s does not hold 3 values per entry of obs_pose %s" % (obs_cov.shape, keep[0].shape))
+        dim, tighten = np.zeros((B, M, 2 * N)), np.zeros((B, TIGHTEN_FIELDS))
+        pose = np.zeros((B, M, 4 * N)) if want_pose else None
+        _check(lib().cilqr_tighten_obstacles(self._h, B, int(N), int(M), _p(X), _p(sigma), None if obs is None else C.byref(obs),
+                                             _p(obs_cov), C.c_double(kappa), C.c_double(max_inflate), _p(pose), _p(dim), _p(tighten)))
+        return dict(dim=dim, pose=pose, tighten=tighten)
+
+    def tighten_obstacles_device(self, stream, B, N, M, X, sigma, obs_pose, obs_dim, strides, dim_out, tighten, pose_out=0, obs_cov=0,
+                                 kappa=0.0, max_inflate=2.0):
+        """`cilqr_tighten_obstacles_device`: device addresses; strides (batch, obstacle, step, weight batch) as `score_batch_device`."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_tighten_obstacles_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(sigma),
+                                                    C.byref(obs) if M else None, _vp(obs_cov), C.c_double(kappa), C.c_double(max_inflate),
+                                                    _vp(pose_out), _vp(dim_out), _vp(tighten)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -1149,6 +1149,84 @@ int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, con
   });
 }
 
+// ---- chance-constraint tightening (cilqr_tighten.hip) ---------------------------------------------------------------------------------
+namespace {
+int tighten_check(const cilqr_handle* h, int B, int N, int M, const double* X, const double* sigma, const cilqr_obstacles* obs,
+                  double kappa, double max_inflate, const double* dim_out, const double* tighten, size_t* span) {
+  if (!X || !sigma || !dim_out || !tighten) return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: null required pointer");
+  if (M > 0 && !obs) return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: M = %d but obs is null", M);
+  if (M > 0 && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: negative stride");
+  if (!(kappa >= 0.0 && kappa <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: kappa is negative or not finite");
+  if (!(max_inflate >= 0.0 && max_inflate <= 1.7e308))
+    return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: max_inflate is negative or not finite");
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, nullptr);
+  if (rc) return rc;
+  if ((int64_t)M * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_tighten_obstacles: M * N beyond 2^31 entries");
+  return CILQR_OK;
+}
+}  // namespace
+
+namespace {
+// (arguments checked by the caller; with M = 0 the host form's dim_out has no place in the arena and is null here)
+int tighten_launch(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* sigma, const cilqr_obstacles* obs,
+                   const double* obs_cov, double kappa, double max_inflate, double* pose_out, double* dim_out, double* tighten) {
+  if (cilqr::tighten_lds_bytes(N) > cilqr::TIGHTEN_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_tighten_obstacles: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::TightenArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.X = X; a.sigma = sigma; a.obs_cov = M > 0 ? obs_cov : nullptr;
+  a.kappa = kappa; a.max_inflate = max_inflate;
+  a.pose_out = M > 0 ? pose_out : nullptr; a.dim_out = dim_out; a.tighten = tighten;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_tighten_obstacles(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_tighten_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* sigma,
+                                   const cilqr_obstacles* obs, const double* obs_cov, double kappa, double max_inflate,
+                                   double* pose_out, double* dim_out, double* tighten) {
+  int rc = tighten_check(h, B, N, M, X, sigma, obs, kappa, max_inflate, dim_out, tighten, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  return tighten_launch(h, stream, B, N, M, X, sigma, obs, obs_cov, kappa, max_inflate, pose_out, dim_out, tighten);
+}
+
+int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* X, const double* sigma, const cilqr_obstacles* obs,
+                            const double* obs_cov, double kappa, double max_inflate, double* pose_out, double* dim_out,
+                            double* tighten) {
+  size_t span = 0;
+  int rc = tighten_check(h, B, N, M, X, sigma, obs, kappa, max_inflate, dim_out, tighten, &span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  if (M == 0) { obs_cov = nullptr; pose_out = nullptr; }
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_tighten_obstacles(p, B, N, M, X, sigma, o, span, obs_cov, pose_out, dim_out, tighten);
+  return cilqr::host_call(h, p, [&] {
+    return tighten_launch(h, h->stream, B, N, M, X, sigma, M > 0 ? &o : nullptr, obs_cov, kappa, max_inflate, pose_out, dim_out, tighten);
+  });
+}
+
+// kappa with erfc(kappa/sqrt 2)/2 = eps: Newton's iteration on log erfc, whose graph is nearly a parabola, from
+// sqrt(-2 log eps) — at or beyond the root, since erfc(k/sqrt 2)/2 <= exp(-k^2/2)/2 — with a fixed number of steps.
+double cilqr_chance_kappa(double eps) {
+  if (!(eps > 0.0 && eps <= 0.5)) return NAN;
+  if (eps == 0.5) return 0.0;
+  const double root_half = 7.07106781186547524401e-01, inv_root_2pi = 3.98942280401432677940e-01;
+  double k = sqrt(-2.0 * log(eps));
+  for (int i = 0; i < 40; ++i) {
+    const double q = 0.5 * erfc(k * root_half);
+    if (!(q > 0.0)) { k -= 0.5; continue; }  // (underflow, eps below 1e-300: back towards the root)
+    k += q / (inv_root_2pi * exp(-0.5 * k * k)) * log(q / eps);
+  }
+  return k;
+}
+
 int cilqr_blur_costmap_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* g, int index, double vtheta,
                               double sigma_x, double sigma_y, double sigma_theta, float* out, int32_t* count_out) {
   if (!h || !src || !g || !out) return fail(CILQR_ERR_ARG, "cilqr_blur_costmap: null argument");

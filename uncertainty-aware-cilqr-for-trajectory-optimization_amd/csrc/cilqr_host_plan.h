@@ -222,6 +222,22 @@ inline void plan_chance_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t s
   p.out(total, B);
 }
 
+// cilqr_tighten_obstacles: 8 arrays; obstacle weights are not read and do not travel; obs_cov travels as 3 doubles per entry of the
+// span.  Per solve, with dense obstacles, 20·N + 15·M·N + 24 doubles with obs_cov and pose_out and 20·N + 8·M·N + 24 without them,
+// against the 22·N + 6·M·N + M + 34 per unit of max_batch that host_arena_bytes reserves below: every B <= 2·max_batch/5 fits with
+// both, every B <= 3·max_batch/4 without, and the 8 roundings stay within its 32 x 16 bytes.
+inline void plan_tighten_obstacles(HostPlan& p, size_t B, size_t N, size_t M, const double*& X, const double*& sigma, cilqr_obstacles& o,
+                                   size_t span, const double*& obs_cov, double*& pose_out, double*& dim_out, double*& tighten) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(sigma, B * (N + 1) * 16);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, span, 0);
+  p.in(obs_cov, span * 3);
+  p.out(pose_out, B * M * 4 * N);
+  p.out(dim_out, B * M * 2 * N);
+  p.out(tighten, B * CILQR_TIGHTEN_FIELDS);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

@@ -214,6 +214,23 @@ struct ChanceArgs {
 hipError_t launch_chance_risk(const ChanceArgs& a, hipStream_t stream);
 size_t chance_risk_lds_bytes(int N, int M);
 
+// Chance-constraint tightening (cilqr_tighten.hip; cilqr_tighten_obstacles*): every obstacle entry's dimensions grown by kappa
+// standard deviations of the relative position along the ellipse's axes.  One workgroup per solve; `s` first, as in ChanceArgs.
+constexpr int TIGHTEN_THREADS = 256;
+constexpr size_t TIGHTEN_LDS_MAX = 64 * 1024;
+struct TightenArgs {
+  SolveArgs s;
+  const double* X;        // [B][4(N + 1)]
+  const double* sigma;    // [B][N + 1][16], sigma_out of the chance risk
+  const double* obs_cov;  // null (zero), or (xx, xy, yy) at obs_cov + 3e for the obstacle entry index e
+  double kappa, max_inflate;
+  double* pose_out;       // [B][M][4N] or null
+  double* dim_out;        // [B][M][2N]
+  double* tighten;        // [B][CILQR_TIGHTEN_FIELDS]
+};
+hipError_t launch_tighten_obstacles(const TightenArgs& a, hipStream_t stream);
+size_t tighten_lds_bytes(int N);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

@@ -85,7 +85,10 @@ void iLQR::pack_obstacles() {
       held_ = memcmp(&o.relative_pos_array.a[(size_t)4 * t], &o.relative_pos_array.a[0], 4 * sizeof(double)) == 0 &&
               memcmp(&o.dimension.a[(size_t)2 * t], &o.dimension.a[0], 2 * sizeof(double)) == 0;
   packed_horizon_ = N;
-  const int M = (int)obstacles_.size(), T = held_ ? 1 : N;  // columns packed per obstacle
+  const int M = (int)obstacles_.size();
+  // a covariance per step needs an entry per step to sit beside (obs_cov shares the poses' entry index)
+  if (M && N > 1 && obs_cov_.size() == (size_t)3 * M * N) held_ = false;
+  const int T = held_ ? 1 : N;  // columns packed per obstacle
   obs_pose_.resize((size_t)M * 4 * T);
   obs_dim_.resize((size_t)M * 2 * T);
   for (int m = 0; m < M; ++m) {
@@ -94,6 +97,14 @@ void iLQR::pack_obstacles() {
       for (int r = 0; r < 4; ++r) obs_pose_[((size_t)m * T + t) * 4 + r] = o.relative_pos_array(r, t);
       for (int r = 0; r < 2; ++r) obs_dim_[((size_t)m * T + t) * 2 + r] = o.dimension(r, t);
     }
+  }
+  obs_cov_packed_.clear();
+  if (M && (obs_cov_.size() == (size_t)3 * M || obs_cov_.size() == (size_t)3 * M * N)) {
+    const bool per_step = obs_cov_.size() != (size_t)3 * M;
+    obs_cov_packed_.resize((size_t)M * T * 3);
+    for (int m = 0; m < M; ++m)
+      for (int t = 0; t < T; ++t)
+        for (int r = 0; r < 3; ++r) obs_cov_packed_[((size_t)m * T + t) * 3 + r] = obs_cov_[per_step ? ((size_t)m * N + t) * 3 + r : (size_t)m * 3 + r];
   }
 }
 
@@ -116,6 +127,7 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
+  if (tighten_) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
   if (n_samples_) {
@@ -176,7 +188,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
-  if (!noise_.empty() || cov_check_) return run_candidates_noise_checked(B, ego_states);
+  if (!noise_.empty() || cov_check_ || tighten_) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
@@ -238,10 +250,14 @@ void hip_check(hipError_t e, const char* what) {
 }  // namespace
 
 namespace {
+const char* const kObstacleCovarianceSize =
+    "set_obstacle_covariance: needs 3 values per obstacle of set_Obstacle, or 3 per obstacle and step";
 const char* const kStoredRowsWithSamples =
     "the stored-rows pose-noise check has no form for sampled obstacles (set_obstacle_samples): use set_pose_noise_check_fused";
 const char* const kCovarianceWithNoise =
     "set_pose_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
+const char* const kTighteningWithSamples =
+    "set_chance_tightening has no form for sampled obstacles (set_obstacle_samples): the sampled solve takes no inflated table";
 const char* const kCovarianceWithSamples =
     "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples) yet: use set_pose_noise_check_fused";
 }  // namespace
@@ -255,12 +271,13 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
       throw std::runtime_error("set_obstacle_samples: needs n_samples >= 2 and n_obs * n_samples * 3 offsets");
     if (offsets.size() / 3 > (size_t)max_obstacles_) throw std::runtime_error("set_obstacle_samples: n_obs * n_samples above max_obstacles");
     if (cov_check_) throw std::logic_error(kCovarianceWithSamples);
+    if (tighten_) throw std::logic_error(kTighteningWithSamples);
     samples_ = offsets;
     n_samples_ = n_samples;
   }
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || cov_check_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+  if (!noise_.empty() || cov_check_ || tighten_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
 }
 
 int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
@@ -298,7 +315,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
   noise_fused_ = false;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty()) reserve_noise_buffers();
+  if (!noise_.empty() || tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
@@ -310,7 +327,7 @@ void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double
   noise_fused_ = true;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty()) reserve_noise_buffers();
+  if (!noise_.empty() || tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits) {
@@ -337,14 +354,40 @@ void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, d
   cov_sum_ = sum_bound;
   last_chance_risk.clear();
   last_step_risk.clear();
-  if (cov_check_) reserve_noise_buffers();
+  if (cov_check_ || tighten_) reserve_noise_buffers();
+}
+
+void iLQR::set_chance_tightening(const double Sigma0[16], const double* W, double eps, int rounds, double max_inflate, double lamb) {
+  const bool on = Sigma0 != nullptr && rounds != 0;
+  if (on && n_samples_) throw std::logic_error(kTighteningWithSamples);
+  if (on && rounds < 0) throw std::runtime_error("set_chance_tightening: rounds is negative");
+  const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
+  if (kappa != kappa) throw std::runtime_error("set_chance_tightening: eps outside (0, 0.5]");
+  if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error("set_chance_tightening: max_inflate is negative or not finite");
+  tighten_ = on;
+  tg_has_W_ = on && W != nullptr;
+  if (on) memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
+  if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
+  tg_kappa_ = kappa;
+  tg_rounds_ = on ? rounds : 0;
+  tg_cap_ = max_inflate;
+  tg_lamb_ = lamb;
+  last_tighten.clear();
+  last_tighten_risk_before.clear();
+  if (tighten_) reserve_noise_buffers();
+}
+
+void iLQR::set_obstacle_covariance(const std::vector<double>& cov) {
+  obs_cov_ = cov;
+  pack_obstacles();
 }
 
 // One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.  The fused
 // check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
 void iLQR::reserve_noise_buffers() {
   // (the covariance check has no draws: it keeps ONE zero offset, the plan itself, for the map risk call, and the fused check's arrays)
-  const bool fused = noise_fused_ || cov_check_;
+  // (tightening alone, with no check behind it, keeps the fused check's score rows and totals for a MinTotalCost pick)
+  const bool fused = noise_fused_ || cov_check_ || noise_.empty();
   const size_t B = max_candidates_, S = cov_check_ ? 1 : noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = fused ? 0 : B * S;
   // with obstacle samples: per-candidate nominal tables and offsets in place of the one shared set (n_obs * n_samples <= M)
   const size_t n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
@@ -366,6 +409,10 @@ void iLQR::reserve_noise_buffers() {
   // the covariance check's inputs and outputs
   L.s0 = take(cov_check_ ? 16 : 0); L.W = take(cov_check_ ? 16 : 0);
   L.crisk = take(cov_check_ ? B * CILQR_CHANCE_FIELDS : 0); L.cstep = take(cov_check_ ? B * N : 0);
+  // the tightening rounds: Sigma0, W, every Sigma_t, the risk row of the round's input plan, the inflated dense table, the fields, obs_cov
+  const size_t tg = tighten_ ? 1 : 0;
+  L.ts0 = take(tg * 16); L.tW = take(tg * 16); L.tsig = take(tg * B * (N + 1) * 16); L.trisk = take(tg * B * CILQR_CHANCE_FIELDS);
+  L.tpose = take(tg * B * M * 4 * N); L.tdim = take(tg * B * M * 2 * N); L.tg = take(tg * B * CILQR_TIGHTEN_FIELDS); L.tcov = take(tg * M * N * 3);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -378,7 +425,7 @@ void iLQR::reserve_noise_buffers() {
   noise_dev_ = nullptr;
   hip_check(hipMalloc(&noise_dev_, L.end * sizeof(double)), "hipMalloc");
   if (cov_check_) hip_check(hipMemset((double*)noise_dev_ + L.delta, 0, 4 * sizeof(double)), "hipMemset");
-  else hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  else if (!noise_.empty()) hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
   noise_horizon_ = params.horizon;
 }
 
@@ -386,6 +433,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   const int N = params.horizon, M = (int)obstacles_.size(), S = cov_check_ ? 1 : (int)(noise_.size() / 4);
   if (cov_check_ && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
   if (cov_check_ && n_samples_) throw std::logic_error(kCovarianceWithSamples);
+  if (tighten_ && n_samples_) throw std::logic_error(kTighteningWithSamples);
   if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
@@ -397,6 +445,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
   const cilqr_obstacles host_obs = obstacle_strides();
+  if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
   hip_check(hipSetDevice(device_), "hipSetDevice");
   hipStream_t st = (hipStream_t)noise_stream_;
   double* d = (double*)noise_dev_;
@@ -427,12 +476,20 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   const cilqr_obstacles* po = M ? &obs : nullptr;
   const int risk_fields = n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS;
   int rc = CILQR_OK;
-  const bool scored = cov_check_ ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
-  if (cov_check_) {  // the analytic check: covariance chain and chance values in place of rollouts
+  const bool plain = !cov_check_ && noise_.empty();  // tightening alone: no check behind it, the pick of run_candidates itself
+  const bool scored = cov_check_ || plain ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
+  const bool tightened = tighten_ && M > 0;
+  if (plain) {
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
+    if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, max_collision_, d + L.score, d + L.total);
+  } else if (cov_check_) {  // the analytic check: covariance chain and chance values in place of rollouts
     up(L.s0, cov_sigma0_, 16);
     if (cov_has_W_) up(L.W, cov_W_, 16);
     rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
     if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, cov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
     if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
@@ -453,6 +510,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   } else {
     rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
     if (noise_fused_) {
       if (!rc) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
@@ -468,11 +526,11 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     rc = cilqr_rollout_risk_map_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
                                        map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + L.total, d + L.mrisk,
                                        (int32_t*)(d + L.mhits), (int32_t*)(d + L.munk), d + L.mtotal);
-  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + (map_checked ? L.mtotal : L.total), d + L.pair);
+  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + (map_checked ? L.mtotal : plain && !scored ? L.J : L.total), d + L.pair);
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(st);
-    throw std::runtime_error("run_candidates (pose-noise check): " + msg);
+    throw std::runtime_error((plain ? "run_candidates (chance tightening): " : "run_candidates (pose-noise check): ") + msg);
   }
   double pair[2] = {0.0, -1.0};
   last_scores.clear();
@@ -486,10 +544,14 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     last_step_risk.assign((size_t)B * N, 0.0);
     down(last_chance_risk.data(), L.crisk, last_chance_risk.size() * sizeof(double));
     down(last_step_risk.data(), L.cstep, last_step_risk.size() * sizeof(double));
-  } else {
+  } else if (!plain) {
     last_risk.assign((size_t)B * risk_fields, 0.0);
     down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
   }
+  std::vector<double> tg_rows;
+  last_tighten.clear();
+  last_tighten_risk_before.clear();
+  if (tightened) fetch_tighten(st, d, B, tg_rows);
   if (scored) {
     last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
     down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
@@ -510,6 +572,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     down(last_map_unknown_hits.data(), L.munk, last_map_unknown_hits.size() * sizeof(int32_t));
   }
   hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (tightened) keep_tighten_risk(B, tg_rows);
   const int best = (int)pair[1];
   if (best < 0) return -1;  // every candidate rejected: results and warm start stay
   Matrix Xb(4, N + 1);
@@ -531,6 +594,105 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   last_exit = status;
   last_cost = J;
   return best;
+}
+
+// The rounds behind a solve whose arrays lie in the device block: gains and covariance chain of the current plan against the ORIGINAL
+// obstacles `po`, the inflated dense table, the re-solve on it from the U the solve before left.  Sigma0, W and obs_cov travel here.
+int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* po) {
+  const int N = params.horizon, M = (int)obstacles_.size();
+  hipStream_t st = (hipStream_t)stream;
+  const NoiseLayout& L = nl_;
+  const auto up = [&](size_t at, const void* src, size_t doubles) {
+    hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  };
+  up(L.ts0, tg_sigma0_, 16);
+  if (tg_has_W_) up(L.tW, tg_W_, 16);
+  if (!obs_cov_packed_.empty()) up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
+  cilqr_obstacles inflated{};
+  inflated.pose = d + L.tpose;
+  inflated.dim = d + L.tdim;
+  inflated.batch_stride = (int64_t)M * N;
+  inflated.obstacle_stride = N;
+  inflated.step_stride = 1;
+  int rc = CILQR_OK;
+  for (int r = 0; r < tg_rounds_ && !rc; ++r) {
+    rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+    if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tg_has_W_ ? d + L.tW : nullptr, po, 0u, 1.0,
+                                           nullptr, d + L.trisk, nullptr, nullptr, d + L.tsig, nullptr);
+    if (!rc) rc = cilqr_tighten_obstacles_device(h_, st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
+                                                 tg_cap_, d + L.tpose, d + L.tdim, d + L.tg);
+    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, &inflated, d + L.X, d + L.J,
+                                                     (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+  }
+  return rc;
+}
+
+void iLQR::fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows) {
+  last_tighten.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0);
+  risk_rows.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0);
+  hip_check(hipMemcpyAsync(last_tighten.data(), d + nl_.tg, last_tighten.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  hip_check(hipMemcpyAsync(risk_rows.data(), d + nl_.trisk, risk_rows.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+}
+
+void iLQR::keep_tighten_risk(int B, const std::vector<double>& risk_rows) {
+  last_tighten_risk_before.resize(B);
+  for (int b = 0; b < B; ++b) last_tighten_risk_before[b] = risk_rows[(size_t)b * CILQR_CHANCE_FIELDS + CILQR_CR_STEP_RISK];
+}
+
+// get_optimal_control_seq under set_chance_tightening: the B = 1 solve and its rounds in the device block, one wait.
+void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]) {
+  const int N = params.horizon, M = (int)obstacles_.size();
+  if (n_samples_) throw std::logic_error(kTighteningWithSamples);
+  if (noise_horizon_ != N) reserve_noise_buffers();
+  const cilqr_obstacles host_obs = obstacle_strides();
+  if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
+  hip_check(hipSetDevice(device_), "hipSetDevice");
+  hipStream_t st = (hipStream_t)noise_stream_;
+  double* d = (double*)noise_dev_;
+  const NoiseLayout& L = nl_;
+  const auto up = [&](size_t at, const void* src, size_t doubles) {
+    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  };
+  const auto down = [&](void* dst, size_t at, size_t bytes) {
+    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  };
+  up(L.x0, x_0, 4);
+  up(L.U, U.a.data(), U.a.size());
+  up(L.poly, poly_coeffs, CILQR_POLY_COEFFS);
+  up(L.fl, fl, 2);
+  up(L.pose, obs_pose_.data(), obs_pose_.size());
+  up(L.dim, obs_dim_.data(), obs_dim_.size());
+  cilqr_obstacles obs = host_obs;  // the same strides over the device copies
+  obs.pose = d + L.pose;
+  obs.dim = d + L.dim;
+  const cilqr_obstacles* po = M ? &obs : nullptr;
+  int rc = cilqr_solve_batch_obstacles_device(h_, st, 1, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+                                              (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+  if (!rc && M) rc = tighten_rounds(st, d, 1, po);
+  if (rc) {
+    const std::string msg = cilqr_last_error();
+    (void)hipStreamSynchronize(st);
+    throw std::runtime_error("run_step (chance tightening): " + msg);
+  }
+  Matrix Xb(4, N + 1);
+  int32_t iters = 0, status = 0;
+  double J = 0.0;
+  std::vector<double> tg_rows;
+  last_tighten.clear();
+  last_tighten_risk_before.clear();
+  down(Xb.a.data(), L.X, Xb.a.size() * sizeof(double));
+  down(U.a.data(), L.U, U.a.size() * sizeof(double));
+  down(&J, L.J, sizeof(double));
+  down(&iters, L.iters, sizeof(int32_t));
+  down(&status, L.status, sizeof(int32_t));
+  if (M) fetch_tighten(st, d, 1, tg_rows);
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (M) keep_tighten_risk(1, tg_rows);
+  X_result = Xb;
+  last_iterations = iters;
+  last_exit = status;
+  last_cost = J;
+  U_result = U;  // I/iLQR.cpp:244
 }
 
 }  // namespace cilqr_host

@@ -150,6 +150,26 @@ class iLQR {
   // Together with set_pose_noise_check(_fused) offsets, or with set_obstacle_samples (the chance value has no sampled form yet),
   // the setters throw std::logic_error naming the conflict.  Sigma0 == nullptr switches the check off (the default).
   void set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb = 1.0, bool sum_bound = false);
+  // Chance-constraint tightening: every check above judges a solved plan and can only reject it; this feeds the pose covariance back
+  // into the solve.  Sigma0 and W as in set_pose_covariance_check; eps the chance allowed per obstacle entry (kappa =
+  // cilqr_chance_kappa(eps) standard deviations).  While set, run_step (get_optimal_control_seq) and run_candidates follow their solve
+  // by `rounds` rounds, enqueued on the check's stream with nothing coming back in between:
+  //   cilqr_gains_batch_device(lamb), on the obstacles of set_Obstacle -> cilqr_chance_risk_device (its sigma_out) ->
+  //   cilqr_tighten_obstacles_device(kappa, max_inflate: no semi-axis grows by more) -> cilqr_solve_batch_obstacles_device on the
+  //   inflated table, warm-started from the U the solve before it left.
+  // X_result, U_result, the warm start, last_cost, last_iterations and last_exit are the LAST re-solve's.  Every score or risk check
+  // that follows — set_candidate_pick, set_pose_noise_check(_fused), set_pose_covariance_check, set_map_risk_check — judges that final
+  // plan against the ORIGINAL obstacles.  last_tighten holds CILQR_TIGHTEN_FIELDS per solve (cilqr_tighten_field) of the last round,
+  // last_tighten_risk_before the CR_STEP_RISK of the plan that round started from, one per solve; with no obstacle set there is
+  // nothing to inflate, the rounds are skipped and both stay empty.  The barriers are soft and the tightening is a first-order,
+  // axis-wise one (include/cilqr.h): it moves a plan that has room to move and guarantees nothing — keep a check behind it.
+  // Sigma0 == nullptr or rounds == 0 switches it off (the default).  Together with set_obstacle_samples (whichever comes second)
+  // the setters throw std::logic_error: the sampled solve has no inflated form here.
+  void set_chance_tightening(const double Sigma0[16], const double* W, double eps, int rounds = 1, double max_inflate = 2.0, double lamb = 1.0);
+  // The obstacles' own position covariance for the tightening (obs_cov of cilqr_tighten_obstacles): (xx, xy, yy) in the world frame
+  // per obstacle of set_Obstacle, in its order — 3 * M values, constant over the horizon, or 3 * M * horizon, obstacle-major.  Empty:
+  // none (the default).  A size that matches neither makes the next run throw std::runtime_error.
+  void set_obstacle_covariance(const std::vector<double>& cov);
 
   // Sampled obstacles: the uncertainty-aware scene form.  `offsets` holds n_obs x n_samples x 3 doubles, (dx, dy, dtheta) per pose
   // sample, drawn ONCE by the node with its own sigmas; the obstacles of set_Obstacle are then the NOMINAL ones (n_obs of them, in
@@ -182,6 +202,8 @@ class iLQR {
   std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
+  // run_step / run_candidates under set_chance_tightening with obstacles set; empty otherwise
+  std::vector<double> last_tighten, last_tighten_risk_before;  // CILQR_TIGHTEN_FIELDS per solve; CR_STEP_RISK per solve
 
  private:
   void pack_obstacles();
@@ -201,7 +223,8 @@ class iLQR {
   // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
   // so that this header needs no HIP
   struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep, end;
+    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
+        ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, end;
   };
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
@@ -225,6 +248,16 @@ class iLQR {
   // pose-covariance check (set_pose_covariance_check): Sigma0 and W travel with every call (32 doubles)
   bool cov_check_ = false, cov_has_W_ = false, cov_sum_ = false;
   double cov_sigma0_[16] = {}, cov_W_[16] = {}, cov_max_risk_ = 1.0, cov_lamb_ = 1.0;
+  // chance-constraint tightening (set_chance_tightening, set_obstacle_covariance)
+  bool tighten_ = false, tg_has_W_ = false;
+  int tg_rounds_ = 0;
+  double tg_sigma0_[16] = {}, tg_W_[16] = {}, tg_kappa_ = 0.0, tg_cap_ = 2.0, tg_lamb_ = 1.0;
+  std::vector<double> obs_cov_, obs_cov_packed_;  // as given; and addressed by the packed obstacles' strides, 3 per entry
+  // `rounds` rounds behind a solve of B plans in the device block `d` (x0, U, poly, fl, X, J, iters, status in place); returns a C-ABI code
+  int tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* po);
+  void fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows);  // enqueues last_tighten and the round's risk rows
+  void keep_tighten_risk(int B, const std::vector<double>& risk_rows);                 // after the wait: their CR_STEP_RISK column
+  void solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]);  // run_step's solve
 };
 
 }  // namespace cilqr_host

@@ -2,7 +2,12 @@
 // odomCallback does per odometry message (I/ilqr_uncertainty_node.cpp:111-130: set_global_plan → set_Obstacle → run_step →
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
-//   cilqr_replay <log> [device]     → one line per tick on stdout
+//   cilqr_replay <log> [device] [--tighten eps[,rounds]]     → one line per tick on stdout
+//
+// --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
+// (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
+// 0.017^2) and no process noise; the line then ends with " tighten <max da> <max db> <entry> <capped> <CR_STEP_RISK before>" when
+// the tick has obstacles.
 //
 // Log (whitespace-separated, '#' starts a comment line):
 //   cilqr-replay 1
@@ -15,6 +20,7 @@
 // Output per tick: "experiment <start_pos 4> <planning_time> <iterations> <exit> <J> X <4(N+1) values> U <2N values>" —
 // X and U in the vehiclepub/Experiment flattening (:243-284).
 #include <chrono>
+#include <cstring>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -58,13 +64,20 @@ struct Tokens {
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 2) {
-    fprintf(stderr, "usage: %s <log> [device]\n", argv[0]);
+  std::vector<const char*> pos;  // the log and the device; options may stand anywhere
+  const char* tighten = nullptr;
+  for (int i = 1; i < argc; ++i) {
+    if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
+    else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
+    else pos.push_back(argv[i]);
+  }
+  if (pos.empty() || pos.size() > 2) {
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]]\n", argv[0]);
     return 2;
   }
   try {
-    std::ifstream f(argv[1]);
-    if (!f) throw std::runtime_error(std::string("cannot open ") + argv[1]);
+    std::ifstream f(pos[0]);
+    if (!f) throw std::runtime_error(std::string("cannot open ") + pos[0]);
     Tokens in(f);
     in.expect("cilqr-replay");
     if (in.integer() != 1) throw std::runtime_error("replay log: unknown version");
@@ -78,7 +91,17 @@ int main(int argc, char** argv) {
 
     Parameters params = default_parameters();
     params.horizon = N;
-    iLQR planner(params, argc > 2 ? atoi(argv[2]) : 0, 64, 1);
+    iLQR planner(params, pos.size() > 1 ? atoi(pos[1]) : 0, 64, 1);
+    if (tighten) {
+      char* rest = nullptr;
+      const double eps = strtod(tighten, &rest);
+      const int rounds = *rest == ',' ? atoi(rest + 1) : 1;
+      if (rest == tighten || (*rest != ',' && *rest != 0)) throw std::runtime_error("--tighten takes eps[,rounds]");
+      double Sigma0[16] = {};
+      Sigma0[0] = Sigma0[5] = 0.16 * 0.16;
+      Sigma0[15] = 0.017 * 0.017;
+      planner.set_chance_tightening(Sigma0, nullptr, eps, rounds);
+    }
     while (!in.done()) {
       in.expect("tick");
       in.expect("ego");
@@ -109,6 +132,9 @@ int main(int argc, char** argv) {
       for (double v : e.X) printf(" %.17g", v);
       printf(" U");
       for (double v : e.U) printf(" %.17g", v);
+      if (!planner.last_tighten.empty())
+        printf(" tighten %.17g %.17g %d %d %.17g", planner.last_tighten[CILQR_TG_MAX_DA], planner.last_tighten[CILQR_TG_MAX_DB],
+               (int)planner.last_tighten[CILQR_TG_MAX_ENTRY], (int)planner.last_tighten[CILQR_TG_CAPPED], planner.last_tighten_risk_before[0]);
       printf("\n");
     }
   } catch (const std::exception& ex) {
