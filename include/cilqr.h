@@ -768,6 +768,93 @@ int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* 
  * same eps.  NaN outside (0, 0.5]; exactly 0 at 0.5. */
 double cilqr_chance_kappa(double eps);
 
+/* --- analytic map risk: the pose covariance against the uncertainty map by quadrature (new) ---------------------------------------
+ * cilqr_chance_risk stops at the ellipses; in the reference's live node that channel is off and the blurred costmap is the only
+ * obstacle information (see cilqr_rollout_risk_map), for which the only risk call so far is the sampled one: risk in steps of 1/S,
+ * dependent on the offsets' seed, every rollout a serial chain over the horizon.  cilqr_chance_risk_map(_device) is the map
+ * counterpart of cilqr_chance_risk: per step it takes the pose marginal (x, y, theta) of Sigma_t, places a caller-supplied set of Q
+ * weighted standard-normal nodes through its Cholesky factor around the plan's pose, and looks the footprint up under every node.
+ * No rollouts, no gains, no chain over the horizon: the N*Q node poses of a solve are independent.
+ * X [B][4*(N+1)], the plan.  sigma [B][N+1][16], exactly sigma_out of cilqr_chance_risk (column-major, entry (r, c) at [r + 4*c]);
+ * of each Sigma_t, t < N, six entries are read: (0,0), (0,1), (1,1), (0,3), (1,3), (3,3).  Sigma_N and x_N are not visited, as in
+ * cilqr_rollout_risk_map.  nodes [Q][3] = (z_x, z_y, z_theta) and weights [Q], shared by the batch, 1 <= Q <= CILQR_MAX_QUAD_NODES;
+ * cilqr_pose_quadrature builds Gauss-Hermite sets, and any other set serves: S equal-weight standard-normal draws make the call
+ * a sampled estimate of the same marginals.  Map, layer stride, poses and probes are those CURRENTLY SET on the handle, indexed
+ * by the solve as in cilqr_rollout_risk_map.
+ *
+ * Definitions.
+ *   factor     with c00 = S(0,0), c10 = S(0,1), c11 = S(1,1), c20 = S(0,3), c21 = S(1,3), c22 = S(3,3) of S = Sigma_t:
+ *                l00 = sqrt(max(c00, 0));                     l10 = c10/l00 and l20 = c20/l00, each 0 when l00 = 0;
+ *                l11 = sqrt(max(c11 - l10^2, 0));             l21 = (c21 - l20*l10)/l11, 0 when l11 = 0;
+ *                l22 = sqrt(max(c22 - l20^2 - l21^2, 0)).
+ *              A marginal that is singular or slightly indefinite loses the directions it does not have; nothing fails.
+ *   node pose  x = X_t[0] + l00*z_x,   y = X_t[1] + l10*z_x + l11*z_y,   theta = X_t[3] + l20*z_x + l21*z_y + l22*z_theta.
+ *   probes, valid, occupancy   word for word those of cilqr_rollout_risk_map: the probes_l x probes_w footprint on safe_length x
+ *              safe_width turned by the node's heading, the rigid transform by the map pose of the solve's index, bilinear
+ *              interpolation over four cell centres in double; a probe is valid when its four cells are inside and finite.
+ *   hit        node q HITS at step t when a valid probe's occupancy is > occ_threshold (strict), or
+ *              CILQR_CHANCE_MAP_UNKNOWN_HITS is set and a probe is invalid.   unknown: at least one probe is invalid.
+ *   per step   r_t = min(1, sum over q of w_q [hit]),   u_t = min(1, sum over q of w_q [unknown]),   e_t = sum over q of w_q m_q
+ *              with m_q the largest valid occupancy among node q's probes, 0 when it has none.  The weights are used as given and
+ *              not normalised; a sum of r_t or u_t that is NaN gives 1 (a weight that is NaN, which only the device form can
+ *              be handed).  r_t is a quadrature of an INDICATOR: with Gauss-Hermite nodes it resolves the mass beyond the
+ *              threshold contour only as finely as the nodes sample it (7 x 7 x 3 nodes were up to 0.05 off the
+ *              rollouts' share on the test scene, while equal-weight draws reproduce it).  e_t, the expected occupancy under the
+ *              footprint, is smooth and converges with a few nodes per axis: both are reported.
+ *   lost step  a step where X_t[0], X_t[1], X_t[3] or one of the six entries is not finite: r_t = 1, u_t = 1, e_t = 0, and the
+ *              step adds nothing to CM_WORST_OCC.
+ * step_risk, step_occ, step_unknown [B][N] hold r_t, e_t, u_t; each may be NULL.  risk [B][CILQR_CHANCE_MAP_FIELDS] (required),
+ * see the enum; ties go to the lowest index.  total [B] or NULL: total[b] = base[b] when the bounded field — CM_STEP_RISK, or
+ * CM_SUM_RISK under CILQR_CHANCE_MAP_BOUND_SUM — is <= max_risk and base[b] is finite, else NaN: the convention of
+ * cilqr_chance_risk, so the call composes with it (base = its total) and with the rollout risk calls and feeds cilqr_argmin_device /
+ * cilqr_argmin_global_device.  total without base is CILQR_ERR_ARG.
+ *   Determinism: every sum over the nodes runs over a tree fixed by Q alone (a lane adds its nodes q = lane, lane + 64, ... in
+ *   ascending order, the 64 lane sums meet in a fixed butterfly), the sum over the horizon over a tree fixed by N alone; maxima are
+ *   lexicographic.  A solve's bits do not depend on B, on its place in the batch, or on whether the layer is shared or one equal
+ *   copy per solve.  (A per-solve pose's cosine and sine are formed on the device, the shared pose's on the host: equal poses
+ *   given the two ways may differ in the last bit, as for every call that reads the map.)
+ * Mapping: lane = node, wavefront = step, a workgroup takes four consecutive steps of one solve: ceil(N/4)*B workgroups, then one
+ * wavefront per solve for the reduction over the horizon; two launches, no atomics.  LDS is 32*Q + 32 bytes whatever N is: every
+ * horizon a handle accepts runs, and CILQR_ERR_UNSUPPORTED is never returned.  Nothing is allocated per call.  Where the caller
+ * passes NULL for a per-step output its values live in device memory the handle reserved at create (3*max_batch*max_horizon
+ * doubles); each workgroup's largest occupancy lies in the buffer of cilqr_rollout_risk's partial records — a cilqr_rollout_risk,
+ * cilqr_rollout_risk_map or cilqr_chance_risk_map on ANOTHER stream of the same handle must not run beside it.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X, sigma, nodes, weights or risk; total without base; Q outside
+ * 1 ... CILQR_MAX_QUAD_NODES; an occ_threshold or max_risk that is NaN; flag bits other than the two below; in the host-buffer
+ * form also a weight that is negative or not finite.  Then: B or N beyond the cilqr_create limits; no uncertainty map set on the
+ * handle (the message says so).  The host-buffer form's arrays must fit the device arena reserved at create (CILQR_ERR_ARG
+ * otherwise; this call adds nothing to it): B*(20*N + 30) + 4*Q doubles, and 3*B*N more with the three per-step outputs, against
+ * the max_batch*(22*max_horizon + 34) doubles the arena holds at least.  Without per-step outputs every B <= max_batch fits once
+ * 4*Q <= max_batch*(2*max_horizon + 4); with them every B <= 7*max_batch/8 fits once 4*Q <= max_batch*(max_horizon + 7). */
+#define CILQR_MAX_QUAD_NODES 1024
+#define CILQR_CHANCE_MAP_FIELDS 8
+typedef enum cilqr_chance_map_field {
+  CILQR_CM_STEP_RISK = 0,     /* max over t of r_t: what max_risk bounds by default */
+  CILQR_CM_WORST_STEP = 1,    /* lowest t of that maximum */
+  CILQR_CM_SUM_RISK = 2,      /* min(1, sum over t of r_t): Boole's bound over the horizon.  Bounded instead of CM_STEP_RISK under
+                                 CILQR_CHANCE_MAP_BOUND_SUM */
+  CILQR_CM_FIRST_STEP = 3,    /* lowest t with r_t > 0;  -1 when none */
+  CILQR_CM_MEAN_OCC = 4,      /* max over t of e_t */
+  CILQR_CM_MEAN_OCC_STEP = 5, /* lowest t of that maximum */
+  CILQR_CM_WORST_OCC = 6,     /* largest valid occupancy under any node, t < N;  -HUGE_VAL when no probe is valid */
+  CILQR_CM_UNKNOWN = 7        /* max over t of u_t */
+} cilqr_chance_map_field;
+#define CILQR_CHANCE_MAP_UNKNOWN_HITS 1u /* flags: an invalid probe counts as a hit */
+#define CILQR_CHANCE_MAP_BOUND_SUM 2u    /* flags: max_risk bounds CM_SUM_RISK */
+int cilqr_chance_risk_map_device(cilqr_handle* h, void* stream, int B, int N, int Q, const double* X, const double* sigma,
+                                 const double* nodes, const double* weights, double occ_threshold, uint32_t flags, double max_risk,
+                                 const double* base, double* risk, double* step_risk, double* step_occ, double* step_unknown,
+                                 double* total);
+int cilqr_chance_risk_map(cilqr_handle* h, int B, int N, int Q, const double* X, const double* sigma, const double* nodes,
+                          const double* weights, double occ_threshold, uint32_t flags, double max_risk, const double* base,
+                          double* risk, double* step_risk, double* step_occ, double* step_unknown, double* total);
+/* Host only, no device: the tensor product of probabilists' Gauss-Hermite rules (weight exp(-z^2/2), each axis' weights summing to
+ * 1) with nx, ny, nth nodes per axis, each in 1 ... 9 (CILQR_ERR_ARG otherwise, or for a NULL pointer).  Writes nx*ny*nth nodes
+ * (z_x, z_y, z_theta) and weights w_x*w_y*w_theta, z_theta fastest, z_x slowest, each axis ascending.  The roots of He_n come by
+ * Newton's iteration inside the brackets the roots of He_(n-1) give (they interlace), mirrored about 0; the weights are
+ * (n-1)! / (n He_(n-1)(z)^2), scaled to sum to 1: no table is involved and the same arguments give the same bits. */
+int cilqr_pose_quadrature(int nx, int ny, int nth, double* nodes, double* weights);
+
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's
  * {J_min, local index, index offset} (24 bytes) through one ncclAllGather (RCCL over xGMI), then the lexicographic minimum

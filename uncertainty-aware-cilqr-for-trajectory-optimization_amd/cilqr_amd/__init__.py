@@ -42,6 +42,13 @@ CHANCE_BOUND_SUM = 1  # flags of `chance_risk`: max_risk bounds CR_SUM_RISK inst
 TIGHTEN_FIELDS = 4
 TG_MAX_DA, TG_MAX_DB, TG_MAX_ENTRY, TG_CAPPED = range(TIGHTEN_FIELDS)
 
+# `cilqr_chance_map_field`: the columns of an analytic map risk row (`Solver.chance_risk_map`)
+CHANCE_MAP_FIELDS = 8
+(CM_STEP_RISK, CM_WORST_STEP, CM_SUM_RISK, CM_FIRST_STEP, CM_MEAN_OCC, CM_MEAN_OCC_STEP, CM_WORST_OCC,
+ CM_UNKNOWN) = range(CHANCE_MAP_FIELDS)
+CHANCE_MAP_UNKNOWN_HITS, CHANCE_MAP_BOUND_SUM = 1, 2  # flags of `chance_risk_map`
+MAX_QUAD_NODES = 1024
+
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
     "cilqr_params_default", "cilqr_abi_version", "cilqr_device_count", "cilqr_last_error", "cilqr_default_control_seq",
@@ -63,6 +70,7 @@ ABI_SYMBOLS = (
     "cilqr_rollout_risk_map", "cilqr_rollout_risk_map_device",
     "cilqr_chance_risk", "cilqr_chance_risk_device",
     "cilqr_tighten_obstacles", "cilqr_tighten_obstacles_device", "cilqr_chance_kappa",
+    "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -213,6 +221,15 @@ def _check(rc):
 def chance_kappa(eps):
     """`cilqr_chance_kappa`: the kappa with erfc(kappa / sqrt 2) / 2 = eps; NaN outside (0, 0.5], exactly 0 at 0.5."""
     return float(lib().cilqr_chance_kappa(float(eps)))
+
+
+def pose_quadrature(nx=5, ny=5, nth=3):
+    """`cilqr_pose_quadrature`: the tensor product of probabilists' Gauss-Hermite rules, 1 ... 9 nodes per axis.  Returns (nodes
+    (nx*ny*nth, 3) = (z_x, z_y, z_theta), weights (nx*ny*nth,)), z_theta fastest, z_x slowest; each axis' weights sum to 1."""
+    Q = max(int(nx), 0) * max(int(ny), 0) * max(int(nth), 0)
+    nodes, weights = np.zeros((max(Q, 1), 3)), np.zeros(max(Q, 1))
+    _check(lib().cilqr_pose_quadrature(int(nx), int(ny), int(nth), _p(nodes), _p(weights)))
+    return nodes[:Q], weights[:Q]
 
 
 def default_params(horizon=None):
@@ -717,6 +734,36 @@ class Solver:
                                               C.c_int64(sigma0_batch_stride), _vp(process_noise), C.byref(obs) if M else None,
                                               C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_risk),
                                               _vp(entry_p), _vp(sigma_out), _vp(total)))
+
+    # ---- analytic map risk: the pose covariance against the uncertainty map by quadrature ----
+    def chance_risk_map(self, N, X, sigma, nodes, weights, occ_threshold, max_risk=1.0, base=None, sum_bound=False, unknown_hits=False,
+                        want_steps=True):
+        """`cilqr_chance_risk_map`: sigma (B, N+1, 16) as `chance_risk` returns it; nodes (Q, 3) and weights (Q,) as
+        `pose_quadrature` builds them (any weighted standard-normal set serves).  Returns dict(risk (B, CHANCE_MAP_FIELDS), step_risk,
+        step_occ, step_unknown (B, N) each or None, total): total[b] is base[b], NaN where CM_STEP_RISK (CM_SUM_RISK with sum_bound)
+        exceeds max_risk or base[b] is not finite; None without `base`."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X, sigma = X.reshape(B, 4 * (N + 1)), _np64(sigma).reshape(B, N + 1, 16)
+        nodes, weights = _np64(nodes).reshape(-1, 3), _np64(weights).reshape(-1)
+        if nodes.shape[0] != weights.shape[0]:
+            raise CilqrError("chance_risk_map: %d nodes but %d weights" % (nodes.shape[0], weights.shape[0]))
+        base = None if base is None else _np64(base).reshape(B)
+        risk = np.zeros((B, CHANCE_MAP_FIELDS))
+        step_risk, step_occ, step_unknown = (np.zeros((B, N)) if want_steps else None for _ in range(3))
+        total = None if base is None else np.zeros(B)
+        flags = (CHANCE_MAP_UNKNOWN_HITS if unknown_hits else 0) | (CHANCE_MAP_BOUND_SUM if sum_bound else 0)
+        _check(lib().cilqr_chance_risk_map(self._h, B, int(N), int(weights.shape[0]), _p(X), _p(sigma), _p(nodes), _p(weights),
+                                           C.c_double(occ_threshold), C.c_uint32(flags), C.c_double(max_risk), _p(base), _p(risk),
+                                           _p(step_risk), _p(step_occ), _p(step_unknown), _p(total)))
+        return dict(risk=risk, step_risk=step_risk, step_occ=step_occ, step_unknown=step_unknown, total=total)
+
+    def chance_risk_map_device(self, stream, B, N, Q, X, sigma, nodes, weights, occ_threshold, risk, step_risk=0, step_occ=0,
+                               step_unknown=0, total=0, base=0, max_risk=1.0, flags=0):
+        """`cilqr_chance_risk_map_device`: device addresses; the map is the one set by `set_uncertainty_map(_device)`."""
+        _check(lib().cilqr_chance_risk_map_device(self._h, _vp(stream), int(B), int(N), int(Q), _vp(X), _vp(sigma), _vp(nodes),
+                                                  _vp(weights), C.c_double(occ_threshold), C.c_uint32(int(flags)), C.c_double(max_risk),
+                                                  _vp(base), _vp(risk), _vp(step_risk), _vp(step_occ), _vp(step_unknown), _vp(total)))
 
     # ---- chance-constraint tightening: obstacles inflated by Sigma_t for a warm-started re-solve ----
     def tighten_obstacles(self, N, X, sigma, obs_pose=None, obs_dim=None, obs_cov=None, kappa=0.0, max_inflate=2.0, want_pose=True):

@@ -276,6 +276,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   // partial records of cilqr_rollout_risk: max_batch of 8 doubles + max_horizon int32 each
   h->risk_part_stride = cilqr::RISK_PART_DOUBLES + (N + 1) / 2;
   if (err == hipSuccess) err = dmalloc(&h->d_risk_part, B * h->risk_part_stride);
+  if (err == hipSuccess) err = dmalloc(&h->d_chance_map_steps, 3 * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
   h->comm_ranks = 1;
@@ -307,7 +308,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1209,6 +1210,145 @@ int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* 
   cilqr::plan_tighten_obstacles(p, B, N, M, X, sigma, o, span, obs_cov, pose_out, dim_out, tighten);
   return cilqr::host_call(h, p, [&] {
     return tighten_launch(h, h->stream, B, N, M, X, sigma, M > 0 ? &o : nullptr, obs_cov, kappa, max_inflate, pose_out, dim_out, tighten);
+  });
+}
+
+// ---- analytic map risk (cilqr_chance_map.hip) ------------------------------------------------------------------------------------------
+namespace {
+// what needs no handle
+int chance_map_args_check(int Q, const double* X, const double* sigma, const double* nodes, const double* weights, double occ_threshold,
+                          uint32_t flags, double max_risk, const double* base, const double* risk, const double* total) {
+  if (!X || !sigma || !nodes || !weights || !risk) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: total needs base");
+  if (Q < 1 || Q > CILQR_MAX_QUAD_NODES)
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: Q = %d outside [1, %d]", Q, CILQR_MAX_QUAD_NODES);
+  if (occ_threshold != occ_threshold || max_risk != max_risk)
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: occ_threshold or max_risk is NaN");
+  if (flags & ~(CILQR_CHANCE_MAP_UNKNOWN_HITS | CILQR_CHANCE_MAP_BOUND_SUM))
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int chance_map_handle_check(const cilqr_handle* h, int B, int N) {
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  if (!h->unc.layer) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: no uncertainty map is set on the handle");
+  return CILQR_OK;
+}
+
+// He_n(x) and He_(n-1)(x) by the recurrence He_(k+1) = x He_k - k He_(k-1)
+void hermite_e(int n, double x, double* he_n, double* he_n1) {
+  double a = 1.0, b = 0.0;  // He_0, "He_-1"
+  for (int k = 0; k < n; ++k) {
+    const double c = x * a - (double)k * b;
+    b = a; a = c;
+  }
+  *he_n = a; *he_n1 = b;
+}
+// The n nodes (ascending) and weights of the probabilists' Gauss-Hermite rule, weights summing to 1.
+void gauss_hermite_e(int n, double* z, double* w) {
+  double prev[10], cur[10];
+  int m_prev = 0;
+  for (int m = 1; m <= n; ++m) {  // the roots of He_m from the brackets the roots of He_(m-1) give
+    const double bound = 2.0 * sqrt((double)m) + 1.0;  // beyond the largest root (< 2 sqrt m)
+    for (int i = 0; i < m; ++i) {
+      double lo = i == 0 ? -bound : prev[i - 1], hi = i == m_prev ? bound : prev[i];
+      double f_lo, d;
+      hermite_e(m, lo, &f_lo, &d);
+      double x = 0.5 * (lo + hi);
+      for (int it = 0; it < 100; ++it) {
+        double f, f1;
+        hermite_e(m, x, &f, &f1);
+        if (f == 0.0) break;
+        if ((f < 0.0) == (f_lo < 0.0)) lo = x; else hi = x;
+        double nx = x - f / ((double)m * f1);  // He_m' = m He_(m-1)
+        if (!(nx > lo && nx < hi)) nx = 0.5 * (lo + hi);  // (a step that leaves the bracket: bisect)
+        if (nx == x) break;
+        x = nx;
+      }
+      cur[i] = x;
+    }
+    for (int i = 0; i < m; ++i) prev[i] = cur[i];
+    m_prev = m;
+  }
+  for (int i = 0; i < n / 2; ++i) {  // mirrored about 0
+    const double r = 0.5 * (prev[n - 1 - i] - prev[i]);
+    prev[i] = -r; prev[n - 1 - i] = r;
+  }
+  if (n & 1) prev[n / 2] = 0.0;
+  double fact = 1.0, sum = 0.0;
+  for (int k = 2; k < n; ++k) fact *= (double)k;  // (n - 1)!
+  for (int i = 0; i < n; ++i) {
+    double f, f1;
+    hermite_e(n, prev[i], &f, &f1);
+    w[i] = fact / ((double)n * f1 * f1);
+    z[i] = prev[i];
+  }
+  for (int i = 0; i < n / 2; ++i) w[n - 1 - i] = w[i];
+  for (int i = 0; i < n; ++i) sum += w[i];
+  for (int i = 0; i < n; ++i) w[i] /= sum;
+}
+}  // namespace
+
+int cilqr_pose_quadrature(int nx, int ny, int nth, double* nodes, double* weights) {
+  if (!nodes || !weights) return fail(CILQR_ERR_ARG, "cilqr_pose_quadrature: null pointer");
+  if (nx < 1 || nx > 9 || ny < 1 || ny > 9 || nth < 1 || nth > 9)
+    return fail(CILQR_ERR_ARG, "cilqr_pose_quadrature: %d x %d x %d nodes, each axis takes 1 ... 9", nx, ny, nth);
+  double zx[9], wx[9], zy[9], wy[9], zt[9], wt[9];
+  gauss_hermite_e(nx, zx, wx);
+  gauss_hermite_e(ny, zy, wy);
+  gauss_hermite_e(nth, zt, wt);
+  size_t q = 0;
+  for (int i = 0; i < nx; ++i)
+    for (int j = 0; j < ny; ++j)
+      for (int k = 0; k < nth; ++k, ++q) {
+        nodes[3 * q] = zx[i]; nodes[3 * q + 1] = zy[j]; nodes[3 * q + 2] = zt[k];
+        weights[q] = wx[i] * wy[j] * wt[k];
+      }
+  return CILQR_OK;
+}
+
+int cilqr_chance_risk_map_device(cilqr_handle* h, void* stream, int B, int N, int Q, const double* X, const double* sigma,
+                                 const double* nodes, const double* weights, double occ_threshold, uint32_t flags, double max_risk,
+                                 const double* base, double* risk, double* step_risk, double* step_occ, double* step_unknown,
+                                 double* total) {
+  int rc = chance_map_args_check(Q, X, sigma, nodes, weights, occ_threshold, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  rc = chance_map_handle_check(h, B, N);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::ChanceMapArgs a = {};
+  a.s = handle_args(h, B, N, 0, 0);
+  a.X = X; a.sigma = sigma; a.nodes = nodes; a.weights = weights;
+  a.occ_threshold = occ_threshold; a.max_risk = max_risk; a.base = base; a.risk = risk; a.total = total;
+  // a per-step output the caller did not ask for lives in the handle's own memory: the finish kernel reads all three
+  const size_t slab = (size_t)h->max_batch * h->max_horizon;
+  a.step_risk = step_risk ? step_risk : h->d_chance_map_steps;
+  a.step_occ = step_occ ? step_occ : h->d_chance_map_steps + slab;
+  a.step_unknown = step_unknown ? step_unknown : h->d_chance_map_steps + 2 * slab;
+  a.partials = h->d_risk_part; a.part_stride = (long long)h->risk_part_stride;
+  a.Q = Q; a.G = (N + cilqr::CHANCE_MAP_WAVES - 1) / cilqr::CHANCE_MAP_WAVES;
+  a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_chance_risk_map(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_chance_risk_map(cilqr_handle* h, int B, int N, int Q, const double* X, const double* sigma, const double* nodes,
+                          const double* weights, double occ_threshold, uint32_t flags, double max_risk, const double* base,
+                          double* risk, double* step_risk, double* step_occ, double* step_unknown, double* total) {
+  int rc = chance_map_args_check(Q, X, sigma, nodes, weights, occ_threshold, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  for (int q = 0; q < Q; ++q)
+    if (!(weights[q] >= 0.0 && weights[q] <= 1.7e308))
+      return fail(CILQR_ERR_ARG, "cilqr_chance_risk_map: weight %d is negative or not finite", q);
+  rc = chance_map_handle_check(h, B, N);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_chance_risk_map(p, B, N, Q, X, sigma, nodes, weights, base, risk, step_risk, step_occ, step_unknown, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_chance_risk_map_device(h, h->stream, B, N, Q, X, sigma, nodes, weights, occ_threshold, flags, max_risk, base, risk,
+                                        step_risk, step_occ, step_unknown, total);
   });
 }
 

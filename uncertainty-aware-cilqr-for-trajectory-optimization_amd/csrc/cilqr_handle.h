@@ -82,6 +82,7 @@ struct cilqr_handle {
   double* d_pair;
   double* d_risk_part;      // partial records of cilqr_rollout_risk: max_batch x risk_part_stride doubles (cilqr_risk.hip)
   size_t risk_part_stride;  // 8 + ceil(max_horizon / 2)
+  double* d_chance_map_steps;  // per-step values of cilqr_chance_risk_map the caller did not ask for: 3 x max_batch x max_horizon doubles
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;
   size_t src_cap, dst_cap, bbox_cap;

@@ -238,6 +238,26 @@ inline void plan_tighten_obstacles(HostPlan& p, size_t B, size_t N, size_t M, co
   p.out(tighten, B * CILQR_TIGHTEN_FIELDS);
 }
 
+// cilqr_chance_risk_map: 10 arrays; the map is the handle's and no gain travels.  Per solve 20·N + 30 doubles — X, sigma, base, the
+// risk row, total — and 3·N more with the three per-step outputs; the Q nodes and weights, shared by the batch, are 4·Q doubles.
+// Against the 22·N + 34 per unit of max_batch that host_arena_bytes reserves below: without per-step outputs every B <= max_batch
+// fits once 4·Q <= max_batch·(2·max_horizon + 4), with them every B <= 7·max_batch/8 once 4·Q <= max_batch·(max_horizon + 7); the
+// 10 roundings stay within its 32 x 16 bytes.
+inline void plan_chance_risk_map(HostPlan& p, size_t B, size_t N, size_t Q, const double*& X, const double*& sigma, const double*& nodes,
+                                 const double*& weights, const double*& base, double*& risk, double*& step_risk, double*& step_occ,
+                                 double*& step_unknown, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(sigma, B * (N + 1) * 16);
+  p.in(nodes, Q * 3);
+  p.in(weights, Q);
+  p.in(base, B);
+  p.out(risk, B * CILQR_CHANCE_MAP_FIELDS);
+  p.out(step_risk, B * N);
+  p.out(step_occ, B * N);
+  p.out(step_unknown, B * N);
+  p.out(total, B);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

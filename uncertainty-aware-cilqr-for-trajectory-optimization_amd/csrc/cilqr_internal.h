@@ -191,6 +191,31 @@ struct MapRiskArgs {
 hipError_t launch_rollout_risk_map(const MapRiskArgs& a, hipStream_t stream);
 size_t rollout_risk_map_lds_bytes(int N);
 
+// Analytic map risk (cilqr_chance_map.hip; cilqr_chance_risk_map*): quadrature nodes placed through the factor of Sigma_t's pose
+// marginal, looked up in the uncertainty map set on the handle.  lane = node, wavefront = step, a workgroup takes
+// CHANCE_MAP_WAVES consecutive steps of one solve, solve b has G = ceil(N / CHANCE_MAP_WAVES) workgroups; a finish kernel, one
+// wavefront per solve, reduces over the steps.  `s` carries B, N and unc.  The three per-step pointers are never null: the
+// caller's arrays, or the handle's.  `partials`: the handle's, one record of part_stride doubles per solve whose first G hold the
+// workgroups' largest occupancies.
+constexpr int CHANCE_MAP_WAVES = 4;
+constexpr int CHANCE_MAP_THREADS = 64 * CHANCE_MAP_WAVES;
+struct ChanceMapArgs {
+  SolveArgs s;
+  const double *X, *sigma;        // [B][4(N + 1)], [B][N + 1][16]
+  const double *nodes, *weights;  // [Q][3], [Q]
+  double occ_threshold, max_risk;
+  const double* base;             // [B] or null (then total is null)
+  double* risk;                   // [B][CILQR_CHANCE_MAP_FIELDS]
+  double *step_risk, *step_occ, *step_unknown;  // [B][N] each
+  double* total;                  // [B] or null
+  double* partials;
+  long long part_stride;
+  int32_t Q, G;
+  uint32_t flags;                 // CILQR_CHANCE_MAP_*
+};
+hipError_t launch_chance_risk_map(const ChanceMapArgs& a, hipStream_t stream);
+size_t chance_risk_map_lds_bytes(int Q);
+
 // Closed-loop covariance chain and Gaussian chance values per solve (cilqr_chance.hip; cilqr_chance_risk*): one workgroup per
 // solve.  `s` carries what the launch shares with a solve — the strided obstacle fields, B, N, M, kp — and comes first, so that
 // phase_args / phase_params of cilqr_device.hpp read it.

@@ -11,8 +11,8 @@
 // per-step counters.  A counter holds the rows that hit at step t in its low 16 bits and the rows that are unknown at step t in
 // its high 16 (a workgroup has at most 256 rows): one LDS atomic per wavefront and step feeds both from two ballot counts.
 // u_t and the state are formed by the statements of cilqr_rollout.hip; probe positions, cell indices, the validity test and the
-// interpolant are the statements of unc_cost_add, restated here with contraction off, on the rollout state's own cos / sin
-// (sincos_fast, carried by dyn_step): WORST_OCC is bit-equal to the occupancy the map cost interpolates at that probe.
+// interpolant are the statements of unc_cost_add, restated in cilqr_map_probes.hpp with contraction off, on the rollout state's
+// own cos / sin (sincos_fast, carried by dyn_step): WORST_OCC is bit-equal to the occupancy the map cost interpolates at that probe.
 //
 // Load scheduling.  Nothing dyn_step needs comes from the map, so no lookup has to sit on the rollout's dependency chain.  The
 // probes are taken in groups of PROBE_GROUP (probes_l, probes_w are runtime values): a group's addresses, validity of position and
@@ -31,7 +31,7 @@
 // A wavefront whose share of S is partial computes its idle lanes on a zero offset and counts nothing for them; a wavefront with no
 // row at all skips the loop.  Every row index is formed in 64 bits.  A solve's results depend on its own inputs and offsets alone.
 // No scratch memory, no spilled vector or scalar register, 128 vector registers at most (make check).
-#include "cilqr_device.hpp"
+#include "cilqr_map_probes.hpp"
 
 namespace cilqr {
 
@@ -40,8 +40,6 @@ using namespace dev;
 namespace {
 
 constexpr int NOM_W = 14;       // doubles per step of the nominal copy (cilqr_rollout.hip)
-constexpr int PROBE_GROUP = 3;  // probes whose 4·PROBE_GROUP loads are issued together: what 128 vector registers hold twice
-constexpr int NO_INDEX = 0x7fffffff;
 
 // The argument block through a pointer the compiler cannot trace back to the preloaded arguments (the phase_args manner), kept in
 // the CONSTANT address space: what is read through it — the map's constants, the dynamics' parameters — comes by scalar loads, which
@@ -51,86 +49,10 @@ __device__ __forceinline__ const MapRiskArgs& risk_args() {
   asm volatile("" : "+s"(q));
   return *(const MapRiskArgs*)q;
 }
-typedef const __attribute__((address_space(1))) float* LayerPtr;  // the layer lies in global memory: global loads, not flat ones
 
-// (max occupancy, lowest entry): cmax_merge of cilqr_score.hip, verbatim
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
-}
 // (max occupancy, lowest row) with the row's own lowest entry carried along
 __device__ __forceinline__ void row_merge(double& c0, int& r0, int& e0, double c1, int r1, int e1) {
   if (c1 > c0 || (c1 == c0 && r1 < r0)) { c0 = c1; r0 = r1; e0 = e1; }
-}
-
-// A wavefront-uniform double moved to scalar registers (the map pose: a per-solve pose is formed by vector instructions).
-__device__ __forceinline__ double uniform_double(double v) {
-  const unsigned long long w = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)w), hi = __builtin_amdgcn_readfirstlane((unsigned)(w >> 32));
-  return __builtin_bit_cast(double, (unsigned long long)hi << 32 | lo);
-}
-
-// PROBE_GROUP probes between their loads and their use.  `exists`: bit i set when probe q0 + i is one of the footprint's;
-// `inside`: its four cells lie inside the map (the loads of a probe that is not inside read cells (0,0)..(1,1)).
-struct ProbeGroup {
-  float f00[PROBE_GROUP], f10[PROBE_GROUP], f01[PROBE_GROUP], f11[PROBE_GROUP];
-  double ti[PROBE_GROUP], tj[PROBE_GROUP];
-  int q0;
-  unsigned exists, inside;
-};
-
-// Probes q0 .. q0 + PROBE_GROUP - 1 of the state (x, y, cos ct, sin st), q = k·probes_w + l; (k, l) is probe q0's on entry and
-// probe (q0 + PROBE_GROUP)'s on return; state_finite: the state's speed is finite.  The statements of unc_cost_add up to its loads.
-__device__ __forceinline__ void probes_issue(const UncArgs& u, const UncPose& po, LayerPtr layer, double x, double y, double ct, double st,
-                                             bool state_finite, int q0, int& k, int& l, ProbeGroup& g) {
-#pragma clang fp contract(off)  // probe positions and cell indices as the plain-C statement forms them
-  const int rows = u.rows, cols = u.cols, nw = u.nw, P = u.nl * nw;
-  g.q0 = q0; g.exists = 0; g.inside = 0;
-#pragma unroll
-  for (int i = 0; i < PROBE_GROUP; ++i) {
-    g.f00[i] = g.f10[i] = g.f01[i] = g.f11[i] = 0.0f;
-    g.ti[i] = g.tj[i] = 0.0;
-    if (q0 + i < P) {  // (uniform)
-      const double a = u.la0 + (double)k * u.la_step;
-      const double bb = u.wb0 + (double)l * u.wb_step;
-      const double Px = x + (a * ct - bb * st), Py = y + (a * st + bb * ct);
-      const double dx = Px - po.px, dy = Py - po.py;
-      const double qx = po.cp * dx + po.sp * dy, qy = po.cp * dy - po.sp * dx;
-      const double fi = (u.x_first - qx) * u.inv_res, fj = (u.y_first - qy) * u.inv_res;
-      // (a state that is not finite has no valid probe: x, y and the heading fail the comparisons by themselves, the speed is asked)
-      const bool in = state_finite && !(!(fi >= 0.0) || !(fj >= 0.0) || !(fi < (double)(rows - 1)) || !(fj < (double)(cols - 1)));
-      const int i0 = in ? (int)fi : 0, j0 = in ? (int)fj : 0;
-      g.ti[i] = fi - (double)i0; g.tj[i] = fj - (double)j0;
-      const LayerPtr c0 = layer + (size_t)j0 * rows + i0;
-      g.f00[i] = c0[0]; g.f10[i] = c0[1]; g.f01[i] = c0[rows]; g.f11[i] = c0[rows + 1];
-      g.exists |= 1u << i;
-      g.inside |= in ? 1u << i : 0u;
-      if (++l == nw) { l = 0; ++k; }
-    }
-  }
-}
-
-// The group's occupancies at step t of N: the validity test and the interpolant of unc_cost_add.  A valid probe enters the row's
-// (max, lowest entry) and hits above the threshold; an invalid one makes the row unknown at this step.
-__device__ __forceinline__ void probes_consume(const ProbeGroup& g, int t, int N, double threshold, double& max_o, int& max_e, bool& hit,
-                                               bool& unknown) {
-#pragma clang fp contract(off)  // the interpolant decides a hit
-#pragma unroll
-  for (int i = 0; i < PROBE_GROUP; ++i) {
-    if (g.exists >> i & 1u) {  // (uniform)
-      const double f00 = g.f00[i], f10 = g.f10[i], f01 = g.f01[i], f11 = g.f11[i];
-      const double ti = g.ti[i], tj = g.tj[i];
-      const double big = 1.0e300;  // finite test without library calls (NaN fails every comparison)
-      const bool valid = (g.inside >> i & 1u) && fabs(f00) < big && fabs(f10) < big && fabs(f01) < big && fabs(f11) < big;
-      const double a0 = f00 + ti * (f10 - f00), a1 = f01 + ti * (f11 - f01);
-      const double o = a0 + tj * (a1 - a0);
-      if (valid) {
-        cmax_merge(max_o, max_e, o, (g.q0 + i) * N + t);
-        hit = hit || o > threshold;
-      } else {
-        unknown = true;
-      }
-    }
-  }
 }
 
 // One partial record (a workgroup's) or G of them → the outputs of solve b.  Run by ONE wavefront.  Record g is

@@ -357,6 +357,29 @@ void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, d
   if (cov_check_ || tighten_) reserve_noise_buffers();
 }
 
+void iLQR::set_map_covariance_check(double occ_threshold, double max_risk, int nx, int ny, int nth, bool sum_bound, bool unknown_hits) {
+  if (max_risk != max_risk) throw std::runtime_error("set_map_covariance_check: max_risk is NaN");
+  const bool on = occ_threshold == occ_threshold;  // NaN: off
+  std::vector<double> nodes, weights;
+  if (on) {  // the nodes are built here, once
+    if (nx < 1 || ny < 1 || nth < 1 || nx > 9 || ny > 9 || nth > 9) throw std::runtime_error("set_map_covariance_check: 1 ... 9 nodes per axis");
+    nodes.assign((size_t)nx * ny * nth * 3, 0.0);
+    weights.assign((size_t)nx * ny * nth, 0.0);
+    check(cilqr_pose_quadrature(nx, ny, nth, nodes.data(), weights.data()), "cilqr_pose_quadrature");
+    if (weights.size() > CILQR_MAX_QUAD_NODES) throw std::runtime_error("set_map_covariance_check: more than CILQR_MAX_QUAD_NODES nodes");
+  }
+  cmap_check_ = on;
+  cmap_nodes_ = nodes;
+  cmap_weights_ = weights;
+  cmap_threshold_ = occ_threshold;
+  cmap_max_risk_ = max_risk;
+  cmap_sum_ = sum_bound;
+  cmap_unknown_hits_ = unknown_hits;
+  last_chance_map_risk.clear();
+  last_map_step_risk.clear();
+  if (cov_check_) reserve_noise_buffers();  // (the device block holds Sigma_t and the nodes while this check is on)
+}
+
 void iLQR::set_chance_tightening(const double Sigma0[16], const double* W, double eps, int rounds, double max_inflate, double lamb) {
   const bool on = Sigma0 != nullptr && rounds != 0;
   if (on && n_samples_) throw std::logic_error(kTighteningWithSamples);
@@ -409,6 +432,10 @@ void iLQR::reserve_noise_buffers() {
   // the covariance check's inputs and outputs
   L.s0 = take(cov_check_ ? 16 : 0); L.W = take(cov_check_ ? 16 : 0);
   L.crisk = take(cov_check_ ? B * CILQR_CHANCE_FIELDS : 0); L.cstep = take(cov_check_ ? B * N : 0);
+  // the map covariance check: every Sigma_t of the chance call, the nodes and weights, its outputs
+  const size_t cm = cov_check_ && cmap_check_ ? 1 : 0, Q = cmap_weights_.size();
+  L.csig = take(cm * B * (N + 1) * 16); L.qn = take(cm * Q * 3); L.qw = take(cm * Q);
+  L.cmrisk = take(cm * B * CILQR_CHANCE_MAP_FIELDS); L.cmstep = take(cm * B * N); L.cmtotal = take(cm * B);
   // the tightening rounds: Sigma0, W, every Sigma_t, the risk row of the round's input plan, the inflated dense table, the fields, obs_cov
   const size_t tg = tighten_ ? 1 : 0;
   L.ts0 = take(tg * 16); L.tW = take(tg * 16); L.tsig = take(tg * B * (N + 1) * 16); L.trisk = take(tg * B * CILQR_CHANCE_FIELDS);
@@ -426,6 +453,10 @@ void iLQR::reserve_noise_buffers() {
   hip_check(hipMalloc(&noise_dev_, L.end * sizeof(double)), "hipMalloc");
   if (cov_check_) hip_check(hipMemset((double*)noise_dev_ + L.delta, 0, 4 * sizeof(double)), "hipMemset");
   else if (!noise_.empty()) hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  if (cm) {
+    hip_check(hipMemcpy((double*)noise_dev_ + L.qn, cmap_nodes_.data(), cmap_nodes_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy((double*)noise_dev_ + L.qw, cmap_weights_.data(), cmap_weights_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  }
   noise_horizon_ = params.horizon;
 }
 
@@ -479,6 +510,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   const bool plain = !cov_check_ && noise_.empty();  // tightening alone: no check behind it, the pick of run_candidates itself
   const bool scored = cov_check_ || plain ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
   const bool tightened = tighten_ && M > 0;
+  const bool cmap_checked = cmap_check_ && map_set_ && cov_check_;
   if (plain) {
     rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
@@ -494,7 +526,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, cov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
     if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
                                            cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
-                                           d + L.cstep, nullptr, nullptr, d + L.total);
+                                           d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
   } else if (n_samples_) {  // the same chain in the compact sampled form
     const int ns = n_samples_;
     const double w = sample_weight();
@@ -521,12 +553,21 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
       if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
     }
   }
+  size_t total_at = plain && !scored ? L.J : L.total;  // each check on top takes the total before it as its base, NaN staying NaN
+  if (cmap_checked && !rc) {  // the covariance against the map: Sigma_t of the chance call placed on the nodes
+    rc = cilqr_chance_risk_map_device(h_, st, B, N, (int)cmap_weights_.size(), d + L.X, d + L.csig, d + L.qn, d + L.qw, cmap_threshold_,
+                                      (cmap_sum_ ? CILQR_CHANCE_MAP_BOUND_SUM : 0u) | (cmap_unknown_hits_ ? CILQR_CHANCE_MAP_UNKNOWN_HITS : 0u),
+                                      cmap_max_risk_, d + total_at, d + L.cmrisk, d + L.cmstep, nullptr, nullptr, d + L.cmtotal);
+    total_at = L.cmtotal;
+  }
   const bool map_checked = map_check_ && map_set_ && (noise_fused_ || cov_check_);
-  if (map_checked && !rc)  // the map's say on top of the obstacles': base = their total, NaN staying NaN
+  if (map_checked && !rc) {  // the map's say on top of the obstacles': base = their total
     rc = cilqr_rollout_risk_map_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
-                                       map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + L.total, d + L.mrisk,
+                                       map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + total_at, d + L.mrisk,
                                        (int32_t*)(d + L.mhits), (int32_t*)(d + L.munk), d + L.mtotal);
-  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + (map_checked ? L.mtotal : plain && !scored ? L.J : L.total), d + L.pair);
+    total_at = L.mtotal;
+  }
+  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + total_at, d + L.pair);
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(st);
@@ -559,6 +600,14 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   if (noise_fused_ && !cov_check_) {
     last_step_hits.assign((size_t)B * N, 0);
     down(last_step_hits.data(), L.hits, last_step_hits.size() * sizeof(int32_t));
+  }
+  last_chance_map_risk.clear();
+  last_map_step_risk.clear();
+  if (cmap_checked) {
+    last_chance_map_risk.assign((size_t)B * CILQR_CHANCE_MAP_FIELDS, 0.0);
+    last_map_step_risk.assign((size_t)B * N, 0.0);
+    down(last_chance_map_risk.data(), L.cmrisk, last_chance_map_risk.size() * sizeof(double));
+    down(last_map_step_risk.data(), L.cmstep, last_map_step_risk.size() * sizeof(double));
   }
   last_map_risk.clear();
   last_map_step_hits.clear();

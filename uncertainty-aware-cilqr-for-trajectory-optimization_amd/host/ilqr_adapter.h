@@ -147,9 +147,24 @@ class iLQR {
   // and the -1 return as under set_pose_noise_check.  set_map_risk_check composes after it through `base` while an uncertainty map
   // is set: with no draws to roll out, the map call sees ONE rollout per candidate, from the zero offset — the plan itself — so a
   // plan whose own footprint enters cells above occ_threshold is rejected whenever max_risk of set_map_risk_check is below 1.
+  // set_map_covariance_check composes after it the same way and is the check that uses the covariance against the map; with both
+  // map checks set the chain is chance -> map covariance -> map rollout, each taking the total before it as its base.
   // Together with set_pose_noise_check(_fused) offsets, or with set_obstacle_samples (the chance value has no sampled form yet),
   // the setters throw std::logic_error naming the conflict.  Sigma0 == nullptr switches the check off (the default).
   void set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb = 1.0, bool sum_bound = false);
+  // Map covariance check: the analytic counterpart of set_map_risk_check.  It has effect under set_pose_covariance_check while an
+  // uncertainty map is set: run_candidates then enqueues, on the check's stream, solve -> (score) -> cilqr_gains_batch_device ->
+  // cilqr_chance_risk_device (its `total` and every Sigma_t in sigma_out; with no obstacle set, the live node's case, it runs with
+  // M = 0 for its Sigma_t alone and rejects nothing) -> cilqr_chance_risk_map_device(occ_threshold, max_risk, base = that total) ->
+  // cilqr_argmin_device on the map call's `total`.  The nodes, the nx x ny x nth tensor product of Gauss-Hermite rules of
+  // cilqr_pose_quadrature (1 ... 9 per axis), are built here, once.  A candidate is rejected when CM_STEP_RISK — with sum_bound
+  // CM_SUM_RISK — exceeds max_risk: the largest per-step (the summed) weighted mass of node poses whose footprint probes enter cells
+  // above occ_threshold (unknown_hits: a probe outside the map or on a cell that is not finite counts as entering one).
+  // last_chance_map_risk holds CILQR_CHANCE_MAP_FIELDS per candidate (cilqr_chance_map_field), last_map_step_risk the per-step r_t,
+  // horizon per candidate.  With no map set, or without the covariance check, behaviour is what it is without this call and both
+  // fields are empty.  An occ_threshold that is NaN switches the check off (the default).
+  void set_map_covariance_check(double occ_threshold, double max_risk, int nx = 5, int ny = 5, int nth = 3, bool sum_bound = false,
+                                bool unknown_hits = false);
   // Chance-constraint tightening: every check above judges a solved plan and can only reject it; this feeds the pose covariance back
   // into the solve.  Sigma0 and W as in set_pose_covariance_check; eps the chance allowed per obstacle entry (kappa =
   // cilqr_chance_kappa(eps) standard deviations).  While set, run_step (get_optimal_control_seq) and run_candidates follow their solve
@@ -202,6 +217,8 @@ class iLQR {
   std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
+  // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
+  std::vector<double> last_chance_map_risk, last_map_step_risk;  // CILQR_CHANCE_MAP_FIELDS per candidate; horizon per candidate
   // run_step / run_candidates under set_chance_tightening with obstacles set; empty otherwise
   std::vector<double> last_tighten, last_tighten_risk_before;  // CILQR_TIGHTEN_FIELDS per solve; CR_STEP_RISK per solve
 
@@ -224,7 +241,7 @@ class iLQR {
   // so that this header needs no HIP
   struct NoiseLayout {
     size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
-        ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, end;
+        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, end;
   };
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
@@ -248,6 +265,10 @@ class iLQR {
   // pose-covariance check (set_pose_covariance_check): Sigma0 and W travel with every call (32 doubles)
   bool cov_check_ = false, cov_has_W_ = false, cov_sum_ = false;
   double cov_sigma0_[16] = {}, cov_W_[16] = {}, cov_max_risk_ = 1.0, cov_lamb_ = 1.0;
+  // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and cov_check_; the nodes as built
+  bool cmap_check_ = false, cmap_sum_ = false, cmap_unknown_hits_ = false;
+  double cmap_threshold_ = 0.0, cmap_max_risk_ = 1.0;
+  std::vector<double> cmap_nodes_, cmap_weights_;
   // chance-constraint tightening (set_chance_tightening, set_obstacle_covariance)
   bool tighten_ = false, tg_has_W_ = false;
   int tg_rounds_ = 0;
