@@ -840,17 +840,40 @@ int cilqr_score_rollouts(cilqr_handle* h, int B, int N, int M, int S, const doub
 
 // ---- fused rollout risk (cilqr_risk.hip) -------------------------------------------------------------------------------------------
 namespace {
+// What the three fused forms (obstacles, sampled obstacles, map) check alike, in the order each of them checks it; `who` heads the
+// messages.  more_missing: one of the form's own required pointers is null; negative_obs_stride: the obstacle form's strides;
+// occ_threshold: the map form's, else null.
+int rollout_common_check(const char* who, const double* X, const double* U, const double* k, const double* K, const double* delta,
+                         const double* risk, bool more_missing, const double* base, const double* total, int S, int64_t delta_batch_stride,
+                         bool negative_obs_stride, double k_scale, double max_risk, const double* occ_threshold) {
+  if (!X || !U || !k || !K || !delta || !risk || more_missing) return fail(CILQR_ERR_ARG, "%s: null required pointer", who);
+  if (total && !base) return fail(CILQR_ERR_ARG, "%s: total needs base", who);
+  if (S < 1) return fail(CILQR_ERR_ARG, "%s: S = %d, needs S >= 1", who, S);
+  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30)) return fail(CILQR_ERR_ARG, "%s: negative stride (or one beyond 2^30)", who);
+  if (negative_obs_stride) return fail(CILQR_ERR_ARG, "%s: negative stride", who);
+  if (k_scale != k_scale || max_risk != max_risk || (occ_threshold && *occ_threshold != *occ_threshold))
+    return fail(CILQR_ERR_ARG, "%s: %s is NaN", who, occ_threshold ? "k_scale, occ_threshold or max_risk" : "k_scale or max_risk");
+  return CILQR_OK;
+}
+// The fields of RolloutRiskArgs the three forms fill alike (a.s and the partial records are the form's own).
+void fill_rollout_risk(cilqr::RolloutRiskArgs& a, int S, const double* X, const double* U, const double* k, const double* K, const double* delta,
+                       int64_t delta_batch_stride, double k_scale, double max_risk, const double* base, double* risk, int32_t* step_hits,
+                       double* total) {
+  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
+  a.delta_bs = (long long)delta_batch_stride * S * 4;
+  a.k_scale = k_scale; a.max_risk = max_risk;
+  a.base = base; a.risk = risk; a.step_hits = step_hits; a.total = total;
+  a.S = S; a.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
+}
 int rollout_risk_check(const cilqr_handle* h, int B, int N, int M, int S, const double* X, const double* U, const double* k,
                        const double* K, const double* delta, int64_t delta_batch_stride, double k_scale, const cilqr_obstacles* obs,
                        double max_risk, const double* base, const double* risk, const double* total, size_t* span, size_t* w_span) {
-  if (!X || !U || !k || !K || !delta || !risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: null required pointer");
-  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: total needs base");
-  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: S = %d, needs S >= 1", S);
-  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30)) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: negative stride (or one beyond 2^30)");
-  if (M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
-    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: negative stride");
-  if (k_scale != k_scale || max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk: k_scale or max_risk is NaN");
-  int rc = check_sizes(h, B, N, M);
+  const bool negative_obs_stride =
+      M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0);
+  int rc = rollout_common_check("cilqr_rollout_risk", X, U, k, K, delta, risk, false, base, total, S, delta_batch_stride, negative_obs_stride,
+                                k_scale, max_risk, nullptr);
+  if (rc) return rc;
+  rc = check_sizes(h, B, N, M);
   if (rc) return rc;
   rc = check_obstacles(B, N, M, obs, span, w_span);
   if (rc) return rc;
@@ -874,12 +897,8 @@ int cilqr_rollout_risk_device(cilqr_handle* h, void* stream, int B, int N, int M
   cilqr::RolloutRiskArgs a = {};
   a.s = handle_args(h, B, N, M, 0);
   set_obstacles(a.s, M, obs);
-  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
-  a.delta_bs = (long long)delta_batch_stride * S * 4;
-  a.k_scale = k_scale; a.max_risk = max_risk;
-  a.base = base; a.risk = risk; a.step_hits = step_hits; a.total = total;
+  fill_rollout_risk(a, S, X, U, k, K, delta, delta_batch_stride, k_scale, max_risk, base, risk, step_hits, total);
   a.partials = h->d_risk_part; a.part_stride = (long long)h->risk_part_stride;
-  a.S = S; a.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(cilqr::launch_rollout_risk(a, (hipStream_t)stream));
   return CILQR_OK;
@@ -917,14 +936,10 @@ int rollout_risk_sampled_check(const cilqr_handle* h, int B, int N, int n_obs, i
                                const double* k, const double* K, const double* delta, int64_t delta_batch_stride, double k_scale,
                                const double* nom_pose, const double* nom_dim, const double* sample_offset, double max_risk,
                                const double* base, const double* risk, const double* total) {
-  if (!X || !U || !k || !K || !delta || !risk || !nom_pose || !nom_dim || !sample_offset)
-    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: null required pointer");
-  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: total needs base");
-  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: S = %d, needs S >= 1", S);
-  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30))
-    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: negative stride (or one beyond 2^30)");
-  if (k_scale != k_scale || max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: k_scale or max_risk is NaN");
-  int rc = check_sampled(h, "cilqr_rollout_risk_sampled", B, N, n_obs, n_samples);
+  int rc = rollout_common_check("cilqr_rollout_risk_sampled", X, U, k, K, delta, risk, !nom_pose || !nom_dim || !sample_offset, base, total, S,
+                                delta_batch_stride, false, k_scale, max_risk, nullptr);
+  if (rc) return rc;
+  rc = check_sampled(h, "cilqr_rollout_risk_sampled", B, N, n_obs, n_samples);
   if (rc) return rc;
   // every count the kernels keep in 32 bits: the sum over a solve's rows of a sample count, an entry index m*N + t, the grid
   if ((int64_t)S * n_samples > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_sampled: S * n_samples beyond 2^31 counts");
@@ -994,12 +1009,8 @@ int cilqr_rollout_risk_sampled_device(cilqr_handle* h, void* stream, int B, int 
   a.s = handle_args(h, B, N, n_obs, 0);
   a.s.obs_pose = nom_pose; a.s.obs_dim = nom_dim;
   a.s.samp_off = sample_offset; a.s.n_samples = n_samples;
-  a.X = X; a.U = U; a.k = k; a.K = K; a.delta = delta;
-  a.delta_bs = (long long)delta_batch_stride * S * 4;
-  a.k_scale = k_scale; a.max_risk = max_risk;
-  a.base = base; a.risk = risk; a.step_hits = step_hits; a.total = total;
+  fill_rollout_risk(a, S, X, U, k, K, delta, delta_batch_stride, k_scale, max_risk, base, risk, step_hits, total);
   a.partials = h->d_obs_tab; a.part_stride = (long long)cilqr::rollout_risk_sampled_part_doubles(N, n_obs);
-  a.S = S; a.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(cilqr::launch_rollout_risk_sampled(a, (hipStream_t)stream));
   return CILQR_OK;
@@ -1030,15 +1041,11 @@ namespace {
 int rollout_risk_map_check(const cilqr_handle* h, int B, int N, int S, const double* X, const double* U, const double* k, const double* K,
                            const double* delta, int64_t delta_batch_stride, double k_scale, double occ_threshold, uint32_t flags,
                            double max_risk, const double* base, const double* risk, const double* total) {
-  if (!X || !U || !k || !K || !delta || !risk) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: null required pointer");
-  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: total needs base");
-  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: S = %d, needs S >= 1", S);
-  if (delta_batch_stride < 0 || delta_batch_stride > ((int64_t)1 << 30))
-    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: negative stride (or one beyond 2^30)");
-  if (k_scale != k_scale || occ_threshold != occ_threshold || max_risk != max_risk)
-    return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: k_scale, occ_threshold or max_risk is NaN");
+  int rc = rollout_common_check("cilqr_rollout_risk_map", X, U, k, K, delta, risk, false, base, total, S, delta_batch_stride, false, k_scale,
+                                max_risk, &occ_threshold);
+  if (rc) return rc;
   if (flags & ~CILQR_MAP_RISK_UNKNOWN_HITS) return fail(CILQR_ERR_ARG, "cilqr_rollout_risk_map: unknown flag bits 0x%x", flags);
-  int rc = check_sizes(h, B, N, 0);
+  rc = check_sizes(h, B, N, 0);
   if (rc) return rc;
   const int64_t G = ((int64_t)S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
   if ((int64_t)B * G > h->max_batch)
@@ -1060,12 +1067,8 @@ int cilqr_rollout_risk_map_device(cilqr_handle* h, void* stream, int B, int N, i
     return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rollout_risk_map: horizon %d does not fit 64 KiB of LDS", N);
   cilqr::MapRiskArgs a = {};
   a.r.s = handle_args(h, B, N, 0, 0);
-  a.r.X = X; a.r.U = U; a.r.k = k; a.r.K = K; a.r.delta = delta;
-  a.r.delta_bs = (long long)delta_batch_stride * S * 4;
-  a.r.k_scale = k_scale; a.r.max_risk = max_risk;
-  a.r.base = base; a.r.risk = risk; a.r.step_hits = step_hits; a.r.total = total;
+  fill_rollout_risk(a.r, S, X, U, k, K, delta, delta_batch_stride, k_scale, max_risk, base, risk, step_hits, total);
   a.r.partials = h->d_risk_part; a.r.part_stride = (long long)h->risk_part_stride;
-  a.r.S = S; a.r.G = (S + cilqr::RISK_THREADS - 1) / cilqr::RISK_THREADS;
   a.occ_threshold = occ_threshold; a.unknown_hits = unknown_hits; a.flags = flags;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(cilqr::launch_rollout_risk_map(a, (hipStream_t)stream));

@@ -21,7 +21,7 @@
 //            standard deviation in closed form.
 // LDS (dynamic, doubles): [F: 16·N][Σ: 16·(N + 1)][r: N][p: M·N] = 8·(33·N + M·N + 16) bytes.
 // No scratch memory, no spilled register (make check).
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 
@@ -29,20 +29,7 @@ using namespace dev;
 
 namespace {
 
-constexpr int NO_INDEX = 0x7fffffff;
-
-__device__ __forceinline__ const ChanceArgs& chance_args() {
-  const ChanceArgs* q = reinterpret_cast<const ChanceArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-  asm volatile("" : "+s"(q));
-  return *q;
-}
-
-// (max value, lowest index): cmax_merge of cilqr_score.hip; a NaN never wins
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
-}
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < 1.7e308; }  // (NaN fails every comparison)
+__device__ __forceinline__ const ChanceArgs& chance_args() { return kernel_args<ChanceArgs>(); }
 
 // The value lane `SRC` of the wavefront holds, in scalar registers.
 template <int SRC>

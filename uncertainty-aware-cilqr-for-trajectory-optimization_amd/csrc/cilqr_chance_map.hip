@@ -30,14 +30,8 @@ using namespace dev;
 
 namespace {
 
-// The argument block through a pointer the compiler cannot trace back to the preloaded arguments, in the CONSTANT address space
-// (risk_args of cilqr_risk_map.hip): the map's constants come by scalar loads where a probe group uses them and are not carried
-// across the node loop, where they would not fit the scalar registers.
-__device__ __forceinline__ const ChanceMapArgs& map_args() {
-  const __attribute__((address_space(4))) ChanceMapArgs* q = (const __attribute__((address_space(4))) ChanceMapArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(q));
-  return *(const ChanceMapArgs*)q;
-}
+__device__ __forceinline__ const ChanceMapArgs& map_args() { return const_kernel_args<ChanceMapArgs>(); }
+
 // The step's factor: the lower Cholesky factor of the (x, y, theta) marginal, zero where a pivot vanishes (include/cilqr.h).
 struct Factor {
   double l00, l10, l11, l20, l21, l22;
@@ -102,9 +96,8 @@ __global__ __launch_bounds__(CHANCE_MAP_THREADS) void cilqr_chance_risk_map_kern
     const double* S = a.sigma + ((size_t)b * (N + 1) + t) * 16;
     const double mx = X[0], my = X[1], mth = X[3];
     const double c00 = S[0], c10 = S[4], c11 = S[5], c20 = S[12], c21 = S[13], c22 = S[15];  // (r, c) at [r + 4c], row <= column
-    const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
-    const bool lost = !(fabs(mx) < big && fabs(my) < big && fabs(mth) < big && fabs(c00) < big && fabs(c10) < big && fabs(c11) < big &&
-                        fabs(c20) < big && fabs(c21) < big && fabs(c22) < big);
+    const bool lost = !(is_finite(mx) && is_finite(my) && is_finite(mth) && is_finite(c00) && is_finite(c10) && is_finite(c11) &&
+                        is_finite(c20) && is_finite(c21) && is_finite(c22));
     double r = 1.0, un = 1.0, e = 0.0;
     if (!lost) {
       Factor f = pose_factor(c00, c10, c11, c20, c21, c22);
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_chance_risk_map_finish_kernel(Chan
     if (a.total) {
       const double base = a.base[b];
       const double bounded = (a.flags & CILQR_CHANCE_MAP_BOUND_SUM) ? sum_risk : max_r;
-      a.total[b] = fabs(base) < 1.7e308 && !(bounded > a.max_risk) ? base : __builtin_nan("");
+      a.total[b] = is_finite(base) && !(bounded > a.max_risk) ? base : __builtin_nan("");
     }
   }
 }

@@ -5,19 +5,24 @@
 // contraction off: the occupancy is bit-equal to the one the map cost interpolates at that probe.
 #pragma once
 
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 namespace dev {
 
 constexpr int PROBE_GROUP = 3;  // probes whose 4·PROBE_GROUP loads are issued together: what 128 vector registers hold twice
-constexpr int NO_INDEX = 0x7fffffff;
 
 typedef const __attribute__((address_space(1))) float* LayerPtr;  // the layer lies in global memory: global loads, not flat ones
 
-// (max occupancy, lowest entry): cmax_merge of cilqr_score.hip, verbatim
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
+// kernel_args (cilqr_rollout_core.hpp) with the pointer kept in the CONSTANT address space: what is read through it — the map's
+// constants, the dynamics' parameters — comes by scalar loads, which no store of the kernel can be thought to clobber and whose waits
+// (lgkmcnt) do not wait for the layer's vector loads (vmcnt).  Read where a probe group uses them, the constants are not carried
+// across the step or node loop, where they would not fit the scalar registers.
+template <class A>
+__device__ __forceinline__ const A& const_kernel_args() {
+  const __attribute__((address_space(4))) A* q = (const __attribute__((address_space(4))) A*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(q));
+  return *(const A*)q;
 }
 
 // A wavefront-uniform double moved to scalar registers (the map pose: a per-solve pose is formed by vector instructions).

@@ -7,17 +7,17 @@
 // lanes per row with their fixed summation tree.
 //
 // Mapping: a workgroup is 64·min(4, ceil(S/64)) lanes of ONE solve; solve b has G = ceil(S/256) workgroups, the grid is B·G.  Per
-// workgroup, once, into LDS: the nominal records {X_t(4), U_t + k_scale·k_t (2), K_t(8)} exactly as cilqr_rollout_kernel forms them;
+// workgroup, once, into LDS: the nominal records {X_t(4), U_t + k_scale·k_t (2), K_t(8)} by load_nominal, as in cilqr_rollout_kernel;
 // the solve's obstacle entries, made by obs_entry_at through the strides of cilqr_obstacles — the call the score kernel makes, so
 // the entries carry the same bits — stored [t][m] so that a step's M entries are consecutive; N per-step hit counters.  In the
 // step loop every lane reads the same LDS address (a broadcast) and keeps its state in registers.
-// u_t, the state and c are formed by the statements of cilqr_rollout.hip and cilqr_score.hip (circle_constraints and cmax_merge are
-// restated verbatim): WORST_C is bit-equal to the worst SCORE_MAX_C of the stored-rows path.
+// u_t, the state and c are formed by the definitions of cilqr_rollout_core.hpp, which cilqr_rollout.hip and cilqr_score.hip use too:
+// WORST_C is bit-equal to the worst SCORE_MAX_C of the stored-rows path.
 // A wavefront whose share of S is partial computes its idle lanes on a zero offset and counts nothing for them; a wavefront with no
 // row at all skips the loop.  Every row index is formed in 64 bits.  A solve's results depend on its own inputs and offsets alone.
-// Arguments are read through risk_args (the phase_args manner of cilqr_device.hpp): no scratch memory, no spilled register, 128
+// Arguments are read through kernel_args (the phase_args manner of cilqr_device.hpp): no scratch memory, no spilled register, 128
 // vector registers at most (make check).
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 
@@ -25,37 +25,7 @@ using namespace dev;
 
 namespace {
 
-constexpr int NOM_W = 14;    // doubles per step of the nominal copy (cilqr_rollout.hip)
-constexpr int ENT_W = 6;     // doubles per obstacle entry (ObsEntry)
-constexpr int NO_INDEX = 0x7fffffff;
-
-__device__ __forceinline__ const RolloutRiskArgs& risk_args() {
-  const RolloutRiskArgs* q = reinterpret_cast<const RolloutRiskArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-  asm volatile("" : "+s"(q));
-  return *q;
-}
-
-// (max c, lowest entry): cilqr_score.hip, verbatim
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
-}
-// (max c, lowest row) with the row's own lowest entry carried along
-__device__ __forceinline__ void row_merge(double& c0, int& r0, int& e0, double c1, int r1, int e1) {
-  if (c1 > c0 || (c1 == c0 && r1 < r0)) { c0 = c1; r0 = r1; e0 = e1; }
-}
-
-// c = 1 - d'Pd of both ego circles (I/Obstacle.cpp:65-73, 86-94): cilqr_score.hip, verbatim
-__device__ __forceinline__ void circle_constraints(const ObsConsts& k, const ObsEntry& e, double& cf, double& cr) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const double ex = (side == 0 ? k.fxp : k.rxp) - e.ox, ey = (side == 0 ? k.fyp : k.ryp) - e.oy;
-    const double d0 = __builtin_fma(e.co, ex, e.so * ey);
-    const double d1 = __builtin_fma(e.co, ey, -(e.so * ex));
-    const double c = 1 - __builtin_fma(d0 * e.ia2, d0, (d1 * e.ib2) * d1);
-    if (side == 0) cf = c; else cr = c;
-  }
-}
+__device__ __forceinline__ const RolloutRiskArgs& risk_args() { return kernel_args<RolloutRiskArgs>(); }
 
 // One partial record (a workgroup's) or G of them → the outputs of solve b.  Run by ONE wavefront.  Record g is
 // {hit rows, worst c, its row, its entry} at rec + g*stride (doubles) with its N int32 step counts at counts + 2*g*stride: the
@@ -93,10 +63,7 @@ __device__ __forceinline__ void risk_finish(const RolloutRiskArgs& a, int b, int
     out[CILQR_RR_WORST_ENTRY] = max_e == NO_INDEX ? -1.0 : (double)max_e;
     out[CILQR_RR_FIRST_STEP] = first == NO_INDEX ? -1.0 : (double)first;
     out[CILQR_RR_STEP_SHARE] = (double)most / (double)S;
-    if (a.total) {
-      const double base = a.base[b];
-      a.total[b] = fabs(base) < 1.7e308 && !(share > a.max_risk) ? base : __builtin_nan("");
-    }
+    if (a.total) a.total[b] = gated_total(a.base[b], share, a.max_risk);
   }
 }
 
@@ -118,26 +85,7 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_kernel(Rollou
   int* red_e = red_r + RISK_WAVES;
   int* red_h = red_e + RISK_WAVES;
 
-  // ---- the nominal trajectory and gains of solve b → LDS (the statements of cilqr_rollout_kernel); the counters
-  {
-    const RolloutRiskArgs& q = risk_args();
-    const double* X = q.X + (size_t)b * 4 * (N + 1);
-    const double* U = q.U + (size_t)b * 2 * N;
-    const double* k = q.k + (size_t)b * 2 * N;
-    const double* K = q.K + (size_t)b * 8 * N;
-    const double ks = q.k_scale;
-    for (int t = tid; t < N; t += threads) {
-      double* r = nom + (size_t)t * NOM_W;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) r[i] = X[4 * t + i];
-      r[4] = U[2 * t] + ks * k[2 * t];
-      r[5] = U[2 * t + 1] + ks * k[2 * t + 1];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) r[6 + i] = K[8 * (size_t)t + i];
-      cnt[t] = 0;
-    }
-    if (tid < 4) nom[(size_t)N * NOM_W + tid] = X[4 * N + tid];
-  }
+  load_nominal(risk_args(), b, N, tid, threads, nom, cnt);  // (and the step counters cleared)
   // ---- the obstacle entries of solve b → LDS, [t][m]
   {
     const SolveArgs& s = phase_args();  // (RolloutRiskArgs starts with its SolveArgs)
@@ -155,28 +103,12 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_kernel(Rollou
   int max_e = NO_INDEX;
   bool hit_any = false;
   if (wave * WAVE < n_rows) {  // (wavefront-uniform: a wavefront without a row has nothing to do)
-    // ---- this lane's start
-    State st;
-    {
-      const RolloutRiskArgs& q = risk_args();
-      double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-      if (active) {
-        const double* d = q.delta + (long long)b * q.delta_bs + 4 * (long long)(s0 + tid);
-        d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
-      }
-      st.x = nom[0] + d0; st.y = nom[1] + d1; st.v = nom[2] + d2; st.th = nom[3] + d3;
-      sincos_fast(st.th, &st.s, &st.c);
-    }
+    State st = start_state(risk_args(), nom, b, s0 + tid, active);
     const KParams& kp = phase_params();
-    const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
     for (int t = 0; t < N; ++t) {
-      const double* r = nom + (size_t)t * NOM_W;
-      const double e0 = st.x - r[0], e1 = st.y - r[1], e2 = st.v - r[2], e3 = st.th - r[3];
-      // K[r + 2c]: the dot product over c = 0..3, then (U + k_scale·k) + it (cilqr_rollout.hip)
-      const double f0 = fma(r[12], e3, fma(r[10], e2, fma(r[8], e1, r[6] * e0)));
-      const double f1 = fma(r[13], e3, fma(r[11], e2, fma(r[9], e1, r[7] * e0)));
-      const double u0 = r[4] + f0, u1 = r[5] + f1;
-      bool hit = !(fabs(st.x) < big && fabs(st.y) < big && fabs(st.v) < big && fabs(st.th) < big && fabs(u0) < big && fabs(u1) < big);
+      double u0, u1;
+      feedback_control(st, nom + (size_t)t * NOM_W, u0, u1);
+      bool hit = state_lost(st, u0, u1);
       {
 #pragma clang fp contract(off)  // the sign of c decides a hit
         const ObsConsts oc = make_obs_consts(kp, st.x, st.y, st.c, st.s);
@@ -200,12 +132,7 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_kernel(Rollou
   // ---- reduction: butterflies inside the wavefronts, then the wavefronts in order by one lane
   int max_r = active && max_e != NO_INDEX ? s0 + tid : NO_INDEX;
   if (max_r == NO_INDEX) { max_c = -__builtin_huge_val(); max_e = NO_INDEX; }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double oc = __shfl_xor(max_c, o, WAVE);
-    const int orow = __shfl_xor(max_r, o, WAVE);
-    const int oe = __shfl_xor(max_e, o, WAVE);
-    row_merge(max_c, max_r, max_e, oc, orow, oe);
-  }
+  wave_row_merge(max_c, max_r, max_e);
   const int wave_hits = __popcll(__ballot(hit_any));
   if (lane == 0) { red_c[wave] = max_c; red_r[wave] = max_r; red_e[wave] = max_e; red_h[wave] = wave_hits; }
   __syncthreads();  // (every counter is final)
@@ -245,15 +172,8 @@ size_t rollout_risk_lds_bytes(int N, int M) {
 }
 
 hipError_t launch_rollout_risk(const RolloutRiskArgs& a, hipStream_t stream) {
-  if (a.s.B <= 0) return hipSuccess;
-  const int waves = (a.S + WAVE - 1) / WAVE;
-  const int threads = WAVE * (waves < RISK_WAVES ? waves : RISK_WAVES);
-  const long long blocks = (long long)a.s.B * a.G;
-  hipLaunchKernelGGL(cilqr_rollout_risk_kernel, dim3((unsigned)blocks), dim3(threads), rollout_risk_lds_bytes(a.s.N, a.s.M), stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || a.G == 1) return e;
-  hipLaunchKernelGGL(cilqr_rollout_risk_finish_kernel, dim3(a.s.B), dim3(WAVE), 0, stream, a);
-  return hipGetLastError();
+  return launch_risk_pair(cilqr_rollout_risk_kernel, cilqr_rollout_risk_finish_kernel, a, a.s.B, a.S, a.G, rollout_risk_lds_bytes(a.s.N, a.s.M),
+                          stream);
 }
 
 }  // namespace cilqr

@@ -7,11 +7,11 @@
 // Nothing here is a floating-point sum.  Counts are integers; (max occupancy, lowest row, lowest entry) is lexicographic.  Both
 // come out the same in any evaluation order, so the mapping is free and is the one of cilqr_risk.hip: lane = rollout row, a
 // workgroup is 64·min(4, ceil(S/64)) lanes of ONE solve, solve b has G = ceil(S/256) workgroups, the grid is B·G.  Per workgroup,
-// once, into LDS: the nominal records {X_t(4), U_t + k_scale·k_t (2), K_t(8)} exactly as cilqr_rollout_kernel forms them, and N
+// once, into LDS: the nominal records {X_t(4), U_t + k_scale·k_t (2), K_t(8)} by load_nominal, as in cilqr_rollout_kernel, and N
 // per-step counters.  A counter holds the rows that hit at step t in its low 16 bits and the rows that are unknown at step t in
 // its high 16 (a workgroup has at most 256 rows): one LDS atomic per wavefront and step feeds both from two ballot counts.
-// u_t and the state are formed by the statements of cilqr_rollout.hip; probe positions, cell indices, the validity test and the
-// interpolant are the statements of unc_cost_add, restated in cilqr_map_probes.hpp with contraction off, on the rollout state's
+// u_t and the state are formed by the definitions of cilqr_rollout_core.hpp; probe positions, cell indices, the validity test and
+// the interpolant are the statements of unc_cost_add, restated in cilqr_map_probes.hpp with contraction off, on the rollout state's
 // own cos / sin (sincos_fast, carried by dyn_step): WORST_OCC is bit-equal to the occupancy the map cost interpolates at that probe.
 //
 // Load scheduling.  Nothing dyn_step needs comes from the map, so no lookup has to sit on the rollout's dependency chain.  The
@@ -39,21 +39,8 @@ using namespace dev;
 
 namespace {
 
-constexpr int NOM_W = 14;       // doubles per step of the nominal copy (cilqr_rollout.hip)
-
-// The argument block through a pointer the compiler cannot trace back to the preloaded arguments (the phase_args manner), kept in
-// the CONSTANT address space: what is read through it — the map's constants, the dynamics' parameters — comes by scalar loads, which
-// no store of the kernel can be thought to clobber and whose waits (lgkmcnt) do not wait for the layer's vector loads (vmcnt).
-__device__ __forceinline__ const MapRiskArgs& risk_args() {
-  const __attribute__((address_space(4))) MapRiskArgs* q = (const __attribute__((address_space(4))) MapRiskArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(q));
-  return *(const MapRiskArgs*)q;
-}
-
-// (max occupancy, lowest row) with the row's own lowest entry carried along
-__device__ __forceinline__ void row_merge(double& c0, int& r0, int& e0, double c1, int r1, int e1) {
-  if (c1 > c0 || (c1 == c0 && r1 < r0)) { c0 = c1; r0 = r1; e0 = e1; }
-}
+// (the constant-address-space accessor, not kernel_args: why, at const_kernel_args in cilqr_map_probes.hpp)
+__device__ __forceinline__ const MapRiskArgs& risk_args() { return const_kernel_args<MapRiskArgs>(); }
 
 // One partial record (a workgroup's) or G of them → the outputs of solve b.  Run by ONE wavefront.  Record g is
 // {hit rows, worst occupancy, its row, its entry, unknown rows} at rec + g*stride (doubles) with its N packed int32 step counters
@@ -101,7 +88,7 @@ __device__ __forceinline__ void map_risk_finish(const MapRiskArgs& a, int b, int
     out[CILQR_MR_UNKNOWN] = (double)unknown_rows / (double)S;
     if (a.r.total) {
       const double base = a.r.base[b];
-      a.r.total[b] = fabs(base) < 1.7e308 && !(share > a.r.max_risk) ? base : __builtin_nan("");
+      a.r.total[b] = gated_total(base, share, a.r.max_risk);
     }
   }
 }
@@ -149,44 +136,14 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_map_kernel(Ma
   double* nom = m.nom;
   int* cnt = m.cnt;
 
-  // ---- the nominal trajectory and gains of solve b → LDS (the statements of cilqr_rollout_kernel); the counters
-  {
-    const MapRiskArgs& q = risk_args();
-    const double* X = q.r.X + (size_t)b * 4 * (N + 1);
-    const double* U = q.r.U + (size_t)b * 2 * N;
-    const double* k = q.r.k + (size_t)b * 2 * N;
-    const double* K = q.r.K + (size_t)b * 8 * N;
-    const double ks = q.r.k_scale;
-    for (int t = tid; t < N; t += threads) {
-      double* r = nom + (size_t)t * NOM_W;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) r[i] = X[4 * t + i];
-      r[4] = U[2 * t] + ks * k[2 * t];
-      r[5] = U[2 * t + 1] + ks * k[2 * t + 1];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) r[6 + i] = K[8 * (size_t)t + i];
-      cnt[t] = 0;
-    }
-    if (tid < 4) nom[(size_t)N * NOM_W + tid] = X[4 * N + tid];
-  }
+  load_nominal(risk_args().r, b, N, tid, threads, nom, cnt);  // (and the step counters cleared)
   __syncthreads();
 
   double max_o = -__builtin_huge_val();
   int max_e = NO_INDEX;
   bool hit_any = false, unknown_any = false;
   if (wave * WAVE < n_rows) {  // (wavefront-uniform: a wavefront without a row has nothing to do)
-    // ---- this lane's start
-    State st;
-    {
-      const MapRiskArgs& q = risk_args();
-      double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-      if (active) {
-        const double* d = q.r.delta + (long long)b * q.r.delta_bs + 4 * (long long)(s0 + tid);
-        d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
-      }
-      st.x = nom[0] + d0; st.y = nom[1] + d1; st.v = nom[2] + d2; st.th = nom[3] + d3;
-      sincos_fast(st.th, &st.s, &st.c);
-    }
+    State st = start_state(risk_args().r, nom, b, s0 + tid, active);
     // (the map's constants and the dynamics' parameters are read anew, by scalar loads, where a step uses them: carried across the
     // loop they would not fit the scalar registers)
     UncPose po = unc_pose(risk_args().r.s.unc, b);
@@ -195,33 +152,29 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_map_kernel(Ma
     const int P = risk_args().r.s.unc.nl * risk_args().r.s.unc.nw;
     const double threshold = risk_args().occ_threshold;
     const bool unknown_hits = (risk_args().flags & CILQR_MAP_RISK_UNKNOWN_HITS) != 0;
-    const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
     // the first group of step 0 leaves; from here on `cur` is a group whose loads are in flight
     int k = 0, l = 0;
     ProbeGroup cur;
-    probes_issue(risk_args().r.s.unc, po, layer, st.x, st.y, st.c, st.s, fabs(st.v) < big, 0, k, l, cur);
+    probes_issue(risk_args().r.s.unc, po, layer, st.x, st.y, st.c, st.s, is_finite(st.v), 0, k, l, cur);
     for (int t = 0; t < N; ++t) {
       bool hit = false, unknown = false;
       const UncArgs& u = risk_args().r.s.unc;
       for (int q0 = PROBE_GROUP; q0 < P; q0 += PROBE_GROUP) {  // the next group's loads leave before this group's are used
         ProbeGroup nx;
-        probes_issue(u, po, layer, st.x, st.y, st.c, st.s, fabs(st.v) < big, q0, k, l, nx);
+        probes_issue(u, po, layer, st.x, st.y, st.c, st.s, is_finite(st.v), q0, k, l, nx);
         probes_consume(cur, t, N, threshold, max_o, max_e, hit, unknown);
         cur = nx;
       }
       // the step's last group is in flight while the state advances
-      const double* r = nom + (size_t)t * NOM_W;
-      const double e0 = st.x - r[0], e1 = st.y - r[1], e2 = st.v - r[2], e3 = st.th - r[3];
-      // K[r + 2c]: the dot product over c = 0..3, then (U + k_scale·k) + it (cilqr_rollout.hip)
-      const double f0 = fma(r[12], e3, fma(r[10], e2, fma(r[8], e1, r[6] * e0)));
-      const double f1 = fma(r[13], e3, fma(r[11], e2, fma(r[9], e1, r[7] * e0)));
-      const double u0 = r[4] + f0, u1 = r[5] + f1;
-      const bool lost = !(fabs(st.x) < big && fabs(st.y) < big && fabs(st.v) < big && fabs(st.th) < big && fabs(u0) < big && fabs(u1) < big);
+      double u0, u1;
+      feedback_control(st, nom + (size_t)t * NOM_W, u0, u1);
+      // (state_lost of cilqr_rollout_core.hpp, written out: through the call this kernel takes 132 vector registers, not 114)
+      const bool lost = !(is_finite(st.x) && is_finite(st.y) && is_finite(st.v) && is_finite(st.th) && is_finite(u0) && is_finite(u1));
       st = dyn_step(risk_args().r.s.kp, st, u0, u1);
       // ... and the first group of the next step leaves before the last of this one is used
       ProbeGroup nx = {};
       k = 0; l = 0;
-      if (t + 1 < N) probes_issue(risk_args().r.s.unc, po, layer, st.x, st.y, st.c, st.s, fabs(st.v) < big, 0, k, l, nx);
+      if (t + 1 < N) probes_issue(risk_args().r.s.unc, po, layer, st.x, st.y, st.c, st.s, is_finite(st.v), 0, k, l, nx);
       probes_consume(cur, t, N, threshold, max_o, max_e, hit, unknown);
       cur = nx;
       hit = (hit || lost || (unknown_hits && unknown)) && active;
@@ -238,12 +191,7 @@ __global__ __launch_bounds__(RISK_THREADS) void cilqr_rollout_risk_map_kernel(Ma
   const Lds e = lds_layout(lds, z.N);
   int max_r = active && max_e != NO_INDEX ? z.s0 + tid : NO_INDEX;
   if (max_r == NO_INDEX) { max_o = -__builtin_huge_val(); max_e = NO_INDEX; }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double oc = __shfl_xor(max_o, o, WAVE);
-    const int orow = __shfl_xor(max_r, o, WAVE);
-    const int oe = __shfl_xor(max_e, o, WAVE);
-    row_merge(max_o, max_r, max_e, oc, orow, oe);
-  }
+  wave_row_merge(max_o, max_r, max_e);
   const int wave_hits = __popcll(__ballot(hit_any)), wave_unknown = __popcll(__ballot(unknown_any));
   if (lane == 0) { e.red_o[wave] = max_o; e.red_r[wave] = max_r; e.red_e[wave] = max_e; e.red_h[wave] = wave_hits; e.red_u[wave] = wave_unknown; }
   __syncthreads();  // (every counter is final)
@@ -284,15 +232,8 @@ size_t rollout_risk_map_lds_bytes(int N) {
 }
 
 hipError_t launch_rollout_risk_map(const MapRiskArgs& a, hipStream_t stream) {
-  if (a.r.s.B <= 0) return hipSuccess;
-  const int waves = (a.r.S + WAVE - 1) / WAVE;
-  const int threads = WAVE * (waves < RISK_WAVES ? waves : RISK_WAVES);
-  const long long blocks = (long long)a.r.s.B * a.r.G;
-  hipLaunchKernelGGL(cilqr_rollout_risk_map_kernel, dim3((unsigned)blocks), dim3(threads), rollout_risk_map_lds_bytes(a.r.s.N), stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || a.r.G == 1) return e;
-  hipLaunchKernelGGL(cilqr_rollout_risk_map_finish_kernel, dim3(a.r.s.B), dim3(WAVE), 0, stream, a);
-  return hipGetLastError();
+  return launch_risk_pair(cilqr_rollout_risk_map_kernel, cilqr_rollout_risk_map_finish_kernel, a, a.r.s.B, a.r.S, a.r.G,
+                          rollout_risk_map_lds_bytes(a.r.s.N), stream);
 }
 
 }  // namespace cilqr

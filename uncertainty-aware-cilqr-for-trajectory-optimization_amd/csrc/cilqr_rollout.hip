@@ -1,6 +1,5 @@
-// cilqr_rollout.hip — S closed-loop rollouts per solve from offset starts (cilqr_rollout_batch*, include/cilqr.h): per row, with
-// x'_0 = X_0 + delta,   u_t = (U_t + k_scale·k_t) + K_t (x'_t − X_t)   (iLQR::forward_pass, I/iLQR.cpp:68-86; stored unclamped, the
-// heading difference not wrapped),   x'_{t+1} = Model::forward_simulate(x'_t, u_t)   (dyn_step: the clamps act on a copy).
+// cilqr_rollout.hip — S closed-loop rollouts per solve from offset starts (cilqr_rollout_batch*, include/cilqr.h): the rollout step
+// defined in cilqr_rollout_core.hpp, every state and every control (unclamped) stored.
 //
 // Mapping: lane = sample.  A workgroup is ONE wavefront holding up to 64 samples of ONE solve, so the nominal X_t, U_t, k_t, K_t are
 // the same for every lane: the block copies them to LDS once ({X_t(4), U_t + k_scale·k_t (2), K_t(8)} per step) and every lane
@@ -14,7 +13,7 @@
 // a smaller one cuts the U segment below a line.
 // A wavefront whose share of S is partial (S = 70: 64 + 6) computes its idle lanes on a zero offset and stores nothing for them.
 // Every row index is formed in 64 bits.  A row depends on its own inputs alone: the same bits whatever B, S and its position.
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 
@@ -23,15 +22,8 @@ using namespace dev;
 namespace {
 
 constexpr int TILE = 8;               // steps staged per write-out
-constexpr int NOM_W = 14;             // doubles per step of the nominal copy
 constexpr int XS = 4 * TILE + 1;      // padded row strides of the staging tiles (doubles)
 constexpr int US = 2 * TILE + 1;
-
-__device__ __forceinline__ const RolloutArgs& rollout_args() {
-  const RolloutArgs* q = reinterpret_cast<const RolloutArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-  asm volatile("" : "+s"(q));
-  return *q;
-}
 
 // LDS (dynamic): [nominal: N·NOM_W + 4 (X_N)][X tile: 64·XS][U tile: 64·US]
 __global__ __launch_bounds__(WAVE) void cilqr_rollout_kernel(RolloutArgs a) {
@@ -45,7 +37,8 @@ __global__ __launch_bounds__(WAVE) void cilqr_rollout_kernel(RolloutArgs a) {
   double* tx = nom + (size_t)N * NOM_W + 4;
   double* tu = tx + WAVE * XS;
 
-  // ---- the nominal trajectory and gains of solve b → LDS
+  // ---- the nominal trajectory and gains of solve b → LDS: load_nominal of cilqr_rollout_core.hpp, written out (through the call
+  // this launch measured 1.3 % slower, profiles/r16_rollout_core.txt)
   {
     const double* X = a.X + (size_t)b * 4 * (N + 1);
     const double* U = a.U + (size_t)b * 2 * N;
@@ -64,19 +57,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_rollout_kernel(RolloutArgs a) {
     if (lane < 4) nom[(size_t)N * NOM_W + lane] = X[4 * N + lane];
   }
   __syncthreads();
-
-  // ---- this lane's start
-  State st;
-  {
-    const RolloutArgs& q = rollout_args();
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-    if (active) {
-      const double* d = q.delta + (long long)b * q.delta_bs + 4 * (long long)(s0 + lane);
-      d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
-    }
-    st.x = nom[0] + d0; st.y = nom[1] + d1; st.v = nom[2] + d2; st.th = nom[3] + d3;
-    sincos_fast(st.th, &st.s, &st.c);
-  }
+  State st = start_state(kernel_args<RolloutArgs>(), nom, b, s0 + lane, active);
   const long long row0 = (long long)b * S + s0;  // first row of this wavefront
   double* Xr = a.X_roll + row0 * 4 * (N + 1);
   double* Ur = a.U_roll + row0 * 2 * N;
@@ -85,7 +66,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_rollout_kernel(RolloutArgs a) {
   for (int i0 = 0; i0 <= N; i0 += TILE) {
     const int n_st = min(TILE, N + 1 - i0), n_u = min(TILE, N - i0);  // states i0 … and controls i0 … of this tile (n_u may be 0)
     {
-      const KParams& kp = rollout_args().kp;
+      const KParams& kp = kernel_args<RolloutArgs>().kp;
       double* mx = tx + lane * XS;
       double* mu = tu + lane * US;
       for (int ii = 0; ii < n_st; ++ii) {
@@ -94,7 +75,7 @@ __global__ __launch_bounds__(WAVE) void cilqr_rollout_kernel(RolloutArgs a) {
         if (i < N) {
           const double* r = nom + (size_t)i * NOM_W;
           const double e0 = st.x - r[0], e1 = st.y - r[1], e2 = st.v - r[2], e3 = st.th - r[3];
-          // K[r + 2c]: the dot product over c = 0..3, then (U + k_scale·k) + it, as oracle_forward_pass sums
+          // (feedback_control of cilqr_rollout_core.hpp, written out: the form that measured no slower than before)
           const double f0 = fma(r[12], e3, fma(r[10], e2, fma(r[8], e1, r[6] * e0)));
           const double f1 = fma(r[13], e3, fma(r[11], e2, fma(r[9], e1, r[7] * e0)));
           const double u0 = r[4] + f0, u1 = r[5] + f1;

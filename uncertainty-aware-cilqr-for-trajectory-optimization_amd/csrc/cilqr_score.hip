@@ -20,7 +20,7 @@
 // score calls' own instantiation): row r is scored against solve r / S; cilqr_risk_kernel then reduces each solve's rows (one
 // wavefront per solve, the same butterflies).
 // x_N carries no cost, as in the reference (get_state_cost and get_J visit t < N).
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 
@@ -31,18 +31,8 @@ namespace {
 constexpr int SCORE_WAVES = SCORE_THREADS / WAVE;
 constexpr int RED_SLOTS = 8;  // doubles per wavefront in the cross-wavefront stage
 
-// The whole argument block through a pointer the compiler cannot trace back to the preloaded arguments (as phase_args of
-// cilqr_device.hpp): the epilogue's pointers and thresholds are loaded there, not carried through every phase.
-__device__ __forceinline__ const ScoreArgs& score_args() {
-  const ScoreArgs* q = reinterpret_cast<const ScoreArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-  asm volatile("" : "+s"(q));
-  return *q;
-}
-
-// (max c, lowest entry): lexicographic, as amin_merge of cilqr_select.hip with the order of the value reversed
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
-}
+// (the epilogue's pointers and thresholds are loaded there, not carried through every phase)
+__device__ __forceinline__ const ScoreArgs& score_args() { return kernel_args<ScoreArgs>(); }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma clang fp contract(off)
@@ -52,19 +42,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ double wave_max(double v) {
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, WAVE));
   return v;
-}
-
-// c = 1 - d'Pd of both ego circles (I/Obstacle.cpp:65-73, 86-94): the statements of obs_prep, which keeps q2·c only
-__device__ __forceinline__ void circle_constraints(const ObsConsts& k, const ObsEntry& e, double& cf, double& cr) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const double ex = (side == 0 ? k.fxp : k.rxp) - e.ox, ey = (side == 0 ? k.fyp : k.ryp) - e.oy;
-    const double d0 = __builtin_fma(e.co, ex, e.so * ey);
-    const double d1 = __builtin_fma(e.co, ey, -(e.so * ex));
-    const double c = 1 - __builtin_fma(d0 * e.ia2, d0, (d1 * e.ib2) * d1);
-    if (side == 0) cf = c; else cr = c;
-  }
 }
 
 // Entry (m, t) of solve b and its weight.  SAMPLED: m = o*n_samples + s is nominal obstacle o moved by sample s's offset — the
@@ -193,7 +170,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
 
   // ---- phase 2: the obstacle entries e = m*N + t
   double obst = 0.0, max_c = -__builtin_huge_val();
-  int max_e = 0x7fffffff;
+  int max_e = NO_INDEX;
   {
 #pragma clang fp contract(off)  // the sign of c decides the collision share
     const SolveArgs& s = phase_args();
@@ -253,12 +230,11 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
     out[CILQR_SCORE_OBSTACLE] = obst;
     out[CILQR_SCORE_UNCERTAINTY] = unc;
     out[CILQR_SCORE_MAX_C] = max_c;
-    out[CILQR_SCORE_MAX_C_ENTRY] = max_e == 0x7fffffff ? -1.0 : (double)max_e;
+    out[CILQR_SCORE_MAX_C_ENTRY] = max_e == NO_INDEX ? -1.0 : (double)max_e;
     out[CILQR_SCORE_MAX_CTRL] = max_ctrl;
     out[CILQR_SCORE_COLLISION] = collision;
     if (fa.total) {
-      const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
-      const bool finite = fabs(track) < big && fabs(ctrl) < big && fabs(obst) < big && fabs(unc) < big;
+      const bool finite = is_finite(track) && is_finite(ctrl) && is_finite(obst) && is_finite(unc);
       const double sum = ((track + ctrl) + obst) + unc;
       fa.total[b] = finite && !(collision > fa.max_collision) ? sum : __builtin_nan("");
     }
@@ -272,14 +248,13 @@ __global__ __launch_bounds__(WAVE) void cilqr_risk_kernel(RiskArgs a) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
   const double* rows = a.row_score + (size_t)b * (size_t)S * CILQR_SCORE_FIELDS;
-  const double big = 1.7e308;  // finite test without library calls (NaN fails every comparison)
   double sum = 0.0, max_c = -__builtin_huge_val();
-  int max_r = 0x7fffffff, hits = 0;
+  int max_r = NO_INDEX, hits = 0;
   for (int r = lane; r < S; r += WAVE) {
     const double* q = rows + (size_t)r * CILQR_SCORE_FIELDS;
     const double track = q[CILQR_SCORE_TRACK], ctrl = q[CILQR_SCORE_CONTROL], obst = q[CILQR_SCORE_OBSTACLE], unc = q[CILQR_SCORE_UNCERTAINTY];
     const double c = q[CILQR_SCORE_MAX_C];
-    const bool finite = fabs(track) < big && fabs(ctrl) < big && fabs(obst) < big && fabs(unc) < big;
+    const bool finite = is_finite(track) && is_finite(ctrl) && is_finite(obst) && is_finite(unc);
     hits += (c > 0.0 || !finite) ? 1 : 0;
     cmax_merge(max_c, max_r, c, r);
     sum = sum + (((track + ctrl) + obst) + unc);
@@ -296,9 +271,9 @@ __global__ __launch_bounds__(WAVE) void cilqr_risk_kernel(RiskArgs a) {
     double* out = a.risk + (size_t)b * CILQR_RISK_FIELDS;
     out[CILQR_RISK_COLLISION] = share;
     out[CILQR_RISK_WORST_C] = max_c;
-    out[CILQR_RISK_WORST_ROW] = max_r == 0x7fffffff ? -1.0 : (double)max_r;
+    out[CILQR_RISK_WORST_ROW] = max_r == NO_INDEX ? -1.0 : (double)max_r;
     out[CILQR_RISK_MEAN_TOTAL] = mean;
-    if (a.total) a.total[b] = fabs(mean) < big && !(share > a.max_risk) ? mean : __builtin_nan("");
+    if (a.total) a.total[b] = gated_total(mean, share, a.max_risk);
   }
 }
 

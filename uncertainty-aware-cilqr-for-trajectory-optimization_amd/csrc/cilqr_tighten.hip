@@ -14,7 +14,7 @@
 //            integer count: no order of evaluation changes a bit.
 // LDS (dynamic, doubles): [C: 6·N][records: 5·4] = 8·(6·N + 20) bytes.
 // No scratch memory, no spilled register (make check).
-#include "cilqr_device.hpp"
+#include "cilqr_rollout_core.hpp"
 
 namespace cilqr {
 
@@ -22,15 +22,7 @@ using namespace dev;
 
 namespace {
 
-constexpr int NO_INDEX = 0x7fffffff;
 constexpr int RECORD = 5;  // doubles a wavefront leaves for the merge
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < 1.7e308; }  // (NaN fails every comparison)
-
-// (max value, lowest index): cmax_merge of cilqr_score.hip; a NaN never wins
-__device__ __forceinline__ void cmax_merge(double& c0, int& e0, double c1, int e1) {
-  if (c1 > c0 || (c1 == c0 && e1 < e0)) { c0 = c1; e0 = e1; }
-}
 
 // The larger of two variances, a NaN losing to a number, and not below 0; NaN when both are.
 __device__ __forceinline__ double larger_variance(double f, double r) {
