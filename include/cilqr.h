@@ -855,6 +855,87 @@ int cilqr_chance_risk_map(cilqr_handle* h, int B, int N, int Q, const double* X,
  * (n-1)! / (n He_(n-1)(z)^2), scaled to sum to 1: no table is involved and the same arguments give the same bits. */
 int cilqr_pose_quadrature(int nx, int ny, int nth, double* nodes, double* weights);
 
+/* --- analytic chance risk against sampled obstacles in compact form (new) --------------------------------------------------------
+ * cilqr_chance_risk stops at ordinary obstacles: for the sampled scene form — n_obs obstacles x n_samples Gaussian pose samples —
+ * the only judge under ego-pose noise so far is cilqr_rollout_risk_sampled: risk in steps of 1/(S*n_samples), dependent on the
+ * offsets' seed, every rollout row a serial chain over the horizon.  cilqr_chance_risk_sampled(_device) is its analytic
+ * counterpart: given Sigma_t it needs no rollouts, no gains and no chain, and the N*n_obs*n_samples entries of a solve are
+ * independent.  Materialising the samples for cilqr_chance_risk is no substitute: that table has no notion of "the samples of one
+ * obstacle are ONE obstacle" (its r_t would add the samples' chances where this call averages them), and its LDS formula rejects
+ * 8 x 32 samples at N = 50.
+ * X [B][4*(N+1)], the plan.  sigma [B][N+1][16], exactly sigma_out of cilqr_chance_risk (column-major, entry (r, c) at [r + 4*c];
+ * that call with M = 0 supplies it); as in cilqr_tighten_obstacles six entries of each Sigma_t, t < N, are read: (0,0), (0,1), (0,3),
+ * (1,1), (1,3), (3,3).  Sigma_N and x_N are not visited.  The scene in the compact form of cilqr_gains_batch_sampled: nom_pose
+ * [B][n_obs][4*N], nom_dim [B][n_obs][2*N], sample_offset [B][n_obs][n_samples][3] = (dx, dy, dtheta).  Materialised obstacle
+ * m = o*n_samples + j has the pose (x + dx, y + dy, v, theta + dtheta) of nominal obstacle o — plain additions, not the solve
+ * kernels' angle-addition shortcut — and o's dimensions: its entry carries the bits of the materialised table's.  Cost weights,
+ * the path and an uncertainty map set on the handle are not read.
+ *
+ * Definitions.
+ *   entry chance   p(m, t): entry_p of cilqr_chance_risk for materialised obstacle m, word for word — cbar, g (lever arm included),
+ *                  s = sqrt(max(g' Sigma_t g, 0)), p = erfc(-cbar / (s*sqrt 2)) / 2; with s = 0: 1 if cbar > 0, else 0; the larger of
+ *                  the two circles' values, taken as erfc of the smaller argument; a NaN never wins a maximum.  Where Sigma_t and the
+ *                  materialised entry agree, p equals that call's entry_p[m*N + t] bit for bit.
+ *   pair chance    q(o, t) = (sum over j of p(o*n_samples + j, t)) / n_samples: the chance of contact with obstacle o at step t
+ *                  under the ego Gaussian and the obstacle's empirical pose distribution (equal-weight samples); the analytic
+ *                  counterpart of RRS_PAIR_SHARE.  The sum runs over a tree fixed by n_samples alone: with W the power of two with
+ *                  n_samples <= W, at least 2 and at most 64, slot i < W holds p(j = i) + p(j = i + W) + ... added in ascending j
+ *                  (one term unless n_samples > 64; +0 where i >= n_samples), and the W slots meet in an xor butterfly: at offsets
+ *                  W/2, W/4, ..., 1 in turn every slot i takes slot[i] + slot[i xor offset]; q is slot 0 divided by n_samples.
+ *   per step       r_t = min(1, sum over o of q(o, t)), Boole's bound over the obstacles, summed in ascending o; a sum that is NaN
+ *                  gives 1.
+ *   lost step      a step where X_t[0], X_t[1], X_t[3] or one of the six entries of Sigma_t is not finite: r_t = 1 (its p and q are
+ *                  still formed as defined).  A U_t or K_t that is not finite reaches this call only through Sigma_{t+1}: the M = 0
+ *                  cilqr_chance_risk call that supplies sigma marks that step ITSELF (its r_t = 1, so its total is NaN under any
+ *                  max_risk < 1).  Pass that call's total as `base` here and composing the two loses nothing.
+ *   nominal share  n(o, t) = #{j : cbar > 0 for either circle of entry (o*n_samples + j, t)} / n_samples, an integer count; with
+ *                  Sigma = 0 it equals q(o, t) exactly.
+ * risk [B][CILQR_CRS_FIELDS] (required), see the enum.  step_risk [B][N] = r_t, pair_p [B][n_obs][N] = q, entry_p
+ * [B][n_obs*n_samples][N] = p; each may be NULL.  total [B] or NULL: total[b] = base[b] when the bounded field — CRS_STEP_RISK, or
+ * CRS_SUM_RISK under CILQR_CHANCE_SAMPLED_BOUND_SUM — is <= max_risk and base[b] is finite, else NaN (a NaN base stays NaN): the
+ * convention of cilqr_chance_risk, so the call composes with it, with cilqr_chance_risk_map and with the rollout risk calls
+ * through `base` and feeds cilqr_argmin_device / cilqr_argmin_global_device.  total without base is CILQR_ERR_ARG.
+ *   Determinism: the sum over the samples runs over the tree above, the sum over the obstacles in ascending o, the sum over the
+ *   horizon over a tree fixed by N alone (lane l of 64 adds r_t for t = l, l + 64, ... ascending, the lane sums meet in the same
+ *   butterfly); maxima are lexicographic, lowest index first.  A solve's bits depend on its own inputs alone: not on B, and not on
+ *   its place in the batch.
+ * Mapping: wavefront = step, a workgroup takes four consecutive steps of one solve: ceil(N/4)*B workgroups whose lanes take the
+ * step's n_obs*n_samples entries, then one wavefront per solve for the reduction over the horizon; two launches, no atomics.
+ * Nothing is allocated per call; the
+ * per-step records between the two launches lie in device memory the handle reserved at create (5*max_batch*max_horizon doubles,
+ * not part of the host arena) — a cilqr_chance_risk_sampled on ANOTHER stream of the same handle must not run beside it; every
+ * other call may.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X, sigma, nom_pose, nom_dim, sample_offset or risk; total without
+ * base; n_obs < 1 or n_samples < 2; a max_risk that is NaN; flag bits other than CILQR_CHANCE_SAMPLED_BOUND_SUM.  Then: B, N or
+ * n_obs*n_samples beyond the cilqr_create limits; n_obs*n_samples*N or B*ceil(N/4) beyond 2^31 - 1.  The host-buffer form's arrays
+ * must fit the device arena reserved at create (CILQR_ERR_ARG otherwise; this call adds nothing to it): per solve 20*N +
+ * 6*n_obs*N + 3*n_obs*n_samples + 30 doubles, N + n_obs*N more with step_risk and pair_p, n_obs*n_samples*N more with entry_p.
+ * Without entry_p every B <= max_batch fits; with it every B <= max_batch fits on a handle of max_horizon >= 2, and every
+ * B <= max_batch/2 on a handle of max_horizon 1.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 32*n_obs*n_samples bytes whatever N is (the erfc arguments of a step, 8 bytes per
+ * entry, for the four steps of a workgroup), exceeds 64 KiB: n_obs*n_samples above 2048.  Every horizon a handle accepts runs. */
+#define CILQR_CRS_FIELDS 8
+typedef enum cilqr_chance_risk_sampled_field {
+  CILQR_CRS_STEP_RISK = 0,     /* max over t of r_t: what max_risk bounds by default */
+  CILQR_CRS_WORST_STEP = 1,    /* lowest t of that maximum */
+  CILQR_CRS_SUM_RISK = 2,      /* min(1, sum over t of r_t), over a tree fixed by N: Boole's bound over the horizon.  Bounded instead
+                                  of CRS_STEP_RISK under CILQR_CHANCE_SAMPLED_BOUND_SUM */
+  CILQR_CRS_MAX_PAIR_P = 3,    /* max over (o, t) of q;  0 when every q is NaN */
+  CILQR_CRS_MAX_PAIR = 4,      /* o*N + t of that maximum, lowest on equal values;  -1 when every q is NaN */
+  CILQR_CRS_MAX_ENTRY_P = 5,   /* max over entries of p;  0 when every p is NaN */
+  CILQR_CRS_MAX_ENTRY = 6,     /* m*N + t of that maximum, lowest on equal values;  -1 when every p is NaN */
+  CILQR_CRS_NOMINAL_SHARE = 7  /* max over (o, t) of n(o, t): equals CILQR_SCORE_COLLISION of cilqr_score_batch_sampled on the plan */
+} cilqr_chance_risk_sampled_field;
+#define CILQR_CHANCE_SAMPLED_BOUND_SUM 1u /* flags: max_risk bounds CRS_SUM_RISK */
+int cilqr_chance_risk_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* sigma, const double* nom_pose, const double* nom_dim, const double* sample_offset,
+                                     uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk,
+                                     double* pair_p, double* entry_p, double* total);
+int cilqr_chance_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* sigma,
+                              const double* nom_pose, const double* nom_dim, const double* sample_offset, uint32_t flags,
+                              double max_risk, const double* base, double* risk, double* step_risk, double* pair_p, double* entry_p,
+                              double* total);
+
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's
  * {J_min, local index, index offset} (24 bytes) through one ncclAllGather (RCCL over xGMI), then the lexicographic minimum

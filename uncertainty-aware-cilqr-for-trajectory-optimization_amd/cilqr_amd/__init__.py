@@ -48,6 +48,11 @@ CHANCE_MAP_FIELDS = 8
  CM_UNKNOWN) = range(CHANCE_MAP_FIELDS)
 CHANCE_MAP_UNKNOWN_HITS, CHANCE_MAP_BOUND_SUM = 1, 2  # flags of `chance_risk_map`
 MAX_QUAD_NODES = 1024
+# `cilqr_chance_risk_sampled_field`: the columns of an analytic risk row against sampled obstacles (`Solver.chance_risk_sampled`)
+CRS_FIELDS = 8
+(CRS_STEP_RISK, CRS_WORST_STEP, CRS_SUM_RISK, CRS_MAX_PAIR_P, CRS_MAX_PAIR, CRS_MAX_ENTRY_P, CRS_MAX_ENTRY,
+ CRS_NOMINAL_SHARE) = range(CRS_FIELDS)
+CHANCE_SAMPLED_BOUND_SUM = 1  # flags of `chance_risk_sampled`: max_risk bounds CRS_SUM_RISK instead of CRS_STEP_RISK
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -71,6 +76,7 @@ ABI_SYMBOLS = (
     "cilqr_chance_risk", "cilqr_chance_risk_device",
     "cilqr_tighten_obstacles", "cilqr_tighten_obstacles_device", "cilqr_chance_kappa",
     "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
+    "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -764,6 +770,39 @@ class Solver:
         _check(lib().cilqr_chance_risk_map_device(self._h, _vp(stream), int(B), int(N), int(Q), _vp(X), _vp(sigma), _vp(nodes),
                                                   _vp(weights), C.c_double(occ_threshold), C.c_uint32(int(flags)), C.c_double(max_risk),
                                                   _vp(base), _vp(risk), _vp(step_risk), _vp(step_occ), _vp(step_unknown), _vp(total)))
+
+    # ---- analytic chance risk against sampled obstacles in compact form ----
+    def chance_risk_sampled(self, N, X, sigma, nom_pose, nom_dim, offsets, max_risk=1.0, base=None, sum_bound=False, want_steps=True,
+                            want_pair_p=True, want_entry_p=True):
+        """`cilqr_chance_risk_sampled`: sigma (B, N+1, 16) as `chance_risk` returns it (its call without obstacles supplies it);
+        nom_pose, nom_dim, offsets as `solve_batch_sampled`.  Returns dict(risk (B, CRS_FIELDS), step_risk (B, N), pair_p
+        (B, n_obs, N), entry_p (B, n_obs*n_samples, N), each or None, total): total[b] is base[b], NaN where CRS_STEP_RISK
+        (CRS_SUM_RISK with sum_bound) exceeds max_risk or base[b] is not finite; None without `base`."""
+        offsets = _np64(offsets)
+        B, n_obs, ns = offsets.shape[0], offsets.shape[1], offsets.shape[2]
+        X, sigma = _np64(X).reshape(B, 4 * (N + 1)), _np64(sigma).reshape(B, N + 1, 16)
+        nom_pose = _np64(nom_pose).reshape(B, n_obs, 4 * N)
+        nom_dim = _np64(nom_dim).reshape(B, n_obs, 2 * N)
+        offsets = offsets.reshape(B, n_obs, ns, 3)
+        base = None if base is None else _np64(base).reshape(B)
+        risk = np.zeros((B, CRS_FIELDS))
+        step_risk = np.zeros((B, N)) if want_steps else None
+        pair_p = np.zeros((B, n_obs, N)) if want_pair_p else None
+        entry_p = np.zeros((B, n_obs * ns, N)) if want_entry_p else None
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_chance_risk_sampled(self._h, B, int(N), int(n_obs), int(ns), _p(X), _p(sigma), _p(nom_pose), _p(nom_dim),
+                                               _p(offsets), C.c_uint32(CHANCE_SAMPLED_BOUND_SUM if sum_bound else 0),
+                                               C.c_double(max_risk), _p(base), _p(risk), _p(step_risk), _p(pair_p), _p(entry_p),
+                                               _p(total)))
+        return dict(risk=risk, step_risk=step_risk, pair_p=pair_p, entry_p=entry_p, total=total)
+
+    def chance_risk_sampled_device(self, stream, B, N, n_obs, n_samples, X, sigma, nom_pose, nom_dim, offsets, risk, step_risk=0,
+                                   pair_p=0, entry_p=0, total=0, base=0, max_risk=1.0, flags=0):
+        """`cilqr_chance_risk_sampled_device`: device addresses."""
+        _check(lib().cilqr_chance_risk_sampled_device(self._h, _vp(stream), int(B), int(N), int(n_obs), int(n_samples), _vp(X),
+                                                      _vp(sigma), _vp(nom_pose), _vp(nom_dim), _vp(offsets), C.c_uint32(int(flags)),
+                                                      C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_risk), _vp(pair_p),
+                                                      _vp(entry_p), _vp(total)))
 
     # ---- chance-constraint tightening: obstacles inflated by Sigma_t for a warm-started re-solve ----
     def tighten_obstacles(self, N, X, sigma, obs_pose=None, obs_dim=None, obs_cov=None, kappa=0.0, max_inflate=2.0, want_pose=True):

@@ -277,6 +277,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   h->risk_part_stride = cilqr::RISK_PART_DOUBLES + (N + 1) / 2;
   if (err == hipSuccess) err = dmalloc(&h->d_risk_part, B * h->risk_part_stride);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_map_steps, 3 * B * N);
+  if (err == hipSuccess) err = dmalloc(&h->d_chance_sampled_steps, cilqr::CHANCE_SAMPLED_REC * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
   h->comm_ranks = 1;
@@ -308,7 +309,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1352,6 +1353,76 @@ int cilqr_chance_risk_map(cilqr_handle* h, int B, int N, int Q, const double* X,
   return cilqr::host_call(h, p, [&] {
     return cilqr_chance_risk_map_device(h, h->stream, B, N, Q, X, sigma, nodes, weights, occ_threshold, flags, max_risk, base, risk,
                                         step_risk, step_occ, step_unknown, total);
+  });
+}
+
+// ---- analytic chance risk against sampled obstacles in compact form (cilqr_chance_sampled.hip) ----------------------------------------
+namespace {
+// what needs no handle
+int chance_sampled_args_check(int n_obs, int n_samples, const double* X, const double* sigma, const double* nom_pose, const double* nom_dim,
+                              const double* sample_offset, uint32_t flags, double max_risk, const double* base, const double* risk,
+                              const double* total) {
+  if (!X || !sigma || !nom_pose || !nom_dim || !sample_offset || !risk)
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: total needs base");
+  if (n_obs < 1 || n_samples < 2) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: needs n_obs >= 1 and n_samples >= 2");
+  if (max_risk != max_risk) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: max_risk is NaN");
+  if (flags & ~CILQR_CHANCE_SAMPLED_BOUND_SUM) return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int chance_sampled_handle_check(const cilqr_handle* h, int B, int N, int n_obs, int n_samples) {
+  int rc = check_sampled(h, "cilqr_chance_risk_sampled", B, N, n_obs, n_samples);
+  if (rc) return rc;
+  // every index the kernels keep in 32 bits: an entry m*N + t, the grid
+  if ((int64_t)n_obs * n_samples * N > 0x7fffffff)
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: n_obs * n_samples * N beyond 2^31 entries");
+  const int64_t G = ((int64_t)N + cilqr::CHANCE_SAMPLED_WAVES - 1) / cilqr::CHANCE_SAMPLED_WAVES;
+  if ((int64_t)B * G > 0x7fffffff)
+    return fail(CILQR_ERR_ARG, "cilqr_chance_risk_sampled: B * ceil(N/%d) beyond 2^31 workgroups", cilqr::CHANCE_SAMPLED_WAVES);
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_chance_risk_sampled_device(cilqr_handle* h, void* stream, int B, int N, int n_obs, int n_samples, const double* X,
+                                     const double* sigma, const double* nom_pose, const double* nom_dim, const double* sample_offset,
+                                     uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk,
+                                     double* pair_p, double* entry_p, double* total) {
+  int rc = chance_sampled_args_check(n_obs, n_samples, X, sigma, nom_pose, nom_dim, sample_offset, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  rc = chance_sampled_handle_check(h, B, N, n_obs, n_samples);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  if (cilqr::chance_risk_sampled_lds_bytes(n_obs, n_samples) > cilqr::CHANCE_SAMPLED_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_chance_risk_sampled: %d x %d obstacle samples do not fit 64 KiB of LDS", n_obs, n_samples);
+  cilqr::ChanceSampledArgs a = {};
+  a.s = handle_args(h, B, N, n_obs, 0);
+  a.s.obs_pose = nom_pose; a.s.obs_dim = nom_dim;
+  a.s.samp_off = sample_offset; a.s.n_samples = n_samples;
+  a.X = X; a.sigma = sigma;
+  a.max_risk = max_risk; a.base = base; a.risk = risk; a.step_risk = step_risk; a.pair_p = pair_p; a.entry_p = entry_p; a.total = total;
+  a.steps = h->d_chance_sampled_steps;
+  a.G = (N + cilqr::CHANCE_SAMPLED_WAVES - 1) / cilqr::CHANCE_SAMPLED_WAVES;
+  a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_chance_risk_sampled(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_chance_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_samples, const double* X, const double* sigma,
+                              const double* nom_pose, const double* nom_dim, const double* sample_offset, uint32_t flags,
+                              double max_risk, const double* base, double* risk, double* step_risk, double* pair_p, double* entry_p,
+                              double* total) {
+  int rc = chance_sampled_args_check(n_obs, n_samples, X, sigma, nom_pose, nom_dim, sample_offset, flags, max_risk, base, risk, total);
+  if (rc) return rc;
+  rc = chance_sampled_handle_check(h, B, N, n_obs, n_samples);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_chance_sampled(p, B, N, n_obs, n_samples, X, sigma, nom_pose, nom_dim, sample_offset, base, risk, step_risk, pair_p,
+                             entry_p, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_chance_risk_sampled_device(h, h->stream, B, N, n_obs, n_samples, X, sigma, nom_pose, nom_dim, sample_offset, flags,
+                                            max_risk, base, risk, step_risk, pair_p, entry_p, total);
   });
 }
 

@@ -21,7 +21,7 @@
 //            standard deviation in closed form.
 // LDS (dynamic, doubles): [F: 16·N][Σ: 16·(N + 1)][r: N][p: M·N] = 8·(33·N + M·N + 16) bytes.
 // No scratch memory, no spilled register (make check).
-#include "cilqr_rollout_core.hpp"
+#include "cilqr_chance_entry.hpp"
 
 namespace cilqr {
 
@@ -39,28 +39,7 @@ __device__ __forceinline__ double lane_value(double v) {
   return __builtin_bit_cast(double, (unsigned long long)hi << 32 | lo);
 }
 
-// One ego circle against one entry: c = 1 - d'Pd by the statements of circle_constraints (cilqr_score.hip), its gradient over the
-// circle centre g_xy = -2 R(θ_o)' P d (I/Obstacle.cpp:82, 101), and under Σ = {xx, xy, xθ, yy, yθ, θθ} the argument z of the chance
-// value p = erfc(z)/2: z = -c̄/(s√2), or with s = 0 the infinity that gives p = 1 (c̄ > 0) or 0.  (lx, ly) = d(centre)/dθ =
-// (-ℓ sin θ, ℓ cos θ).
-__device__ __forceinline__ double circle_chance_arg(const ObsEntry& e, double cx, double cy, double lx, double ly, const double* S) {
-  double c, gx, gy;
-  {
-#pragma clang fp contract(off)
-    const double ex = cx - e.ox, ey = cy - e.oy;
-    const double d0 = __builtin_fma(e.co, ex, e.so * ey);
-    const double d1 = __builtin_fma(e.co, ey, -(e.so * ex));
-    c = 1 - __builtin_fma(d0 * e.ia2, d0, (d1 * e.ib2) * d1);
-    const double p0 = d0 * e.ia2, p1 = d1 * e.ib2;
-    gx = -2 * (e.co * p0 - e.so * p1);
-    gy = -2 * (e.so * p0 + e.co * p1);
-  }
-  const double gt = gx * lx + gy * ly;
-  const double q = gx * gx * S[0] + gy * gy * S[3] + gt * gt * S[5] + 2.0 * (gx * gy * S[1] + gx * gt * S[2] + gy * gt * S[4]);
-  const double s = sqrt(fmax(q, 0.0));  // (fmax: a NaN form counts as 0)
-  if (!(s > 0.0)) return c > 0.0 ? -__builtin_huge_val() : __builtin_huge_val();
-  return -c / (s * 1.41421356237309514547e+00);
-}
+// (circle_chance_arg, the entry's arithmetic: cilqr_chance_entry.hpp, shared with cilqr_chance_sampled.hip)
 
 __global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(ChanceArgs a) {
   extern __shared__ __attribute__((aligned(16))) double chance_lds[];
@@ -165,8 +144,8 @@ __global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(Chanc
       const double S6[6] = {S[0], S[4], S[12], S[5], S[13], S[15]};  // xx, xy, xθ, yy, yθ, θθ
       // erfc decreases: the larger of the two circles' chance values is the one of the smaller argument (a NaN never wins)
       const double lf = kp.ego_front, lr = -kp.ego_rear;
-      const double zf = circle_chance_arg(en, oc.fxp, oc.fyp, -lf * sn, lf * cs, S6);
-      const double zr = circle_chance_arg(en, oc.rxp, oc.ryp, -lr * sn, lr * cs, S6);
+      const double zf = circle_chance_arg<true>(en, oc.fxp, oc.fyp, -lf * sn, lf * cs, S6);
+      const double zr = circle_chance_arg<false>(en, oc.rxp, oc.ryp, -lr * sn, lr * cs, S6);
       pe[e] = fmin(zf, zr);
     }
     // (a loop of its own: erfc alone is live in it — side by side with the entry's arithmetic it needs more than 128 registers)

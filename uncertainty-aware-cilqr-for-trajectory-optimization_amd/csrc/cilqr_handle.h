@@ -83,6 +83,7 @@ struct cilqr_handle {
   double* d_risk_part;      // partial records of cilqr_rollout_risk: max_batch x risk_part_stride doubles (cilqr_risk.hip)
   size_t risk_part_stride;  // 8 + ceil(max_horizon / 2)
   double* d_chance_map_steps;  // per-step values of cilqr_chance_risk_map the caller did not ask for: 3 x max_batch x max_horizon doubles
+  double* d_chance_sampled_steps;  // step records of cilqr_chance_risk_sampled: CHANCE_SAMPLED_REC x max_batch x max_horizon doubles
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;
   size_t src_cap, dst_cap, bbox_cap;

@@ -258,6 +258,28 @@ inline void plan_chance_risk_map(HostPlan& p, size_t B, size_t N, size_t Q, cons
   p.out(total, B);
 }
 
+// cilqr_chance_risk_sampled: 11 arrays; M its n_obs, the nominal tables dense; no gain and no weight travels.  With E = M·n_samples
+// (<= max_obstacles) and M <= E/2, per solve 20·N + 6·M·N + 3·E + 30 doubles — X, sigma, the nominal tables, the offsets, base, the
+// risk row, total — plus N + M·N with step_risk and pair_p and E·N with entry_p: at most 21·N + 3.5·E·N + 3·E + 30 without entry_p
+// and 21·N + 4.5·E·N + 3·E + 30 with it, against the 22·N + 6·E·N + E + 34 per unit of max_batch that host_arena_bytes reserves
+// below at the create sizes.  Without entry_p every B <= max_batch fits; with it every B <= max_batch fits on a handle of
+// max_horizon >= 2 and every B <= max_batch/2 on one of max_horizon 1; the 11 roundings stay within its 32 x 16 bytes.
+inline void plan_chance_sampled(HostPlan& p, size_t B, size_t N, size_t M, size_t n_samples, const double*& X, const double*& sigma,
+                                const double*& nom_pose, const double*& nom_dim, const double*& samp_off, const double*& base,
+                                double*& risk, double*& step_risk, double*& pair_p, double*& entry_p, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(sigma, B * (N + 1) * 16);
+  p.in(nom_pose, B * M * N * 4);
+  p.in(nom_dim, B * M * N * 2);
+  p.in(samp_off, B * M * n_samples * 3);
+  p.in(base, B);
+  p.out(risk, B * CILQR_CRS_FIELDS);
+  p.out(step_risk, B * N);
+  p.out(pair_p, B * M * N);
+  p.out(entry_p, B * M * n_samples * N);
+  p.out(total, B);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

@@ -216,6 +216,30 @@ struct ChanceMapArgs {
 hipError_t launch_chance_risk_map(const ChanceMapArgs& a, hipStream_t stream);
 size_t chance_risk_map_lds_bytes(int Q);
 
+// Analytic chance risk against sampled obstacles in compact form (cilqr_chance_sampled.hip; cilqr_chance_risk_sampled*): the
+// mapping of the map kernel above — wavefront = step, a workgroup takes CHANCE_SAMPLED_WAVES consecutive steps of one solve, solve b
+// has G = ceil(N / CHANCE_SAMPLED_WAVES) workgroups, lanes take the step's n_obs·n_samples entries; a finish kernel, one wavefront
+// per solve, reduces over the steps.  `s` carries the dense nominal tables, M = n_obs, samp_off, n_samples > 0, B, N and kp.
+// `steps`: the handle's, one record of CHANCE_SAMPLED_REC doubles per (solve, step).
+constexpr int CHANCE_SAMPLED_WAVES = 4;
+constexpr int CHANCE_SAMPLED_THREADS = 64 * CHANCE_SAMPLED_WAVES;
+constexpr int CHANCE_SAMPLED_REC = 5;
+struct ChanceSampledArgs {
+  SolveArgs s;
+  const double *X, *sigma;               // [B][4(N + 1)], [B][N + 1][16]
+  double max_risk;
+  const double* base;                    // [B] or null (then total is null)
+  double* risk;                          // [B][CILQR_CRS_FIELDS]
+  double *step_risk, *pair_p, *entry_p;  // [B][N], [B][n_obs][N], [B][n_obs·n_samples][N]; each may be null
+  double* total;                         // [B] or null
+  double* steps;
+  int32_t G;
+  uint32_t flags;                        // CILQR_CHANCE_SAMPLED_*
+};
+hipError_t launch_chance_risk_sampled(const ChanceSampledArgs& a, hipStream_t stream);
+size_t chance_risk_sampled_lds_bytes(int n_obs, int n_samples);  // 8 bytes per entry of a step and wavefront, whatever N is
+constexpr size_t CHANCE_SAMPLED_LDS_MAX = 64 * 1024;
+
 // Closed-loop covariance chain and Gaussian chance values per solve (cilqr_chance.hip; cilqr_chance_risk*): one workgroup per
 // solve.  `s` carries what the launch shares with a solve — the strided obstacle fields, B, N, M, kp — and comes first, so that
 // phase_args / phase_params of cilqr_device.hpp read it.

@@ -34,6 +34,7 @@ iLQR::iLQR(const Parameters& params, int device, int max_obstacles, int max_cand
 iLQR::~iLQR() {
   if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);
   if (noise_dev_) (void)hipFree(noise_dev_);
+  if (scov_dev_) (void)hipFree(scov_dev_);
   if (noise_stream_) (void)hipStreamDestroy((hipStream_t)noise_stream_);
   cilqr_destroy(h_);
 }
@@ -188,6 +189,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
+  if (scov_check_) return run_candidates_sample_covariance(B, ego_states);
   if (!noise_.empty() || cov_check_ || tighten_) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
@@ -259,7 +261,11 @@ const char* const kCovarianceWithNoise =
 const char* const kTighteningWithSamples =
     "set_chance_tightening has no form for sampled obstacles (set_obstacle_samples): the sampled solve takes no inflated table";
 const char* const kCovarianceWithSamples =
-    "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples) yet: use set_pose_noise_check_fused";
+    "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
+const char* const kSampleCovarianceWithNoise =
+    "set_sample_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
+const char* const kSampleCovarianceWithoutSamples =
+    "set_sample_covariance_check has effect with obstacle samples (set_obstacle_samples) only: without samples use set_pose_covariance_check";
 }  // namespace
 
 void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_samples) {
@@ -309,6 +315,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check: offsets must hold 4 doubles per sample");
   if (n_samples_ && !offsets.empty()) throw std::logic_error(kStoredRowsWithSamples);
   if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
+  if (scov_check_ && !offsets.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
@@ -321,6 +328,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check_fused: offsets must hold 4 doubles per sample");
   if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
+  if (scov_check_ && !offsets.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
@@ -355,6 +363,19 @@ void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, d
   last_chance_risk.clear();
   last_step_risk.clear();
   if (cov_check_ || tighten_) reserve_noise_buffers();
+}
+
+void iLQR::set_sample_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
+  if (Sigma0 && !noise_.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
+  if (max_risk != max_risk) throw std::runtime_error("set_sample_covariance_check: max_risk is NaN");
+  scov_check_ = Sigma0 != nullptr;
+  scov_has_W_ = scov_check_ && W != nullptr;
+  if (scov_check_) memcpy(scov_sigma0_, Sigma0, sizeof(scov_sigma0_));
+  if (scov_has_W_) memcpy(scov_W_, W, sizeof(scov_W_));
+  scov_max_risk_ = max_risk;
+  scov_lamb_ = lamb;
+  scov_sum_ = sum_bound;
+  last_chance_risk_sampled.clear();
 }
 
 void iLQR::set_map_covariance_check(double occ_threshold, double max_risk, int nx, int ny, int nth, bool sum_bound, bool unknown_hits) {
@@ -629,6 +650,130 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   double J = 0.0;
   down(Xb.a.data(), L.X + (size_t)best * 4 * (N + 1), Xb.a.size() * sizeof(double));
   std::vector<double> Ub((size_t)2 * N);
+  down(Ub.data(), L.U + (size_t)best * 2 * N, Ub.size() * sizeof(double));
+  down(&J, L.J + (size_t)best, sizeof(double));
+  hip_check(hipMemcpyAsync(&iters, (int32_t*)(d + L.iters) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  hip_check(hipMemcpyAsync(&status, (int32_t*)(d + L.status) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  X_result = Xb;
+  control_seq_.a = Ub;
+  U_result = control_seq_;
+  ref_traj_result = Matrix(2, n_ref[best]);
+  for (int i = 0; i < 2 * n_ref[best]; ++i) ref_traj_result.a[i] = ref[(size_t)best * 2 * W + i];
+  last_iterations = iters;
+  last_exit = status;
+  last_cost = J;
+  return best;
+}
+
+// run_candidates under set_sample_covariance_check: the analytic chain in the compact sampled form, in a device block of its own
+// (grown when a call needs more), on the checks' stream.
+int iLQR::run_candidates_sample_covariance(int B, const std::vector<double>& ego_states) {
+  const int N = params.horizon;
+  if (!n_samples_) throw std::logic_error(kSampleCovarianceWithoutSamples);
+  if (!noise_.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
+  std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
+  const int W = params.num_of_local_wpts;
+  std::vector<double> ref((size_t)B * 2 * W);
+  std::vector<int32_t> n_ref(B);
+  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), poly.data(), fl.data(),
+                               ref.data(), n_ref.data()), "cilqr_local_plan_batch");
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
+  std::vector<double> nom_pose, nom_dim, samp_off;  // (alive until the stream has been waited for)
+  const int n_obs = pack_sampled(B, nom_pose, nom_dim, samp_off), ns = n_samples_;
+  const bool cmap_checked = cmap_check_ && map_set_;
+  const size_t Q = cmap_checked ? cmap_weights_.size() : 0;
+  struct { size_t x0, U, poly, fl, pose, dim, soff, X, J, iters, status, k, K, ok, score, base, s0, W, crisk, ctotal, csig, srisk, stotal, qn, qw, cmrisk, cmtotal, pair, end; } L;
+  size_t o = 0;
+  const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
+  L.x0 = take((size_t)B * 4); L.U = take(U.size()); L.poly = take(poly.size()); L.fl = take(fl.size());
+  L.pose = take(nom_pose.size()); L.dim = take(nom_dim.size()); L.soff = take(samp_off.size());
+  L.X = take((size_t)B * 4 * (N + 1)); L.J = take(B); L.iters = take(B); L.status = take(B);
+  L.k = take((size_t)B * 2 * N); L.K = take((size_t)B * 8 * N); L.ok = take(B);
+  L.score = take((size_t)B * CILQR_SCORE_FIELDS); L.base = take(B);
+  L.s0 = take(16); L.W = take(16); L.crisk = take((size_t)B * CILQR_CHANCE_FIELDS); L.ctotal = take(B);
+  L.csig = take((size_t)B * (N + 1) * 16); L.srisk = take((size_t)B * CILQR_CRS_FIELDS); L.stotal = take(B);
+  L.qn = take(Q * 3); L.qw = take(Q); L.cmrisk = take(cmap_checked ? (size_t)B * CILQR_CHANCE_MAP_FIELDS : 0); L.cmtotal = take(cmap_checked ? B : 0);
+  L.pair = take(2);
+  L.end = o;
+  hip_check(hipSetDevice(device_), "hipSetDevice");
+  if (!noise_stream_) {
+    hipStream_t created;
+    hip_check(hipStreamCreateWithFlags(&created, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+    noise_stream_ = created;
+  }
+  hipStream_t st = (hipStream_t)noise_stream_;
+  if (L.end > scov_cap_) {
+    hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (scov_dev_) hip_check(hipFree(scov_dev_), "hipFree");
+    scov_dev_ = nullptr; scov_cap_ = 0;
+    hip_check(hipMalloc(&scov_dev_, L.end * sizeof(double)), "hipMalloc");
+    scov_cap_ = L.end;
+  }
+  double* d = (double*)scov_dev_;
+  const auto up = [&](size_t at, const void* src, size_t doubles) {
+    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  };
+  const auto down = [&](void* dst, size_t at, size_t bytes) {
+    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  };
+  up(L.x0, ego_states.data(), (size_t)B * 4);
+  up(L.U, U.data(), U.size());
+  up(L.poly, poly.data(), poly.size());
+  up(L.fl, fl.data(), fl.size());
+  up(L.pose, nom_pose.data(), nom_pose.size());
+  up(L.dim, nom_dim.data(), nom_dim.size());
+  up(L.soff, samp_off.data(), samp_off.size());
+  up(L.s0, scov_sigma0_, 16);
+  if (scov_has_W_) up(L.W, scov_W_, 16);
+  if (cmap_checked) { up(L.qn, cmap_nodes_.data(), cmap_nodes_.size()); up(L.qw, cmap_weights_.data(), cmap_weights_.size()); }
+  const double w = sample_weight();
+  int rc = cilqr_solve_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim, d + L.soff, w,
+                                            d + L.X, d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+  if (!rc) rc = cilqr_gains_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                 d + L.soff, w, scov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+  if (!rc) rc = cilqr_score_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                 d + L.soff, w, 1.0, d + L.score, d + L.base);
+  // the chain alone (M = 0): every Sigma_t, and the steps whose U_t or K_t is not finite marked in its total
+  if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, 0, d + L.X, d + L.U, d + L.K, d + L.s0, 0, scov_has_W_ ? d + L.W : nullptr, nullptr,
+                                         scov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, scov_max_risk_, d + L.base, d + L.crisk, nullptr, nullptr,
+                                         d + L.csig, d + L.ctotal);
+  if (!rc) rc = cilqr_chance_risk_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.csig, d + L.pose, d + L.dim, d + L.soff,
+                                                 scov_sum_ ? CILQR_CHANCE_SAMPLED_BOUND_SUM : 0u, scov_max_risk_, d + L.ctotal, d + L.srisk,
+                                                 nullptr, nullptr, nullptr, d + L.stotal);
+  size_t total_at = L.stotal;
+  if (cmap_checked && !rc) {
+    rc = cilqr_chance_risk_map_device(h_, st, B, N, (int)Q, d + L.X, d + L.csig, d + L.qn, d + L.qw, cmap_threshold_,
+                                      (cmap_sum_ ? CILQR_CHANCE_MAP_BOUND_SUM : 0u) | (cmap_unknown_hits_ ? CILQR_CHANCE_MAP_UNKNOWN_HITS : 0u),
+                                      cmap_max_risk_, d + total_at, d + L.cmrisk, nullptr, nullptr, nullptr, d + L.cmtotal);
+    total_at = L.cmtotal;
+  }
+  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + total_at, d + L.pair);
+  if (rc) {
+    const std::string msg = cilqr_last_error();
+    (void)hipStreamSynchronize(st);
+    throw std::runtime_error("run_candidates (sample covariance check): " + msg);
+  }
+  double pair[2] = {0.0, -1.0};
+  down(pair, L.pair, sizeof(pair));
+  last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
+  down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
+  last_chance_risk_sampled.assign((size_t)B * CILQR_CRS_FIELDS, 0.0);
+  down(last_chance_risk_sampled.data(), L.srisk, last_chance_risk_sampled.size() * sizeof(double));
+  last_chance_map_risk.clear();
+  if (cmap_checked) {
+    last_chance_map_risk.assign((size_t)B * CILQR_CHANCE_MAP_FIELDS, 0.0);
+    down(last_chance_map_risk.data(), L.cmrisk, last_chance_map_risk.size() * sizeof(double));
+  }
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  const int best = (int)pair[1];
+  if (best < 0) return -1;  // every candidate rejected: results and warm start stay
+  Matrix Xb(4, N + 1);
+  std::vector<double> Ub((size_t)2 * N);
+  int32_t iters = 0, status = 0;
+  double J = 0.0;
+  down(Xb.a.data(), L.X + (size_t)best * 4 * (N + 1), Xb.a.size() * sizeof(double));
   down(Ub.data(), L.U + (size_t)best * 2 * N, Ub.size() * sizeof(double));
   down(&J, L.J + (size_t)best, sizeof(double));
   hip_check(hipMemcpyAsync(&iters, (int32_t*)(d + L.iters) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");

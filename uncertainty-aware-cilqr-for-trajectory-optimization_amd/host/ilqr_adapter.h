@@ -149,8 +149,9 @@ class iLQR {
   // plan whose own footprint enters cells above occ_threshold is rejected whenever max_risk of set_map_risk_check is below 1.
   // set_map_covariance_check composes after it the same way and is the check that uses the covariance against the map; with both
   // map checks set the chain is chance -> map covariance -> map rollout, each taking the total before it as its base.
-  // Together with set_pose_noise_check(_fused) offsets, or with set_obstacle_samples (the chance value has no sampled form yet),
-  // the setters throw std::logic_error naming the conflict.  Sigma0 == nullptr switches the check off (the default).
+  // Together with set_pose_noise_check(_fused) offsets, or with set_obstacle_samples (the sampled scene form has a setter of its own:
+  // set_sample_covariance_check), the setters throw std::logic_error naming the conflict.  Sigma0 == nullptr switches the check off
+  // (the default).
   void set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb = 1.0, bool sum_bound = false);
   // Map covariance check: the analytic counterpart of set_map_risk_check.  It has effect under set_pose_covariance_check while an
   // uncertainty map is set: run_candidates then enqueues, on the check's stream, solve -> (score) -> cilqr_gains_batch_device ->
@@ -199,6 +200,20 @@ class iLQR {
   // set_pose_noise_check (and a run_candidates under it) throws std::logic_error naming set_pose_noise_check_fused.  An empty
   // `offsets` switches the samples off (the default): everything behaves as without this call.
   void set_obstacle_samples(const std::vector<double>& offsets, int n_samples);
+  // Sample covariance check: set_pose_covariance_check for the sampled scene form.  Sigma0, W, lamb and sum_bound as there.  It has
+  // effect while set_obstacle_samples is in force; without samples set run_candidates throws std::logic_error naming
+  // set_pose_covariance_check.  Together with set_pose_noise_check(_fused) offsets, whichever comes second throws std::logic_error:
+  // the pose noise is given either as a covariance or as draws.  run_candidates then enqueues, on the checks' stream:
+  // cilqr_solve_batch_sampled_device -> cilqr_gains_batch_sampled_device(lamb) -> cilqr_score_batch_sampled_device (nominal totals,
+  // max_collision 1) -> cilqr_chance_risk_device (M = 0: every Sigma_t in sigma_out; base = those totals, so a step whose U_t or K_t
+  // is not finite is marked in its total) -> cilqr_chance_risk_sampled_device (base = that total) -> cilqr_chance_risk_map_device
+  // (base = that total; only while set_map_covariance_check is on and an uncertainty map is set) -> cilqr_argmin_device.  A
+  // candidate is rejected when CRS_STEP_RISK — with sum_bound CRS_SUM_RISK — exceeds max_risk: the largest per-step (the summed)
+  // chance of contact, under the closed-loop covariance along its plan, with the obstacles' empirical pose distributions.
+  // last_chance_risk_sampled holds CILQR_CRS_FIELDS per candidate (cilqr_chance_risk_sampled_field), last_scores the nominal score
+  // rows, last_chance_map_risk the map call's rows when it ran.  Rejection and the -1 return as under set_pose_noise_check.
+  // Sigma0 == nullptr switches the check off (the default).
+  void set_sample_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb = 1.0, bool sum_bound = false);
 
   Parameters params;
   Matrix X_result;         // 4 × (horizon + 1)
@@ -219,6 +234,8 @@ class iLQR {
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
   // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
   std::vector<double> last_chance_map_risk, last_map_step_risk;  // CILQR_CHANCE_MAP_FIELDS per candidate; horizon per candidate
+  // run_candidates under set_sample_covariance_check; empty otherwise
+  std::vector<double> last_chance_risk_sampled;  // CILQR_CRS_FIELDS per candidate
   // run_step / run_candidates under set_chance_tightening with obstacles set; empty otherwise
   std::vector<double> last_tighten, last_tighten_risk_before;  // CILQR_TIGHTEN_FIELDS per solve; CR_STEP_RISK per solve
 
@@ -265,6 +282,12 @@ class iLQR {
   // pose-covariance check (set_pose_covariance_check): Sigma0 and W travel with every call (32 doubles)
   bool cov_check_ = false, cov_has_W_ = false, cov_sum_ = false;
   double cov_sigma0_[16] = {}, cov_W_[16] = {}, cov_max_risk_ = 1.0, cov_lamb_ = 1.0;
+  // sample covariance check (set_sample_covariance_check): a device block of its own, grown on demand (scov_cap_ doubles)
+  bool scov_check_ = false, scov_has_W_ = false, scov_sum_ = false;
+  double scov_sigma0_[16] = {}, scov_W_[16] = {}, scov_max_risk_ = 1.0, scov_lamb_ = 1.0;
+  void* scov_dev_ = nullptr;
+  size_t scov_cap_ = 0;
+  int run_candidates_sample_covariance(int B, const std::vector<double>& ego_states);
   // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and cov_check_; the nodes as built
   bool cmap_check_ = false, cmap_sum_ = false, cmap_unknown_hits_ = false;
   double cmap_threshold_ = 0.0, cmap_max_risk_ = 1.0;
