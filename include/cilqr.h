@@ -45,6 +45,7 @@
  *                                                                and Gaussian chance values per obstacle and step, no samples
  *                                                                cilqr_tighten_obstacles(_device): obstacles inflated by that
  *                                                                covariance for a warm-started re-solve; cilqr_chance_kappa
+ *                                                                cilqr_tighten_map(_device): the costmap dilated by it instead
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -767,6 +768,86 @@ int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* 
  * iteration on (the logarithm of) erfc from the fixed start sqrt(-2 log eps) with a fixed number of steps: the same bits for the
  * same eps.  NaN outside (0, 0.5]; exactly 0 at 0.5. */
 double cilqr_chance_kappa(double eps);
+
+/* --- map tightening: the costmap dilated by Sigma_t along the plan for a re-solve (new) -------------------------------------------
+ * cilqr_tighten_obstacles knows ellipses only; in the reference's live node that channel is off and the blurred costmap of
+ * cilqr_set_uncertainty_map is the planner's only obstacle information, so there every check could only reject.
+ * cilqr_tighten_map(_device) is the map counterpart: from the Sigma_t that cilqr_chance_risk left in sigma_out (M = 0 supplies it) it
+ * writes, per solve, a tightened copy of the layer set on the handle that a warm-started re-solve runs against.  The reference's own
+ * uncertainty blur (M/src/arbitrary_transformation.cu) is the same idea with three constant sigmas — a per-cell covariance whose
+ * heading lever grows with the cell's offset, then a confidence ellipse; here the covariance comes from the closed loop along the
+ * plan.  One round:  solve -> cilqr_gains_batch -> cilqr_chance_risk (sigma_out) -> cilqr_tighten_map -> cilqr_set_uncertainty_map_device
+ * (layer_out, layer_stride = rows*cols, the same geometry, poses and probes) -> solve, warm-started from the plan's U.  No solve
+ * kernel changes: the solve already reads a layer and a pose per solve.
+ * X [B][4*(N+1)], the plan.  sigma [B][N+1][16], exactly sigma_out of cilqr_chance_risk (column-major, entry (r, c) at [r + 4*c]);
+ * the six entries cilqr_chance_risk_map reads are read, for steps t < N: (0,0), (0,1), (1,1), (0,3), (1,3), (3,3).  Map, geometry,
+ * layer_stride and poses are those CURRENTLY SET on the handle, indexed by the solve as every map call indexes them: solve b reads
+ * layer + b*layer_stride and poses[b], or the shared pose.  layer_out [B][rows*cols] float32, dense, column-major like the input;
+ * it must not overlap the set layer (CILQR_ERR_ARG where the two ranges meet).
+ *
+ * Definition for solve b and cell (i, j).  Everything is in the map frame; every formula is evaluated in double as C evaluates it
+ * as written, left to right, with no fused multiply-add.
+ *   frame      c, s are the cosine and sine of the solve's map pose heading, obtained as the other map calls obtain them (the shared
+ *              pose's on the host, a per-solve pose's on the device).  With dx = X_t[0] - pose.x, dy = X_t[1] - pose.y:
+ *                p_t = R'(X_t.xy - pose.xy) = (c*dx + s*dy,  c*dy - s*dx),   t = 0 ... N-1.
+ *              The position block P of S = Sigma_t, the cross terms (S03, S13) and S33 are rotated the same way, P_m = R'PR and
+ *              c_theta = R'(S03, S13):  with cc = c*c, ss = s*s, cs = c*s
+ *                Pxx = cc*S00 + 2*cs*S01 + ss*S11,    Pxy = cs*(S11 - S00) + (cc - ss)*S01,    Pyy = ss*S00 - 2*cs*S01 + cc*S11,
+ *                cx = c*S03 + s*S13,                  cy = c*S13 - s*S03,                      Stt = S33.
+ *              A step whose X_t[0], X_t[1], X_t[3] or one of whose six entries is not finite is LOST and takes no part.
+ *   cell centre    m = (x_first - i*res, y_first - j*res), with x_first = pos_x + (len_x/2 - res/2) and y_first likewise, as in the
+ *              bilinear lookup; res is the geometry's, as it was set.
+ *   nearest step   t* is the live step with the smallest |m - p_t|^2 = ex*ex + ey*ey of e = m - p_t, strict <, lowest t on equal
+ *              values (a distance that is not finite — a plan 1e150 m away — is never the smallest).  If there is no live step,
+ *              out = in for every cell of the solve, no cell is CAPPED and TM_MAX_REACH is 0.
+ *   covariance at the cell   d = m - p_t*, scaled down to length r_fp = sqrt(safe_length^2 + safe_width^2)/2 where longer: with
+ *              len = sqrt(dx*dx + dy*dy) > r_fp, f = r_fp/len and d = (dx*f, dy*f).  j = (-dy, dx), the footprint point's derivative
+ *              over heading.
+ *                Cxx = Pxx + 2 jx cx + jx^2 Stt,    Cyy = Pyy + 2 jy cy + jy^2 Stt,    Cxy = Pxy + jx cy + jy cx + jx jy Stt
+ *              — the formulas of cilqr_tighten_obstacles (2*jx*cx, jx*jx*Stt, jx*jy*Stt, each product left to right), with the lever
+ *              taken at the cell.
+ *   reach      hx = kappa*sqrt(max(Cxx, 0)), hy = kappa*sqrt(max(Cyy, 0)) (max(C, 0): 0 where C < 0, else C).  Each is replaced by
+ *              max_inflate when it is not finite or exceeds max_inflate: such a cell counts as CAPPED.  ni = floor(hx/res),
+ *              nj = floor(hy/res).
+ *   dilation   out = the largest finite value among the cell itself and its neighbours (i+a, j+b) that meet all of: |a| <= ni and
+ *              |b| <= nj; inside the layer; and, with e = (-a*res, -b*res), det = Cxx*Cyy - Cxy*Cxy,
+ *                Cyy*(ex*ex) - 2*Cxy*ex*ey + Cxx*(ey*ey) <= (kappa*kappa)*det.
+ *              When det is not above 0 the box alone decides.  A neighbour replaces the running value only where it is strictly
+ *              larger (b ascending, then a ascending; this matters between +0 and -0 only).  A cell whose own value is not finite is
+ *              copied through: unknown stays unknown.  Every output value is therefore a bit copy of an input value.
+ * What this is: the worst occupancy within kappa standard deviations of where the footprint point over that cell may really be —
+ * the map form of "grow the ellipse by kappa sigma".  It is axis-capped, first order, and soft, like its sibling: it guarantees
+ * nothing.  Judge the final plan against the ORIGINAL map, always.  A cell takes the covariance of the step that passes closest;
+ * where a plan crosses itself, or returns to where it was, the LOWEST such step wins and the later, larger Sigma_t is not seen there.
+ * tighten [B][CILQR_TIGHTEN_MAP_FIELDS] (required), see the enum.  No floating sums: maxima are lexicographic, counts are integers.
+ *   A solve's bits do not depend on B, on its place in the batch, or on whether the layer is shared or one equal copy per solve.
+ * Mapping: lane = cell; a solve has G = min(ceil(rows*cols/256), 64) workgroups of 256 lanes that stride over its cells; the
+ * per-step records (p_t and the six map-frame entries, 8 doubles per step) are formed once per workgroup in LDS, which the search
+ * over t reads at one address per wavefront; the gather reads the set layer.  Each workgroup leaves one record of 5 doubles, merged
+ * by a second launch of one wavefront per solve; two launches, no atomics, no arrival order in any result.  Nothing is allocated
+ * per call: the records lie in device memory of their own that the handle reserved at create (320*max_batch doubles, not part of the
+ * host arena) — a cilqr_tighten_map on ANOTHER stream of the same handle must not run beside it; every other call may.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X, sigma, layer_out or tighten; a kappa or max_inflate that is
+ * negative or not finite.  Then: B or N beyond the cilqr_create limits; no uncertainty map set on the handle (the message says so);
+ * layer_out overlapping the set layer; a map of 2^31 cells or more, or B*G beyond 2^31 - 1.  The host-buffer form stages layer_out through the device arena reserved at create and adds
+ * nothing to it: its arrays take B*(20*N + 26 + rows*cols/2) doubles against the max_batch*(22*max_horizon + 34) doubles the arena
+ * holds at least, CILQR_ERR_ARG where they do not fit (the node's 150 x 100 map at N = 50: B <= max_batch/8).  The device form is
+ * the production path.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(8*N + 20) bytes, = 64*N + 160, exceeds 64 KiB: N above 1021, which CILQR_MAX_HORIZON = 384
+ * keeps out of reach — every horizon a handle accepts runs. */
+#define CILQR_TIGHTEN_MAP_FIELDS 6
+typedef enum cilqr_tighten_map_field {
+  CILQR_TM_RAISED = 0,    /* cells with out > in (an integer count) */
+  CILQR_TM_MAX_RAISE = 1, /* largest out - in, formed in double;  0 when none */
+  CILQR_TM_MAX_CELL = 2,  /* i + rows*j of that maximum, lowest index on equal values;  -1 when none */
+  CILQR_TM_MAX_REACH = 3, /* largest of hx, hy after the cap, in metres */
+  CILQR_TM_CAPPED = 4,    /* count of capped cells */
+  CILQR_TM_LOST = 5       /* number of lost steps */
+} cilqr_tighten_map_field;
+int cilqr_tighten_map_device(cilqr_handle* h, void* stream, int B, int N, const double* X, const double* sigma, double kappa,
+                             double max_inflate, float* layer_out, double* tighten);
+int cilqr_tighten_map(cilqr_handle* h, int B, int N, const double* X, const double* sigma, double kappa, double max_inflate,
+                      float* layer_out, double* tighten);
 
 /* --- analytic map risk: the pose covariance against the uncertainty map by quadrature (new) ---------------------------------------
  * cilqr_chance_risk stops at the ellipses; in the reference's live node that channel is off and the blurred costmap is the only

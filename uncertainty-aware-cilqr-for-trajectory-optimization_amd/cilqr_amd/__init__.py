@@ -41,6 +41,9 @@ CHANCE_BOUND_SUM = 1  # flags of `chance_risk`: max_risk bounds CR_SUM_RISK inst
 # `cilqr_tighten_field`: the columns of a tightening row (`Solver.tighten_obstacles`)
 TIGHTEN_FIELDS = 4
 TG_MAX_DA, TG_MAX_DB, TG_MAX_ENTRY, TG_CAPPED = range(TIGHTEN_FIELDS)
+# `cilqr_tighten_map_field`: the columns of a map tightening row (`Solver.tighten_map`)
+TIGHTEN_MAP_FIELDS = 6
+TM_RAISED, TM_MAX_RAISE, TM_MAX_CELL, TM_MAX_REACH, TM_CAPPED, TM_LOST = range(TIGHTEN_MAP_FIELDS)
 
 # `cilqr_chance_map_field`: the columns of an analytic map risk row (`Solver.chance_risk_map`)
 CHANCE_MAP_FIELDS = 8
@@ -75,6 +78,7 @@ ABI_SYMBOLS = (
     "cilqr_rollout_risk_map", "cilqr_rollout_risk_map_device",
     "cilqr_chance_risk", "cilqr_chance_risk_device",
     "cilqr_tighten_obstacles", "cilqr_tighten_obstacles_device", "cilqr_chance_kappa",
+    "cilqr_tighten_map", "cilqr_tighten_map_device",
     "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
     "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
 )
@@ -831,6 +835,28 @@ class Solver:
         _check(lib().cilqr_tighten_obstacles_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(sigma),
                                                     C.byref(obs) if M else None, _vp(obs_cov), C.c_double(kappa), C.c_double(max_inflate),
                                                     _vp(pose_out), _vp(dim_out), _vp(tighten)))
+
+    # ---- map tightening: the set uncertainty map dilated by Sigma_t for a warm-started re-solve ----
+    def tighten_map(self, N, X, sigma, shape, kappa=0.0, max_inflate=1.0):
+        """`cilqr_tighten_map`: sigma (B, N+1, 16) as `chance_risk` returns it; shape = (rows, cols) of the map set on the handle by
+        `set_uncertainty_map(_device)`.  Returns dict(layer (B, rows, cols) float32, each layer Fortran-ordered like the input,
+        tighten (B, TIGHTEN_MAP_FIELDS)).  The layers travel through the device arena: large batches take the device form."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        sigma = _np64(sigma).reshape(B, N + 1, 16)
+        rows, cols = int(shape[0]), int(shape[1])
+        flat = np.zeros((B, rows * cols), dtype=np.float32)
+        tighten = np.zeros((B, TIGHTEN_MAP_FIELDS))
+        _check(lib().cilqr_tighten_map(self._h, B, int(N), _p(X), _p(sigma), C.c_double(kappa), C.c_double(max_inflate), _p(flat, _fp),
+                                       _p(tighten)))
+        return dict(layer=flat.reshape(B, cols, rows).transpose(0, 2, 1), tighten=tighten)
+
+    def tighten_map_device(self, stream, B, N, X, sigma, layer_out, tighten, kappa=0.0, max_inflate=1.0):
+        """`cilqr_tighten_map_device`: device addresses; layer_out (B, rows*cols) float32 feeds `set_uncertainty_map_device` with
+        layer_stride = rows*cols."""
+        _check(lib().cilqr_tighten_map_device(self._h, _vp(stream), int(B), int(N), _vp(X), _vp(sigma), C.c_double(kappa),
+                                              C.c_double(max_inflate), _vp(layer_out), _vp(tighten)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -278,6 +278,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   if (err == hipSuccess) err = dmalloc(&h->d_risk_part, B * h->risk_part_stride);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_map_steps, 3 * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_sampled_steps, cilqr::CHANCE_SAMPLED_REC * B * N);
+  if (err == hipSuccess) err = dmalloc(&h->d_tighten_map_part, (size_t)cilqr::TIGHTEN_MAP_REC * cilqr::TIGHTEN_MAP_MAX_G * B);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
   h->comm_ranks = 1;
@@ -309,7 +310,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_tighten_map_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -361,6 +362,7 @@ int cilqr_set_uncertainty_map_device(cilqr_handle* h, const cilqr_uncertainty_ma
   int rc = fill_unc(h, map, u);
   if (rc) return rc;
   h->unc = u;
+  h->unc_res = map->geom.res;
   return CILQR_OK;
 }
 
@@ -385,12 +387,14 @@ int cilqr_set_uncertainty_map(cilqr_handle* h, const cilqr_uncertainty_map* map)
   HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's buffer is free again, and device-pointer solves on other streams see the layer
   u.layer = h->d_unc_layer;
   h->unc = u;
+  h->unc_res = map->geom.res;
   return CILQR_OK;
 }
 
 int cilqr_clear_uncertainty_map(cilqr_handle* h) {
   if (!h) return fail(CILQR_ERR_ARG, "null handle");
   memset(&h->unc, 0, sizeof(h->unc));
+  h->unc_res = 0.0;
   return CILQR_OK;
 }
 
@@ -1215,6 +1219,68 @@ int cilqr_tighten_obstacles(cilqr_handle* h, int B, int N, int M, const double* 
   return cilqr::host_call(h, p, [&] {
     return tighten_launch(h, h->stream, B, N, M, X, sigma, M > 0 ? &o : nullptr, obs_cov, kappa, max_inflate, pose_out, dim_out, tighten);
   });
+}
+
+// ---- map tightening (cilqr_tighten_map.hip) --------------------------------------------------------------------------------------------
+namespace {
+// what needs no handle
+int tighten_map_args_check(const double* X, const double* sigma, double kappa, double max_inflate, const float* layer_out,
+                           const double* tighten) {
+  if (!X || !sigma || !layer_out || !tighten) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: null required pointer");
+  if (!(kappa >= 0.0 && kappa <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: kappa is negative or not finite");
+  if (!(max_inflate >= 0.0 && max_inflate <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: max_inflate is negative or not finite");
+  return CILQR_OK;
+}
+int tighten_map_handle_check(const cilqr_handle* h, int B, int N) {
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  if (!h->unc.layer) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: no uncertainty map is set on the handle");
+  if ((int64_t)h->unc.rows * h->unc.cols > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: the map has 2^31 cells or more");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_tighten_map_device(cilqr_handle* h, void* stream, int B, int N, const double* X, const double* sigma, double kappa,
+                             double max_inflate, float* layer_out, double* tighten) {
+  int rc = tighten_map_args_check(X, sigma, kappa, max_inflate, layer_out, tighten);
+  if (rc) return rc;
+  rc = tighten_map_handle_check(h, B, N);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  const size_t cells = (size_t)h->unc.rows * h->unc.cols;
+  {  // the dilation reads neighbours: the output must not be the layer it reads
+    const float* in0 = h->unc.layer;
+    const float* in1 = in0 + (size_t)(B - 1) * (size_t)h->unc.stride + cells;
+    if (layer_out < in1 && in0 < layer_out + (size_t)B * cells)
+      return fail(CILQR_ERR_ARG, "cilqr_tighten_map: layer_out overlaps the layer set on the handle");
+  }
+  if (cilqr::tighten_map_lds_bytes(N) > cilqr::TIGHTEN_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_tighten_map: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::TightenMapArgs a = {};
+  a.s = handle_args(h, B, N, 0, 0);
+  a.X = X; a.sigma = sigma; a.kappa = kappa; a.max_inflate = max_inflate;
+  a.res = h->unc_res;
+  a.r_fp = 0.5 * sqrt(h->params.safe_length * h->params.safe_length + h->params.safe_width * h->params.safe_width);
+  a.layer_out = layer_out; a.tighten = tighten;
+  a.partials = h->d_tighten_map_part;  // (reserved at create: TIGHTEN_MAP_MAX_G records per solve of max_batch)
+  const size_t tiles = (cells + cilqr::TIGHTEN_MAP_THREADS - 1) / cilqr::TIGHTEN_MAP_THREADS;
+  a.G = (int)(tiles < (size_t)cilqr::TIGHTEN_MAP_MAX_G ? tiles : (size_t)cilqr::TIGHTEN_MAP_MAX_G);
+  if ((int64_t)B * a.G > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_tighten_map: B * %d workgroups per solve beyond 2^31 - 1", a.G);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_tighten_map(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_tighten_map(cilqr_handle* h, int B, int N, const double* X, const double* sigma, double kappa, double max_inflate,
+                      float* layer_out, double* tighten) {
+  int rc = tighten_map_args_check(X, sigma, kappa, max_inflate, layer_out, tighten);
+  if (rc) return rc;
+  rc = tighten_map_handle_check(h, B, N);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_tighten_map(p, B, N, (size_t)h->unc.rows * h->unc.cols, X, sigma, layer_out, tighten);
+  return cilqr::host_call(h, p, [&] { return cilqr_tighten_map_device(h, h->stream, B, N, X, sigma, kappa, max_inflate, layer_out, tighten); });
 }
 
 // ---- analytic map risk (cilqr_chance_map.hip) ------------------------------------------------------------------------------------------

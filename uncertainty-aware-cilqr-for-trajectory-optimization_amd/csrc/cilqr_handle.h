@@ -83,6 +83,7 @@ struct cilqr_handle {
   double* d_risk_part;      // partial records of cilqr_rollout_risk: max_batch x risk_part_stride doubles (cilqr_risk.hip)
   size_t risk_part_stride;  // 8 + ceil(max_horizon / 2)
   double* d_chance_map_steps;  // per-step values of cilqr_chance_risk_map the caller did not ask for: 3 x max_batch x max_horizon doubles
+  double* d_tighten_map_part;  // workgroup records of cilqr_tighten_map: max_batch x TIGHTEN_MAP_MAX_G x TIGHTEN_MAP_REC doubles
   double* d_chance_sampled_steps;  // step records of cilqr_chance_risk_sampled: CHANCE_SAMPLED_REC x max_batch x max_horizon doubles
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;
@@ -98,6 +99,7 @@ struct cilqr_handle {
   int32_t* passes;           // caller-owned device buffer or null (cilqr_set_pass_count_buffer)
   // uncertainty map (cilqr_set_uncertainty_map*): what the kernels read, and the device copy made from a host layer
   cilqr::UncArgs unc;
+  double unc_res;  // the set map's resolution as given (unc holds its inverse); read by cilqr_tighten_map
   float* d_unc_layer;
   size_t unc_layer_cap;
   // cross-rank min-cost exchange (cilqr_comm.cpp)

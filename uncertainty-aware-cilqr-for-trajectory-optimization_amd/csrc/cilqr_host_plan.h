@@ -238,6 +238,17 @@ inline void plan_tighten_obstacles(HostPlan& p, size_t B, size_t N, size_t M, co
   p.out(tighten, B * CILQR_TIGHTEN_FIELDS);
 }
 
+// cilqr_tighten_map: 4 arrays; the map is the handle's.  Per solve 20·N + 26 doubles — X, sigma, the tighten row — and one output
+// layer of `cells` floats, cells/2 doubles: B·(20·N + 26 + cells/2) doubles against the max_batch·(22·max_horizon + 34) that
+// host_arena_bytes reserves below; the 4 roundings stay within its 32 x 16 bytes.
+inline void plan_tighten_map(HostPlan& p, size_t B, size_t N, size_t cells, const double*& X, const double*& sigma, float*& layer_out,
+                             double*& tighten) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(sigma, B * (N + 1) * 16);
+  p.out(layer_out, B * cells);
+  p.out(tighten, B * CILQR_TIGHTEN_MAP_FIELDS);
+}
+
 // cilqr_chance_risk_map: 10 arrays; the map is the handle's and no gain travels.  Per solve 20·N + 30 doubles — X, sigma, base, the
 // risk row, total — and 3·N more with the three per-step outputs; the Q nodes and weights, shared by the batch, are 4·Q doubles.
 // Against the 22·N + 34 per unit of max_batch that host_arena_bytes reserves below: without per-step outputs every B <= max_batch

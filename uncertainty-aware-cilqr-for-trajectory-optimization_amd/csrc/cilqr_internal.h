@@ -280,6 +280,27 @@ struct TightenArgs {
 hipError_t launch_tighten_obstacles(const TightenArgs& a, hipStream_t stream);
 size_t tighten_lds_bytes(int N);
 
+// Map tightening (cilqr_tighten_map.hip; cilqr_tighten_map*): the layer set on the handle dilated, per cell, by kappa standard
+// deviations of the footprint point over that cell, taken from the Sigma_t of the plan's nearest step.  lane = cell; solve b has G
+// workgroups of TIGHTEN_MAP_THREADS lanes that stride over its cells; a finish kernel, one wavefront per solve, merges the G
+// records of TIGHTEN_MAP_REC doubles each workgroup leaves in `partials`.  `s` carries B, N and unc.
+constexpr int TIGHTEN_MAP_THREADS = 256;
+constexpr int TIGHTEN_MAP_REC = 5;   // raised count, largest raise, its cell, largest reach, capped count
+constexpr int TIGHTEN_MAP_MAX_G = 64;  // workgroups per solve at most: the node's 150 x 100 map is 59 tiles of 256 cells
+constexpr int TIGHTEN_MAP_STEP = 8;  // doubles per step in LDS: p_t and six map-frame covariance entries
+struct TightenMapArgs {
+  SolveArgs s;
+  const double *X, *sigma;  // [B][4(N + 1)], [B][N + 1][16]
+  double kappa, max_inflate;
+  double res, r_fp;         // the map's resolution as it was set; half the footprint's diagonal
+  float* layer_out;         // [B][rows·cols]
+  double* tighten;          // [B][CILQR_TIGHTEN_MAP_FIELDS]
+  double* partials;         // the handle's: B·G records of TIGHTEN_MAP_REC doubles
+  int32_t G;
+};
+hipError_t launch_tighten_map(const TightenMapArgs& a, hipStream_t stream);
+size_t tighten_map_lds_bytes(int N);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

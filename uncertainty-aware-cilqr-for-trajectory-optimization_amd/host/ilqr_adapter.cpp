@@ -35,6 +35,7 @@ iLQR::~iLQR() {
   if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);
   if (noise_dev_) (void)hipFree(noise_dev_);
   if (scov_dev_) (void)hipFree(scov_dev_);
+  if (map_dev_) (void)hipFree(map_dev_);
   if (noise_stream_) (void)hipStreamDestroy((hipStream_t)noise_stream_);
   cilqr_destroy(h_);
 }
@@ -56,15 +57,57 @@ void iLQR::clear_Obstacle() {
 
 void iLQR::set_uncertainty_map(const Uncertainty& u) {
   if (u.layer.size() != (size_t)u.geom.rows * u.geom.cols) throw std::runtime_error("set_uncertainty_map: layer size does not match its geometry");
+  apply_map(u);
+  unc_ = u;  // (kept: set_map_tightening moves the layer between the handle's device copy and this object's)
+  map_set_ = true;
+}
+
+namespace {
+cilqr_uncertainty_map map_of(const Uncertainty& u, const float* layer, int64_t layer_stride) {
   cilqr_uncertainty_map m{};
-  m.layer = u.layer.data();
+  m.layer = layer;
   m.geom = u.geom;
   m.pose_x = u.pose_x; m.pose_y = u.pose_y; m.pose_theta = u.pose_theta;
   m.poses = nullptr;
-  m.layer_stride = 0;
+  m.layer_stride = layer_stride;
   m.probes_l = u.probes_l; m.probes_w = u.probes_w;
-  check(cilqr_set_uncertainty_map(h_, &m), "cilqr_set_uncertainty_map");
-  map_set_ = true;
+  return m;
+}
+}  // namespace
+
+// Without the map tightening: the host form, the handle keeps its own device copy.  With it: the layer is copied into map_dev_, in
+// front of one tightened layer per candidate, and the handle is pointed there, so that the rounds can swap layers without a copy.
+void iLQR::apply_map(const Uncertainty& u) {
+  if (!map_tighten_) {
+    const cilqr_uncertainty_map m = map_of(u, u.layer.data(), 0);
+    check(cilqr_set_uncertainty_map(h_, &m), "cilqr_set_uncertainty_map");
+    return;
+  }
+  const size_t cells = (size_t)u.geom.rows * u.geom.cols, need = cells * (1 + (size_t)max_candidates_);
+  if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error("set_uncertainty_map: hipSetDevice failed");
+  if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);  // nothing enqueued may still read the old block
+  if (need > map_dev_cap_) {
+    if (map_dev_) (void)hipFree(map_dev_);
+    map_dev_ = nullptr; map_dev_cap_ = 0;
+    if (hipMalloc((void**)&map_dev_, need * sizeof(float)) != hipSuccess) throw std::runtime_error("set_uncertainty_map: hipMalloc failed");
+    map_dev_cap_ = need;
+  }
+  if (hipMemcpy(map_dev_, u.layer.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    throw std::runtime_error("set_uncertainty_map: hipMemcpy failed");
+  const cilqr_uncertainty_map m = map_of(u, map_dev_, 0);
+  check(cilqr_set_uncertainty_map_device(h_, &m), "cilqr_set_uncertainty_map_device");
+}
+
+std::vector<double> iLQR::debug_map_cost(const std::vector<double>& states) const {
+  const int n = (int)(states.size() / 4);
+  std::vector<double> out((size_t)6 * n, 0.0);
+  check(cilqr_debug_uncertainty_cost(h_, n, states.data(), out.data(), out.data() + n, out.data() + 3 * (size_t)n), "cilqr_debug_uncertainty_cost");
+  return out;
+}
+
+cilqr_uncertainty_map iLQR::device_map(bool tightened) const {
+  const int64_t cells = (int64_t)unc_.geom.rows * unc_.geom.cols;
+  return tightened ? map_of(unc_, map_dev_ + cells, cells) : map_of(unc_, map_dev_, 0);
 }
 
 void iLQR::clear_uncertainty_map() {
@@ -128,7 +171,7 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
-  if (tighten_) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
+  if (tighten_ || map_tighten_) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
   if (n_samples_) {
@@ -190,7 +233,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
   if (scov_check_) return run_candidates_sample_covariance(B, ego_states);
-  if (!noise_.empty() || cov_check_ || tighten_) return run_candidates_noise_checked(B, ego_states);
+  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
@@ -260,6 +303,11 @@ const char* const kCovarianceWithNoise =
     "set_pose_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
 const char* const kTighteningWithSamples =
     "set_chance_tightening has no form for sampled obstacles (set_obstacle_samples): the sampled solve takes no inflated table";
+const char* const kMapTighteningWithSamples =
+    "set_map_tightening has no form for sampled obstacles (set_obstacle_samples), like set_chance_tightening";
+const char* const kTighteningsDisagree =
+    "set_chance_tightening and set_map_tightening are both set and must agree on Sigma0, W, lamb and rounds: one covariance chain and one "
+    "re-solve per round serve both";
 const char* const kCovarianceWithSamples =
     "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
 const char* const kSampleCovarianceWithNoise =
@@ -278,12 +326,13 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
     if (offsets.size() / 3 > (size_t)max_obstacles_) throw std::runtime_error("set_obstacle_samples: n_obs * n_samples above max_obstacles");
     if (cov_check_) throw std::logic_error(kCovarianceWithSamples);
     if (tighten_) throw std::logic_error(kTighteningWithSamples);
+    if (map_tighten_) throw std::logic_error(kMapTighteningWithSamples);
     samples_ = offsets;
     n_samples_ = n_samples;
   }
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || cov_check_ || tighten_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
 }
 
 int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
@@ -322,7 +371,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
   noise_fused_ = false;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || tighten_) reserve_noise_buffers();
+  if (!noise_.empty() || tighten_ || map_tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
@@ -335,7 +384,7 @@ void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double
   noise_fused_ = true;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || tighten_) reserve_noise_buffers();
+  if (!noise_.empty() || tighten_ || map_tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits) {
@@ -362,7 +411,7 @@ void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, d
   cov_sum_ = sum_bound;
   last_chance_risk.clear();
   last_step_risk.clear();
-  if (cov_check_ || tighten_) reserve_noise_buffers();
+  if (cov_check_ || tighten_ || map_tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_sample_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
@@ -408,17 +457,54 @@ void iLQR::set_chance_tightening(const double Sigma0[16], const double* W, doubl
   const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
   if (kappa != kappa) throw std::runtime_error("set_chance_tightening: eps outside (0, 0.5]");
   if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error("set_chance_tightening: max_inflate is negative or not finite");
+  if (on) check_tightening_agrees(map_tighten_, mt_rounds_, Sigma0, W, lamb, rounds);
   tighten_ = on;
-  tg_has_W_ = on && W != nullptr;
-  if (on) memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
-  if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
+  if (on) {  // (Sigma0, W and lamb are the one set both tightenings read; switched off, a map tightening keeps them as they are)
+    tg_has_W_ = W != nullptr;
+    memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
+    if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
+    tg_lamb_ = lamb;
+  } else if (!map_tighten_) {
+    tg_has_W_ = false;
+  }
   tg_kappa_ = kappa;
   tg_rounds_ = on ? rounds : 0;
   tg_cap_ = max_inflate;
-  tg_lamb_ = lamb;
   last_tighten.clear();
   last_tighten_risk_before.clear();
-  if (tighten_) reserve_noise_buffers();
+  if (tighten_ || map_tighten_) reserve_noise_buffers();
+}
+
+void iLQR::check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const {
+  if (!other_on) return;
+  const bool same = memcmp(tg_sigma0_, Sigma0, sizeof(tg_sigma0_)) == 0 && tg_has_W_ == (W != nullptr) &&
+                    (!tg_has_W_ || memcmp(tg_W_, W, sizeof(tg_W_)) == 0) && tg_lamb_ == lamb && other_rounds == rounds;
+  if (!same) throw std::logic_error(kTighteningsDisagree);
+}
+
+void iLQR::set_map_tightening(const double Sigma0[16], const double* W, double eps, int rounds, double max_inflate, double lamb) {
+  const bool on = Sigma0 != nullptr && rounds != 0;
+  if (on && n_samples_) throw std::logic_error(kMapTighteningWithSamples);
+  if (on && rounds < 0) throw std::runtime_error("set_map_tightening: rounds is negative");
+  const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
+  if (kappa != kappa) throw std::runtime_error("set_map_tightening: eps outside (0, 0.5]");
+  if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error("set_map_tightening: max_inflate is negative or not finite");
+  if (on) check_tightening_agrees(tighten_, tg_rounds_, Sigma0, W, lamb, rounds);
+  const bool was = map_tighten_;
+  map_tighten_ = on;
+  if (on) {  // (Sigma0, W and lamb are the one set both tightenings read)
+    tg_has_W_ = W != nullptr;
+    memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
+    if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
+    tg_lamb_ = lamb;
+  }
+  mt_kappa_ = kappa;
+  mt_rounds_ = on ? rounds : 0;
+  mt_cap_ = max_inflate;
+  last_tighten_map.clear();
+  last_tighten_map_risk_before.clear();
+  if (was != on && map_set_) apply_map(unc_);  // the layer moves to this object's device block, or back to the handle's
+  if (tighten_ || map_tighten_) reserve_noise_buffers();
 }
 
 void iLQR::set_obstacle_covariance(const std::vector<double>& cov) {
@@ -458,9 +544,11 @@ void iLQR::reserve_noise_buffers() {
   L.csig = take(cm * B * (N + 1) * 16); L.qn = take(cm * Q * 3); L.qw = take(cm * Q);
   L.cmrisk = take(cm * B * CILQR_CHANCE_MAP_FIELDS); L.cmstep = take(cm * B * N); L.cmtotal = take(cm * B);
   // the tightening rounds: Sigma0, W, every Sigma_t, the risk row of the round's input plan, the inflated dense table, the fields, obs_cov
-  const size_t tg = tighten_ ? 1 : 0;
-  L.ts0 = take(tg * 16); L.tW = take(tg * 16); L.tsig = take(tg * B * (N + 1) * 16); L.trisk = take(tg * B * CILQR_CHANCE_FIELDS);
+  // (the map tightening shares the chain's arrays and adds its fields; its layers are floats and lie in map_dev_)
+  const size_t tg = tighten_ ? 1 : 0, chain = tighten_ || map_tighten_ ? 1 : 0;
+  L.ts0 = take(chain * 16); L.tW = take(chain * 16); L.tsig = take(chain * B * (N + 1) * 16); L.trisk = take(chain * B * CILQR_CHANCE_FIELDS);
   L.tpose = take(tg * B * M * 4 * N); L.tdim = take(tg * B * M * 2 * N); L.tg = take(tg * B * CILQR_TIGHTEN_FIELDS); L.tcov = take(tg * M * N * 3);
+  L.tmg = take((map_tighten_ ? 1 : 0) * B * CILQR_TIGHTEN_MAP_FIELDS);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -486,6 +574,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   if (cov_check_ && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
   if (cov_check_ && n_samples_) throw std::logic_error(kCovarianceWithSamples);
   if (tighten_ && n_samples_) throw std::logic_error(kTighteningWithSamples);
+  if (map_tighten_ && n_samples_) throw std::logic_error(kMapTighteningWithSamples);
   if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
@@ -530,7 +619,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   int rc = CILQR_OK;
   const bool plain = !cov_check_ && noise_.empty();  // tightening alone: no check behind it, the pick of run_candidates itself
   const bool scored = cov_check_ || plain ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
-  const bool tightened = tighten_ && M > 0;
+  const bool obs_tightened = tighten_ && M > 0, tightened = obs_tightened || map_tightened();
   const bool cmap_checked = cmap_check_ && map_set_ && cov_check_;
   if (plain) {
     rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
@@ -613,6 +702,8 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   std::vector<double> tg_rows;
   last_tighten.clear();
   last_tighten_risk_before.clear();
+  last_tighten_map.clear();
+  last_tighten_map_risk_before.clear();
   if (tightened) fetch_tighten(st, d, B, tg_rows);
   if (scored) {
     last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
@@ -801,42 +892,64 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   };
   up(L.ts0, tg_sigma0_, 16);
   if (tg_has_W_) up(L.tW, tg_W_, 16);
-  if (!obs_cov_packed_.empty()) up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
+  if (tighten_ && !obs_cov_packed_.empty()) up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
   cilqr_obstacles inflated{};
   inflated.pose = d + L.tpose;
   inflated.dim = d + L.tdim;
   inflated.batch_stride = (int64_t)M * N;
   inflated.obstacle_stride = N;
   inflated.step_stride = 1;
+  // with both tightenings on one round serves both and re-solves once (the setters made the two round counts agree)
+  const bool obs_on = tighten_ && M > 0, map_on = map_tightened();
+  const int rounds = obs_on ? tg_rounds_ : mt_rounds_;
+  const cilqr_uncertainty_map original = map_on ? device_map(false) : cilqr_uncertainty_map{};
+  const cilqr_uncertainty_map layers = map_on ? device_map(true) : cilqr_uncertainty_map{};
+  const size_t cells = map_on ? (size_t)unc_.geom.rows * unc_.geom.cols : 0;
   int rc = CILQR_OK;
-  for (int r = 0; r < tg_rounds_ && !rc; ++r) {
+  for (int r = 0; r < rounds && !rc; ++r) {
     rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
     if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tg_has_W_ ? d + L.tW : nullptr, po, 0u, 1.0,
                                            nullptr, d + L.trisk, nullptr, nullptr, d + L.tsig, nullptr);
-    if (!rc) rc = cilqr_tighten_obstacles_device(h_, st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
-                                                 tg_cap_, d + L.tpose, d + L.tdim, d + L.tg);
-    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, &inflated, d + L.X, d + L.J,
-                                                     (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc && obs_on)
+      rc = cilqr_tighten_obstacles_device(h_, st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
+                                          tg_cap_, d + L.tpose, d + L.tdim, d + L.tg);
+    // the ORIGINAL layer is the one on the handle here: the inflation never compounds over rounds
+    if (!rc && map_on) rc = cilqr_tighten_map_device(h_, st, B, N, d + L.X, d + L.tsig, mt_kappa_, mt_cap_, map_dev_ + cells, d + L.tmg);
+    if (!rc && map_on) rc = cilqr_set_uncertainty_map_device(h_, &layers);
+    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, obs_on ? &inflated : po, d + L.X,
+                                                     d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (map_on) {  // the original map is back on the handle whatever happened: what follows judges the plan against it
+      const int back = cilqr_set_uncertainty_map_device(h_, &original);  // (a success leaves cilqr_last_error as it is)
+      if (!rc) rc = back;
+    }
   }
   return rc;
 }
 
 void iLQR::fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows) {
-  last_tighten.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0);
   risk_rows.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0);
-  hip_check(hipMemcpyAsync(last_tighten.data(), d + nl_.tg, last_tighten.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  if (map_tightened()) {
+    last_tighten_map.assign((size_t)B * CILQR_TIGHTEN_MAP_FIELDS, 0.0);
+    hip_check(hipMemcpyAsync(last_tighten_map.data(), d + nl_.tmg, last_tighten_map.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  }
+  if (tighten_ && !obstacles_.empty()) {
+    last_tighten.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0);
+    hip_check(hipMemcpyAsync(last_tighten.data(), d + nl_.tg, last_tighten.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  }
   hip_check(hipMemcpyAsync(risk_rows.data(), d + nl_.trisk, risk_rows.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
 }
 
 void iLQR::keep_tighten_risk(int B, const std::vector<double>& risk_rows) {
-  last_tighten_risk_before.resize(B);
-  for (int b = 0; b < B; ++b) last_tighten_risk_before[b] = risk_rows[(size_t)b * CILQR_CHANCE_FIELDS + CILQR_CR_STEP_RISK];
+  std::vector<double> before(B);
+  for (int b = 0; b < B; ++b) before[b] = risk_rows[(size_t)b * CILQR_CHANCE_FIELDS + CILQR_CR_STEP_RISK];
+  if (tighten_ && !obstacles_.empty()) last_tighten_risk_before = before;
+  if (map_tightened()) last_tighten_map_risk_before = before;
 }
 
 // get_optimal_control_seq under set_chance_tightening: the B = 1 solve and its rounds in the device block, one wait.
 void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]) {
   const int N = params.horizon, M = (int)obstacles_.size();
-  if (n_samples_) throw std::logic_error(kTighteningWithSamples);
+  if (n_samples_) throw std::logic_error(tighten_ ? kTighteningWithSamples : kMapTighteningWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();
   const cilqr_obstacles host_obs = obstacle_strides();
   if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
@@ -862,7 +975,8 @@ void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coe
   const cilqr_obstacles* po = M ? &obs : nullptr;
   int rc = cilqr_solve_batch_obstacles_device(h_, st, 1, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
                                               (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-  if (!rc && M) rc = tighten_rounds(st, d, 1, po);
+  const bool tightened = (tighten_ && M > 0) || map_tightened();
+  if (!rc && tightened) rc = tighten_rounds(st, d, 1, po);
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(st);
@@ -874,14 +988,16 @@ void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coe
   std::vector<double> tg_rows;
   last_tighten.clear();
   last_tighten_risk_before.clear();
+  last_tighten_map.clear();
+  last_tighten_map_risk_before.clear();
   down(Xb.a.data(), L.X, Xb.a.size() * sizeof(double));
   down(U.a.data(), L.U, U.a.size() * sizeof(double));
   down(&J, L.J, sizeof(double));
   down(&iters, L.iters, sizeof(int32_t));
   down(&status, L.status, sizeof(int32_t));
-  if (M) fetch_tighten(st, d, 1, tg_rows);
+  if (tightened) fetch_tighten(st, d, 1, tg_rows);
   hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-  if (M) keep_tighten_risk(1, tg_rows);
+  if (tightened) keep_tighten_risk(1, tg_rows);
   X_result = Xb;
   last_iterations = iters;
   last_exit = status;

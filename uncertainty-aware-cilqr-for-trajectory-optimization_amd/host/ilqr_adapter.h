@@ -186,6 +186,29 @@ class iLQR {
   // per obstacle of set_Obstacle, in its order — 3 * M values, constant over the horizon, or 3 * M * horizon, obstacle-major.  Empty:
   // none (the default).  A size that matches neither makes the next run throw std::runtime_error.
   void set_obstacle_covariance(const std::vector<double>& cov);
+  // Map tightening: the map counterpart of set_chance_tightening, for the configuration the live node runs — no obstacle set, the
+  // blurred costmap of set_uncertainty_map the planner's only obstacle information — where every check above can only reject.  Sigma0,
+  // W, eps, rounds and lamb as in set_chance_tightening.  While it and an uncertainty map are set, run_step (get_optimal_control_seq)
+  // and run_candidates follow their solve by `rounds` rounds, enqueued on the checks' stream with nothing coming back in between:
+  //   cilqr_gains_batch_device(lamb) -> cilqr_chance_risk_device, for its sigma_out (with M = 0 when no obstacle is set) ->
+  //   cilqr_tighten_map_device(kappa = cilqr_chance_kappa(eps), max_inflate: no cell reaches further, in metres) on the ORIGINAL
+  //   layer, so inflation never compounds over rounds -> the tightened per-solve layers set on the handle -> the re-solve,
+  //   warm-started from the U the solve before it left -> the original map set on the handle again.
+  // After the rounds the original map is on the handle, bit for bit, and every later score or risk check — set_candidate_pick,
+  // set_map_risk_check, set_map_covariance_check, ... — judges the final plan against it.  last_tighten_map holds
+  // CILQR_TIGHTEN_MAP_FIELDS per solve (cilqr_tighten_map_field) of the last round, last_tighten_map_risk_before the CR_STEP_RISK of
+  // the plan that round started from, one per solve: the chance of contact with the OBSTACLES of set_Obstacle, 0 with none set (the
+  // map has no part in it).  With no map set the rounds are skipped and both stay empty.  When set_chance_tightening is also set and
+  // obstacles are set, one round tightens both and re-solves once; the two setters must then agree on Sigma0, W, lamb and rounds, or
+  // the second one throws std::logic_error (switching either off leaves the other's inputs as they are).  The layer is soft, first order and axis-capped
+  // (include/cilqr.h): it guarantees nothing — keep a check behind it.  While it is on, the layer of set_uncertainty_map lives in
+  // device memory of this object, beside one tightened layer per candidate, and the handle reads it there.
+  // Sigma0 == nullptr or rounds == 0 switches it off (the default: nothing changes for existing callers).  Together with
+  // set_obstacle_samples (whichever comes second) the setters throw std::logic_error, like set_chance_tightening.
+  void set_map_tightening(const double Sigma0[16], const double* W, double eps, int rounds = 1, double max_inflate = 1.0, double lamb = 1.0);
+  // Test hook: cilqr_debug_uncertainty_cost on the map this object's handle holds right now, at n = states.size() / 4 states
+  // (x, y, v, theta) -> n costs, then 2n of vx, then 3n of mx.  Throws std::runtime_error when no map is set.
+  std::vector<double> debug_map_cost(const std::vector<double>& states) const;
 
   // Sampled obstacles: the uncertainty-aware scene form.  `offsets` holds n_obs x n_samples x 3 doubles, (dx, dy, dtheta) per pose
   // sample, drawn ONCE by the node with its own sigmas; the obstacles of set_Obstacle are then the NOMINAL ones (n_obs of them, in
@@ -238,6 +261,8 @@ class iLQR {
   std::vector<double> last_chance_risk_sampled;  // CILQR_CRS_FIELDS per candidate
   // run_step / run_candidates under set_chance_tightening with obstacles set; empty otherwise
   std::vector<double> last_tighten, last_tighten_risk_before;  // CILQR_TIGHTEN_FIELDS per solve; CR_STEP_RISK per solve
+  // run_step / run_candidates under set_map_tightening with an uncertainty map set; empty otherwise
+  std::vector<double> last_tighten_map, last_tighten_map_risk_before;  // CILQR_TIGHTEN_MAP_FIELDS per solve; CR_STEP_RISK per solve
 
  private:
   void pack_obstacles();
@@ -258,7 +283,7 @@ class iLQR {
   // so that this header needs no HIP
   struct NoiseLayout {
     size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
-        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, end;
+        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, end;
   };
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
@@ -302,6 +327,18 @@ class iLQR {
   void fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows);  // enqueues last_tighten and the round's risk rows
   void keep_tighten_risk(int B, const std::vector<double>& risk_rows);                 // after the wait: their CR_STEP_RISK column
   void solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]);  // run_step's solve
+  // map tightening (set_map_tightening): Sigma0, W and lamb are the tightening's above (the setters agree on them).  The map as it was
+  // set, and, while the tightening is on, one device block of floats: the original layer, then a tightened layer per candidate
+  bool map_tighten_ = false;
+  int mt_rounds_ = 0;
+  double mt_kappa_ = 0.0, mt_cap_ = 1.0;
+  Uncertainty unc_;
+  float* map_dev_ = nullptr;
+  size_t map_dev_cap_ = 0;
+  void apply_map(const Uncertainty& u);  // puts `u` on the handle: through map_dev_ while the map tightening is on
+  cilqr_uncertainty_map device_map(bool tightened) const;  // the original in map_dev_, or the per-solve layers behind it
+  bool map_tightened() const { return map_tighten_ && map_set_; }
+  void check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const;
 };
 
 }  // namespace cilqr_host
