@@ -1017,6 +1017,76 @@ int cilqr_chance_risk_sampled(cilqr_handle* h, int B, int N, int n_obs, int n_sa
                               double max_risk, const double* base, double* risk, double* step_risk, double* pair_p, double* entry_p,
                               double* total);
 
+/* --- tracked obstacles predicted over the horizon, with their covariance (new) ----------------------------------------------------
+ * Every call above that reads ordinary obstacles takes a finished table, [M][4*N] poses and [M][2*N] dimensions, and the obs_cov of
+ * cilqr_tighten_obstacles had no producer.  cilqr_predict_obstacles(_device) makes both on the device from what a tracker hands
+ * over once per tick: one state and one covariance per vehicle, rolled out at constant acceleration and yaw rate.
+ * T track sets of M vehicles.  T = 1 is the planner's case, one set of vehicles for every candidate: the outputs are then addressed
+ * with cilqr_obstacles strides (0, N, 1), and cov_out by the same entry index as obs_cov.  T = B gives one set per solve, strides
+ * (M*N, N, 1).
+ *   track       [T][M][6]   (x, y, v, theta, a, omega): the state in the planner's order, then a constant acceleration and yaw rate
+ *   track_dim   [T][M][2]   (length, width)
+ *   track_cov   [T][M][16]  or NULL (zero): P_0, column-major, entry (r, c) at [r + 4*c], state order (x, y, v, theta); only
+ *                           row <= column is read, the convention of sigma0
+ *   track_noise [16]        or NULL (zero): Q per step, shared by every track; only row <= column is read
+ *   pose_out    [T][M][4*N] required: the predicted poses
+ *   dim_out     [T][M][2*N] required: track_dim bit-copied to every step
+ *   cov_out     [T][M][N][3]  or NULL: (xx, xy, yy) of P_t — exactly the obs_cov layout of cilqr_tighten_obstacles
+ *   sigma_out   [T][M][N][16] or NULL: every P_t, exactly symmetric
+ * Definition per track, dt = Parameters::timestep.  Entry t belongs to the ego's X_t, so entry 0 is the tracked state itself:
+ *   pose[t] = (x_t, y_t, v_t, theta_t); cov[t] and sigma[t] come from P_t.  Entry 0 is a bit copy of the inputs (for P_0 the lower
+ *   triangle is mirrored from the upper).  Step t -> t+1:
+ *     stop = (v_t + a*dt < 0),   a_t = stop ? -v_t/dt : a,   adv = v_t*dt + a_t*dt^2/2,
+ *     x_{t+1} = x_t + cos(theta_t)*adv,   y_{t+1} = y_t + sin(theta_t)*adv,
+ *     v_{t+1} = stop ? 0 : v_t + a*dt     (a braking vehicle stops and does not reverse),
+ *     theta_{t+1} = theta_t + omega*dt.
+ *   The ego's acceleration, yaw-rate and speed clamps are NOT applied: they are the ego's limits, not the other vehicle's.
+ *     P_{t+1} = A_t P_t A_t' + Q,   A_t the A of cilqr_chance_risk above (Model::get_A_matrix) at (v_t, theta_t, a_t):
+ *     A = I + { (0,2): dt*cos theta, (1,2): dt*sin theta, (0,3): -sin theta*adv, (1,3): cos theta*adv }.
+ *   Entries with row <= column are computed and mirrored.  The floor on v does not enter A_t: A(2,2) = 1 always, so after a stop
+ *   the speed variance is carried on and the position covariance keeps growing — the conservative side.
+ *   Values are not checked: a NaN propagates through its own track only.  A track's outputs depend on that track's inputs (and on
+ *   track_noise and N) alone: the same bits whatever T and M are and wherever the track sits.
+ * Mapping: one wavefront per track, T*M workgroups, one launch, nothing allocated per call.  Speeds and headings by their
+ * recurrences, then the steps' sincos and A_t entries in parallel, then the serial chain written out for the four non-zero
+ * entries of A_t - I, then coalesced stores from LDS.
+ * CILQR_ERR_ARG, decided before the handle is looked at where no handle is needed: NULL track, track_dim, pose_out or dim_out; T, N
+ * or M < 1; then T beyond max_batch, N beyond max_horizon, M beyond max_obstacles.  The host-buffer form's arrays must fit the
+ * device arena reserved at create (CILQR_ERR_ARG otherwise; this call adds nothing to it): T*M*(24 + 25*N) + 16 doubles with every
+ * output, T*M*(24 + 9*N) + 16 without sigma_out.  With every output every T <= max_batch/8 always fits; without sigma_out every
+ * T <= max_batch/5 does.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*18*N bytes (per step the pose, four coefficients and ten covariance entries),
+ * exceeds 64 KiB: N above 455, which CILQR_MAX_HORIZON = 384 keeps out of reach — every horizon a handle accepts runs. */
+int cilqr_predict_obstacles_device(cilqr_handle* h, void* stream, int T, int N, int M, const double* track, const double* track_dim,
+                                   const double* track_cov, const double* track_noise, double* pose_out, double* dim_out,
+                                   double* cov_out, double* sigma_out);
+int cilqr_predict_obstacles(cilqr_handle* h, int T, int N, int M, const double* track, const double* track_dim, const double* track_cov,
+                            const double* track_noise, double* pose_out, double* dim_out, double* cov_out, double* sigma_out);
+
+/* --- the analytic pose-noise risk with the obstacle's own covariance (new) -----------------------------------------------------------
+ * cilqr_chance_risk takes the obstacle as certain.  cilqr_chance_risk_cov(_device) is that call with one more argument after obs:
+ * obs_cov, NULL or 3 doubles (xx, xy, yy; world frame) at obs_cov + 3*e for the same entry index e = b*batch_stride +
+ * m*obstacle_stride + t*step_stride that addresses the entry's pose — the convention of cilqr_tighten_obstacles, and what
+ * cilqr_predict_obstacles writes to cov_out.  With gx, gy the first two components of g, the quadratic form of an entry becomes
+ *     q' = g' Sigma_t g + (gx^2*Cxx + 2*gx*gy*Cxy + gy^2*Cyy),     s = sqrt(max(q', 0)),
+ * and the rest is cilqr_chance_risk's.  The ego's and the obstacle's errors are taken as INDEPENDENT; the obstacle's heading and
+ * size uncertainty are left out (the ellipse keeps its axes and its orientation).  An entry whose three obs_cov values are not all
+ * finite gets entry_p = 1: the judge cannot vouch for it.  The fields, step_risk, entry_p, sigma_out, total / base / max_risk and
+ * the flags are unchanged in meaning.  obs_cov == NULL: every output has the bits of cilqr_chance_risk; so it has with an obs_cov
+ * that is all zero (q + 0 is q).  A solve's bits do not depend on the batch or on the strides.
+ * Errors, limits and the LDS formula are those of cilqr_chance_risk (a second instantiation of its kernel).  The host-buffer form
+ * carries 3 doubles of obs_cov per entry of the obstacle span, as cilqr_tighten_obstacles does, and adds nothing to the arena: with
+ * dense obstacles 15*N + 9*M*N + 28 doubles per solve without sigma_out and entry_p, 31*N + 10*M*N + 44 with both — with obs_cov
+ * every B <= max_batch/2 always fits, with or without the two outputs. */
+int cilqr_chance_risk_cov_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                                 const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
+                                 const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double max_risk, const double* base,
+                                 double* risk, double* step_risk, double* entry_p, double* sigma_out, double* total);
+int cilqr_chance_risk_cov(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                          int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, const double* obs_cov,
+                          uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk, double* entry_p,
+                          double* sigma_out, double* total);
+
 /* --- the cross-GPU exchange step (SURVEY §8b "Entry point", §8e; new: the reference has no collective) ------------------
  * The batch shards by scene with no data-path collective; the ONE exchange is the min-cost pick: every rank's
  * {J_min, local index, index offset} (24 bytes) through one ncclAllGather (RCCL over xGMI), then the lexicographic minimum

@@ -81,6 +81,7 @@ ABI_SYMBOLS = (
     "cilqr_tighten_map", "cilqr_tighten_map_device",
     "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
     "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
+    "cilqr_predict_obstacles", "cilqr_predict_obstacles_device", "cilqr_chance_risk_cov", "cilqr_chance_risk_cov_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -744,6 +745,79 @@ class Solver:
                                               C.c_int64(sigma0_batch_stride), _vp(process_noise), C.byref(obs) if M else None,
                                               C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base), _vp(risk), _vp(step_risk),
                                               _vp(entry_p), _vp(sigma_out), _vp(total)))
+
+    def chance_risk_cov(self, N, X, U, K, sigma0, process_noise=None, obs_pose=None, obs_dim=None, obs_cov=None, max_risk=1.0, base=None,
+                        sum_bound=False, want_entry_p=True, want_sigma=True):
+        """`cilqr_chance_risk_cov`: `chance_risk` with the obstacles' own position covariance, obs_cov None or (xx, xy, yy) per
+        obstacle entry in the obstacles' own shape with 3 (or 3N) columns — what `predict_obstacles` returns as `cov`.  Same returns."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X = X.reshape(B, 4 * (N + 1))
+        U, K = _np64(U).reshape(B, 2 * N), _np64(K).reshape(B, 8 * N)
+        sigma0 = _np64(sigma0)
+        if sigma0.size == 16:
+            sigma0, stride = sigma0.reshape(16), 0
+        elif sigma0.size == 16 * B:
+            sigma0, stride = sigma0.reshape(B, 16), 1
+        else:
+            raise CilqrError("chance_risk_cov: sigma0 %s holds neither 16 nor %d x 16 values" % (sigma0.shape, B))
+        W = None if process_noise is None else _np64(process_noise).reshape(16)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        obs_cov = None if obs_cov is None or M == 0 else _np64(obs_cov)
+        if obs_cov is not None and obs_cov.size * 4 != keep[0].size * 3:
+            raise CilqrError("chance_risk_cov: obs_cov %s does not hold 3 values per entry of obs_pose %s" % (obs_cov.shape, keep[0].shape))
+        base = None if base is None else _np64(base).reshape(B)
+        risk, step_risk = np.zeros((B, CHANCE_FIELDS)), np.zeros((B, N))
+        entry_p = np.zeros((B, M * N)) if want_entry_p else None
+        sigma = np.zeros((B, N + 1, 16)) if want_sigma else None
+        total = None if base is None else np.zeros(B)
+        _check(lib().cilqr_chance_risk_cov(self._h, B, int(N), int(M), _p(X), _p(U), _p(K), _p(sigma0), C.c_int64(stride), _p(W),
+                                           None if obs is None else C.byref(obs), _p(obs_cov),
+                                           C.c_uint32(CHANCE_BOUND_SUM if sum_bound else 0), C.c_double(max_risk), _p(base), _p(risk),
+                                           _p(step_risk), _p(entry_p), _p(sigma), _p(total)))
+        return dict(risk=risk, step_risk=step_risk, entry_p=entry_p, sigma=sigma, total=total)
+
+    def chance_risk_cov_device(self, stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs_pose, obs_dim, strides,
+                               obs_cov, risk, step_risk=0, entry_p=0, sigma_out=0, total=0, base=0, max_risk=1.0, flags=0):
+        """`cilqr_chance_risk_cov_device`: device addresses; obs_cov 0 or 3 doubles per entry, addressed by the strides' entry index."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_chance_risk_cov_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), _vp(U), _vp(K), _vp(sigma0),
+                                                  C.c_int64(sigma0_batch_stride), _vp(process_noise), C.byref(obs) if M else None,
+                                                  _vp(obs_cov), C.c_uint32(int(flags)), C.c_double(max_risk), _vp(base), _vp(risk),
+                                                  _vp(step_risk), _vp(entry_p), _vp(sigma_out), _vp(total)))
+
+    # ---- tracked obstacles predicted over the horizon, with their covariance ----
+    def predict_obstacles(self, N, track, track_dim, track_cov=None, track_noise=None, want_cov=True, want_sigma=True):
+        """`cilqr_predict_obstacles`: track (M, 6) — one set for every solve — or (T, M, 6), rows (x, y, v, theta, a, omega);
+        track_dim the same shape with 2 columns; track_cov None or the same shape with 16 (or 4, 4) per track, column-major, only
+        row <= column read; track_noise None or 16 values.  Returns dict(pose (…, M, 4N), dim (…, M, 2N), cov (…, M, 3N) or None,
+        sigma (…, M, N, 16) or None): pose, dim and cov in a shape `obstacle_strides` and the obs_cov arguments take as they are."""
+        track = _np64(track)
+        lead = track.shape[:-1]
+        if track.ndim not in (2, 3) or track.shape[-1] != 6:
+            raise CilqrError("predict_obstacles: track %s is not (M, 6) or (T, M, 6)" % (track.shape,))
+        T, M = (1, lead[0]) if len(lead) == 1 else lead
+        track_dim = _np64(track_dim)
+        if track_dim.size != T * M * 2:
+            raise CilqrError("predict_obstacles: track_dim %s does not hold 2 values per track" % (track_dim.shape,))
+        track_cov = None if track_cov is None else _np64(track_cov)
+        if track_cov is not None and track_cov.size != T * M * 16:
+            raise CilqrError("predict_obstacles: track_cov %s does not hold 16 values per track" % (track_cov.shape,))
+        Q = None if track_noise is None else _np64(track_noise).reshape(16)
+        pose, dim = np.zeros(lead + (4 * N,)), np.zeros(lead + (2 * N,))
+        cov = np.zeros(lead + (3 * N,)) if want_cov else None
+        sigma = np.zeros(lead + (N, 16)) if want_sigma else None
+        _check(lib().cilqr_predict_obstacles(self._h, int(T), int(N), int(M), _p(track), _p(track_dim), _p(track_cov), _p(Q), _p(pose),
+                                             _p(dim), _p(cov), _p(sigma)))
+        return dict(pose=pose, dim=dim, cov=cov, sigma=sigma)
+
+    def predict_obstacles_device(self, stream, T, N, M, track, track_dim, pose_out, dim_out, track_cov=0, track_noise=0, cov_out=0,
+                                 sigma_out=0):
+        """`cilqr_predict_obstacles_device`: device addresses."""
+        _check(lib().cilqr_predict_obstacles_device(self._h, _vp(stream), int(T), int(N), int(M), _vp(track), _vp(track_dim),
+                                                    _vp(track_cov), _vp(track_noise), _vp(pose_out), _vp(dim_out), _vp(cov_out),
+                                                    _vp(sigma_out)))
 
     # ---- analytic map risk: the pose covariance against the uncertainty map by quadrature ----
     def chance_risk_map(self, N, X, sigma, nodes, weights, occ_threshold, max_risk=1.0, base=None, sum_bound=False, unknown_hits=False,

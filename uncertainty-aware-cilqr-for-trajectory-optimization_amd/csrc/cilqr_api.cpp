@@ -1119,10 +1119,12 @@ int chance_risk_check(const cilqr_handle* h, int B, int N, int M, const double* 
 }
 }  // namespace
 
-int cilqr_chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
-                             const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
-                             const cilqr_obstacles* obs, uint32_t flags, double max_risk, const double* base, double* risk,
-                             double* step_risk, double* entry_p, double* sigma_out, double* total) {
+namespace {
+// cilqr_chance_risk_device (obs_cov null) and cilqr_chance_risk_cov_device
+int chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                       const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs,
+                       const double* obs_cov, uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk,
+                       double* entry_p, double* sigma_out, double* total) {
   int rc = chance_risk_check(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, obs, flags, max_risk, base, risk, total, nullptr);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
@@ -1136,25 +1138,114 @@ int cilqr_chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M,
   a.max_risk = max_risk; a.base = base; a.risk = risk; a.step_risk = step_risk; a.entry_p = entry_p; a.sigma_out = sigma_out;
   a.total = total; a.flags = flags;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(cilqr::launch_chance_risk(a, (hipStream_t)stream));
+  if (obs_cov && M > 0) {
+    cilqr::ChanceCovArgs c;
+    static_cast<cilqr::ChanceArgs&>(c) = a;
+    c.obs_cov = obs_cov;
+    HIP_TRY(cilqr::launch_chance_risk_cov(c, (hipStream_t)stream));
+  } else {
+    HIP_TRY(cilqr::launch_chance_risk(a, (hipStream_t)stream));
+  }
   return CILQR_OK;
 }
 
-int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
-                      int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, uint32_t flags,
-                      double max_risk, const double* base, double* risk, double* step_risk, double* entry_p, double* sigma_out,
-                      double* total) {
+// cilqr_chance_risk (obs_cov null) and cilqr_chance_risk_cov
+int chance_risk_host(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                     int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, const double* obs_cov,
+                     uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk, double* entry_p,
+                     double* sigma_out, double* total) {
   size_t span = 0;
   int rc = chance_risk_check(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, obs, flags, max_risk, base, risk, total, &span);
   if (rc) return rc;
   if (B == 0) return CILQR_OK;
   cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
   cilqr::HostPlan p(h->d_arena);
-  cilqr::plan_chance_risk(p, B, N, M, sigma0_batch_stride == 0 ? 1 : B, X, U, K, sigma0, process_noise, o, span, base, risk, step_risk,
-                          entry_p, sigma_out, total);
+  if (M == 0) obs_cov = nullptr;
+  if (obs_cov)
+    cilqr::plan_chance_risk_cov(p, B, N, M, sigma0_batch_stride == 0 ? 1 : B, X, U, K, sigma0, process_noise, o, span, obs_cov, base, risk,
+                                step_risk, entry_p, sigma_out, total);
+  else
+    cilqr::plan_chance_risk(p, B, N, M, sigma0_batch_stride == 0 ? 1 : B, X, U, K, sigma0, process_noise, o, span, base, risk, step_risk,
+                            entry_p, sigma_out, total);
   return cilqr::host_call(h, p, [&] {
-    return cilqr_chance_risk_device(h, h->stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, M > 0 ? &o : nullptr, flags,
-                                    max_risk, base, risk, step_risk, entry_p, sigma_out, total);
+    return chance_risk_device(h, h->stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, M > 0 ? &o : nullptr, obs_cov,
+                              flags, max_risk, base, risk, step_risk, entry_p, sigma_out, total);
+  });
+}
+}  // namespace
+
+int cilqr_chance_risk_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                             const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
+                             const cilqr_obstacles* obs, uint32_t flags, double max_risk, const double* base, double* risk,
+                             double* step_risk, double* entry_p, double* sigma_out, double* total) {
+  return chance_risk_device(h, stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs, nullptr, flags, max_risk, base,
+                            risk, step_risk, entry_p, sigma_out, total);
+}
+
+int cilqr_chance_risk(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                      int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, uint32_t flags,
+                      double max_risk, const double* base, double* risk, double* step_risk, double* entry_p, double* sigma_out,
+                      double* total) {
+  return chance_risk_host(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs, nullptr, flags, max_risk, base, risk,
+                          step_risk, entry_p, sigma_out, total);
+}
+
+int cilqr_chance_risk_cov_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const double* U, const double* K,
+                                 const double* sigma0, int64_t sigma0_batch_stride, const double* process_noise,
+                                 const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double max_risk, const double* base,
+                                 double* risk, double* step_risk, double* entry_p, double* sigma_out, double* total) {
+  return chance_risk_device(h, stream, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs, obs_cov, flags, max_risk, base,
+                            risk, step_risk, entry_p, sigma_out, total);
+}
+
+int cilqr_chance_risk_cov(cilqr_handle* h, int B, int N, int M, const double* X, const double* U, const double* K, const double* sigma0,
+                          int64_t sigma0_batch_stride, const double* process_noise, const cilqr_obstacles* obs, const double* obs_cov,
+                          uint32_t flags, double max_risk, const double* base, double* risk, double* step_risk, double* entry_p,
+                          double* sigma_out, double* total) {
+  return chance_risk_host(h, B, N, M, X, U, K, sigma0, sigma0_batch_stride, process_noise, obs, obs_cov, flags, max_risk, base, risk,
+                          step_risk, entry_p, sigma_out, total);
+}
+
+// ---- tracked obstacles predicted over the horizon (cilqr_predict.hip) -----------------------------------------------------------------
+namespace {
+int predict_check(const cilqr_handle* h, int T, int N, int M, const double* track, const double* track_dim, const double* pose_out,
+                  const double* dim_out) {
+  if (!track || !track_dim || !pose_out || !dim_out) return fail(CILQR_ERR_ARG, "cilqr_predict_obstacles: null required pointer");
+  if (T < 1 || N < 1 || M < 1) return fail(CILQR_ERR_ARG, "cilqr_predict_obstacles: T = %d, N = %d, M = %d: each must be at least 1", T, N, M);
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (T > h->max_batch) return fail(CILQR_ERR_ARG, "T=%d outside [1,%d]", T, h->max_batch);
+  if (N > h->max_horizon) return fail(CILQR_ERR_ARG, "N=%d outside [1,%d]", N, h->max_horizon);
+  if (M > h->max_obstacles) return fail(CILQR_ERR_ARG, "M=%d outside [1,%d]", M, h->max_obstacles);
+  if ((int64_t)T * M > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_predict_obstacles: T * M beyond 2^31 tracks");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_predict_obstacles_device(cilqr_handle* h, void* stream, int T, int N, int M, const double* track, const double* track_dim,
+                                   const double* track_cov, const double* track_noise, double* pose_out, double* dim_out,
+                                   double* cov_out, double* sigma_out) {
+  int rc = predict_check(h, T, N, M, track, track_dim, pose_out, dim_out);
+  if (rc) return rc;
+  if (cilqr::predict_lds_bytes(N) > cilqr::PREDICT_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_predict_obstacles: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::PredictArgs a = {};
+  a.track = track; a.track_dim = track_dim; a.track_cov = track_cov; a.noise = track_noise;
+  a.pose_out = pose_out; a.dim_out = dim_out; a.cov_out = cov_out; a.sigma_out = sigma_out;
+  a.dt = h->kp.dt; a.half_dt2 = h->kp.half_dt2; a.N = N; a.tracks = (long long)T * M;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_predict_obstacles(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_predict_obstacles(cilqr_handle* h, int T, int N, int M, const double* track, const double* track_dim, const double* track_cov,
+                            const double* track_noise, double* pose_out, double* dim_out, double* cov_out, double* sigma_out) {
+  int rc = predict_check(h, T, N, M, track, track_dim, pose_out, dim_out);
+  if (rc) return rc;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_predict_obstacles(p, T, N, M, track, track_dim, track_cov, track_noise, pose_out, dim_out, cov_out, sigma_out);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_predict_obstacles_device(h, h->stream, T, N, M, track, track_dim, track_cov, track_noise, pose_out, dim_out, cov_out,
+                                          sigma_out);
   });
 }
 

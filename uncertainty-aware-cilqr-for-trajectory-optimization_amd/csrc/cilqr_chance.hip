@@ -39,9 +39,13 @@ __device__ __forceinline__ double lane_value(double v) {
   return __builtin_bit_cast(double, (unsigned long long)hi << 32 | lo);
 }
 
-// (circle_chance_arg, the entry's arithmetic: cilqr_chance_entry.hpp, shared with cilqr_chance_sampled.hip)
+// (circle_chance_arg = circle_chance_form + chance_arg, the entry's arithmetic: cilqr_chance_entry.hpp, shared with
+// cilqr_chance_sampled.hip)
 
-__global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(ChanceArgs a) {
+// COV: cilqr_chance_risk_cov — every entry's form gains the obstacle's covariance, read at the entry's own index; an entry whose
+// three values are not all finite gets the argument of p = 1.  Nothing else differs, and COV = false is cilqr_chance_risk's kernel.
+template <bool COV>
+__global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(typename ChanceKernelArgs<COV>::type a) {
   extern __shared__ __attribute__((aligned(16))) double chance_lds[];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), threads = blockDim.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
@@ -144,9 +148,24 @@ __global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(Chanc
       const double S6[6] = {S[0], S[4], S[12], S[5], S[13], S[15]};  // xx, xy, xθ, yy, yθ, θθ
       // erfc decreases: the larger of the two circles' chance values is the one of the smaller argument (a NaN never wins)
       const double lf = kp.ego_front, lr = -kp.ego_rear;
-      const double zf = circle_chance_arg<true>(en, oc.fxp, oc.fyp, -lf * sn, lf * cs, S6);
-      const double zr = circle_chance_arg<false>(en, oc.rxp, oc.ryp, -lr * sn, lr * cs, S6);
-      pe[e] = fmin(zf, zr);
+      if (COV) {
+        const ChanceForm ff = circle_chance_form<true>(en, oc.fxp, oc.fyp, -lf * sn, lf * cs, S6);
+        const ChanceForm fr = circle_chance_form<false>(en, oc.rxp, oc.ryp, -lr * sn, lr * cs, S6);
+        // (the entry's index is formed again here, from a copy of e the compiler cannot trace: m, or the address, carried from the
+        // entry's loads across the two forms takes the kernel past 128 registers)
+        int ec = e;
+        asm volatile("" : "+v"(ec));
+        const int mc = ec / N, tc = ec - mc * N;
+        const double* oc3 = kernel_args<ChanceCovArgs>().obs_cov + 3 * obs_entry_index(s, b, mc, tc);
+        const double cxx = oc3[0], cxy = oc3[1], cyy = oc3[2];
+        const double zf = chance_arg(ff.c, chance_form_with_cov(ff, cxx, cxy, cyy));
+        const double zr = chance_arg(fr.c, chance_form_with_cov(fr, cxx, cxy, cyy));
+        pe[e] = is_finite(cxx) && is_finite(cxy) && is_finite(cyy) ? fmin(zf, zr) : -__builtin_huge_val();
+      } else {
+        const double zf = circle_chance_arg<true>(en, oc.fxp, oc.fyp, -lf * sn, lf * cs, S6);
+        const double zr = circle_chance_arg<false>(en, oc.rxp, oc.ryp, -lr * sn, lr * cs, S6);
+        pe[e] = fmin(zf, zr);
+      }
     }
     // (a loop of its own: erfc alone is live in it — side by side with the entry's arithmetic it needs more than 128 registers)
     for (int e = tid; e < n_ent; e += threads) {
@@ -219,12 +238,25 @@ __global__ __launch_bounds__(CHANCE_THREADS) void cilqr_chance_risk_kernel(Chanc
 
 size_t chance_risk_lds_bytes(int N, int M) { return ((size_t)33 * N + (size_t)M * N + 16) * sizeof(double); }
 
+namespace {
+int chance_threads(int N, int M) {
+  const long long work = (long long)N * (M > 1 ? M : 1);
+  const long long waves = (work + WAVE - 1) / WAVE;
+  return WAVE * (int)(waves < CHANCE_THREADS / WAVE ? waves : CHANCE_THREADS / WAVE);
+}
+}  // namespace
+
 hipError_t launch_chance_risk(const ChanceArgs& a, hipStream_t stream) {
   if (a.s.B <= 0) return hipSuccess;
-  const long long work = (long long)a.s.N * (a.s.M > 1 ? a.s.M : 1);
-  const long long waves = (work + WAVE - 1) / WAVE;
-  const int threads = WAVE * (int)(waves < CHANCE_THREADS / WAVE ? waves : CHANCE_THREADS / WAVE);
-  hipLaunchKernelGGL(cilqr_chance_risk_kernel, dim3((unsigned)a.s.B), dim3(threads), chance_risk_lds_bytes(a.s.N, a.s.M), stream, a);
+  hipLaunchKernelGGL(cilqr_chance_risk_kernel<false>, dim3((unsigned)a.s.B), dim3(chance_threads(a.s.N, a.s.M)), chance_risk_lds_bytes(a.s.N, a.s.M),
+                     stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_chance_risk_cov(const ChanceCovArgs& a, hipStream_t stream) {
+  if (a.s.B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cilqr_chance_risk_kernel<true>, dim3((unsigned)a.s.B), dim3(chance_threads(a.s.N, a.s.M)),
+                     chance_risk_lds_bytes(a.s.N, a.s.M), stream, a);
   return hipGetLastError();
 }
 

@@ -18,7 +18,7 @@
 namespace cilqr {
 
 struct HostPlan {
-  enum { CAP = 16 };  // (the largest call, the chance risk, declares 13 arrays)
+  enum { CAP = 16 };  // (the largest call, the chance risk with obs_cov, declares 14 arrays)
   struct Entry {
     const void* src;  // host source, null: nothing travels in
     void* dst;        // host destination, null: nothing travels back
@@ -199,7 +199,7 @@ inline void plan_rollout_risk_map(HostPlan& p, size_t B, size_t N, size_t S, siz
   p.out(total, B);
 }
 
-// cilqr_chance_risk: 13 arrays, the most any call declares; obstacle weights are not read and do not travel.  sigma_sets: B, or 1
+// cilqr_chance_risk: 13 arrays (cilqr_chance_risk_cov below declares one more, the most of any call); obstacle weights are not read and do not travel.  sigma_sets: B, or 1
 // for one Σ0 shared by the solves.  Per solve 15·N + 6·M·N + 28 doubles without sigma_out and entry_p — inside the 22·N + 6·M·N +
 // M + 34 per unit of max_batch that host_arena_bytes reserves below, for every B <= max_batch — and 31·N + 7·M·N + 44 with both,
 // which fits for every B <= max_batch / 2; the shared W and the 13 roundings stay within its 32 x 16 bytes and that margin.
@@ -220,6 +220,48 @@ inline void plan_chance_risk(HostPlan& p, size_t B, size_t N, size_t M, size_t s
   p.out(entry_p, B * M * N);
   p.out(sigma_out, B * (N + 1) * 16);
   p.out(total, B);
+}
+
+// cilqr_chance_risk_cov: the plan above with obs_cov, 3 doubles per entry of the span, behind the obstacles — 14 arrays.  With dense
+// obstacles 15·N + 9·M·N + 28 doubles per solve without sigma_out and entry_p and 31·N + 10·M·N + 44 with both: half of either is
+// inside what host_arena_bytes reserves below per unit of max_batch — the 22·N + 6·M·N + M + 34 of a solve, which the plans above
+// quote, and the 6·N + 16 of a row beside it: 28·N + 6·M·N + M + 50 — so every B <= max_batch / 2 fits.
+inline void plan_chance_risk_cov(HostPlan& p, size_t B, size_t N, size_t M, size_t sigma_sets, const double*& X, const double*& U,
+                                 const double*& K, const double*& sigma0, const double*& W, cilqr_obstacles& o, size_t span,
+                                 const double*& obs_cov, const double*& base, double*& risk, double*& step_risk, double*& entry_p,
+                                 double*& sigma_out, double*& total) {
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(K, B * 8 * N);
+  p.in(sigma0, sigma_sets * 16);
+  p.in(W, 16);
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, span, 0);
+  p.in(obs_cov, span * 3);
+  p.in(base, B);
+  p.out(risk, B * CILQR_CHANCE_FIELDS);
+  p.out(step_risk, B * N);
+  p.out(entry_p, B * M * N);
+  p.out(sigma_out, B * (N + 1) * 16);
+  p.out(total, B);
+}
+
+// cilqr_predict_obstacles: 8 arrays.  Per track 24 doubles in (state, dimensions, covariance) and 6·N out for the table, 3·N more
+// with cov_out and 16·N more with sigma_out; the shared noise is 16.  Against the same 28·N + 6·M·N + M + 50 per unit of max_batch
+// (22·N + 6·M·N + M + 34 per solve and 6·N + 16 per row) that host_arena_bytes reserves below at the create sizes: T·M·(24 + 25·N) + 16 with every output fits for every T <= max_batch/8
+// (M/8·(24 + 25·N) = 3·M + 3.125·M·N), T·M·(24 + 9·N) + 16 without sigma_out for every T <= max_batch/5 (4.8·M + 1.8·M·N); the 8
+// roundings stay within its 32 x 16 bytes.
+inline void plan_predict_obstacles(HostPlan& p, size_t T, size_t N, size_t M, const double*& track, const double*& track_dim,
+                                   const double*& track_cov, const double*& noise, double*& pose_out, double*& dim_out,
+                                   double*& cov_out, double*& sigma_out) {
+  p.in(track, T * M * 6);
+  p.in(track_dim, T * M * 2);
+  p.in(track_cov, T * M * 16);
+  p.in(noise, 16);
+  p.out(pose_out, T * M * 4 * N);
+  p.out(dim_out, T * M * 2 * N);
+  p.out(cov_out, T * M * 3 * N);
+  p.out(sigma_out, T * M * 16 * N);
 }
 
 // cilqr_tighten_obstacles: 8 arrays; obstacle weights are not read and do not travel; obs_cov travels as 3 doubles per entry of the

@@ -261,7 +261,35 @@ struct ChanceArgs {
   uint32_t flags;            // CILQR_CHANCE_*
 };
 hipError_t launch_chance_risk(const ChanceArgs& a, hipStream_t stream);
+// cilqr_chance_risk_cov: the same with the obstacles' own covariance, (xx, xy, yy) at obs_cov + 3e for the obstacle entry index e,
+// for the kernel's second instantiation (ChanceArgs stays as it is: so does the argument segment of the first)
+struct ChanceCovArgs : ChanceArgs {
+  const double* obs_cov;     // never null
+};
+template <bool COV> struct ChanceKernelArgs { typedef ChanceArgs type; };
+template <> struct ChanceKernelArgs<true> { typedef ChanceCovArgs type; };
+hipError_t launch_chance_risk_cov(const ChanceCovArgs& a, hipStream_t stream);
 size_t chance_risk_lds_bytes(int N, int M);
+
+// Constant-acceleration, constant-yaw-rate prediction of tracked obstacles with their covariance (cilqr_predict.hip;
+// cilqr_predict_obstacles*): one wavefront per track, `tracks` = T·M workgroups.
+constexpr int PREDICT_THREADS = 64;
+constexpr size_t PREDICT_LDS_MAX = 64 * 1024;
+struct PredictArgs {
+  const double* track;      // [tracks][6]
+  const double* track_dim;  // [tracks][2]
+  const double* track_cov;  // [tracks][16] or null (zero)
+  const double* noise;      // [16] or null (zero)
+  double* pose_out;         // [tracks][4N]
+  double* dim_out;          // [tracks][2N]
+  double* cov_out;          // [tracks][N][3] or null
+  double* sigma_out;        // [tracks][N][16] or null
+  double dt, half_dt2;
+  int32_t N;
+  long long tracks;
+};
+hipError_t launch_predict_obstacles(const PredictArgs& a, hipStream_t stream);
+size_t predict_lds_bytes(int N);
 
 // Chance-constraint tightening (cilqr_tighten.hip; cilqr_tighten_obstacles*): every obstacle entry's dimensions grown by kappa
 // standard deviations of the relative position along the ellipse's axes.  One workgroup per solve; `s` first, as in ChanceArgs.

@@ -46,13 +46,62 @@ void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
     if (o.dimension.rows != 2 || o.relative_pos_array.rows != 4 || o.dimension.cols < params.horizon ||
         o.relative_pos_array.cols < params.horizon)
       throw std::runtime_error("set_Obstacle: dimension must be 2×horizon and relative_pos_array 4×horizon");
+  if (tracked_horizon_ >= 0) obs_cov_.clear();  // (the covariance the prediction installed goes with its obstacles)
+  tracked_horizon_ = -1;
   obstacles_ = obstacles;
   pack_obstacles();
 }
 
 void iLQR::clear_Obstacle() {
+  if (tracked_horizon_ >= 0) obs_cov_.clear();
+  tracked_horizon_ = -1;
+  tracks_.clear(); track_dims_.clear(); track_cov_.clear(); track_Q_.clear();
   obstacles_.clear();
   pack_obstacles();
+}
+
+void iLQR::set_tracked_obstacles(const std::vector<double>& tracks, const std::vector<double>& dims, const std::vector<double>& cov,
+                                 const std::vector<double>& Q) {
+  const size_t M = tracks.size() / 6;
+  if (tracks.size() != 6 * M || dims.size() != 2 * M || (!cov.empty() && cov.size() != 16 * M) || (!Q.empty() && Q.size() != 16))
+    throw std::runtime_error("set_tracked_obstacles: needs 6 values per track, 2 dimensions, 16 covariance values or none, and 16 of Q or none");
+  if ((int)M > max_obstacles_) throw std::runtime_error("set_tracked_obstacles: more tracks than max_obstacles");
+  if (M == 0) { clear_Obstacle(); return; }
+  tracks_ = tracks; track_dims_ = dims; track_cov_ = cov; track_Q_ = Q;
+  install_tracked();
+}
+
+// The host form, in as few calls as the handle's arena allows: a call whose arrays do not fit is halved (a track's results depend on
+// that track alone, so the split changes no bit).
+void iLQR::install_tracked() {
+  const int N = params.horizon, M = (int)(tracks_.size() / 6);
+  std::vector<double> pose((size_t)M * 4 * N), dim((size_t)M * 2 * N), cov((size_t)M * 3 * N);
+  int chunk = M;
+  for (int m = 0; m < M;) {
+    const int n = chunk < M - m ? chunk : M - m;
+    const int rc = cilqr_predict_obstacles(h_, 1, N, n, &tracks_[(size_t)6 * m], &track_dims_[(size_t)2 * m],
+                                           track_cov_.empty() ? nullptr : &track_cov_[(size_t)16 * m], track_Q_.empty() ? nullptr : track_Q_.data(),
+                                           &pose[(size_t)m * 4 * N], &dim[(size_t)m * 2 * N], &cov[(size_t)m * 3 * N], nullptr);
+    if (rc == CILQR_ERR_ARG && n > 1 && strstr(cilqr_last_error(), "does not fit")) { chunk = (n + 1) / 2; continue; }
+    check(rc, "cilqr_predict_obstacles");
+    m += n;
+  }
+  obstacles_.clear();
+  for (int m = 0; m < M; ++m) {
+    Matrix d(2, N), r(4, N);
+    memcpy(d.a.data(), &dim[(size_t)m * 2 * N], (size_t)2 * N * sizeof(double));   // (column-major 2 x N is the table's [2N] row)
+    memcpy(r.a.data(), &pose[(size_t)m * 4 * N], (size_t)4 * N * sizeof(double));
+    obstacles_.emplace_back(params, d, r);
+  }
+  obs_cov_ = cov;
+  tracked_horizon_ = N;
+  pack_obstacles();
+}
+
+void iLQR::set_obstacle_covariance_check(bool on) {
+  const bool was = obs_cov_check_;
+  obs_cov_check_ = on;
+  if (was != on && cov_check_) reserve_noise_buffers();
 }
 
 void iLQR::set_uncertainty_map(const Uncertainty& u) {
@@ -153,6 +202,7 @@ void iLQR::pack_obstacles() {
 }
 
 cilqr_obstacles iLQR::obstacle_strides() {
+  if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();  // (the horizon changed: predict again)
   if (packed_horizon_ != params.horizon) pack_obstacles();  // (params is public: the horizon may have changed since set_Obstacle)
   cilqr_obstacles o{};
   o.pose = obs_pose_.data();
@@ -167,6 +217,7 @@ cilqr_obstacles iLQR::obstacle_strides() {
 
 void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double poly_coeffs[6],
                                    const std::vector<double>& x_local_plan) {
+  if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
   const int N = params.horizon, M = (int)obstacles_.size();
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
@@ -229,6 +280,7 @@ void iLQR::set_candidate_pick(CandidatePick pick, double max_collision) {
 }
 
 int iLQR::run_candidates(const std::vector<double>& ego_states) {
+  if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
@@ -539,6 +591,7 @@ void iLQR::reserve_noise_buffers() {
   // the covariance check's inputs and outputs
   L.s0 = take(cov_check_ ? 16 : 0); L.W = take(cov_check_ ? 16 : 0);
   L.crisk = take(cov_check_ ? B * CILQR_CHANCE_FIELDS : 0); L.cstep = take(cov_check_ ? B * N : 0);
+  L.ccov = take(cov_check_ && obs_cov_check_ ? M * N * 3 : 0);  // the obstacles' covariance for the judge (set_obstacle_covariance_check)
   // the map covariance check: every Sigma_t of the chance call, the nodes and weights, its outputs
   const size_t cm = cov_check_ && cmap_check_ ? 1 : 0, Q = cmap_weights_.size();
   L.csig = take(cm * B * (N + 1) * 16); L.qn = take(cm * Q * 3); L.qw = take(cm * Q);
@@ -586,7 +639,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   for (int b = 0; b < B; ++b)
     for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
   const cilqr_obstacles host_obs = obstacle_strides();
-  if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
+  if ((tighten_ || (cov_check_ && obs_cov_check_)) && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
   hip_check(hipSetDevice(device_), "hipSetDevice");
   hipStream_t st = (hipStream_t)noise_stream_;
   double* d = (double*)noise_dev_;
@@ -634,9 +687,17 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
     if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
     if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, cov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-    if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
-                                           cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
-                                           d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
+    // (the judge counts the obstacles' own covariance when asked to and one is set; its entries lie by the packed obstacles' strides)
+    const bool judge_cov = obs_cov_check_ && M > 0 && !obs_cov_packed_.empty();
+    if (judge_cov) up(L.ccov, obs_cov_packed_.data(), obs_cov_packed_.size());
+    if (!rc && judge_cov)
+      rc = cilqr_chance_risk_cov_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po, d + L.ccov,
+                                        cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
+                                        d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
+    else if (!rc)
+      rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
+                                    cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
+                                    d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
   } else if (n_samples_) {  // the same chain in the compact sampled form
     const int ns = n_samples_;
     const double w = sample_weight();

@@ -186,6 +186,21 @@ class iLQR {
   // per obstacle of set_Obstacle, in its order — 3 * M values, constant over the horizon, or 3 * M * horizon, obstacle-major.  Empty:
   // none (the default).  A size that matches neither makes the next run throw std::runtime_error.
   void set_obstacle_covariance(const std::vector<double>& cov);
+  // Tracked obstacles: what a tracker hands over once per tick in place of a finished table.  tracks holds 6 values per vehicle,
+  // (x, y, v, theta, a, omega); dims 2, (length, width); cov 16, P_0 column-major over (x, y, v, theta) (only row <= column is read),
+  // or empty: none; Q 16 values added per step, or empty: none.  The vehicles are predicted over params.horizon by
+  // cilqr_predict_obstacles (the host form; see include/cilqr.h for the model) and the result is installed where set_Obstacle and
+  // set_obstacle_covariance (its 3 * M * horizon form) would put it: every later call behaves as if those two had been called with
+  // the predicted table and (xx, xy, yy) of every P_t.  When params.horizon has changed by the next run the vehicles are predicted
+  // again.  clear_Obstacle removes the tracks, the obstacles and that covariance; set_Obstacle replaces the obstacles and removes the
+  // covariance the prediction installed.  A size that does not match throws std::runtime_error.
+  void set_tracked_obstacles(const std::vector<double>& tracks, const std::vector<double>& dims, const std::vector<double>& cov,
+                             const std::vector<double>& Q);
+  // Off (the default): nothing changes.  On: the judge of set_pose_covariance_check is cilqr_chance_risk_cov_device with whatever
+  // obstacle covariance is set (set_obstacle_covariance, set_tracked_obstacles); with none set it is cilqr_chance_risk_device as
+  // before.  Under set_chance_tightening the final plan is then judged against the ORIGINAL obstacles WITH their covariance — what
+  // the tightening inflated them by.  A covariance whose size matches neither form makes the next run throw std::runtime_error.
+  void set_obstacle_covariance_check(bool on);
   // Map tightening: the map counterpart of set_chance_tightening, for the configuration the live node runs — no obstacle set, the
   // blurred costmap of set_uncertainty_map the planner's only obstacle information — where every check above can only reject.  Sigma0,
   // W, eps, rounds and lamb as in set_chance_tightening.  While it and an uncertainty map are set, run_step (get_optimal_control_seq)
@@ -283,8 +298,13 @@ class iLQR {
   // so that this header needs no HIP
   struct NoiseLayout {
     size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
-        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, end;
+        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, ccov, end;
   };
+  // tracked obstacles (set_tracked_obstacles): the inputs as given, and the horizon they were last predicted over (-1: none set)
+  std::vector<double> tracks_, track_dims_, track_cov_, track_Q_;
+  int tracked_horizon_ = -1;
+  void install_tracked();  // predicts over params.horizon and fills obstacles_, obs_cov_ and the packed forms
+  bool obs_cov_check_ = false;  // set_obstacle_covariance_check
   // obstacle samples (set_obstacle_samples): the offsets [n_obs][n_samples][3]; n_samples_ == 0: none
   std::vector<double> samples_;
   int n_samples_ = 0;
