@@ -849,6 +849,90 @@ int cilqr_tighten_map_device(cilqr_handle* h, void* stream, int B, int N, const 
 int cilqr_tighten_map(cilqr_handle* h, int B, int N, const double* X, const double* sigma, double kappa, double max_inflate,
                       float* layer_out, double* tighten);
 
+/* --- predicted tracks rasterised into the costmap along each plan, for a re-solve (new) -------------------------------------------
+ * cilqr_predict_obstacles predicts every tracked vehicle over the horizon with its covariance; its one consumer,
+ * cilqr_chance_risk_cov, reads ellipses.  In the reference's live node that channel is off and the blurred costmap of
+ * cilqr_set_uncertainty_map is the planner's only obstacle information; a tracked vehicle enters that map in one way only:
+ * bondingBoxHandle (here cilqr_rasterize_polygons) paints its box where it is NOW — certain, and it does not move.  So the whole map
+ * branch (the map cost in the solve, cilqr_rollout_risk_map, cilqr_chance_risk_map, cilqr_tighten_map) never sees where a mover will be
+ * or how sure the tracker is of it.  cilqr_rasterize_tracks(_device) writes, per solve, a copy of the layer set on the handle in which
+ * every cell is raised to 100 x the probability that a predicted vehicle covers it, taken at the steps when THAT solve's plan is near
+ * the cell.  The layers go where cilqr_tighten_map's go:  predict -> solve -> cilqr_rasterize_tracks -> cilqr_set_uncertainty_map_device
+ * (layer_out, layer_stride = rows*cols, the same geometry, poses and probes) -> solve, warm-started from the plan's U.  No solve kernel
+ * changes.  With X == NULL the same kernel sweeps the whole horizon (swept mode): the stripe a crossing vehicle paints, for a published
+ * predicted-occupancy grid; with zero covariance and inflate 0 its cells at 100 are the cells cilqr_rasterize_polygons marks for the
+ * union of the boxes.
+ * obs, obs_cov: exactly what cilqr_chance_risk_cov takes — pose [4N] and dim [2N] rows addressed by the strides of cilqr_obstacles,
+ * obs_cov 3 doubles (xx, xy, yy) at the pose's entry index or NULL for zero; weight is not read.  Strides (0, N, 1) give one
+ * predicted set for all solves: what cilqr_predict_obstacles writes at T = 1.  Entry t belongs to X_t, as that call defines it.  Map,
+ * geometry, layer_stride and poses are those CURRENTLY SET on the handle, indexed by the solve as cilqr_tighten_map indexes them.
+ * layer_out [B][rows*cols] float32, dense, column-major like the input; it must not overlap the set layer.  X [B][4*(N+1)], the
+ * plan, or NULL: swept mode.
+ *
+ * Definition for solve b and cell (i, j).  Every formula is evaluated in double as C evaluates it as written, left to right, with
+ * no fused multiply-add.
+ *   cell centre    m = (x_first - i*res, y_first - j*res) as in cilqr_tighten_map, then taken into the planning frame with c, s the
+ *              cosine and sine of the solve's map pose heading (obtained as the other map calls obtain them):
+ *                w = (pose.x + (c*m.x - s*m.y),  pose.y + (s*m.x + c*m.y)).
+ *   entry      e = m*N + t, t = 0 ... N-1, of track m: centre o = (pose[0], pose[1]), heading th = pose[3], co = cos th, so = sin th;
+ *                hl = (length + inflate)/2,   hw = (width + inflate)/2      (bondingBoxHandle's rule, whose inflate is 0.2);
+ *              with d = w - o the body-frame offsets   du = co*d.x + so*d.y,   dw = co*d.y - so*d.x;   with cc = co*co, ss = so*so,
+ *              cs = co*so the variances along the body axes
+ *                su2 = cc*Cxx + 2*cs*Cxy + ss*Cyy,   sw2 = ss*Cxx - 2*cs*Cxy + cc*Cyy,   su = sqrt(max(su2, 0)), sw likewise.
+ *              An entry whose x, y, th, length, width, Cxx, Cxy or Cyy is not finite is LOST and takes no part.
+ *   reach      the entry contributes to the cell only if |du| <= hl + z_max*su and |dw| <= hw + z_max*sw.
+ *   marginals  with ku = 1/(su*sqrt 2) where su >= 1e-150:   Pu = 0.5*(erf((du + hl)*ku) - erf((du - hl)*ku));
+ *              where su < 1e-150 (it counts as 0: its reciprocal would not be finite) Pu = 1 if |du| <= hl, else 0.  Pw likewise.
+ *                p = Pu*Pw                 exact when the covariance is diagonal in the vehicle's frame;
+ *                p = min(Pu, Pw)           under CILQR_TRACK_MAP_BOUND_MIN: an upper bound on the covered probability whatever the
+ *                                          correlation (the box is inside either strip).
+ *              LEFT OUT: the uncertainty of the track's heading and of its size.  The box is taken at its predicted heading.
+ *   steps      X == NULL: every t takes part.  Otherwise t* is the plan's nearest live step to the cell by cilqr_tighten_map's rule:
+ *              p_t = R'(X_t.xy - pose.xy) for t < N against m in the map frame, the smallest ex*ex + ey*ey, strict <, lowest t on
+ *              equal values; a step whose X_t[0] or X_t[1] is not finite is LOST.  The entries with
+ *              max(0, t* - window) <= t <= min(N-1, t* + window) take part.  With no live step out = in for every cell.
+ *   output     v = (float)(100*max p) over the contributing entries (0 when none).  Where v is 0, out is a bit copy of in: unknown
+ *              stays unknown.  Otherwise out = v where in is NaN, else the larger of in and v.
+ * What this is: a soft, first-order, time-windowed occupancy.  A cell far from the plan takes the window of a step that never
+ * reaches it: harmless, and it raises TKM_RAISED.  It guarantees nothing.  Judge the final plan against the tracks themselves
+ * (cilqr_chance_risk_cov) and the ORIGINAL map, always.
+ * fields [B][CILQR_TRACK_MAP_FIELDS] (required), see the enum.  Maxima are lexicographic, counts are integers: the largest v, at the
+ * lowest cell that has it, with the entry that gave THAT cell its p (the lowest e among the cell's largest p).
+ *   A solve's bits do not depend on B, on its place in the batch, or on whether layer, pose and tracks are shared or repeated per
+ *   solve.  (A per-solve pose's cosine and sine are formed on the device, the shared pose's on the host, as for every map call.)
+ * Mapping: three launches, no atomics, nothing allocated per call.  One lane per entry forms its record (10 doubles, in the planning
+ * frame: it depends on neither the map pose nor the solve) — ONE set per call when batch_stride is 0, else one per solve — in device
+ * memory the handle reserved at create (10*max_batch*max_obstacles*max_horizon doubles).  Then lane = cell: a solve has
+ * G = min(ceil(rows*cols/256), 64) workgroups of 256 lanes that stride over its cells; the plan's positions are staged once per
+ * workgroup in LDS, which the search over t reads at one address per wavefront; a cell then reads (2*window + 1)*M records, in swept
+ * mode all M*N.  Each workgroup leaves one record of 4 doubles (256*max_batch doubles reserved at create), merged by one wavefront
+ * per solve.  A cilqr_rasterize_tracks on ANOTHER stream of the same handle must not run beside it; every other call may.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL obs, obs->pose, obs->dim, layer_out or fields; B, N or M below 1; an
+ * inflate or z_max that is negative or not finite; a negative window; a negative stride; a flag bit other than
+ * CILQR_TRACK_MAP_BOUND_MIN.  Then: B, N or M beyond the cilqr_create limits; no uncertainty map set on the handle (the message says
+ * so); layer_out overlapping the set layer; a map of 2^31 cells or more, or B*G beyond 2^31 - 1.  The host-buffer form stages
+ * layer_out through the device arena reserved at create and adds nothing to it: its arrays take B*(4*N + 10 + rows*cols/2) doubles (6
+ * without X) and 9 per entry of the span the strides address (6 without obs_cov), CILQR_ERR_ARG where they do not fit.  With one
+ * shared set of M tracks on the node's 150 x 100 map at N = 50, M = 8: every B <= max_batch/8 fits on a handle of max_batch >= 8.
+ * The device form is the production path.
+ * CILQR_ERR_UNSUPPORTED where the kernel's LDS, 8*(2*N + 20) bytes, exceeds 64 KiB: N above 4086, which CILQR_MAX_HORIZON = 384 keeps
+ * out of reach — every (N, M) a handle accepts runs. */
+#define CILQR_TRACK_MAP_FIELDS 6
+typedef enum cilqr_track_map_field {
+  CILQR_TKM_RAISED = 0,       /* cells whose output differs from the input (integer count) */
+  CILQR_TKM_MAX_VALUE = 1,    /* largest v of the solve (0..100), 0 when none */
+  CILQR_TKM_MAX_CELL = 2,     /* i + rows*j of it, lowest on equal values; -1 when none */
+  CILQR_TKM_MAX_ENTRY = 3,    /* m*N + t of the entry that gave it, lowest on equal values; -1 when none */
+  CILQR_TKM_LOST_ENTRIES = 4, /* entries that took no part (not finite) */
+  CILQR_TKM_LOST_STEPS = 5    /* plan steps that took no part; 0 in swept mode */
+} cilqr_track_map_field;
+#define CILQR_TRACK_MAP_BOUND_MIN 1u
+int cilqr_rasterize_tracks_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const cilqr_obstacles* obs,
+                                  const double* obs_cov, double inflate, double z_max, int window, uint32_t flags, float* layer_out,
+                                  double* fields);
+int cilqr_rasterize_tracks(cilqr_handle* h, int B, int N, int M, const double* X, const cilqr_obstacles* obs, const double* obs_cov,
+                           double inflate, double z_max, int window, uint32_t flags, float* layer_out, double* fields);
+
 /* --- analytic map risk: the pose covariance against the uncertainty map by quadrature (new) ---------------------------------------
  * cilqr_chance_risk stops at the ellipses; in the reference's live node that channel is off and the blurred costmap is the only
  * obstacle information (see cilqr_rollout_risk_map), for which the only risk call so far is the sampled one: risk in steps of 1/S,

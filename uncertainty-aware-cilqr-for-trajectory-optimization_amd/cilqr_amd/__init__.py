@@ -44,6 +44,10 @@ TG_MAX_DA, TG_MAX_DB, TG_MAX_ENTRY, TG_CAPPED = range(TIGHTEN_FIELDS)
 # `cilqr_tighten_map_field`: the columns of a map tightening row (`Solver.tighten_map`)
 TIGHTEN_MAP_FIELDS = 6
 TM_RAISED, TM_MAX_RAISE, TM_MAX_CELL, TM_MAX_REACH, TM_CAPPED, TM_LOST = range(TIGHTEN_MAP_FIELDS)
+# `cilqr_track_map_field`: the columns of a track rasterisation row (`Solver.rasterize_tracks`)
+TRACK_MAP_FIELDS = 6
+TKM_RAISED, TKM_MAX_VALUE, TKM_MAX_CELL, TKM_MAX_ENTRY, TKM_LOST_ENTRIES, TKM_LOST_STEPS = range(TRACK_MAP_FIELDS)
+TRACK_MAP_BOUND_MIN = 1  # flags of `rasterize_tracks`: p = min(Pu, Pw), an upper bound whatever the correlation
 
 # `cilqr_chance_map_field`: the columns of an analytic map risk row (`Solver.chance_risk_map`)
 CHANCE_MAP_FIELDS = 8
@@ -79,6 +83,7 @@ ABI_SYMBOLS = (
     "cilqr_chance_risk", "cilqr_chance_risk_device",
     "cilqr_tighten_obstacles", "cilqr_tighten_obstacles_device", "cilqr_chance_kappa",
     "cilqr_tighten_map", "cilqr_tighten_map_device",
+    "cilqr_rasterize_tracks", "cilqr_rasterize_tracks_device",
     "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
     "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
     "cilqr_predict_obstacles", "cilqr_predict_obstacles_device", "cilqr_chance_risk_cov", "cilqr_chance_risk_cov_device",
@@ -931,6 +936,40 @@ class Solver:
         layer_stride = rows*cols."""
         _check(lib().cilqr_tighten_map_device(self._h, _vp(stream), int(B), int(N), _vp(X), _vp(sigma), C.c_double(kappa),
                                               C.c_double(max_inflate), _vp(layer_out), _vp(tighten)))
+
+    # ---- predicted tracks rasterised into the set uncertainty map along each plan, for a warm-started re-solve ----
+    def rasterize_tracks(self, N, shape, obs_pose, obs_dim, obs_cov=None, X=None, B=None, inflate=0.2, z_max=3.0, window=2,
+                         bound_min=False):
+        """`cilqr_rasterize_tracks`: tracks in any shape of `obstacle_strides` (what `predict_obstacles` returns serves as it is), obs_cov
+        None or 3 values per entry in the tracks' own shape; X (B, 4(N+1)) the plans, or None with B given: swept mode; shape =
+        (rows, cols) of the map set on the handle.  Returns dict(layer (B, rows, cols) float32, fields (B, TRACK_MAP_FIELDS)).  The
+        layers travel through the device arena: large batches take the device form."""
+        if X is not None:
+            X = _np64(X)
+            B = X.size // (4 * (N + 1))
+            X = X.reshape(B, 4 * (N + 1))
+        B = int(B)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        obs_cov = None if obs_cov is None else _np64(obs_cov)
+        if obs_cov is not None and obs_cov.size * 4 != keep[0].size * 3:
+            raise CilqrError("rasterize_tracks: obs_cov %s does not hold 3 values per entry of obs_pose %s" % (obs_cov.shape, keep[0].shape))
+        rows, cols = int(shape[0]), int(shape[1])
+        flat = np.zeros((B, rows * cols), dtype=np.float32)
+        fields = np.zeros((B, TRACK_MAP_FIELDS))
+        _check(lib().cilqr_rasterize_tracks(self._h, B, int(N), int(M), _p(X), None if obs is None else C.byref(obs), _p(obs_cov),
+                                            C.c_double(inflate), C.c_double(z_max), int(window),
+                                            C.c_uint32(TRACK_MAP_BOUND_MIN if bound_min else 0), _p(flat, _fp), _p(fields)))
+        return dict(layer=flat.reshape(B, cols, rows).transpose(0, 2, 1), fields=fields)
+
+    def rasterize_tracks_device(self, stream, B, N, M, X, obs_pose, obs_dim, strides, layer_out, fields, obs_cov=0, inflate=0.2,
+                                z_max=3.0, window=2, flags=0):
+        """`cilqr_rasterize_tracks_device`: device addresses; X 0: swept mode; strides (batch, obstacle, step, weight batch) as
+        `score_batch_device`; layer_out (B, rows*cols) float32 feeds `set_uncertainty_map_device` with layer_stride = rows*cols."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_rasterize_tracks_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), C.byref(obs), _vp(obs_cov),
+                                                   C.c_double(inflate), C.c_double(z_max), int(window), C.c_uint32(int(flags)),
+                                                   _vp(layer_out), _vp(fields)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -279,6 +279,8 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   if (err == hipSuccess) err = dmalloc(&h->d_chance_map_steps, 3 * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_sampled_steps, cilqr::CHANCE_SAMPLED_REC * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_tighten_map_part, (size_t)cilqr::TIGHTEN_MAP_REC * cilqr::TIGHTEN_MAP_MAX_G * B);
+  if (err == hipSuccess) err = dmalloc(&h->d_track_map_rec, (size_t)cilqr::TRACK_MAP_ENTRY * B * M * N);
+  if (err == hipSuccess) err = dmalloc(&h->d_track_map_part, (size_t)cilqr::TRACK_MAP_REC * cilqr::TRACK_MAP_MAX_G * B);
   if (err == hipSuccess) err = dmalloc(&h->d_triple, (size_t)3);
   if (err == hipSuccess) err = dmalloc(&h->d_gather, (size_t)3);
   h->comm_ranks = 1;
@@ -310,7 +312,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_tighten_map_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_tighten_map_part, h->d_track_map_rec, h->d_track_map_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1372,6 +1374,83 @@ int cilqr_tighten_map(cilqr_handle* h, int B, int N, const double* X, const doub
   cilqr::HostPlan p(h->d_arena);
   cilqr::plan_tighten_map(p, B, N, (size_t)h->unc.rows * h->unc.cols, X, sigma, layer_out, tighten);
   return cilqr::host_call(h, p, [&] { return cilqr_tighten_map_device(h, h->stream, B, N, X, sigma, kappa, max_inflate, layer_out, tighten); });
+}
+
+// ---- predicted tracks rasterised into the map along each plan (cilqr_track_map.hip) ---------------------------------------------------
+namespace {
+// what needs no handle
+int track_map_args_check(int B, int N, int M, const cilqr_obstacles* obs, double inflate, double z_max, int window, uint32_t flags,
+                         const float* layer_out, const double* fields) {
+  if (!obs || !obs->pose || !obs->dim || !layer_out || !fields) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: null required pointer");
+  if (B < 1 || N < 1 || M < 1) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: B = %d, N = %d, M = %d: each must be at least 1", B, N, M);
+  if (!(inflate >= 0.0 && inflate <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: inflate is negative or not finite");
+  if (!(z_max >= 0.0 && z_max <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: z_max is negative or not finite");
+  if (window < 0) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: window is negative");
+  if (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0)
+    return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: negative stride");
+  if (flags & ~CILQR_TRACK_MAP_BOUND_MIN) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int track_map_handle_check(const cilqr_handle* h, int B, int N, int M, const cilqr_obstacles* obs, size_t* span) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, nullptr);
+  if (rc) return rc;
+  if (!h->unc.layer) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: no uncertainty map is set on the handle");
+  if ((int64_t)h->unc.rows * h->unc.cols > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: the map has 2^31 cells or more");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_rasterize_tracks_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* X, const cilqr_obstacles* obs,
+                                  const double* obs_cov, double inflate, double z_max, int window, uint32_t flags, float* layer_out,
+                                  double* fields) {
+  int rc = track_map_args_check(B, N, M, obs, inflate, z_max, window, flags, layer_out, fields);
+  if (rc) return rc;
+  rc = track_map_handle_check(h, B, N, M, obs, nullptr);
+  if (rc) return rc;
+  const size_t cells = (size_t)h->unc.rows * h->unc.cols;
+  {  // the output must not be the layer the call reads
+    const float* in0 = h->unc.layer;
+    const float* in1 = in0 + (size_t)(B - 1) * (size_t)h->unc.stride + cells;
+    if (layer_out < in1 && in0 < layer_out + (size_t)B * cells)
+      return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: layer_out overlaps the layer set on the handle");
+  }
+  if (cilqr::track_map_lds_bytes(N) > cilqr::TRACK_MAP_LDS_MAX)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_rasterize_tracks: horizon %d does not fit 64 KiB of LDS", N);
+  cilqr::TrackMapArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.X = X; a.obs_cov = obs_cov; a.inflate = inflate; a.z_max = z_max; a.res = h->unc_res;
+  a.layer_out = layer_out; a.fields = fields;
+  a.records = h->d_track_map_rec;    // (reserved at create: max_batch sets of max_obstacles·max_horizon records)
+  a.partials = h->d_track_map_part;  // (reserved at create: TRACK_MAP_MAX_G records per solve of max_batch)
+  const size_t tiles = (cells + cilqr::TRACK_MAP_THREADS - 1) / cilqr::TRACK_MAP_THREADS;
+  a.G = (int)(tiles < (size_t)cilqr::TRACK_MAP_MAX_G ? tiles : (size_t)cilqr::TRACK_MAP_MAX_G);
+  a.window = window < N ? window : N;  // (beyond N - 1 every step takes part: the sums of the kernel stay inside an int)
+  a.sets = obs->batch_stride == 0 ? 1 : B;
+  a.flags = flags;
+  const int64_t chunks = ((int64_t)M * N + cilqr::TRACK_MAP_THREADS - 1) / cilqr::TRACK_MAP_THREADS;
+  if ((int64_t)B * a.G > 0x7fffffff || (int64_t)a.sets * chunks > 0x7fffffff || (int64_t)M * N > 0x7fffffff)
+    return fail(CILQR_ERR_ARG, "cilqr_rasterize_tracks: B * %d workgroups per solve, or the entries' workgroups, beyond 2^31 - 1", a.G);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_rasterize_tracks(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_rasterize_tracks(cilqr_handle* h, int B, int N, int M, const double* X, const cilqr_obstacles* obs, const double* obs_cov,
+                           double inflate, double z_max, int window, uint32_t flags, float* layer_out, double* fields) {
+  int rc = track_map_args_check(B, N, M, obs, inflate, z_max, window, flags, layer_out, fields);
+  if (rc) return rc;
+  size_t span = 0;
+  rc = track_map_handle_check(h, B, N, M, obs, &span);
+  if (rc) return rc;
+  cilqr_obstacles o = *obs;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_rasterize_tracks(p, B, N, (size_t)h->unc.rows * h->unc.cols, X, o, span, obs_cov, layer_out, fields);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_rasterize_tracks_device(h, h->stream, B, N, M, X, &o, obs_cov, inflate, z_max, window, flags, layer_out, fields);
+  });
 }
 
 // ---- analytic map risk (cilqr_chance_map.hip) ------------------------------------------------------------------------------------------

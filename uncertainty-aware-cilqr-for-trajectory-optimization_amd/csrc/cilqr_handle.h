@@ -84,6 +84,8 @@ struct cilqr_handle {
   size_t risk_part_stride;  // 8 + ceil(max_horizon / 2)
   double* d_chance_map_steps;  // per-step values of cilqr_chance_risk_map the caller did not ask for: 3 x max_batch x max_horizon doubles
   double* d_tighten_map_part;  // workgroup records of cilqr_tighten_map: max_batch x TIGHTEN_MAP_MAX_G x TIGHTEN_MAP_REC doubles
+  double* d_track_map_rec;   // entry records of cilqr_rasterize_tracks: max_batch x max_obstacles x max_horizon x TRACK_MAP_ENTRY doubles
+  double* d_track_map_part;  // its workgroup records: max_batch x TRACK_MAP_MAX_G x TRACK_MAP_REC doubles
   double* d_chance_sampled_steps;  // step records of cilqr_chance_risk_sampled: CHANCE_SAMPLED_REC x max_batch x max_horizon doubles
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;

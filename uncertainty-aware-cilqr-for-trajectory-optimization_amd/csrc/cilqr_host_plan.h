@@ -291,6 +291,22 @@ inline void plan_tighten_map(HostPlan& p, size_t B, size_t N, size_t cells, cons
   p.out(tighten, B * CILQR_TIGHTEN_MAP_FIELDS);
 }
 
+// cilqr_rasterize_tracks: 6 arrays; the map is the handle's; obstacle weights are not read and do not travel; obs_cov travels as 3
+// doubles per entry of the span.  Per solve 4·N + 10 doubles — X, the fields row — and one output layer of `cells` floats, cells/2
+// doubles; the tracks are 9 doubles per entry of the span, M·N entries for one shared set: B·(4·N + 10 + cells/2) + 9·span doubles
+// against the 28·N + 6·M·N + M + 50 per unit of max_batch that host_arena_bytes reserves below at create sizes that admit the call.
+// On the node's 150 x 100 map at N = 50 with one shared set of 8 tracks every B <= max_batch/8 fits once max_batch >= 8; the 6
+// roundings stay within its 32 x 16 bytes.
+inline void plan_rasterize_tracks(HostPlan& p, size_t B, size_t N, size_t cells, const double*& X, cilqr_obstacles& o, size_t span,
+                                  const double*& obs_cov, float*& layer_out, double*& fields) {
+  p.in(X, B * 4 * (N + 1));
+  o.weight = nullptr;
+  plan_obstacles(p, 1, o, span, 0);
+  p.in(obs_cov, span * 3);
+  p.out(layer_out, B * cells);
+  p.out(fields, B * CILQR_TRACK_MAP_FIELDS);
+}
+
 // cilqr_chance_risk_map: 10 arrays; the map is the handle's and no gain travels.  Per solve 20·N + 30 doubles — X, sigma, base, the
 // risk row, total — and 3·N more with the three per-step outputs; the Q nodes and weights, shared by the batch, are 4·Q doubles.
 // Against the 22·N + 34 per unit of max_batch that host_arena_bytes reserves below: without per-step outputs every B <= max_batch

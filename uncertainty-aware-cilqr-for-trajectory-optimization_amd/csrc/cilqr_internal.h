@@ -329,6 +329,37 @@ struct TightenMapArgs {
 hipError_t launch_tighten_map(const TightenMapArgs& a, hipStream_t stream);
 size_t tighten_map_lds_bytes(int N);
 
+// Predicted tracks rasterised into the map along each plan (cilqr_track_map.hip; cilqr_rasterize_tracks*): per solve a copy of the
+// layer set on the handle, every cell raised to 100 x the probability that a predicted vehicle covers it.  Three launches:
+//   records  one lane per entry e = m·N + t: the entry's record of TRACK_MAP_ENTRY doubles in the planning frame, into `records`;
+//            `sets` = 1 record set when the obstacles' batch stride is 0, else one per solve
+//   cells    lane = cell; solve b has G workgroups of TRACK_MAP_THREADS lanes that stride over its cells (the G of the map
+//            tightening: a function of the map alone) and leave one record of TRACK_MAP_REC doubles each in `partials`
+//   finish   one wavefront per solve merges the G records and counts the lost entries
+// `s` carries B, N, M, the strided obstacle fields and unc.
+constexpr int TRACK_MAP_THREADS = 256;
+constexpr int TRACK_MAP_ENTRY = 10;  // o.x, o.y, cos, sin, hl, hw, 1/(su·sqrt 2), 1/(sw·sqrt 2), reach along, reach across (-1: lost)
+constexpr int TRACK_MAP_REC = 4;     // raised count, largest v, its cell, the entry that gave it
+constexpr int TRACK_MAP_MAX_G = 64;
+constexpr int TRACK_MAP_STEP = 2;    // doubles per plan step in LDS: p_t in the map frame
+constexpr int TRACK_MAP_POSE = 4;    // doubles of the solve's map pose in LDS: position, cos and sin of its heading
+constexpr size_t TRACK_MAP_LDS_MAX = 64 * 1024;
+struct TrackMapArgs {
+  SolveArgs s;
+  const double* X;         // [B][4(N + 1)], or null: swept mode
+  const double* obs_cov;   // null (zero), or (xx, xy, yy) at obs_cov + 3e for the obstacle entry index e
+  double inflate, z_max;
+  double res;              // the map's resolution as it was set
+  float* layer_out;        // [B][rows·cols]
+  double* fields;          // [B][CILQR_TRACK_MAP_FIELDS]
+  double* records;         // the handle's: sets·M·N records of TRACK_MAP_ENTRY doubles
+  double* partials;        // the handle's: B·G records of TRACK_MAP_REC doubles
+  int32_t G, window, sets; // window already clamped to N
+  uint32_t flags;          // CILQR_TRACK_MAP_*
+};
+hipError_t launch_rasterize_tracks(const TrackMapArgs& a, hipStream_t stream);
+size_t track_map_lds_bytes(int N);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

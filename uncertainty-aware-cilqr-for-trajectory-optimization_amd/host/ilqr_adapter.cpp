@@ -127,12 +127,13 @@ cilqr_uncertainty_map map_of(const Uncertainty& u, const float* layer, int64_t l
 // Without the map tightening: the host form, the handle keeps its own device copy.  With it: the layer is copied into map_dev_, in
 // front of one tightened layer per candidate, and the handle is pointed there, so that the rounds can swap layers without a copy.
 void iLQR::apply_map(const Uncertainty& u) {
-  if (!map_tighten_) {
+  if (!map_in_block()) {
     const cilqr_uncertainty_map m = map_of(u, u.layer.data(), 0);
     check(cilqr_set_uncertainty_map(h_, &m), "cilqr_set_uncertainty_map");
     return;
   }
-  const size_t cells = (size_t)u.geom.rows * u.geom.cols, need = cells * (1 + (size_t)max_candidates_);
+  // (with the track map beside the map tightening a round keeps two layers per candidate: the rasterised one and the tightened one)
+  const size_t cells = (size_t)u.geom.rows * u.geom.cols, need = cells * (1 + (size_t)max_candidates_ * (map_tighten_ && tm_rounds_ > 0 ? 2 : 1));
   if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error("set_uncertainty_map: hipSetDevice failed");
   if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);  // nothing enqueued may still read the old block
   if (need > map_dev_cap_) {
@@ -222,7 +223,7 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
-  if (tighten_ || map_tighten_) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
+  if (tighten_ || map_tighten_ || track_map_on()) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
   if (n_samples_) {
@@ -284,8 +285,10 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
+  if (scov_check_ && track_map_on())
+    throw std::logic_error("set_track_map has no form for sampled obstacles (set_obstacle_samples), like set_map_tightening");
   if (scov_check_) return run_candidates_sample_covariance(B, ego_states);
-  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_) return run_candidates_noise_checked(B, ego_states);
+  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_ || track_map_on()) return run_candidates_noise_checked(B, ego_states);
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
@@ -360,6 +363,12 @@ const char* const kMapTighteningWithSamples =
 const char* const kTighteningsDisagree =
     "set_chance_tightening and set_map_tightening are both set and must agree on Sigma0, W, lamb and rounds: one covariance chain and one "
     "re-solve per round serve both";
+const char* const kTrackMapWithSamples =
+    "set_track_map has no form for sampled obstacles (set_obstacle_samples), like set_map_tightening";
+const char* const kTrackMapRoundsDisagree =
+    "set_track_map beside set_chance_tightening or set_map_tightening: one re-solve per round serves them all, so the round counts must agree";
+const char* const kTrackMapEllipsesOffTightened =
+    "set_track_map with ellipses = false beside set_chance_tightening: the solves read no ellipse that the tightening could inflate";
 const char* const kCovarianceWithSamples =
     "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
 const char* const kSampleCovarianceWithNoise =
@@ -384,7 +393,7 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
   }
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+  if (!noise_.empty() || cov_check_ || rounds_on()) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
 }
 
 int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
@@ -423,7 +432,7 @@ void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_r
   noise_fused_ = false;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || tighten_ || map_tighten_) reserve_noise_buffers();
+  if (!noise_.empty() || rounds_on()) reserve_noise_buffers();
 }
 
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
@@ -436,7 +445,7 @@ void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double
   noise_fused_ = true;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || tighten_ || map_tighten_) reserve_noise_buffers();
+  if (!noise_.empty() || rounds_on()) reserve_noise_buffers();
 }
 
 void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits) {
@@ -463,7 +472,7 @@ void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, d
   cov_sum_ = sum_bound;
   last_chance_risk.clear();
   last_step_risk.clear();
-  if (cov_check_ || tighten_ || map_tighten_) reserve_noise_buffers();
+  if (cov_check_ || rounds_on()) reserve_noise_buffers();
 }
 
 void iLQR::set_sample_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
@@ -524,7 +533,7 @@ void iLQR::set_chance_tightening(const double Sigma0[16], const double* W, doubl
   tg_cap_ = max_inflate;
   last_tighten.clear();
   last_tighten_risk_before.clear();
-  if (tighten_ || map_tighten_) reserve_noise_buffers();
+  if (rounds_on()) reserve_noise_buffers();
 }
 
 void iLQR::check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const {
@@ -555,8 +564,27 @@ void iLQR::set_map_tightening(const double Sigma0[16], const double* W, double e
   mt_cap_ = max_inflate;
   last_tighten_map.clear();
   last_tighten_map_risk_before.clear();
-  if (was != on && map_set_) apply_map(unc_);  // the layer moves to this object's device block, or back to the handle's
-  if (tighten_ || map_tighten_) reserve_noise_buffers();
+  if (map_set_ && (was != on || map_in_block())) apply_map(unc_);  // the layer moves to this object's device block, or back to the handle's
+  if (rounds_on()) reserve_noise_buffers();
+}
+
+void iLQR::set_track_map(double inflate, double z_max, int window, int rounds, bool ellipses) {
+  if (rounds < 0 || window < 0 || !(inflate >= 0.0 && inflate <= 1.7e308) || !(z_max >= 0.0 && z_max <= 1.7e308))
+    throw std::runtime_error("set_track_map: rounds and window must not be negative, inflate and z_max neither negative nor not finite");
+  const bool was = map_in_block();
+  tm_rounds_ = rounds; tm_window_ = window; tm_inflate_ = inflate; tm_z_max_ = z_max; tm_ellipses_ = ellipses;
+  last_track_map.clear();
+  if (map_set_ && (was != map_in_block() || map_in_block())) apply_map(unc_);  // the layer moves to this object's device block, or back
+  if (rounds_on()) reserve_noise_buffers();
+}
+
+// Before anything is enqueued: what a run under set_track_map cannot be combined with.
+void iLQR::check_track_map_conflicts() const {
+  if (!track_map_on()) return;
+  if (n_samples_) throw std::logic_error(kTrackMapWithSamples);
+  const bool obs_on = tighten_ && !obstacles_.empty(), map_on = map_tightened();
+  if (obs_on && !tm_ellipses_) throw std::logic_error(kTrackMapEllipsesOffTightened);
+  if ((obs_on && tg_rounds_ != tm_rounds_) || (map_on && mt_rounds_ != tm_rounds_)) throw std::logic_error(kTrackMapRoundsDisagree);
 }
 
 void iLQR::set_obstacle_covariance(const std::vector<double>& cov) {
@@ -602,6 +630,8 @@ void iLQR::reserve_noise_buffers() {
   L.ts0 = take(chain * 16); L.tW = take(chain * 16); L.tsig = take(chain * B * (N + 1) * 16); L.trisk = take(chain * B * CILQR_CHANCE_FIELDS);
   L.tpose = take(tg * B * M * 4 * N); L.tdim = take(tg * B * M * 2 * N); L.tg = take(tg * B * CILQR_TIGHTEN_FIELDS); L.tcov = take(tg * M * N * 3);
   L.tmg = take((map_tighten_ ? 1 : 0) * B * CILQR_TIGHTEN_MAP_FIELDS);
+  // the track map's rounds: the tracks' covariance by the packed obstacles' strides, the fields
+  L.tkcov = take((tm_rounds_ > 0 ? 1 : 0) * M * N * 3); L.tkf = take((tm_rounds_ > 0 ? 1 : 0) * B * CILQR_TRACK_MAP_FIELDS);
   L.end = o;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (!noise_stream_) {
@@ -629,6 +659,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   if (tighten_ && n_samples_) throw std::logic_error(kTighteningWithSamples);
   if (map_tighten_ && n_samples_) throw std::logic_error(kMapTighteningWithSamples);
   if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
+  check_track_map_conflicts();
   if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
   std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
   const int W = params.num_of_local_wpts;
@@ -668,21 +699,24 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   obs.pose = d + L.pose;
   obs.dim = d + L.dim;
   const cilqr_obstacles* po = M ? &obs : nullptr;
+  // under set_track_map with ellipses off the SOLVES read no ellipse: the tracks reach them through the map only; every check still sees them
+  const int Ms = track_map_on() && !tm_ellipses_ ? 0 : M;
+  const cilqr_obstacles* pos = Ms ? po : nullptr;
   const int risk_fields = n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS;
   int rc = CILQR_OK;
   const bool plain = !cov_check_ && noise_.empty();  // tightening alone: no check behind it, the pick of run_candidates itself
   const bool scored = cov_check_ || plain ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
-  const bool obs_tightened = tighten_ && M > 0, tightened = obs_tightened || map_tightened();
+  const bool obs_tightened = tighten_ && M > 0, tightened = obs_tightened || map_tightened() || track_map_on();
   const bool cmap_checked = cmap_check_ && map_set_ && cov_check_;
   if (plain) {
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
     if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, max_collision_, d + L.score, d + L.total);
   } else if (cov_check_) {  // the analytic check: covariance chain and chance values in place of rollouts
     up(L.s0, cov_sigma0_, 16);
     if (cov_has_W_) up(L.W, cov_W_, 16);
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
     if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
@@ -711,7 +745,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
                                                     d + L.pose, d + L.dim, d + L.soff, max_risk_, d + L.base, d + L.risk,
                                                     (int32_t*)(d + L.hits), d + L.total);
   } else {
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
                                             (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
     if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
     if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
@@ -765,6 +799,7 @@ int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_sta
   last_tighten_risk_before.clear();
   last_tighten_map.clear();
   last_tighten_map_risk_before.clear();
+  last_track_map.clear();
   if (tightened) fetch_tighten(st, d, B, tg_rows);
   if (scored) {
     last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
@@ -951,8 +986,8 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   const auto up = [&](size_t at, const void* src, size_t doubles) {
     hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   };
-  up(L.ts0, tg_sigma0_, 16);
-  if (tg_has_W_) up(L.tW, tg_W_, 16);
+  if (tighten_ || map_tighten_) up(L.ts0, tg_sigma0_, 16);
+  if ((tighten_ || map_tighten_) && tg_has_W_) up(L.tW, tg_W_, 16);
   if (tighten_ && !obs_cov_packed_.empty()) up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
   cilqr_obstacles inflated{};
   inflated.pose = d + L.tpose;
@@ -960,26 +995,44 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   inflated.batch_stride = (int64_t)M * N;
   inflated.obstacle_stride = N;
   inflated.step_stride = 1;
-  // with both tightenings on one round serves both and re-solves once (the setters made the two round counts agree)
-  const bool obs_on = tighten_ && M > 0, map_on = map_tightened();
-  const int rounds = obs_on ? tg_rounds_ : mt_rounds_;
-  const cilqr_uncertainty_map original = map_on ? device_map(false) : cilqr_uncertainty_map{};
-  const cilqr_uncertainty_map layers = map_on ? device_map(true) : cilqr_uncertainty_map{};
-  const size_t cells = map_on ? (size_t)unc_.geom.rows * unc_.geom.cols : 0;
+  // with both tightenings on one round serves both and re-solves once (the setters made the two round counts agree); so it is with the
+  // track map beside them: rasterise along the plan, tighten the RASTERISED layers, one re-solve
+  const bool trk_on = track_map_on();
+  const int Ms = trk_on && !tm_ellipses_ ? 0 : M;  // what the solves read
+  const cilqr_obstacles* pos = Ms ? po : nullptr;
+  const bool obs_on = tighten_ && M > 0, map_on = map_tightened(), chain = obs_on || map_on;
+  const int rounds = obs_on ? tg_rounds_ : map_on ? mt_rounds_ : tm_rounds_;
+  const bool layers_on = map_on || trk_on;
+  const size_t cells = layers_on ? (size_t)unc_.geom.rows * unc_.geom.cols : 0;
+  // map_dev_: the original layer, one layer per candidate, and with both kinds of round a second one per candidate
+  float* first_layers = map_dev_ + cells;
+  float* second_layers = first_layers + (size_t)max_candidates_ * cells;
+  const cilqr_uncertainty_map original = layers_on ? device_map(false) : cilqr_uncertainty_map{};
+  const cilqr_uncertainty_map rastered = layers_on ? device_map(true) : cilqr_uncertainty_map{};
+  cilqr_uncertainty_map layers = rastered;  // what the re-solve reads
+  if (map_on && trk_on) layers.layer = second_layers;
+  const bool trk_cov = trk_on && !obs_cov_packed_.empty();
+  if (trk_cov) up(L.tkcov, obs_cov_packed_.data(), obs_cov_packed_.size());
   int rc = CILQR_OK;
   for (int r = 0; r < rounds && !rc; ++r) {
-    rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-    if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tg_has_W_ ? d + L.tW : nullptr, po, 0u, 1.0,
-                                           nullptr, d + L.trisk, nullptr, nullptr, d + L.tsig, nullptr);
+    if (chain) {
+      rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
+      if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tg_has_W_ ? d + L.tW : nullptr, po, 0u, 1.0,
+                                             nullptr, d + L.trisk, nullptr, nullptr, d + L.tsig, nullptr);
+    }
     if (!rc && obs_on)
       rc = cilqr_tighten_obstacles_device(h_, st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
                                           tg_cap_, d + L.tpose, d + L.tdim, d + L.tg);
-    // the ORIGINAL layer is the one on the handle here: the inflation never compounds over rounds
-    if (!rc && map_on) rc = cilqr_tighten_map_device(h_, st, B, N, d + L.X, d + L.tsig, mt_kappa_, mt_cap_, map_dev_ + cells, d + L.tmg);
-    if (!rc && map_on) rc = cilqr_set_uncertainty_map_device(h_, &layers);
-    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, obs_on ? &inflated : po, d + L.X,
+    // the ORIGINAL layer is the one on the handle here: neither the rasterisation nor the inflation compounds over rounds
+    if (!rc && trk_on)
+      rc = cilqr_rasterize_tracks_device(h_, st, B, N, M, d + L.X, po, trk_cov ? d + L.tkcov : nullptr, tm_inflate_, tm_z_max_, tm_window_, 0u,
+                                         first_layers, d + L.tkf);
+    if (!rc && map_on && trk_on) rc = cilqr_set_uncertainty_map_device(h_, &rastered);  // the tightening reads the rasterised layers
+    if (!rc && map_on) rc = cilqr_tighten_map_device(h_, st, B, N, d + L.X, d + L.tsig, mt_kappa_, mt_cap_, trk_on ? second_layers : first_layers, d + L.tmg);
+    if (!rc && layers_on) rc = cilqr_set_uncertainty_map_device(h_, &layers);
+    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, obs_on ? &inflated : pos, d + L.X,
                                                      d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-    if (map_on) {  // the original map is back on the handle whatever happened: what follows judges the plan against it
+    if (layers_on) {  // the original map is back on the handle whatever happened: what follows judges the plan against it
       const int back = cilqr_set_uncertainty_map_device(h_, &original);  // (a success leaves cilqr_last_error as it is)
       if (!rc) rc = back;
     }
@@ -997,7 +1050,12 @@ void iLQR::fetch_tighten(void* stream, double* d, int B, std::vector<double>& ri
     last_tighten.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0);
     hip_check(hipMemcpyAsync(last_tighten.data(), d + nl_.tg, last_tighten.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
   }
-  hip_check(hipMemcpyAsync(risk_rows.data(), d + nl_.trisk, risk_rows.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  if (track_map_on()) {
+    last_track_map.assign((size_t)B * CILQR_TRACK_MAP_FIELDS, 0.0);
+    hip_check(hipMemcpyAsync(last_track_map.data(), d + nl_.tkf, last_track_map.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  }
+  if (tighten_ || map_tighten_)  // (the chain ran: the risk row of the plan the last round started from)
+    hip_check(hipMemcpyAsync(risk_rows.data(), d + nl_.trisk, risk_rows.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
 }
 
 void iLQR::keep_tighten_risk(int B, const std::vector<double>& risk_rows) {
@@ -1010,7 +1068,8 @@ void iLQR::keep_tighten_risk(int B, const std::vector<double>& risk_rows) {
 // get_optimal_control_seq under set_chance_tightening: the B = 1 solve and its rounds in the device block, one wait.
 void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]) {
   const int N = params.horizon, M = (int)obstacles_.size();
-  if (n_samples_) throw std::logic_error(tighten_ ? kTighteningWithSamples : kMapTighteningWithSamples);
+  check_track_map_conflicts();
+  if (n_samples_ && (tighten_ || map_tighten_)) throw std::logic_error(tighten_ ? kTighteningWithSamples : kMapTighteningWithSamples);
   if (noise_horizon_ != N) reserve_noise_buffers();
   const cilqr_obstacles host_obs = obstacle_strides();
   if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
@@ -1034,9 +1093,10 @@ void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coe
   obs.pose = d + L.pose;
   obs.dim = d + L.dim;
   const cilqr_obstacles* po = M ? &obs : nullptr;
-  int rc = cilqr_solve_batch_obstacles_device(h_, st, 1, N, M, d + L.x0, d + L.U, d + L.poly, d + L.fl, po, d + L.X, d + L.J,
+  const int Ms = track_map_on() && !tm_ellipses_ ? 0 : M;  // (ellipses off: the tracks reach the solve through the map only)
+  int rc = cilqr_solve_batch_obstacles_device(h_, st, 1, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, Ms ? po : nullptr, d + L.X, d + L.J,
                                               (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-  const bool tightened = (tighten_ && M > 0) || map_tightened();
+  const bool tightened = (tighten_ && M > 0) || map_tightened() || track_map_on();
   if (!rc && tightened) rc = tighten_rounds(st, d, 1, po);
   if (rc) {
     const std::string msg = cilqr_last_error();
@@ -1051,6 +1111,7 @@ void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coe
   last_tighten_risk_before.clear();
   last_tighten_map.clear();
   last_tighten_map_risk_before.clear();
+  last_track_map.clear();
   down(Xb.a.data(), L.X, Xb.a.size() * sizeof(double));
   down(U.a.data(), L.U, U.a.size() * sizeof(double));
   down(&J, L.J, sizeof(double));

@@ -221,6 +221,26 @@ class iLQR {
   // Sigma0 == nullptr or rounds == 0 switches it off (the default: nothing changes for existing callers).  Together with
   // set_obstacle_samples (whichever comes second) the setters throw std::logic_error, like set_chance_tightening.
   void set_map_tightening(const double Sigma0[16], const double* W, double eps, int rounds = 1, double max_inflate = 1.0, double lamb = 1.0);
+  // Track map: the tracks of set_tracked_obstacles rasterised into the map along each plan, for the configuration the live node runs.
+  // While it is on, tracks are set (set_tracked_obstacles) and an uncertainty map is set, run_step (get_optimal_control_seq) and
+  // run_candidates follow their solve by `rounds` rounds, enqueued on the checks' stream with nothing coming back in between:
+  //   cilqr_rasterize_tracks_device(inflate, z_max, window) along the current plans, always from the ORIGINAL layer, with the
+  //   predicted covariance -> the per-solve layers set on the handle (layer_stride = rows*cols) -> the re-solve, warm-started from
+  //   the U the solve before it left -> the original map set on the handle again.
+  // ellipses = false: the SOLVES run with M = 0, so the tracks reach the planner through the map only — the live node's
+  // configuration; every later score and check (set_candidate_pick, set_pose_covariance_check with set_obstacle_covariance_check,
+  // the pose-noise checks, the map checks) still sees the tracks, and judges the final plan against them and the original map.
+  // With set_map_tightening on, one round is: gains and covariance chain -> rasterise -> cilqr_tighten_map_device on the RASTERISED
+  // layers -> one re-solve; with set_chance_tightening the inflated ellipses go into that same re-solve.  The round counts must then
+  // agree, and set_chance_tightening beside ellipses = false has nothing to inflate: a run throws std::logic_error for either.
+  // last_track_map holds CILQR_TRACK_MAP_FIELDS per solve (cilqr_track_map_field) of the last round; with no tracks or no map set the
+  // rounds are skipped and it stays empty.  The layer is soft and first order (include/cilqr.h): it guarantees nothing — keep a check
+  // behind it.  While rounds > 0 the layer of set_uncertainty_map lives in device memory of this object, as under set_map_tightening,
+  // beside one layer per candidate (two with set_map_tightening).  With obstacle samples (set_obstacle_samples,
+  // set_sample_covariance_check) in force a run under it throws std::logic_error, like set_map_tightening.
+  // rounds == 0 switches it off (the default: nothing changes for existing callers).  A negative rounds or window, or an inflate or
+  // z_max that is negative or not finite, throws std::runtime_error.
+  void set_track_map(double inflate, double z_max, int window, int rounds = 1, bool ellipses = true);
   // Test hook: cilqr_debug_uncertainty_cost on the map this object's handle holds right now, at n = states.size() / 4 states
   // (x, y, v, theta) -> n costs, then 2n of vx, then 3n of mx.  Throws std::runtime_error when no map is set.
   std::vector<double> debug_map_cost(const std::vector<double>& states) const;
@@ -278,6 +298,8 @@ class iLQR {
   std::vector<double> last_tighten, last_tighten_risk_before;  // CILQR_TIGHTEN_FIELDS per solve; CR_STEP_RISK per solve
   // run_step / run_candidates under set_map_tightening with an uncertainty map set; empty otherwise
   std::vector<double> last_tighten_map, last_tighten_map_risk_before;  // CILQR_TIGHTEN_MAP_FIELDS per solve; CR_STEP_RISK per solve
+  // run_step / run_candidates under set_track_map with tracks and an uncertainty map set; empty otherwise
+  std::vector<double> last_track_map;  // CILQR_TRACK_MAP_FIELDS per solve
 
  private:
   void pack_obstacles();
@@ -298,7 +320,7 @@ class iLQR {
   // so that this header needs no HIP
   struct NoiseLayout {
     size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
-        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, ccov, end;
+        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, ccov, tkcov, tkf, end;
   };
   // tracked obstacles (set_tracked_obstacles): the inputs as given, and the horizon they were last predicted over (-1: none set)
   std::vector<double> tracks_, track_dims_, track_cov_, track_Q_;
@@ -359,6 +381,14 @@ class iLQR {
   cilqr_uncertainty_map device_map(bool tightened) const;  // the original in map_dev_, or the per-solve layers behind it
   bool map_tightened() const { return map_tighten_ && map_set_; }
   void check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const;
+  // track map (set_track_map): its rounds run in tighten_rounds, its layers lie in map_dev_ behind the original
+  int tm_rounds_ = 0, tm_window_ = 0;
+  double tm_inflate_ = 0.0, tm_z_max_ = 0.0;
+  bool tm_ellipses_ = true;
+  bool track_map_on() const { return tm_rounds_ > 0 && tracked_horizon_ >= 0 && map_set_; }
+  void check_track_map_conflicts() const;  // throws std::logic_error, before a run enqueues anything
+  bool map_in_block() const { return map_tighten_ || tm_rounds_ > 0; }  // the map lives in map_dev_
+  bool rounds_on() const { return tighten_ || map_tighten_ || tm_rounds_ > 0; }  // solves run in the checks' device block
 };
 
 }  // namespace cilqr_host
