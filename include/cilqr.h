@@ -154,11 +154,15 @@ typedef enum cilqr_exit {
 typedef struct cilqr_handle cilqr_handle;
 
 /* Geometry of a grid_map layer (G/grid_map_core/src/GridMap.cpp:45-62): float32, column-major
- * rows×cols, cell (i,j) centre = pos + (len/2 - res/2) - res*(i,j)  (GridMapMath.cpp:114-127). */
+ * rows×cols, cell (i,j) centre = pos + (len/2 - res/2) - res*(i,j)  (GridMapMath.cpp:114-127).
+ * Fill it with cilqr_map_geom_set.  Where a geometry is the SOURCE of a warp (src_geom of cilqr_warp_costmap*, global_geom of
+ * cilqr_costmap_frame*) its lengths must be exactly what setGeometry writes: len_x == (double)rows * res and
+ * len_y == (double)cols * res, bit for bit.  Any other value is CILQR_ERR_ARG (the message names the field) before anything is
+ * enqueued: the warp kernels' in-map test relies on that equality. */
 typedef struct cilqr_map_geom {
   int32_t rows, cols;     /* size_(0), size_(1)  */
   double res;             /* resolution_ */
-  double len_x, len_y;    /* length_  (= size*res after setGeometry) */
+  double len_x, len_y;    /* length_  (= (double)size*res after setGeometry; REQUIRED of a warp's source geometry) */
   double pos_x, pos_y;    /* position_ (map centre in its parent frame) */
 } cilqr_map_geom;
 
@@ -1289,7 +1293,9 @@ int cilqr_wait(cilqr_handle* h);
  * → g = Rot(theta)·C + (vx, vy) → nearest source cell (GridMap::atPosition, G/grid_map_core/src/GridMap.cpp:160-166);
  * if bbox != NULL and bbox(cell) > 90 the destination takes the bbox value (:260-263).  Where the reference
  * would throw std::out_of_range the destination is set to NaN and counted in *n_out_of_range (may be NULL).
- * src: src_geom.rows×cols float32 column-major; dst/bbox: dst_geom.rows×cols float32 column-major. */
+ * src: src_geom.rows×cols float32 column-major; dst/bbox: dst_geom.rows×cols float32 column-major.
+ * src_geom (global_geom of the frame calls) must carry len == (double)size * res, see cilqr_map_geom: otherwise CILQR_ERR_ARG from
+ * every warp and frame entry point below, with nothing enqueued and no output written. */
 int cilqr_warp_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* src_geom,
                        float* dst, const cilqr_map_geom* dst_geom,
                        double vx, double vy, double vtheta, const float* bbox, int64_t* n_out_of_range);

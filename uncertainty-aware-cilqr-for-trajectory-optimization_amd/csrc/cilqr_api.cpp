@@ -1819,6 +1819,24 @@ int cilqr_layer_to_occupancy(cilqr_handle* h, const float* layer, int64_t n_cell
   return convert_host(h, layer, (size_t)n_cells * sizeof(float), occ, (size_t)n_cells, false, n_cells, data_min, data_max);
 }
 
+namespace {
+bool good_geom(const cilqr_map_geom* g) { return g->rows >= 1 && g->cols >= 1 && g->res > 0.0; }
+
+// The SOURCE geometry of a warp must carry the lengths setGeometry writes (cilqr_map_geom_set: len = (double)size * res, these
+// very bits).  The warp kernels decide most cells from the quotient alone (0 < q < size, costmap_warp.hip cell_estimated) and the
+// others as the reference does (t < len AND index < size); the two agree only under this equality, so a hand-filled geometry with
+// a shorter length would give cells of one lane's run different answers.  Needs no handle and no device.
+int source_geom_lengths(const char* who, const cilqr_map_geom* g) {
+  if (!(g->len_x == (double)g->rows * g->res))
+    return fail(CILQR_ERR_ARG, "%s: source geometry len_x=%.17g is not rows*res=%.17g (fill it with cilqr_map_geom_set)", who, g->len_x,
+                (double)g->rows * g->res);
+  if (!(g->len_y == (double)g->cols * g->res))
+    return fail(CILQR_ERR_ARG, "%s: source geometry len_y=%.17g is not cols*res=%.17g (fill it with cilqr_map_geom_set)", who, g->len_y,
+                (double)g->cols * g->res);
+  return CILQR_OK;
+}
+}  // namespace
+
 int cilqr_costmap_frame_device(cilqr_handle* h, void* stream, const float* global_layer, const cilqr_map_geom* global_geom,
                                const cilqr_map_geom* vehicle_geom, double vx, double vy, double vtheta, const float* bbox,
                                double sigma_x, double sigma_y, double sigma_theta, float* vehicle_layer,
@@ -1957,6 +1975,8 @@ int cilqr_warp_costmap_polygons_device(cilqr_handle* h, void* stream, const floa
   if (rc) return rc;
   if (!h || !src || !sg || !dst) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_polygons: null argument");
   if (sg->rows < 1 || sg->cols < 1 || !(sg->res > 0.0)) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_polygons: bad geometry");
+  rc = source_geom_lengths("cilqr_warp_costmap_polygons", sg);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->device));
   cilqr::PolygonTable t;
@@ -2014,6 +2034,7 @@ int cilqr_warp_costmap_device(cilqr_handle* h, void* stream, const float* src, c
   if (!h || !src || !sg || !dst || !dg) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap: null argument");
   if (sg->rows < 1 || sg->cols < 1 || dg->rows < 1 || dg->cols < 1 || !(sg->res > 0.0) || !(dg->res > 0.0))
     return fail(CILQR_ERR_ARG, "cilqr_warp_costmap: bad geometry");
+  if (int rc = source_geom_lengths("cilqr_warp_costmap", sg)) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->device));
   cilqr::WarpArgs a;
@@ -2048,7 +2069,6 @@ int upload_pose_table(cilqr_handle* h, hipStream_t s, int K, const double* rows,
   return CILQR_OK;
 }
 
-bool good_geom(const cilqr_map_geom* g) { return g->rows >= 1 && g->cols >= 1 && g->res > 0.0; }
 }  // namespace
 
 int cilqr_warp_costmap_batch_device(cilqr_handle* h, void* stream, const float* src, const cilqr_map_geom* sg, float* dst,
@@ -2057,6 +2077,7 @@ int cilqr_warp_costmap_batch_device(cilqr_handle* h, void* stream, const float* 
   if (K < 1 || K > 1024) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_batch: K=%d outside [1,1024]", K);
   if (sg->rows < 1 || sg->cols < 1 || dg->rows < 1 || dg->cols < 1 || !(sg->res > 0.0) || !(dg->res > 0.0))
     return fail(CILQR_ERR_ARG, "cilqr_warp_costmap_batch: bad geometry");
+  if (int rc = source_geom_lengths("cilqr_warp_costmap_batch", sg)) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->device));
   if (dg->rows % 4 != 0 && K == 1)  // rows not in fours: one frame is the single-frame kernel's, its pose in the arguments
@@ -2107,6 +2128,7 @@ int cilqr_costmap_frame_batch_device(cilqr_handle* h, void* stream, const float*
     return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: null argument");
   if (K < 1 || K > 1024) return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: K=%d outside [1,1024]", K);
   if (!good_geom(global_geom) || !good_geom(vehicle_geom)) return fail(CILQR_ERR_ARG, "cilqr_costmap_frame_batch: bad geometry");
+  if (int rc = source_geom_lengths("cilqr_costmap_frame_batch", global_geom)) return rc;
   if (K == 1)
     return cilqr_costmap_frame_device(h, stream, global_layer, global_geom, vehicle_geom, poses[0], poses[1], poses[2], bbox, sigma_x, sigma_y,
                                       sigma_theta, vehicle_layers, uncertainty_layers, occupancy_out, n_out_of_range_dev);
@@ -2136,6 +2158,7 @@ int cilqr_warp_costmap(cilqr_handle* h, const float* src, const cilqr_map_geom* 
                        double vx, double vy, double vtheta, const float* bbox, int64_t* n_out_of_range) {
   if (!h || !src || !sg || !dst || !dg) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap: null argument");
   if (sg->rows < 1 || sg->cols < 1 || dg->rows < 1 || dg->cols < 1) return fail(CILQR_ERR_ARG, "cilqr_warp_costmap: bad geometry");
+  if (int rc0 = source_geom_lengths("cilqr_warp_costmap", sg)) return rc0;  // before the copies below are enqueued
   HIP_TRY(hipSetDevice(h->device));
   const size_t ns = (size_t)sg->rows * sg->cols, nd = (size_t)dg->rows * dg->cols;
   int rc = grow(&h->d_src, &h->src_cap, ns);

@@ -299,17 +299,20 @@ __global__ __launch_bounds__(NTHREADS) void warp_tile_kernel(WarpBatchArgs a, in
   {
     const int ia = ti * LT_I, ib = min(ia + LT_I, drows) - 1, ja = tj * LT_J, jb = min(ja + LT_J, dcols) - 1;
     double qx_lo = 1e300, qx_hi = -1e300, qy_lo = 1e300, qy_hi = -1e300;
+    // NaN / infinite poses: a corner fails these comparisons and the box is empty — every cell then takes the global path or is
+    // out of range.  The test is on every corner's own quotient: fmin/fmax drop a NaN, so after a NaN pose the bounds would still
+    // be the ±1e300 they start from, pass as finite, and convert to a box at the far end of the int range.
+    bool fin = true;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const double Cx = (a.dg.pos_x + off_dx) + a.dg.res * (double)(-((c & 1) ? ib : ia));
       const double Cy = (a.dg.pos_y + off_dy) + a.dg.res * (double)(-((c & 2) ? jb : ja));
       const double qx = (((Cx * cos_t - Cy * sin_t) + vx - off_sx) - a.sg.pos_x) * nrres;
       const double qy = (((Cx * sin_t + Cy * cos_t) + vy - off_sy) - a.sg.pos_y) * nrres;
+      fin = fin && qx > -2e9 && qx < 2e9 && qy > -2e9 && qy < 2e9;
       qx_lo = __builtin_fmin(qx_lo, qx); qx_hi = __builtin_fmax(qx_hi, qx);
       qy_lo = __builtin_fmin(qy_lo, qy); qy_hi = __builtin_fmax(qy_hi, qy);
     }
-    // (NaN / infinite poses: the comparisons below fail and the box is empty — every cell then takes the global path or is out of range)
-    const bool fin = qx_lo > -2e9 && qx_hi < 2e9 && qy_lo > -2e9 && qy_hi < 2e9;
     si_lo = fin ? max((int)__builtin_floor(qx_lo) - 2, 0) : 0;
     si_hi = fin ? min((int)__builtin_floor(qx_hi) + 2, a.sg.rows - 1) : -1;
     sj_lo = fin ? max((int)__builtin_floor(qy_lo) - 2, 0) : 0;
