@@ -1254,7 +1254,8 @@ int cilqr_solve_family(const cilqr_handle* h, int B, int N, int M);
  * Jacobian and control-barrier terms of phase L while the first searches the closest path samples (cilqr_solve_share_kernel, DESIGN.md
  * §4.2: three up to three quarters of a solve per SIMD, at least two obstacles and N ≤ 64, two up to two solves per SIMD and N ≤ 127; obstacle
  * table in LDS — a solve's LDS share grows where fewer solves share a CU; with an uncertainty map set, whose term then goes to the
- * last of the further wavefronts: three up to half a solve per SIMD, two up to one; results bit-identical to the one-wavefront kernel; CILQR_NO_SHARE_KERNEL in the environment at create switches it
+ * last of the further wavefronts: three up to half a solve per SIMD, two up to one — two also where the partial sums of three would
+ * take a solve with a large obstacle table past the 160 KiB of LDS of a CU; results bit-identical to the one-wavefront kernel; CILQR_NO_SHARE_KERNEL in the environment at create switches it
  * off, CILQR_SHARE_W = 2 or 3 fixes the number), else 1 (also for every shape cilqr_solve_family sends to the grouped family).
  * CILQR_FLAG_FAITHFUL_ITERS always runs on one, and under CILQR_PAIR_KERNEL (the two-wavefront experiment) the answer
  * is 1 at every batch size.  Together with cilqr_solve_family and cilqr_solve_sampled_wavefronts it reads the launch plan the solve

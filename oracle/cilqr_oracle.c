@@ -470,12 +470,78 @@ int oracle_quu_inverse(const double* Quu, double lamb, double* Qinv, double* eva
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * The same regularised inverse in two further forms (cilqr_oracle.h, ORACLE_QUU_*): what the kernels evaluate, and what the
+ * formula is worth.  Neither follows reference code; both take the symmetric part of the input, b = (Quu[1] + Quu[2])/2.
+ * ---------------------------------------------------------------------------------------------- */
+#ifdef ORACLE_HAVE_QUADMATH
+#include <quadmath.h>
+static __float128 quad_hypot(__float128 h, __float128 b) { return sqrtq(h * h + b * b); }
+#else
+/* Without libquadmath: s·sqrt(x), x = (h/s)² + (b/s)² in [1, 2] with s = max(|h|, |b|), by Newton steps on y = sqrt(x) from the
+ * double root (53 → 106 → 113 good bits; a third step costs nothing). */
+static __float128 quad_hypot(__float128 h, __float128 b) {
+  if (h < 0) h = -h;
+  if (b < 0) b = -b;
+  const __float128 s = h > b ? h : b;
+  if (!(s > 0)) return 0;
+  const __float128 x = (h / s) * (h / s) + (b / s) * (b / s);
+  __float128 y = (__float128)sqrt((double)x);
+  for (int i = 0; i < 3; i++) y = (y + x / y) / 2;
+  return s * y;
+}
+#endif
+
+/* V·diag(1/(max(eig,0)+lamb))·Vᵀ of [[a,b],[b,d]] in the closed form: eigenvalues m ± r with m = (a+d)/2, h = (a-d)/2,
+ * r = sqrt(h² + b²); with x_i = max(eig_i, 0) + lamb the result is ((x1+x2)/2·I - (x1-x2)/2·[[h,b],[b,-h]]/r) / (x1·x2).
+ * __float128 throughout, each entry rounded to double once.  Arranged so that no difference of nearly equal quantities is formed
+ * beyond what the input holds: the eigenvalue on the side of m as m ± r, the other as det/that (a·d and b·b are exact in quad), and
+ * x1 - x2 from the clamped eigenvalues, not from the reciprocals. */
+static int quu_inverse_exact(const double* Quu, double lamb, double* Qinv) {
+  for (int i = 0; i < 4; i++)
+    if (!isfinite(Quu[i])) return -1;
+  const __float128 a = Quu[0], d = Quu[3], b = ((__float128)Quu[1] + (__float128)Quu[2]) / 2, l = lamb;
+  const __float128 m = (a + d) / 2, h = (a - d) / 2;
+  const __float128 r = quad_hypot(h, b);
+  const __float128 det = a * d - b * b;
+  __float128 e1, e2;
+  if (m >= 0) { e1 = m + r; e2 = e1 > 0 ? det / e1 : 0; }
+  else { e2 = m - r; e1 = det / e2; }
+  const __float128 p1 = e1 > 0 ? e1 : 0, p2 = e2 > 0 ? e2 : 0;
+  const __float128 prod = (p1 + l) * (p2 + l), hs = (p1 + p2) / 2 + l, hd = (p1 - p2) / 2;
+  __float128 c2 = 1, s2 = 0;
+  if (r > 0) { c2 = h / r; s2 = b / r; }
+  Qinv[0] = (double)((hs - hd * c2) / prod);
+  Qinv[3] = (double)((hs + hd * c2) / prod);
+  Qinv[1] = Qinv[2] = (double)(-(hd * s2) / prod);
+  return 0;
+}
+
+int oracle_quu_inverse_form(const double* Quu, double lamb, int form, double* Qinv) {
+  if (form == ORACLE_QUU_EXACT) return quu_inverse_exact(Quu, lamb, Qinv);
+  if (form == ORACLE_QUU_ADJUGATE) {
+    const double a = Quu[0], d = Quu[3], b = 0.5 * (Quu[1] + Quu[2]);
+    const double bb = b * b;
+    if (fma(a, d, -bb) >= 0 && a + d >= 0) { /* both eigenvalues pass the clamp: inv(Q_uu + lamb·I), adjugate over determinant */
+      const double ar = a + lamb, dr = d + lamb;
+      const double rdet = 1.0 / fma(ar, dr, -bb);
+      Qinv[0] = dr * rdet;
+      Qinv[3] = ar * rdet;
+      Qinv[1] = Qinv[2] = -b * rdet;
+      return 0;
+    }
+  } else if (form != ORACLE_QUU_REFERENCE) {
+    return -1;
+  }
+  return oracle_quu_inverse(Quu, lamb, Qinv, NULL, NULL);
+}
+
+/* ------------------------------------------------------------------------------------------------
  * iLQR::backward_pass — I/iLQR.cpp:91-195
  * ---------------------------------------------------------------------------------------------- */
 static int backward_pass_samples(const cilqr_params* p, int N, const double* X, const double* U, int S,
                                  const double* sx, const double* sy, int M, const double* obs_pose,
                                  const double* obs_dim, const double* obs_weight, const cilqr_uncertainty_map* um, int ub,
-                                 double lamb, double* k, double* K) {
+                                 double lamb, int quu_form, double* k, double* K) {
   double* buf = (double*)malloc(sizeof(double) * (size_t)N * (4 + 16 + 2 + 4 + 16 + 8 + 3));
   double* l_x = buf;
   double* l_xx = l_x + 4 * N;
@@ -550,7 +616,7 @@ static int backward_pass_samples(const cilqr_params* p, int N, const double* X, 
       }
     /* :155-175 */
     double Qinv[4];
-    if (oracle_quu_inverse(Q_uu, lamb, Qinv, NULL, NULL) != 0) { ok = 0; break; }
+    if (oracle_quu_inverse_form(Q_uu, lamb, quu_form, Qinv) != 0) { ok = 0; break; }
     /* :177-178 */
     double kj[2], Kj[8];
     for (int r = 0; r < 2; r++) kj[r] = ((-1) * Qinv[r]) * Q_u[0] + ((-1) * Qinv[r + 2]) * Q_u[1];
@@ -579,7 +645,7 @@ int oracle_backward_pass(const cilqr_params* p, int N, const double* X, const do
   const int S = p->num_of_local_wpts * 10;
   double* sx = (double*)malloc(sizeof(double) * 2 * (size_t)S);
   build_samples(p, coeffs, xplan_first, xplan_last, sx, sx + S);
-  int ok = backward_pass_samples(p, N, X, U, S, sx, sx + S, M, obs_pose, obs_dim, obs_weight, NULL, 0, lamb, k, K);
+  int ok = backward_pass_samples(p, N, X, U, S, sx, sx + S, M, obs_pose, obs_dim, obs_weight, NULL, 0, lamb, ORACLE_QUU_REFERENCE, k, K);
   free(sx);
   return ok;
 }
@@ -613,6 +679,15 @@ int oracle_solve_unc(const cilqr_params* p, int N, int M, const double* x0, doub
                      double xplan_first, double xplan_last, const double* obs_pose, const double* obs_dim,
                      const double* obs_weight, const cilqr_uncertainty_map* um, int ub, double* X_out, double* J_out,
                      int* status_out, double* trace) {
+  return oracle_solve_form(p, N, M, x0, U, coeffs, xplan_first, xplan_last, obs_pose, obs_dim, obs_weight, um, ub, ORACLE_QUU_REFERENCE,
+                           X_out, J_out, status_out, trace);
+}
+
+/* ... and with the form of the Q_uu inverse chosen by the caller (an argument, not a global: the batch driver runs threads) */
+int oracle_solve_form(const cilqr_params* p, int N, int M, const double* x0, double* U, const double* coeffs,
+                      double xplan_first, double xplan_last, const double* obs_pose, const double* obs_dim,
+                      const double* obs_weight, const cilqr_uncertainty_map* um, int ub, int quu_form, double* X_out, double* J_out,
+                      int* status_out, double* trace) {
   const int S = p->num_of_local_wpts * 10;
   size_t nd = (size_t)2 * S + 4 * (N + 1) * 2 + 2 * N + 2 * N + 8 * N;
   double* buf = (double*)malloc(sizeof(double) * nd);
@@ -633,7 +708,7 @@ int oracle_solve_unc(const cilqr_params* p, int N, int M, const double* x0, doub
   int status = CILQR_EXIT_MAX_ITER;
   for (int i = 0; i < p->max_iterations; i++) {
     iteration_times++;
-    int ok = backward_pass_samples(p, N, X, U, S, sx, sy, M, obs_pose, obs_dim, obs_weight, um, ub, lamb, k, K);
+    int ok = backward_pass_samples(p, N, X, U, S, sx, sy, M, obs_pose, obs_dim, obs_weight, um, ub, lamb, quu_form, k, K);
     if (!ok) { status = CILQR_EXIT_NUMERIC; break; }
     oracle_forward_pass(p, N, X, U, k, K, X_new, U_new);
     J_new = get_J_samples(p, N, X, U, S, sx, sy); /* :217 — on the current (old) X, U */
@@ -680,6 +755,14 @@ int oracle_solve_batch_unc(const cilqr_params* p, int B, int N, int M, const dou
                            const double* poly, const double* xplan_fl, const double* obs_pose,
                            const double* obs_dim, const double* obs_weight, const cilqr_uncertainty_map* um, double* X_out,
                            double* J_out, int* iters_out, int* status_out, int threads) {
+  return oracle_solve_batch_form(p, B, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, um, ORACLE_QUU_REFERENCE, X_out, J_out,
+                                 iters_out, status_out, threads);
+}
+
+int oracle_solve_batch_form(const cilqr_params* p, int B, int N, int M, const double* x0, double* U,
+                            const double* poly, const double* xplan_fl, const double* obs_pose,
+                            const double* obs_dim, const double* obs_weight, const cilqr_uncertainty_map* um, int quu_form,
+                            double* X_out, double* J_out, int* iters_out, int* status_out, int threads) {
   if (threads < 1) threads = 1;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic) num_threads(threads)
@@ -687,10 +770,11 @@ int oracle_solve_batch_unc(const cilqr_params* p, int B, int N, int M, const dou
   for (int b = 0; b < B; b++) {
     int st = 0;
     double J = 0;
-    int it = oracle_solve_unc(p, N, M, x0 + 4 * (size_t)b, U + 2 * (size_t)N * b, poly + 6 * (size_t)b,
-                              xplan_fl[2 * b], xplan_fl[2 * b + 1],
-                              M ? obs_pose + (size_t)b * M * N * 4 : NULL, M ? obs_dim + (size_t)b * M * N * 2 : NULL,
-                              obs_weight ? obs_weight + (size_t)b * M : NULL, um, b, X_out + 4 * (size_t)(N + 1) * b, &J, &st, NULL);
+    int it = oracle_solve_form(p, N, M, x0 + 4 * (size_t)b, U + 2 * (size_t)N * b, poly + 6 * (size_t)b,
+                               xplan_fl[2 * b], xplan_fl[2 * b + 1],
+                               M ? obs_pose + (size_t)b * M * N * 4 : NULL, M ? obs_dim + (size_t)b * M * N * 2 : NULL,
+                               obs_weight ? obs_weight + (size_t)b * M : NULL, um, b, quu_form, X_out + 4 * (size_t)(N + 1) * b, &J, &st,
+                               NULL);
     if (J_out) J_out[b] = J;
     if (iters_out) iters_out[b] = it;
     if (status_out) status_out[b] = st;

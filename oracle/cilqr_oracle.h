@@ -57,6 +57,16 @@ void oracle_AB(const cilqr_params* p, int N, const double* vel, const double* th
  * (column-major Quu[4] → Qinv[4]).  Returns 0, or -1 where the reference's solver would not return
  * real eigenvectors. */
 int oracle_quu_inverse(const double* Quu, double lamb, double* Qinv, double* eval2, double* evec4);
+/* The same quantity in a form the caller chooses (tests/test_quu_conditioning.py):
+ *   REFERENCE  oracle_quu_inverse above — what every entry point without a form argument uses;
+ *   ADJUGATE   where fma(a,d,-b·b) >= 0 and a+d >= 0 (both eigenvalues pass the clamp): inv(Q_uu + lamb·I) as adjugate over
+ *              determinant in double, 1.0/fma(a+lamb, d+lamb, -b·b) — the form of the kernels' PSD path; REFERENCE elsewhere;
+ *   EXACT      V·diag(1/(max(eig,0)+lamb))·Vᵀ through the closed form (eigenvalues m ± r) in __float128, each entry rounded to
+ *              double once; defined for every finite input (its symmetric part), -1 for a non-finite one.
+ * On an ill-conditioned Q_uu (one control barrier's Hessian at 1e10 on the diagonal) REFERENCE loses the small eigenvalue to
+ * eps·1e10 and is the inaccurate one of the three. */
+enum { ORACLE_QUU_REFERENCE = 0, ORACLE_QUU_ADJUGATE = 1, ORACLE_QUU_EXACT = 2 };
+int oracle_quu_inverse_form(const double* Quu, double lamb, int form, double* Qinv);
 /* I/iLQR.cpp:91-195.  Returns 1 on success (reference `true`). */
 int oracle_backward_pass(const cilqr_params* p, int N, const double* X, const double* U, const double* coeffs,
                          double xplan_first, double xplan_last, int M, const double* obs_pose,
@@ -88,6 +98,17 @@ int oracle_solve_batch_unc(const cilqr_params* p, int B, int N, int M, const dou
                            const double* poly, const double* xplan_fl, const double* obs_pose,
                            const double* obs_dim, const double* obs_weight, const cilqr_uncertainty_map* m, double* X_out,
                            double* J_out, int* iters_out, int* status_out, int threads);
+
+/* oracle_solve_unc / oracle_solve_batch_unc with the form of the Q_uu inverse (ORACLE_QUU_*) as an argument of the call — never a
+ * global: the batch driver runs threads.  ORACLE_QUU_REFERENCE gives the bits of the calls above, which are wrappers of these. */
+int oracle_solve_form(const cilqr_params* p, int N, int M, const double* x0, double* U, const double* coeffs,
+                      double xplan_first, double xplan_last, const double* obs_pose, const double* obs_dim,
+                      const double* obs_weight, const cilqr_uncertainty_map* m, int b, int quu_form, double* X_out, double* J_out,
+                      int* status_out, double* trace);
+int oracle_solve_batch_form(const cilqr_params* p, int B, int N, int M, const double* x0, double* U,
+                            const double* poly, const double* xplan_fl, const double* obs_pose,
+                            const double* obs_dim, const double* obs_weight, const cilqr_uncertainty_map* m, int quu_form,
+                            double* X_out, double* J_out, int* iters_out, int* status_out, int threads);
 
 /* Batch driver (layouts of include/cilqr.h), OpenMP over the batch with `threads` threads. */
 int oracle_solve_batch(const cilqr_params* p, int B, int N, int M, const double* x0, double* U,

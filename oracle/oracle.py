@@ -95,8 +95,23 @@ def default_control_seq(N):
     return U
 
 
-def solve(p, N, x0, U, coeffs, xf, xl, obs_pose=None, obs_dim=None, obs_weight=None):
-    """One reference-order solve.  Returns dict(U, X, J, iters, status, trace)."""
+QUU_FORMS = {"reference": 0, "adjugate": 1, "exact": 2}  # ORACLE_QUU_* (cilqr_oracle.h): the form of the regularised Q_uu inverse
+
+
+def quu_inverse(Q, lamb, form="reference"):
+    """The regularised Q_uu inverse of (n, 4) column-major 2×2 matrices (or one (4,)) in the given form → ((n, 4) or (4,), rc (n,) or int)."""
+    Q2 = np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(-1, 4))
+    lamb = np.broadcast_to(np.asarray(lamb, dtype=np.float64), (Q2.shape[0],))
+    out = np.full_like(Q2, np.nan)
+    rc = np.zeros(Q2.shape[0], dtype=np.int32)
+    fn = lib().oracle_quu_inverse_form
+    for i in range(Q2.shape[0]):
+        rc[i] = fn(_dp(Q2[i]), C.c_double(lamb[i]), QUU_FORMS[form], _dp(out[i]))
+    return (out[0], int(rc[0])) if np.ndim(Q) == 1 else (out, rc)
+
+
+def solve(p, N, x0, U, coeffs, xf, xl, obs_pose=None, obs_dim=None, obs_weight=None, quu="reference"):
+    """One reference-order solve (quu: the form of the Q_uu inverse, QUU_FORMS).  Returns dict(U, X, J, iters, status, trace)."""
     M = 0 if obs_pose is None else int(np.asarray(obs_pose).reshape(-1, 4 * N).shape[0])
     x0 = _f64(x0)
     U = _f64(U).copy()
@@ -108,28 +123,14 @@ def solve(p, N, x0, U, coeffs, xf, xl, obs_pose=None, obs_dim=None, obs_weight=N
     J = C.c_double(0)
     st = C.c_int(0)
     trace = np.full(3 * p.max_iterations, np.nan)
-    it = lib().oracle_solve(C.byref(p), N, M, _dp(x0), _dp(U), _dp(coeffs), C.c_double(xf), C.c_double(xl),
-                            _dp(obs_pose), _dp(obs_dim), _dp(obs_weight), _dp(X), C.byref(J), C.byref(st), _dp(trace))
+    it = lib().oracle_solve_form(C.byref(p), N, M, _dp(x0), _dp(U), _dp(coeffs), C.c_double(xf), C.c_double(xl),
+                                 _dp(obs_pose), _dp(obs_dim), _dp(obs_weight), None, 0, QUU_FORMS[quu], _dp(X), C.byref(J), C.byref(st),
+                                 _dp(trace))
     return dict(U=U, X=X, J=J.value, iters=it, status=st.value, trace=trace.reshape(-1, 3)[:it])
 
 
-def solve_batch(p, N, M, x0, U, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, threads=1):
-    B = int(np.asarray(x0).reshape(-1, 4).shape[0])
-    x0 = _f64(x0)
-    U = _f64(U).copy()
-    poly = _f64(poly)
-    xplan_fl = _f64(xplan_fl)
-    obs_pose = _f64(obs_pose)
-    obs_dim = _f64(obs_dim)
-    obs_weight = _f64(obs_weight)
-    X = np.zeros((B, 4 * (N + 1)))
-    J = np.zeros(B)
-    iters = np.zeros(B, dtype=np.int32)
-    status = np.zeros(B, dtype=np.int32)
-    lib().oracle_solve_batch(C.byref(p), B, N, M, _dp(x0), _dp(U), _dp(poly), _dp(xplan_fl), _dp(obs_pose),
-                             _dp(obs_dim), _dp(obs_weight), _dp(X), _dp(J), iters.ctypes.data_as(c_int_p),
-                             status.ctypes.data_as(c_int_p), int(threads))
-    return dict(U=U.reshape(B, 2 * N), X=X, J=J, iters=iters, status=status)
+def solve_batch(p, N, M, x0, U, poly, xplan_fl, obs_pose=None, obs_dim=None, obs_weight=None, threads=1, quu="reference"):
+    return solve_batch_unc(p, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, None, threads=threads, quu=quu)
 
 
 def max_threads():
@@ -282,7 +283,8 @@ def uncertainty_cost(p, umap, states, b=0):
     return cost, vx, mx.reshape(n, 4, 4)
 
 
-def solve_batch_unc(p, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, umap, threads=1):
+def solve_batch_unc(p, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weight, umap, threads=1, quu="reference"):
+    """The batch driver, with an uncertainty map or None; quu: the form of the Q_uu inverse (QUU_FORMS), an argument of the call."""
     B = int(np.asarray(x0).reshape(-1, 4).shape[0])
     x0 = _f64(x0)
     U = _f64(U).copy()
@@ -295,9 +297,9 @@ def solve_batch_unc(p, N, M, x0, U, poly, xplan_fl, obs_pose, obs_dim, obs_weigh
     J = np.zeros(B)
     iters = np.zeros(B, dtype=np.int32)
     status = np.zeros(B, dtype=np.int32)
-    lib().oracle_solve_batch_unc(C.byref(p), B, N, M, _dp(x0), _dp(U), _dp(poly), _dp(xplan_fl), _dp(obs_pose),
-                                 _dp(obs_dim), _dp(obs_weight), C.byref(umap) if umap is not None else None, _dp(X), _dp(J),
-                                 iters.ctypes.data_as(c_int_p), status.ctypes.data_as(c_int_p), int(threads))
+    lib().oracle_solve_batch_form(C.byref(p), B, N, M, _dp(x0), _dp(U), _dp(poly), _dp(xplan_fl), _dp(obs_pose),
+                                  _dp(obs_dim), _dp(obs_weight), C.byref(umap) if umap is not None else None, QUU_FORMS[quu], _dp(X),
+                                  _dp(J), iters.ctypes.data_as(c_int_p), status.ctypes.data_as(c_int_p), int(threads))
     return dict(U=U.reshape(B, 2 * N), X=X, J=J, iters=iters, status=status)
 
 

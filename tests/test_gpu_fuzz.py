@@ -79,29 +79,22 @@ def test_random_static_scenes(cilqr, oracle, monkeypatch, seed):
     _compare(got, want, "seed %d: N=%d M=%d B=%d G=%d share=%s" % (seed, N, M, B, G, share))
 
 
-@pytest.mark.parametrize("seed", range(12 * SCALE))
-def test_random_static_scenes_wavefront_family(cilqr, oracle, monkeypatch, seed):
-    """The one-wavefront family on its own: one, two or three wavefronts per solve (cilqr_solve_share_kernel where the shape allows it,
-    cilqr_solve_kernel otherwise), horizons up to the 63 the shared kernel takes and a little beyond, tables that fit LDS and tables
-    that do not, weights, warm starts, moving obstacles, parameter sets off the defaults."""
+def wavefront_family_scene(seed, default_params, oracle_default_params, local_plan=None):
+    """Draw `seed` of test_random_static_scenes_wavefront_family: (N, M, B, p, po, scene).  default_params / oracle_default_params:
+    horizon → the product's / the oracle's parameter struct (p, po); local_plan: the planner that fits the scene's paths (None: the
+    product's).  tests/test_quu_conditioning.py draws its scene here too, with the oracle's planner on the CPU and the GPU alike."""
     from cilqr_amd import scenes
     rng = np.random.default_rng(9600 + seed)
     N, M, B = int(rng.integers(1, 70)), int(rng.integers(0, 11)), int(rng.integers(1, 700))
     if seed >= 8:  # (added with the long-horizon form of the shared kernel: horizons up to 130)
         N += 62
-    share = ["rule", "2", "3", "off"][seed % 4]
-    monkeypatch.setenv("CILQR_FORCE_G", "64")
-    if share == "off":
-        monkeypatch.setenv("CILQR_NO_SHARE_KERNEL", "1")
-    elif share != "rule":
-        monkeypatch.setenv("CILQR_SHARE_W", share)
-    p, po = cilqr.default_params(N), oracle.default_params(N)
+    p, po = default_params(N), oracle_default_params(N)
     if seed % 3 == 0:
         state = rng.bit_generator.state
         _tweak(p, rng)
         rng.bit_generator.state = state
         _tweak(po, rng)
-    sc = scenes.make_static(B, N, M, p, 9700 + seed)
+    sc = scenes.make_static(B, N, M, p, 9700 + seed, local_plan)
     if M and rng.random() < 0.5:
         sc["obs_weight"] = rng.uniform(0.2, 2.0, (B, M))
     if rng.random() < 0.5:
@@ -113,6 +106,21 @@ def test_random_static_scenes_wavefront_family(cilqr, oracle, monkeypatch, seed)
         pose[..., 0] += v * np.cos(pose[..., 3]) * p.timestep * np.arange(N)
         pose[..., 1] += v * np.sin(pose[..., 3]) * p.timestep * np.arange(N)
         sc["obs_pose"] = pose.reshape(B, M, 4 * N)
+    return N, M, B, p, po, sc
+
+
+@pytest.mark.parametrize("seed", range(12 * SCALE))
+def test_random_static_scenes_wavefront_family(cilqr, oracle, monkeypatch, seed):
+    """The one-wavefront family on its own: one, two or three wavefronts per solve (cilqr_solve_share_kernel where the shape allows it,
+    cilqr_solve_kernel otherwise), horizons up to the 63 the shared kernel takes and a little beyond, tables that fit LDS and tables
+    that do not, weights, warm starts, moving obstacles, parameter sets off the defaults."""
+    N, M, B, p, po, sc = wavefront_family_scene(seed, cilqr.default_params, oracle.default_params)
+    share = ["rule", "2", "3", "off"][seed % 4]
+    monkeypatch.setenv("CILQR_FORCE_G", "64")
+    if share == "off":
+        monkeypatch.setenv("CILQR_NO_SHARE_KERNEL", "1")
+    elif share != "rule":
+        monkeypatch.setenv("CILQR_SHARE_W", share)
     s = cilqr.Solver(p, max_batch=B, max_horizon=N, max_obstacles=max(M, 1), device=0)
     try:
         w = s.solve_wavefronts(B, N, M)

@@ -1,10 +1,12 @@
 """The launch plan of the one-wavefront-per-solve family (csrc/cilqr_wave_plan.h) — which kernel, how many wavefronts per solve, the
 obstacle table where, how much LDS — is plain integer arithmetic on the host: checked here without a GPU through
 tests/cpp/wave_plan_dump.cpp, for a device of 1024 SIMDs (an MI355X) and the default 200 path samples."""
+import itertools
 import json
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 from conftest import PKG, ROOT
@@ -14,11 +16,15 @@ SIMDS = 1024
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
+def exe(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("wave_plan") / "wave_plan_dump")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(ROOT, "include"), "-o", exe,
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(ROOT, "include"), "-o", exe,
                     os.path.join(ROOT, "tests", "cpp", "wave_plan_dump.cpp")], check=True)
+    return exe
 
+
+@pytest.fixture(scope="module")
+def plan(exe):
     def run(B, N, M, **kw):
         shape = ",".join("%s=%d" % kv for kv in dict(B=B, N=N, M=M, **kw).items())
         r = subprocess.run([exe, shape], check=True, capture_output=True, text=True)
@@ -149,3 +155,49 @@ def test_lds_bytes(plan):
     assert (p["family"], p["kernel"], p["W"], p["tab"], p["lds_fast"], p["lds_general"]) == (64, "SPLIT", 2, 2, 25056, 27088)
     p = plan(1024, 50, 4, pair_on=1)  # the pair kernel: 50 + 4 doubles behind the table
     assert (p["kernel"], p["lds_fast"], p["lds_general"]) == ("PAIR", 10624 + 9600 + 432, 24272)
+
+
+SOLVE_LDS_MAX = 160 * 1024  # cilqr::SOLVE_LDS_MAX: the LDS of one CU
+
+
+def _enumerate(exe):
+    """Every shape of the static-obstacle sweep through `wave_plan_dump --stdin` → (shapes (n, 6), plans (n, 8)); plan columns:
+    kernel (2 = SHARE), W, long_form, tab, lds_fast, lds_general, too_large, solve_wavefronts."""
+    shapes = np.array(list(itertools.product(range(1, 128), (2, 44, 50, 200), range(0, 65), (1, 256, 257, 512, 513, 1024), (0, 1), (0, 2, 3))))
+    text = "".join("N=%d,path_samples=%d,M=%d,B=%d,map=%d,share_w=%d\n" % tuple(s) for s in shapes)
+    r = subprocess.run([exe, "--stdin"], input=text, check=True, capture_output=True, text=True)
+    plans = np.array(r.stdout.split(), dtype=np.int64).reshape(-1, 8)
+    assert plans.shape[0] == shapes.shape[0] == 127 * 4 * 65 * 6 * 2 * 3
+    return shapes, plans
+
+
+def test_every_plan_fits_the_lds_of_a_cu(exe):
+    """No plan asks for more dynamic LDS than a CU has: launch_solve_wave hands max(lds_fast, lds_general) to hipFuncSetAttribute, which
+    refuses more than 160 KiB, so an over-limit plan turns a valid call into CILQR_ERR_HIP.  Before the share kernel's candidate was
+    bounded, B=256 N=53 M=58 with a map and 44 path samples planned three wavefronts with 163 856 B (limit 163 840) while the GENERAL
+    kernel's 161 744 B fit; two wavefronts need 161 728 B.  Also: cilqr_solve_wavefronts answers the W of the plan that will run."""
+    shapes, plans = _enumerate(exe)
+    kernel, W, lds_fast, lds_general, too_large, query = plans[:, 0], plans[:, 1], plans[:, 4], plans[:, 5], plans[:, 6], plans[:, 7]
+    over = (too_large == 0) & ((lds_fast > SOLVE_LDS_MAX) | (lds_general > SOLVE_LDS_MAX))
+    assert not over.any(), "%d plans beyond the LDS of a CU, first (N, path_samples, M, B, map, share_w) = %s: %s" % (
+        int(over.sum()), shapes[over][0].tolist(), plans[over][0].tolist())
+    assert ((too_large == 1) == (lds_general > SOLVE_LDS_MAX)).all()
+    share = kernel == 2
+    assert (query[share] == W[share]).all() and (query[~share] == 1).all() and (W[share] >= 2).all() and (W[~share] == 1).all()
+    # the sweep reaches two and three wavefronts, the short and the long form, tables in LDS and in the workspace, and plans within a
+    # few bytes of the limit (no horizon up to 127 is too large on its own: a table that does not fit goes to the workspace)
+    assert (W == 2).sum() > 10000 and (W == 3).sum() > 10000 and (plans[share, 2] == 1).sum() > 10000 and (plans[:, 3] == 0).sum() > 10000
+    assert np.max(np.maximum(lds_fast, lds_general)) > SOLVE_LDS_MAX - 64 and too_large.sum() == 0
+
+
+def test_share_plan_steps_down_at_the_lds_limit(plan):
+    """The shape above and the one tests/test_quu_conditioning.py solves on a device (50 path samples: the nearest a parameter set
+    reaches, path samples being 10·num_of_local_wpts): three wavefronts do not fit, two do, and the query says two."""
+    p = plan(256, 53, 58, map=1, path_samples=44)
+    assert (p["kernel"], p["W"], p["tab"], p["lds_fast"], p["lds_general"], p["too_large"], p["solve_wavefronts"]) == ("SHARE", 2, 1, 161728, 161744, 0, 2)
+    p = plan(4, 53, 58, map=1, path_samples=50)
+    assert (p["kernel"], p["W"], p["tab"], p["lds_fast"], p["lds_general"], p["too_large"], p["solve_wavefronts"]) == ("SHARE", 2, 1, 161776, 161792, 0, 2)
+    assert plan(4, 53, 57, map=1, path_samples=50)["W"] == 3  # (one obstacle fewer: three fit)
+    # (only three wavefronts with a map can pass the GENERAL kernel's size: their 15N partial sums against its 10N + 6 doubles of
+    # candidate buffers; 10N + 4 for two with a map or three without always fit where it does)
+    assert plan(256, 53, 58, path_samples=44)["W"] == 3 and plan(256, 53, 58, path_samples=44)["lds_fast"] <= SOLVE_LDS_MAX

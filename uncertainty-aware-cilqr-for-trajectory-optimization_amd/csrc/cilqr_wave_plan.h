@@ -173,7 +173,8 @@ inline size_t lds_table_budget(const SolveKnobs& kn, int B) {
 //   SPLIT  sampled obstacles, shape as split_shape_wavefronts says, both kernels within the default 64 KiB of LDS;
 //   PAIR   CILQR_PAIR_KERNEL, up to one solve per SIMD, no map, both kernels within the default 64 KiB (the experiment was measured
 //          and tested on small tables only; slower at every batch size, DESIGN.md §5: not the default);
-//   SHARE  static obstacles, N ≤ 127, wavefronts as share_wavefronts says (beyond 64 KiB the launcher raises both kernels' limit).
+//   SHARE  static obstacles, N ≤ 127, wavefronts as share_wavefronts says — one fewer, or the one-wavefront kernel, where their partial
+//          sums would take the solve past the CU's 160 KiB (beyond 64 KiB the launcher raises both kernels' limit).
 inline WavePlan plan_wave(const SolveKnobs& k, const WaveShape& s) {
   const int N = s.N, S = s.path_samples;
   const bool sampled = s.n_samples > 0, early_exit = (s.flags & CILQR_FLAG_FAITHFUL_ITERS) == 0;
@@ -197,8 +198,10 @@ inline WavePlan plan_wave(const SolveKnobs& k, const WaveShape& s) {
     return with(WavePlan::SPLIT, W, split_lds_bytes(N, S, W, s.has_map, extra), SOLVE_LDS_DEFAULT);
   }
   if (k.pair_on && s.B <= k.simds) return with(WavePlan::PAIR, s.has_map ? 1 : 2, pair_lds_bytes(N, S, extra), SOLVE_LDS_DEFAULT);
-  const int W = N < 2 * dev::WAVE ? share_wavefronts(k, s.B, N, s.M, s.has_map) : 1;
-  return with(WavePlan::SHARE, W, share_lds_bytes(N, S, W, s.has_map, extra), ~(size_t)0);
+  // (every further wavefront adds 5N partial sums: where three no longer fit the CU beside a large table, two may — and else one)
+  int W = N < 2 * dev::WAVE ? share_wavefronts(k, s.B, N, s.M, s.has_map) : 1;
+  while (W > 1 && share_lds_bytes(N, S, W, s.has_map, extra) > SOLVE_LDS_MAX) --W;
+  return with(WavePlan::SHARE, W, share_lds_bytes(N, S, W, s.has_map, extra), SOLVE_LDS_MAX);
 }
 
 // cilqr_solve_wavefronts (include/cilqr.h): the wavefronts of the share kernel where an ordinary call of this shape (no flags, the
