@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -35,15 +35,7 @@ int main(int argc, char** argv) {
   params.safe_width = 0.9;
   Matrix path(2, 200);
   for (int i = 0; i < 200; ++i) { path(0, i) = i; path(1, i) = 0.5 * std::sin(0.05 * i); }
-  std::vector<Obstacle> obstacles;
-  for (int o = 0; o < M; ++o) {
-    Matrix dim(2, N), pose(4, N);
-    for (int t = 0; t < N; ++t) {
-      dim(0, t) = 4.79; dim(1, t) = 2.16;
-      pose(0, t) = 15 + 12 * o; pose(1, t) = (o % 2) ? -1.0 : 0.8; pose(2, t) = 0; pose(3, t) = 0.1 * o;
-    }
-    obstacles.emplace_back(params, dim, pose);
-  }
+  const std::vector<Obstacle> obstacles = staggered_obstacles(params, N, M, 15, 12, 0.8, -1.0);
   const double ego[4] = {0, 0.1, 3.0, 0.02};
   printf("{");
   {

@@ -9,7 +9,9 @@
 //      offset, base = the chance total);
 //   2. with every candidate rejected (max_risk = -1) the call returns -1 and X_result / U_result / last_cost are untouched;
 //   3. Sigma0 == nullptr switches the check off;
-//   4. together with set_pose_noise_check(_fused) offsets or set_obstacle_samples, whichever comes second throws std::logic_error.
+//   4. together with set_pose_noise_check(_fused) offsets or set_obstacle_samples, whichever comes second throws std::logic_error;
+//   5. params.horizon lowered to 12 after a checked run: the next run equals the sequence by hand at that horizon, from the first 12
+//      steps of the warm start the first run left (the device block is laid out anew).
 // Prints "chance pick ok" and "conflicts throw ok" on success.
 #include <cmath>
 #include <cstdint>
@@ -18,7 +20,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -26,13 +28,6 @@ namespace {
 const int N = 30, M = 1, B = 16;
 const double kMaxRisk = 0.2, kThreshold = 50.0, kMapMaxRisk = 0.5;  // (the solved plans all pass within 2 m of the obstacle: the safest read 0.08 and 0.15)
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
 
 struct Scene {
   Parameters params;
@@ -47,15 +42,9 @@ struct Scene {
 bool run_case(const Scene& sc, const char* name, CandidatePick pick, bool sum_bound, bool with_map) {
   cilqr_handle* h = nullptr;
   if (cilqr_create(&sc.params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }
-  cilqr_uncertainty_map m{};
-  m.layer = sc.um.layer.data(); m.geom = sc.um.geom;
-  m.pose_x = sc.um.pose_x; m.pose_y = sc.um.pose_y; m.pose_theta = sc.um.pose_theta;
-  m.probes_l = sc.um.probes_l; m.probes_w = sc.um.probes_w;
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  const cilqr_uncertainty_map m = abi_map(sc.um);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B), ok(B), mhits((size_t)B * N), munk((size_t)B * N);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const double pose1[4] = {12.0, -1.0, 0.0, 0.0}, dim1[2] = {4.79, 2.16}, zero[4] = {0.0, 0.0, 0.0, 0.0};
   const cilqr_obstacles obs{pose1, dim1, nullptr, 0, 1, 0, 0};  // one set for the batch, constant over the horizon
   std::vector<double> k((size_t)B * 2 * N), K((size_t)B * 8 * N), score((size_t)B * CILQR_SCORE_FIELDS), base(B);
@@ -149,16 +138,52 @@ bool run_case(const Scene& sc, const char* name, CandidatePick pick, bool sum_bo
   return true;
 }
 
-template <typename F>
-bool throws_logic_error(F&& f, const char* needle) {
-  try {
-    f();
-  } catch (const std::logic_error& e) {
-    return strstr(e.what(), needle) != nullptr;
-  } catch (...) {
+// params.horizon changed after the setter, under the check: the block is laid out anew, and the run equals the sequence by hand at the
+// new horizon N2 on a handle made as the planner's was, from the first N2 steps of the warm start the first run left.
+bool horizon_case(const Scene& sc) {
+  const int N2 = 12;
+  iLQR planner(sc.params, 0, M, B);
+  planner.set_global_plan(sc.path);
+  planner.set_Obstacle(sc.obstacles);
+  planner.set_pose_covariance_check(sc.sigma0, sc.W, kMaxRisk);
+  if (planner.run_candidates(sc.egos) < 0) { printf("horizon: no pick at the first horizon\n"); return false; }
+  const std::vector<double> warm(planner.U_result.a.begin(), planner.U_result.a.begin() + 2 * N2);
+
+  cilqr_handle* h = nullptr;
+  if (cilqr_create(&sc.params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N2), X((size_t)B * 4 * (N2 + 1)), J(B);
+  std::vector<double> k((size_t)B * 2 * N2), K((size_t)B * 8 * N2), risk((size_t)B * CILQR_CHANCE_FIELDS), step((size_t)B * N2), total(B);
+  std::vector<int32_t> iters(B), status(B), ok(B);
+  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N2], warm.data(), warm.size() * sizeof(double));
+  const double pose1[4] = {12.0, -1.0, 0.0, 0.0}, dim1[2] = {4.79, 2.16};
+  const cilqr_obstacles obs{pose1, dim1, nullptr, 0, 1, 0, 0};
+  const bool done =
+      cilqr_local_plan_batch(h, B, sc.path.cols, sc.path.a.data(), 0, sc.egos.data(), poly.data(), fl.data(), nullptr, nullptr) == CILQR_OK &&
+      cilqr_solve_batch_obstacles(h, B, N2, M, sc.egos.data(), U.data(), poly.data(), fl.data(), &obs, X.data(), J.data(), iters.data(),
+                                  status.data(), CILQR_FLAG_NONE) == CILQR_OK &&
+      cilqr_gains_batch(h, B, N2, M, X.data(), U.data(), poly.data(), fl.data(), &obs, 1.0, k.data(), K.data(), ok.data()) == CILQR_OK &&
+      cilqr_chance_risk(h, B, N2, M, X.data(), U.data(), K.data(), sc.sigma0, 0, sc.W, &obs, 0u, kMaxRisk, J.data(), risk.data(), step.data(),
+                        nullptr, nullptr, total.data()) == CILQR_OK;
+  if (!done) { printf("horizon: the sequence by hand failed: %s\n", cilqr_last_error()); return false; }
+  cilqr_destroy(h);
+  const int want = first_minimum(total);
+  printf("horizon %d: pick by hand %d; %d of %d candidates rejected\n", N2, want, count_nan(total), B);
+  if (want < 0) { printf("horizon: every candidate is rejected at the new horizon\n"); return false; }
+
+  planner.params.horizon = N2;
+  const int best = planner.run_candidates(sc.egos);
+  if (best != want) { printf("horizon: the check picked %d, the sequence by hand %d\n", best, want); return false; }
+  if (!same(planner.last_chance_risk, risk) || !same(planner.last_step_risk, step)) {
+    printf("horizon: last_chance_risk / last_step_risk differ from cilqr_chance_risk at the new horizon\n");
     return false;
   }
-  return false;
+  if (planner.X_result.cols != N2 + 1 || !same(planner.X_result.a.data(), &X[(size_t)best * 4 * (N2 + 1)], 4 * (size_t)(N2 + 1)) ||
+      !same(planner.U_result.a.data(), &U[(size_t)best * 2 * N2], 2 * (size_t)N2) || !same(&planner.last_cost, &J[best], 1) ||
+      planner.last_iterations != iters[best] || planner.last_exit != status[best]) {
+    printf("horizon: the pick's X / U / J differ from the hand-written solve at the new horizon\n");
+    return false;
+  }
+  return true;
 }
 }  // namespace
 
@@ -166,39 +191,20 @@ int main() {
   Scene sc;
   sc.params = default_parameters();
   sc.params.horizon = N;
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
-  sc.egos.resize(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    sc.egos[4 * b + 0] = 0.0;
-    sc.egos[4 * b + 1] = -3.0 + 0.5 * b;
-    sc.egos[4 * b + 2] = 5.0;
-    sc.egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -1.0; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  sc.obstacles = {Obstacle(sc.params, dim, pose)};
+  sc.path = straight_path();
+  sc.egos = spread_egos(B, -3.0, 0.5);
+  sc.obstacles = {standing_obstacle(sc.params, N, 12.0, -1.0)};
   sc.sigma0[0] = 0.16 * 0.16; sc.sigma0[5] = 0.16 * 0.16; sc.sigma0[15] = 0.017 * 0.017;
   sc.W[0] = 1e-4; sc.W[5] = 1e-4; sc.W[10] = 4e-4; sc.W[15] = 1e-6;
   // the costmap: 200 x 80 cells of 0.2 m centred 15 m ahead; cell (i, j) has its centre at (34.9 - 0.2 i, 7.9 - 0.2 j); a smooth
   // occupied region around (20, 3.5), where candidates far from the obstacle drive
-  if (cilqr_map_geom_set(&sc.um.geom, 40.0, 16.0, 0.2, 15.0, 0.0) != CILQR_OK) return 1;
-  const int rows = sc.um.geom.rows, cols = sc.um.geom.cols;
-  sc.um.layer.resize((size_t)rows * cols);
-  for (int j = 0; j < cols; ++j)
-    for (int i = 0; i < rows; ++i) {
-      const double x = 34.9 - 0.2 * i, y = 7.9 - 0.2 * j;
-      const double z = 90.0 * std::exp(-0.5 * (std::pow((x - 20.0) / 5.0, 2) + std::pow((y - 3.5) / 0.7, 2)));
-      sc.um.layer[(size_t)j * rows + i] = (float)(100.0 * std::tanh(z / 100.0));
-    }
-  sc.um.pose_x = 0.0; sc.um.pose_y = 0.0; sc.um.pose_theta = 0.0;
+  if (!bump_costmap(sc.um, {{90.0, 20.0, 3.5, 5.0, 0.7}})) return 1;
 
   if (!run_case(sc, "J", CandidatePick::MinTrackingCost, false, false)) return 1;
   if (!run_case(sc, "total", CandidatePick::MinTotalCost, false, false)) return 1;
   if (!run_case(sc, "sum", CandidatePick::MinTrackingCost, true, false)) return 1;
   if (!run_case(sc, "map", CandidatePick::MinTotalCost, false, true)) return 1;
+  if (!horizon_case(sc)) return 1;
   printf("chance pick ok\n");
 
   // 4. the conflicts, in both orders

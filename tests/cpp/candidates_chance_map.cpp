@@ -25,7 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -33,22 +33,6 @@ namespace {
 const int N = 30, B = 16, NX = 5, NY = 5, NTH = 3, Q = NX * NY * NTH, CM = CILQR_CHANCE_MAP_FIELDS;
 const double kThreshold = 50.0, kMapMaxRisk = 0.1, kChanceMaxRisk = 0.2, kRolloutMapMaxRisk = 0.5;
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same_v(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && same(a.data(), b.data(), a.size()); }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-int count_nan(const std::vector<double>& v) {
-  int n = 0;
-  for (double x : v) n += x != x;
-  return n;
-}
-void put(FILE* f, const std::vector<double>& v) {
-  for (double x : v) fprintf(f, "%.17g\n", x);
-}
 
 struct Scene {
   Parameters params;
@@ -56,7 +40,6 @@ struct Scene {
   std::vector<double> egos;
   std::vector<Obstacle> obstacles;
   Uncertainty um;
-  double geom[5] = {40.0, 16.0, 0.2, 15.0, 0.0}, map_pose[3] = {0.0, 0.0, 0.0};
   double sigma0[16] = {};
 };
 
@@ -71,20 +54,15 @@ bool by_hand(const Scene& sc, bool with_obstacle, bool with_map, uint32_t flags,
   cilqr_handle* h = nullptr;
   // (max_batch 2 B: the host form of cilqr_chance_risk with sigma_out fits the arena for B <= max_batch / 2)
   if (cilqr_create(&sc.params, 2 * B, N, 1, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }
-  cilqr_uncertainty_map m{};
-  m.layer = sc.um.layer.data(); m.geom = sc.um.geom;
-  m.pose_x = sc.um.pose_x; m.pose_y = sc.um.pose_y; m.pose_theta = sc.um.pose_theta;
-  m.probes_l = sc.um.probes_l; m.probes_w = sc.um.probes_w;
+  const cilqr_uncertainty_map m = abi_map(sc.um);
   std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), k((size_t)B * 2 * N), score((size_t)B * CILQR_SCORE_FIELDS), base(B);
   std::vector<double> sigma((size_t)B * (N + 1) * 16), mrisk((size_t)B * CILQR_MAP_RISK_FIELDS), mtotal(B);
   std::vector<int32_t> ok(B);
-  o.X.assign((size_t)B * 4 * (N + 1), 0.0); o.U.assign((size_t)B * 2 * N, 0.0); o.J.assign(B, 0.0); o.K.assign((size_t)B * 8 * N, 0.0);
+  o.X.assign((size_t)B * 4 * (N + 1), 0.0); o.J.assign(B, 0.0); o.K.assign((size_t)B * 8 * N, 0.0);
   o.total.assign(B, 0.0); o.cmrisk.assign((size_t)B * CM, 0.0); o.cmstep.assign((size_t)B * N, 0.0); o.cmtotal.assign(B, 0.0);
   o.crisk.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0); o.nodes.assign((size_t)Q * 3, 0.0); o.weights.assign(Q, 0.0);
   o.iters.assign(B, 0); o.status.assign(B, 0);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&o.U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
+  o.U = default_controls(B, N);
   const double pose1[4] = {12.0, -1.0, 0.0, 0.0}, dim1[2] = {4.79, 2.16}, zero[4] = {0.0, 0.0, 0.0, 0.0};
   const cilqr_obstacles obs{pose1, dim1, nullptr, 0, 1, 0, 0};
   const cilqr_obstacles* po = M ? &obs : nullptr;
@@ -136,36 +114,16 @@ int main(int argc, char** argv) {
   sc.params.horizon = N;
   sc.params.safe_length = 1.1;  // the launch file's values (Experiment.launch:7-8)
   sc.params.safe_width = 0.9;
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
-  sc.egos.resize(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    sc.egos[4 * b + 0] = 0.0;
-    sc.egos[4 * b + 1] = -3.0 + 0.5 * b;
-    sc.egos[4 * b + 2] = 5.0;
-    sc.egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -1.0; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  sc.obstacles = {Obstacle(sc.params, dim, pose)};
+  sc.path = straight_path();
+  sc.egos = spread_egos(B, -3.0, 0.5);
+  sc.obstacles = {standing_obstacle(sc.params, N, 12.0, -1.0)};
   sc.sigma0[0] = 0.16 * 0.16; sc.sigma0[5] = 0.16 * 0.16; sc.sigma0[15] = 0.017 * 0.017;
   // the costmap of candidates_risk_map.cpp: 200 x 80 cells of 0.2 m centred 15 m ahead; cell (i, j) has its centre at
   // (34.9 - 0.2 i, 7.9 - 0.2 j); a smooth occupied region around (3.5, -0.6), a weaker one around (20, -4.5); six unknown cells
-  if (cilqr_map_geom_set(&sc.um.geom, sc.geom[0], sc.geom[1], sc.geom[2], sc.geom[3], sc.geom[4]) != CILQR_OK) return 1;
+  if (!bump_costmap(sc.um, {{80.0, 3.5, -0.6, 1.5, 0.5}, {60.0, 20.0, -4.5, 5.0, 1.5}})) return 1;
   const int rows = sc.um.geom.rows, cols = sc.um.geom.cols;
-  sc.um.layer.resize((size_t)rows * cols);
-  for (int j = 0; j < cols; ++j)
-    for (int i = 0; i < rows; ++i) {
-      const double x = 34.9 - 0.2 * i, y = 7.9 - 0.2 * j;
-      const double z = 80.0 * std::exp(-0.5 * (std::pow((x - 3.5) / 1.5, 2) + std::pow((y + 0.6) / 0.5, 2))) +
-                       60.0 * std::exp(-0.5 * (std::pow((x - 20.0) / 5.0, 2) + std::pow((y + 4.5) / 1.5, 2)));
-      sc.um.layer[(size_t)j * rows + i] = (float)(100.0 * std::tanh(z / 100.0));
-    }
   const int nan_cells[6][2] = {{170, 52}, {171, 52}, {168, 47}, {165, 38}, {166, 38}, {150, 26}};
   for (const auto& c : nan_cells) sc.um.layer[(size_t)c[1] * rows + c[0]] = NAN;
-  sc.um.pose_x = sc.map_pose[0]; sc.um.pose_y = sc.map_pose[1]; sc.um.pose_theta = sc.map_pose[2];
 
   // 1. the live node's case
   ByHand live, alone;
@@ -188,8 +146,8 @@ int main(int argc, char** argv) {
   planner.set_map_covariance_check(kThreshold, kMapMaxRisk);
   const int best = planner.run_candidates(sc.egos);
   if (best != want) { printf("live: the check picked %d, the sequence by hand %d\n", best, want); return 1; }
-  if (!same_v(planner.last_chance_map_risk, live.cmrisk) || !same_v(planner.last_map_step_risk, live.cmstep) ||
-      !same_v(planner.last_chance_risk, live.crisk)) {
+  if (!same(planner.last_chance_map_risk, live.cmrisk) || !same(planner.last_map_step_risk, live.cmstep) ||
+      !same(planner.last_chance_risk, live.crisk)) {
     printf("live: last_chance_map_risk / last_map_step_risk / last_chance_risk differ from the hand-called sequence\n");
     return 1;
   }
@@ -198,8 +156,8 @@ int main(int argc, char** argv) {
     FILE* f = fopen(argv[1], "w");
     if (!f) { printf("cannot write %s\n", argv[1]); return 1; }
     fprintf(f, "%d\n%d\n%d\n%d\n%d\n%.17g\n%.17g\n%d\n", B, N, Q, rows, cols, kThreshold, kMapMaxRisk, best);
-    for (double v : sc.geom) fprintf(f, "%.17g\n", v);
-    for (double v : sc.map_pose) fprintf(f, "%.17g\n", v);
+    for (double v : kBumpGeom) fprintf(f, "%.17g\n", v);
+    for (double v : kBumpMapPose) fprintf(f, "%.17g\n", v);
     put(f, live.X); put(f, live.U); put(f, live.K); put(f, live.total);
     for (double v : sc.sigma0) fprintf(f, "%.17g\n", v);
     put(f, live.nodes); put(f, live.weights); put(f, planner.last_chance_map_risk); put(f, planner.last_map_step_risk);
@@ -226,7 +184,7 @@ int main(int argc, char** argv) {
     configure(p, sc, false, false);  // no map
     p.set_map_covariance_check(kThreshold, kMapMaxRisk);
     const int nb = p.run_candidates(sc.egos);
-    if (nb != want_alone || !p.last_chance_map_risk.empty() || !p.last_map_step_risk.empty() || !same_v(p.last_chance_risk, alone.crisk) ||
+    if (nb != want_alone || !p.last_chance_map_risk.empty() || !p.last_map_step_risk.empty() || !same(p.last_chance_risk, alone.crisk) ||
         !results_are(p, alone, nb)) {
       printf("no map: pick %d, the covariance check alone by hand %d, or fields not empty\n", nb, want_alone);
       return 1;
@@ -238,7 +196,7 @@ int main(int argc, char** argv) {
     p.set_map_covariance_check(kThreshold, kMapMaxRisk);
     p.set_map_covariance_check(NAN, kMapMaxRisk);  // off
     const int ob = p.run_candidates(sc.egos);
-    if (ob != want_chance || !p.last_chance_map_risk.empty() || !p.last_map_step_risk.empty() || !same_v(p.last_chance_risk, live.crisk)) {
+    if (ob != want_chance || !p.last_chance_map_risk.empty() || !p.last_map_step_risk.empty() || !same(p.last_chance_risk, live.crisk)) {
       printf("check off: pick %d, by hand %d\n", ob, want_chance);
       return 1;
     }
@@ -270,7 +228,7 @@ int main(int argc, char** argv) {
     p.set_map_covariance_check(kThreshold, kMapMaxRisk, NX, NY, NTH, true, true);
     if (chain) p.set_map_risk_check(kThreshold, kRolloutMapMaxRisk);
     const int ob = p.run_candidates(sc.egos);
-    if (ob != w || !same_v(p.last_chance_map_risk, o.cmrisk) || !same_v(p.last_map_step_risk, o.cmstep) || !same_v(p.last_chance_risk, o.crisk) ||
+    if (ob != w || !same(p.last_chance_map_risk, o.cmrisk) || !same(p.last_map_step_risk, o.cmstep) || !same(p.last_chance_risk, o.crisk) ||
         (chain ? p.last_map_risk.empty() : !p.last_map_risk.empty()) || (ob >= 0 && !results_are(p, o, ob))) {
       printf("obstacle%s: pick %d, by hand %d, or the fields differ\n", chain ? " + map rollout" : "", ob, w);
       return 1;

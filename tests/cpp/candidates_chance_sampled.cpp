@@ -10,8 +10,10 @@
 //   2. a max_risk below every chance (-1) rejects all: the index is -1 and the results stay;
 //   3. together with set_pose_noise_check(_fused) offsets whichever comes second throws std::logic_error naming the other setter;
 //      without samples set run_candidates throws std::logic_error naming set_pose_covariance_check; and set_pose_covariance_check
-//      with samples set still throws std::logic_error.
-// Prints "sample chance pick ok", "rejects all ok" and "conflicts throw ok" on success.
+//      with samples set still throws std::logic_error;
+//   4. one planner switched fused check -> sample covariance check -> fused check -> sample covariance check: a field the mode in force
+//      does not produce is empty, and every run equals a run from the same warm start on a planner that never switched.
+// Prints "sample chance pick ok", "rejects all ok", "conflicts throw ok" and "mode switches ok" on success.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -20,71 +22,20 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
-
-namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && same(a.data(), b.data(), a.size()); }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-// sums of four uniforms from a fixed linear congruential sequence, scaled to the given sigma
-struct Draws {
-  uint64_t state = 0x9e3779b97f4a7c15ull;
-  double unit() {  // in [-1, 1)
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(state >> 11) / 4503599627370496.0 - 1.0;
-  }
-  double gauss(double sigma) { return (unit() + unit() + unit() + unit()) * sigma * 0.8660254037844386; }  // var 4/3 -> 1
-};
-template <class F>
-bool throws_logic_error(F&& f, const char* needle) {
-  try {
-    f();
-  } catch (const std::logic_error& e) {
-    return strstr(e.what(), needle) != nullptr;
-  }
-  return false;
-}
-}  // namespace
 
 int main() {
   const int N = 30, n_obs = 1, ns = 8, M = n_obs * ns, B = 4, S = 70;
   const int F = CILQR_CRS_FIELDS;
   Parameters params = default_parameters();
   params.horizon = N;
-  Matrix path(2, 200);
-  for (int i = 0; i < 200; ++i) { path(0, i) = 1.0 * i; path(1, i) = 0.0; }
-  std::vector<double> egos(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    egos[4 * b + 0] = 0.0;
-    egos[4 * b + 1] = 0.6 * b;
-    egos[4 * b + 2] = 5.0;
-    egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -2.5; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  const std::vector<Obstacle> obstacles{Obstacle(params, dim, pose)};
+  const Matrix path = straight_path();
+  const std::vector<double> egos = spread_egos(B, 0.0, 0.6);
+  const std::vector<Obstacle> obstacles{standing_obstacle(params, N, 12.0, -2.5)};
   Draws draws;
-  std::vector<double> offsets(4 * (size_t)S, 0.0), samples(3 * (size_t)n_obs * ns);
-  for (int s = 0; s < S; ++s) {
-    offsets[4 * s + 0] = draws.gauss(0.16);
-    offsets[4 * s + 1] = draws.gauss(0.16);
-    offsets[4 * s + 3] = draws.gauss(0.017);
-  }
-  for (int j = 0; j < n_obs * ns; ++j) {
-    samples[3 * j + 0] = draws.gauss(0.45);
-    samples[3 * j + 1] = draws.gauss(0.45);
-    samples[3 * j + 2] = draws.gauss(0.05);
-  }
+  const std::vector<double> offsets = make_offsets(S, draws), samples = make_pose_samples(n_obs * ns, draws);
   const double weight = params.w_obstacle / ns;
   double sigma0[16] = {};
   sigma0[0] = 0.16 * 0.16; sigma0[5] = 0.16 * 0.16; sigma0[15] = 0.017 * 0.017;
@@ -92,16 +43,13 @@ int main() {
   // by hand: the host-buffer forms, the obstacle set repeated for every candidate
   cilqr_handle* h = nullptr;
   if (cilqr_create(&params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B), ok(B);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   std::vector<double> nom_pose((size_t)B * n_obs * 4 * N), nom_dim((size_t)B * n_obs * 2 * N), off((size_t)B * samples.size());
   for (int b = 0; b < B; ++b) {
     for (int t = 0; t < N; ++t) {
-      for (int r = 0; r < 4; ++r) nom_pose[((size_t)b * N + t) * 4 + r] = pose(r, t);
-      for (int r = 0; r < 2; ++r) nom_dim[((size_t)b * N + t) * 2 + r] = dim(r, t);
+      for (int r = 0; r < 4; ++r) nom_pose[((size_t)b * N + t) * 4 + r] = obstacles[0].relative_pos_array(r, t);
+      for (int r = 0; r < 2; ++r) nom_dim[((size_t)b * N + t) * 2 + r] = obstacles[0].dimension(r, t);
     }
     memcpy(&off[(size_t)b * samples.size()], samples.data(), samples.size() * sizeof(double));
   }
@@ -215,6 +163,52 @@ int main() {
       return 1;
     }
     printf("conflicts throw ok\n");
+  }
+
+  // 4. one planner across mode switches, in the one device block: fused check -> sample covariance check -> fused check -> sample
+  //    covariance check.  The first three runs reject every candidate (max_risk -1), so the warm start stays the fresh planner's and
+  //    each run can be held against a run from that start: the planner of 2. (its rows are `risk`), the first run, the planner of 1.
+  {
+    iLQR a(params, 0, M, B);
+    a.set_global_plan(path);
+    a.set_Obstacle(obstacles);
+    a.set_obstacle_samples(samples, ns);
+    a.set_pose_noise_check_fused(offsets, -1.0);
+    if (a.run_candidates(egos) != -1 || a.last_risk.size() != (size_t)B * CILQR_RRS_FIELDS || a.last_step_hits.size() != (size_t)B * N ||
+        !same(a.last_scores, score) || !a.last_chance_risk_sampled.empty()) {
+      printf("mode switches: the fused run\n");
+      return 1;
+    }
+    const std::vector<double> risk1 = a.last_risk;
+    const std::vector<int32_t> hits1 = a.last_step_hits;
+    a.set_pose_noise_check_fused({}, 1.0);
+    a.set_sample_covariance_check(sigma0, nullptr, -1.0);
+    if (a.run_candidates(egos) != -1) { printf("mode switches: max_risk -1 under the sample covariance check gave a pick\n"); return 1; }
+    if (!a.last_risk.empty() || !a.last_step_hits.empty()) {
+      printf("mode switches: last_risk / last_step_hits are not empty under the sample covariance check\n");
+      return 1;
+    }
+    if (!same(a.last_chance_risk_sampled, risk) || !same(a.last_scores, score)) {
+      printf("mode switches: last_chance_risk_sampled differs from a fresh planner's\n");
+      return 1;
+    }
+    a.set_sample_covariance_check(nullptr, nullptr, 1.0);
+    a.set_pose_noise_check_fused(offsets, -1.0);
+    if (a.run_candidates(egos) != -1 || !same(a.last_risk, risk1) || !same_i(a.last_step_hits, hits1) || !same(a.last_scores, score) ||
+        !a.last_chance_risk_sampled.empty()) {
+      printf("mode switches: the fused run after the sample covariance check differs from the one before it\n");
+      return 1;
+    }
+    a.set_pose_noise_check_fused({}, 1.0);
+    a.set_sample_covariance_check(sigma0, nullptr, max_risk);
+    if (a.run_candidates(egos) != best || !same(a.last_chance_risk_sampled, planner.last_chance_risk_sampled) ||
+        !same(a.last_scores, planner.last_scores) || !a.last_risk.empty() || !a.last_step_hits.empty() ||
+        !same(a.X_result.a, planner.X_result.a) || !same(a.U_result.a, planner.U_result.a) || !same(&a.last_cost, &planner.last_cost, 1) ||
+        a.last_iterations != planner.last_iterations || a.last_exit != planner.last_exit) {
+      printf("mode switches: the pick differs from a fresh planner's\n");
+      return 1;
+    }
+    printf("mode switches ok\n");
   }
   return 0;
 }

@@ -25,7 +25,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -36,13 +36,6 @@ const double kGeom[5] = {16.0, 8.0, 0.1, 6.0, 0.0}, kMapPose[3] = {0.0, 0.0, 0.0
 const double kBlob[3] = {6.0, -1.4, 0.7};  // world x, y of the blob's centre and its width
 const double kPose[4] = {9.0, 2.6, 0.0, 0.0}, kDim[2] = {4.79, 2.16};  // the obstacle of the composed case: ahead, to the other side
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
 
 struct Scene {
   Parameters params;
@@ -51,15 +44,6 @@ struct Scene {
   Uncertainty map;
   double sigma0[16] = {}, W[16] = {};
 };
-
-cilqr_uncertainty_map host_map(const Scene& sc, const float* layer) {
-  cilqr_uncertainty_map m{};
-  m.layer = layer;
-  m.geom = sc.map.geom;
-  m.pose_x = sc.map.pose_x; m.pose_y = sc.map.pose_y; m.pose_theta = sc.map.pose_theta;
-  m.probes_l = sc.map.probes_l; m.probes_w = sc.map.probes_w;
-  return m;
-}
 
 // The sequence by hand for nb solves whose path fit is given; everything it leaves.
 struct Hand {
@@ -70,16 +54,14 @@ struct Hand {
 
 bool by_hand(cilqr_handle* h, const Scene& sc, int nb, const double* egos, const double* poly, const double* fl, int rounds, Hand& o) {
   const size_t cells = sc.map.layer.size();
-  o.U.assign((size_t)nb * 2 * N, 0.0); o.X.assign((size_t)nb * 4 * (N + 1), 0.0); o.J.assign(nb, 0.0);
+  o.U = default_controls(nb, N); o.X.assign((size_t)nb * 4 * (N + 1), 0.0); o.J.assign(nb, 0.0);
   o.iters.assign(nb, 0); o.status.assign(nb, 0);
   o.k.assign((size_t)nb * 2 * N, 0.0); o.K.assign((size_t)nb * 8 * N, 0.0);
   o.tm.assign((size_t)nb * CILQR_TIGHTEN_MAP_FIELDS, 0.0); o.risk_before.assign(nb, 0.0);
   o.sigma.assign((size_t)nb * (N + 1) * 16, 0.0); o.layers.assign((size_t)nb * cells, 0.0f);
-  std::vector<double> seq(2 * (size_t)N), risk((size_t)nb * CILQR_CHANCE_FIELDS);
+  std::vector<double> risk((size_t)nb * CILQR_CHANCE_FIELDS);
   std::vector<int32_t> ok(nb);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < nb; ++b) memcpy(&o.U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
-  const cilqr_uncertainty_map original = host_map(sc, sc.map.layer.data());
+  const cilqr_uncertainty_map original = abi_map(sc.map, sc.map.layer.data());
   const double kappa = cilqr_chance_kappa(kEps);
   bool done = cilqr_set_uncertainty_map(h, &original) == CILQR_OK &&
               cilqr_solve_batch(h, nb, N, 0, egos, o.U.data(), poly, fl, nullptr, nullptr, nullptr, o.X.data(), o.J.data(), o.iters.data(),
@@ -92,7 +74,7 @@ bool by_hand(cilqr_handle* h, const Scene& sc, int nb, const double* egos, const
                              nullptr, o.sigma.data(), nullptr) == CILQR_OK &&
            cilqr_tighten_map(h, nb, N, o.X.data(), o.sigma.data(), kappa, kCap, o.layers.data(), o.tm.data()) == CILQR_OK;
     for (int b = 0; b < nb && done; ++b) {  // the host form of the map takes one shared layer: candidate by candidate
-      const cilqr_uncertainty_map tight = host_map(sc, &o.layers[(size_t)b * cells]);
+      const cilqr_uncertainty_map tight = abi_map(sc.map, &o.layers[(size_t)b * cells]);
       done = cilqr_set_uncertainty_map(h, &tight) == CILQR_OK &&
              cilqr_solve_batch(h, 1, N, 0, egos + 4 * b, &o.U[(size_t)b * 2 * N], poly + CILQR_POLY_COEFFS * b, fl + 2 * b, nullptr, nullptr, nullptr,
                                &o.X[(size_t)b * 4 * (N + 1)], &o.J[b], &o.iters[b], &o.status[b], CILQR_FLAG_NONE) == CILQR_OK;
@@ -254,11 +236,6 @@ bool run_step_case(const Scene& sc) {
 // inflated obstacle and the tightened layer.
 bool composed_case(const Scene& sc) {
   const int M = 1;
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = kDim[0]; dim(1, t) = kDim[1];
-    for (int r = 0; r < 4; ++r) pose(r, t) = kPose[r];
-  }
   const double* ego = &sc.egos[0];
   cilqr_handle* h = nullptr;
   if (cilqr_create(&sc.params, 16, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }
@@ -271,7 +248,7 @@ bool composed_case(const Scene& sc) {
   int n = 0;
   const cilqr_obstacles obs{kPose, kDim, nullptr, 0, 1, 0, 0};
   const cilqr_obstacles inflated{tpose.data(), tdim.data(), nullptr, (int64_t)M * N, N, 1, 0};
-  const cilqr_uncertainty_map original = host_map(sc, sc.map.layer.data()), tight = host_map(sc, layer.data());
+  const cilqr_uncertainty_map original = abi_map(sc.map, sc.map.layer.data()), tight = abi_map(sc.map, layer.data());
   const double kappa = cilqr_chance_kappa(kEps);
   cilqr_default_control_seq(N, U.data());
   bool done = cilqr_local_plan(&sc.params, sc.path.a.data(), sc.path.cols, ego, poly, ref.data(), &n) == CILQR_OK && n > 0;
@@ -290,7 +267,7 @@ bool composed_case(const Scene& sc) {
   if (!done) return false;
   iLQR planner(sc.params, 0, M, 1);
   planner.set_global_plan(sc.path);
-  planner.set_Obstacle({Obstacle(sc.params, dim, pose)});
+  planner.set_Obstacle({standing_obstacle(sc.params, N, kPose[0], kPose[1], kPose[3], kDim[0], kDim[1])});
   planner.set_uncertainty_map(sc.map);
   planner.set_chance_tightening(sc.sigma0, sc.W, kEps, 1, 2.0);
   planner.set_map_tightening(sc.sigma0, sc.W, kEps, 1, kCap);
@@ -304,17 +281,6 @@ bool composed_case(const Scene& sc) {
          same(planner.U_result.a.data(), U.data(), U.size()) && same(&planner.last_cost, &J, 1) && planner.last_iterations == iters;
 }
 
-template <typename F>
-bool throws_logic_error(F&& f, const char* needle) {
-  try {
-    f();
-  } catch (const std::logic_error& e) {
-    return strstr(e.what(), needle) != nullptr;
-  } catch (...) {
-    return false;
-  }
-  return false;
-}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -323,14 +289,8 @@ int main(int argc, char** argv) {
   sc.params.horizon = N;
   sc.params.safe_length = 1.1; sc.params.safe_width = 0.9;
   sc.params.w_uncertainty = 5.0;  // (at the default 1 the map term is too weak to move a plan off the blob)
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
-  sc.egos.resize(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    sc.egos[4 * b + 0] = 0.0;
-    sc.egos[4 * b + 1] = -1.0 + 0.4 * b;
-    sc.egos[4 * b + 2] = 4.0;
-    sc.egos[4 * b + 3] = 0.0;
-  }
+  sc.path = straight_path();
+  sc.egos = spread_egos(B, -1.0, 0.4, 4.0);
   if (cilqr_map_geom_set(&sc.map.geom, kGeom[0], kGeom[1], kGeom[2], kGeom[3], kGeom[4]) != CILQR_OK) return 1;
   sc.map.pose_x = kMapPose[0]; sc.map.pose_y = kMapPose[1]; sc.map.pose_theta = kMapPose[2];
   const cilqr_map_geom& g = sc.map.geom;

@@ -13,66 +13,25 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
-
-namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-// S offsets (dx, dy, 0, dtheta): sums of four uniforms from a fixed linear congruential sequence, scaled to sigma 0.16 m / 0.017 rad
-std::vector<double> make_offsets(int S) {
-  uint64_t state = 0x9e3779b97f4a7c15ull;
-  const auto unit = [&state]() {  // in [-1, 1)
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(state >> 11) / 4503599627370496.0 - 1.0;
-  };
-  const auto gauss = [&unit](double sigma) { return (unit() + unit() + unit() + unit()) * sigma * 0.8660254037844386; };  // var 4/3 -> 1
-  std::vector<double> d(4 * (size_t)S, 0.0);
-  for (int s = 0; s < S; ++s) {
-    d[4 * s + 0] = gauss(0.16);
-    d[4 * s + 1] = gauss(0.16);
-    d[4 * s + 3] = gauss(0.017);
-  }
-  return d;
-}
-}  // namespace
 
 int main() {
   const int N = 30, M = 1, B = 16, S = 70;
   const double max_risk = 0.1;
   Parameters params = default_parameters();
   params.horizon = N;
-  Matrix path(2, 200);
-  for (int i = 0; i < 200; ++i) { path(0, i) = 1.0 * i; path(1, i) = 0.0; }
-  std::vector<double> egos(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    egos[4 * b + 0] = 0.0;
-    egos[4 * b + 1] = -3.0 + 0.5 * b;
-    egos[4 * b + 2] = 5.0;
-    egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -1.0; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  const std::vector<Obstacle> obstacles{Obstacle(params, dim, pose)};
+  const Matrix path = straight_path();
+  const std::vector<double> egos = spread_egos(B, -3.0, 0.5);
+  const std::vector<Obstacle> obstacles{standing_obstacle(params, N, 12.0, -1.0)};
   const std::vector<double> offsets = make_offsets(S);
 
   // by hand: the host-buffer forms on a handle whose max_batch holds the B*S rows
   cilqr_handle* h = nullptr;
   if (cilqr_create(&params, B * S, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B), ok(B);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const double pose1[4] = {12.0, -1.0, 0.0, 0.0}, dim1[2] = {4.79, 2.16};
   const cilqr_obstacles obs{pose1, dim1, nullptr, 0, 1, 0, 0};  // one set for the batch, constant over the horizon
   std::vector<double> k((size_t)B * 2 * N), K((size_t)B * 8 * N), Xr((size_t)B * S * 4 * (N + 1)), Ur((size_t)B * S * 2 * N);

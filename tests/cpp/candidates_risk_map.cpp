@@ -25,49 +25,9 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
-
-namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same_i(const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
-  return a.size() == b.size() && memcmp(a.data(), b.data(), a.size() * sizeof(int32_t)) == 0;
-}
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-int count_nan(const std::vector<double>& v) {
-  int n = 0;
-  for (double x : v) n += x != x;
-  return n;
-}
-// S offsets (dx, dy, 0, dtheta): the sequence of candidates_risk_fused.cpp
-std::vector<double> make_offsets(int S) {
-  uint64_t state = 0x9e3779b97f4a7c15ull;
-  const auto unit = [&state]() {  // in [-1, 1)
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(state >> 11) / 4503599627370496.0 - 1.0;
-  };
-  const auto gauss = [&unit](double sigma) { return (unit() + unit() + unit() + unit()) * sigma * 0.8660254037844386; };  // var 4/3 -> 1
-  std::vector<double> d(4 * (size_t)S, 0.0);
-  for (int s = 0; s < S; ++s) {
-    d[4 * s + 0] = gauss(0.16);
-    d[4 * s + 1] = gauss(0.16);
-    d[4 * s + 3] = gauss(0.017);
-  }
-  return d;
-}
-void put(FILE* f, const std::vector<double>& v) {
-  for (double x : v) fprintf(f, "%.17g\n", x);
-}
-void put_i(FILE* f, const std::vector<int32_t>& v) {
-  for (int32_t x : v) fprintf(f, "%d\n", (int)x);
-}
-}  // namespace
 
 int main(int argc, char** argv) {
   const int N = 30, M = 1, B = 16, S = 70;
@@ -77,53 +37,25 @@ int main(int argc, char** argv) {
   params.horizon = N;
   params.safe_length = 1.1;  // the launch file's values (Experiment.launch:7-8)
   params.safe_width = 0.9;
-  Matrix path(2, 200);
-  for (int i = 0; i < 200; ++i) { path(0, i) = 1.0 * i; path(1, i) = 0.0; }
-  std::vector<double> egos(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    egos[4 * b + 0] = 0.0;
-    egos[4 * b + 1] = -3.0 + 0.5 * b;
-    egos[4 * b + 2] = 5.0;
-    egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -1.0; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  const std::vector<Obstacle> obstacles{Obstacle(params, dim, pose)};
+  const Matrix path = straight_path();
+  const std::vector<double> egos = spread_egos(B, -3.0, 0.5);
+  const std::vector<Obstacle> obstacles{standing_obstacle(params, N, 12.0, -1.0)};
   const std::vector<double> offsets = make_offsets(S);
 
   // the costmap: 200 x 80 cells of 0.2 m centred 15 m ahead; cell (i, j) has its centre at (34.9 - 0.2 i, 7.9 - 0.2 j); a smooth
   // occupied region around (3.5, -0.6) and a weaker one around (20, -4.5); six unknown cells near the candidates' starts
   Uncertainty um;
-  const double geom[5] = {40.0, 16.0, 0.2, 15.0, 0.0}, map_pose[3] = {0.0, 0.0, 0.0};
-  if (cilqr_map_geom_set(&um.geom, geom[0], geom[1], geom[2], geom[3], geom[4]) != CILQR_OK) return 1;
+  if (!bump_costmap(um, {{80.0, 3.5, -0.6, 1.5, 0.5}, {60.0, 20.0, -4.5, 5.0, 1.5}})) return 1;
   const int rows = um.geom.rows, cols = um.geom.cols;
-  um.layer.resize((size_t)rows * cols);
-  for (int j = 0; j < cols; ++j)
-    for (int i = 0; i < rows; ++i) {
-      const double x = 34.9 - 0.2 * i, y = 7.9 - 0.2 * j;
-      const double z = 80.0 * std::exp(-0.5 * (std::pow((x - 3.5) / 1.5, 2) + std::pow((y + 0.6) / 0.5, 2))) +
-                       60.0 * std::exp(-0.5 * (std::pow((x - 20.0) / 5.0, 2) + std::pow((y + 4.5) / 1.5, 2)));
-      um.layer[(size_t)j * rows + i] = (float)(100.0 * std::tanh(z / 100.0));
-    }
   const int nan_cells[6][2] = {{170, 52}, {171, 52}, {168, 47}, {165, 38}, {166, 38}, {150, 26}};
   for (const auto& c : nan_cells) um.layer[(size_t)c[1] * rows + c[0]] = NAN;
-  um.pose_x = map_pose[0]; um.pose_y = map_pose[1]; um.pose_theta = map_pose[2];
 
   // by hand: the host-buffer forms
   cilqr_handle* h = nullptr;
   if (cilqr_create(&params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  cilqr_uncertainty_map m{};
-  m.layer = um.layer.data(); m.geom = um.geom;
-  m.pose_x = um.pose_x; m.pose_y = um.pose_y; m.pose_theta = um.pose_theta;
-  m.probes_l = um.probes_l; m.probes_w = um.probes_w;
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  const cilqr_uncertainty_map m = abi_map(um);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B), ok(B);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const double pose1[4] = {12.0, -1.0, 0.0, 0.0}, dim1[2] = {4.79, 2.16};
   const cilqr_obstacles obs{pose1, dim1, nullptr, 0, 1, 0, 0};  // one set for the batch, constant over the horizon
   std::vector<double> k((size_t)B * 2 * N), K((size_t)B * 8 * N), score((size_t)B * CILQR_SCORE_FIELDS), base(B), risk((size_t)B * RR), total(B);
@@ -197,8 +129,8 @@ int main(int argc, char** argv) {
     FILE* f = fopen(argv[1], "w");
     if (!f) { printf("cannot write %s\n", argv[1]); return 1; }
     fprintf(f, "%d\n%d\n%d\n%d\n%d\n%.17g\n%.17g\n%d\n", B, N, S, rows, cols, threshold, map_max_risk, best);
-    for (double v : geom) fprintf(f, "%.17g\n", v);
-    for (double v : map_pose) fprintf(f, "%.17g\n", v);
+    for (double v : kBumpGeom) fprintf(f, "%.17g\n", v);
+    for (double v : kBumpMapPose) fprintf(f, "%.17g\n", v);
     put(f, X); put(f, U); put(f, k); put(f, K); put(f, total); put(f, offsets); put(f, planner.last_map_risk);
     put_i(f, planner.last_map_step_hits); put_i(f, planner.last_map_unknown_hits);
     for (float v : um.layer) fprintf(f, "%.9g\n", (double)v);

@@ -22,31 +22,11 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
 namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && same(a.data(), b.data(), a.size()); }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-// sums of four uniforms from a fixed linear congruential sequence, scaled to the given sigma
-struct Draws {
-  uint64_t state = 0x9e3779b97f4a7c15ull;
-  double unit() {  // in [-1, 1)
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(state >> 11) / 4503599627370496.0 - 1.0;
-  }
-  double gauss(double sigma) { return (unit() + unit() + unit() + unit()) * sigma * 0.8660254037844386; }  // var 4/3 -> 1
-};
-void put(FILE* f, const std::vector<double>& v) {
-  for (double x : v) fprintf(f, "%.17g\n", x);
-}
 bool results_equal(const iLQR& a, const iLQR& b) {
   return same(a.X_result.a, b.X_result.a) && same(a.U_result.a, b.U_result.a) && same(&a.last_cost, &b.last_cost, 1) &&
          a.last_iterations == b.last_iterations && a.last_exit == b.last_exit && same(a.last_risk, b.last_risk) &&
@@ -60,54 +40,30 @@ int main(int argc, char** argv) {
   const int F = CILQR_RRS_FIELDS;
   Parameters params = default_parameters();
   params.horizon = N;
-  Matrix path(2, 200);
-  for (int i = 0; i < 200; ++i) { path(0, i) = 1.0 * i; path(1, i) = 0.0; }
-  std::vector<double> egos(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    egos[4 * b + 0] = 0.0;
-    egos[4 * b + 1] = 0.6 * b;
-    egos[4 * b + 2] = 5.0;
-    egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -2.5; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  const std::vector<Obstacle> obstacles{Obstacle(params, dim, pose)};
+  const Matrix path = straight_path();
+  const std::vector<double> egos = spread_egos(B, 0.0, 0.6);
+  const std::vector<Obstacle> obstacles{standing_obstacle(params, N, 12.0, -2.5)};
   Draws draws;
-  std::vector<double> offsets(4 * (size_t)S, 0.0), samples(3 * (size_t)n_obs * ns);
-  for (int s = 0; s < S; ++s) {
-    offsets[4 * s + 0] = draws.gauss(0.16);
-    offsets[4 * s + 1] = draws.gauss(0.16);
-    offsets[4 * s + 3] = draws.gauss(0.017);
-  }
-  for (int j = 0; j < n_obs * ns; ++j) {
-    samples[3 * j + 0] = draws.gauss(0.45);
-    samples[3 * j + 1] = draws.gauss(0.45);
-    samples[3 * j + 2] = draws.gauss(0.05);
-  }
+  const std::vector<double> offsets = make_offsets(S, draws), samples = make_pose_samples(n_obs * ns, draws);
   const double weight = params.w_obstacle / ns;
 
   // by hand: the host-buffer forms, the obstacle set repeated for every candidate
   cilqr_handle* h = nullptr;
   if (cilqr_create(&params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U0((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), X((size_t)B * 4 * (N + 1)), J(B);
+  const std::vector<double> U0 = default_controls(B, N);
   std::vector<int32_t> iters(B), status(B), ok(B);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U0[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   std::vector<double> U = U0;
   std::vector<double> nom_pose((size_t)B * n_obs * 4 * N), nom_dim((size_t)B * n_obs * 2 * N), off((size_t)B * samples.size());
   for (int b = 0; b < B; ++b) {
     for (int t = 0; t < N; ++t) {
-      for (int r = 0; r < 4; ++r) nom_pose[((size_t)b * N + t) * 4 + r] = pose(r, t);
-      for (int r = 0; r < 2; ++r) nom_dim[((size_t)b * N + t) * 2 + r] = dim(r, t);
+      for (int r = 0; r < 4; ++r) nom_pose[((size_t)b * N + t) * 4 + r] = obstacles[0].relative_pos_array(r, t);
+      for (int r = 0; r < 2; ++r) nom_dim[((size_t)b * N + t) * 2 + r] = obstacles[0].dimension(r, t);
     }
     memcpy(&off[(size_t)b * samples.size()], samples.data(), samples.size() * sizeof(double));
   }
   std::vector<double> k((size_t)B * 2 * N), K((size_t)B * 8 * N), score((size_t)B * CILQR_SCORE_FIELDS), base(B), risk((size_t)B * F), total(B);
-  std::vector<double> score0((size_t)B * CILQR_SCORE_FIELDS), total0(B), X1(4 * (size_t)(N + 1)), U1 = seq;
+  std::vector<double> score0((size_t)B * CILQR_SCORE_FIELDS), total0(B), X1(4 * (size_t)(N + 1)), U1(U0.begin(), U0.begin() + 2 * N);
   std::vector<int32_t> hits((size_t)B * N);
   double J1 = 0.0;
   int32_t it1 = 0, st1 = 0;

@@ -13,48 +13,23 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
-
-namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
-}  // namespace
 
 int main() {
   const int N = 30, M = 1, B = 16;
   Parameters params = default_parameters();
   params.horizon = N;
-  Matrix path(2, 200);
-  for (int i = 0; i < 200; ++i) { path(0, i) = 1.0 * i; path(1, i) = 0.0; }
-  std::vector<double> egos(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    egos[4 * b + 0] = 0.0;
-    egos[4 * b + 1] = -3.0 + 0.5 * b;
-    egos[4 * b + 2] = 5.0;
-    egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = 4.79; dim(1, t) = 2.16;
-    pose(0, t) = 12.0; pose(1, t) = -1.0; pose(2, t) = 0.0; pose(3, t) = 0.0;
-  }
-  const std::vector<Obstacle> obstacles{Obstacle(params, dim, pose)};
+  const Matrix path = straight_path();
+  const std::vector<double> egos = spread_egos(B, -3.0, 0.5);
+  const std::vector<Obstacle> obstacles{standing_obstacle(params, N, 12.0, -1.0)};
 
   // by hand: the same pre-step and solve, then the scores
   cilqr_handle* h = nullptr;
   if (cilqr_create(&params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
-  std::vector<double> seq(2 * (size_t)N);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   if (cilqr_local_plan_batch(h, B, path.cols, path.a.data(), 0, egos.data(), poly.data(), fl.data(), nullptr, nullptr) != CILQR_OK) {
     printf("cilqr_local_plan_batch: %s\n", cilqr_last_error());
     return 1;

@@ -7,13 +7,9 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
-
-namespace {
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-}  // namespace
 
 int main() {
   const int N = 50, M = 4, B = 96;
@@ -49,11 +45,8 @@ int main() {
     // by hand: the same pre-step, B copies of the obstacle set, the dense solve, the pick
     cilqr_handle* h = nullptr;
     if (cilqr_create(&params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-    std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B);
+    std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
     std::vector<int32_t> iters(B), status(B);
-    std::vector<double> seq(2 * (size_t)N);
-    cilqr_default_control_seq(N, seq.data());
-    for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
     if (cilqr_local_plan_batch(h, B, path.cols, path.a.data(), 0, egos.data(), poly.data(), fl.data(), nullptr, nullptr) != CILQR_OK) {
       printf("cilqr_local_plan_batch: %s\n", cilqr_last_error());
       return 1;

@@ -8,7 +8,8 @@
 //      / last_exit of that candidate and last_tighten, last_tighten_risk_before equal to that sequence's, bit for bit; one round and
 //      two, with and without set_obstacle_covariance;
 //   2. composed with set_pose_covariance_check: the check's gains and chance risk run on the FINAL plan against the original obstacle,
-//      and last_chance_risk is that call's;
+//      and last_chance_risk is that call's; and with the stored-rows check (set_pose_noise_check): cilqr_gains_batch, cilqr_rollout_batch
+//      and cilqr_score_rollouts on the final plans against the original obstacle, last_risk that call's;
 //   3. run_step: the same sequence at B = 1 behind cilqr_local_plan;
 //   4. rounds = 0 and Sigma0 == nullptr switch it off: the plain pick, empty last_tighten;
 //   5. together with set_obstacle_samples, whichever comes second throws std::logic_error.
@@ -20,7 +21,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -29,13 +30,6 @@ const int N = 30, M = 1;
 const double kEps = 0.05, kCap = 2.0, kMaxRisk = 0.2;
 const double kPose[4] = {12.0, -1.0, 0.0, 0.0}, kDim[2] = {4.79, 2.16}, kCov[3] = {0.09, 0.01, 0.04};
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-int first_minimum(const std::vector<double>& v) {  // strict <, NaN never wins; -1: none
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
 
 struct Scene {
   Parameters params;
@@ -52,15 +46,13 @@ struct Hand {
 };
 
 bool by_hand(cilqr_handle* h, const Scene& sc, int B, const double* egos, const double* poly, const double* fl, int rounds, bool with_cov, Hand& o) {
-  o.U.assign((size_t)B * 2 * N, 0.0); o.X.assign((size_t)B * 4 * (N + 1), 0.0); o.J.assign(B, 0.0);
+  o.U = default_controls(B, N); o.X.assign((size_t)B * 4 * (N + 1), 0.0); o.J.assign(B, 0.0);
   o.iters.assign(B, 0); o.status.assign(B, 0);
   o.k.assign((size_t)B * 2 * N, 0.0); o.K.assign((size_t)B * 8 * N, 0.0);
   o.tg.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0); o.risk_before.assign(B, 0.0);
-  std::vector<double> seq(2 * (size_t)N), risk((size_t)B * CILQR_CHANCE_FIELDS), sigma((size_t)B * (N + 1) * 16);
+  std::vector<double> risk((size_t)B * CILQR_CHANCE_FIELDS), sigma((size_t)B * (N + 1) * 16);
   std::vector<double> tpose((size_t)B * M * 4 * N), tdim((size_t)B * M * 2 * N);
   std::vector<int32_t> ok(B);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&o.U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const cilqr_obstacles obs{kPose, kDim, nullptr, 0, 1, 0, 0};  // one set for the batch, constant over the horizon
   const cilqr_obstacles inflated{tpose.data(), tdim.data(), nullptr, (int64_t)M * N, N, 1, 0};
   const double kappa = cilqr_chance_kappa(kEps);
@@ -169,6 +161,48 @@ bool run_case(const Scene& sc, const char* name, int B, CandidatePick pick, int 
   return true;
 }
 
+// The stored-rows pose-noise check (set_pose_noise_check, not fused) behind one round of tightening: the rollouts start from the final
+// plans and are scored against the ORIGINAL obstacle.
+bool stored_rows_case(const Scene& sc, int B) {
+  const int S = 32;
+  const double max_risk = 0.1;
+  const std::vector<double> offsets = make_offsets(S);
+  cilqr_handle* h = nullptr;
+  if (cilqr_create(&sc.params, B * S, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }  // (holds the B*S rows)
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), Xr((size_t)B * S * 4 * (N + 1)), Ur((size_t)B * S * 2 * N);
+  std::vector<double> rows((size_t)B * S * CILQR_SCORE_FIELDS), risk((size_t)B * CILQR_RISK_FIELDS), total(B);
+  std::vector<int32_t> ok(B);
+  Hand o;
+  const cilqr_obstacles obs{kPose, kDim, nullptr, 0, 1, 0, 0};
+  const bool done =
+      cilqr_local_plan_batch(h, B, sc.path.cols, sc.path.a.data(), 0, sc.egos.data(), poly.data(), fl.data(), nullptr, nullptr) == CILQR_OK &&
+      by_hand(h, sc, B, sc.egos.data(), poly.data(), fl.data(), 1, false, o) &&
+      cilqr_gains_batch(h, B, N, M, o.X.data(), o.U.data(), poly.data(), fl.data(), &obs, 1.0, o.k.data(), o.K.data(), ok.data()) == CILQR_OK &&
+      cilqr_rollout_batch(h, B, N, S, o.X.data(), o.U.data(), o.k.data(), o.K.data(), offsets.data(), 0, 0.0, Xr.data(), Ur.data()) == CILQR_OK &&
+      cilqr_score_rollouts(h, B, N, M, S, Xr.data(), Ur.data(), poly.data(), fl.data(), &obs, max_risk, rows.data(), risk.data(), total.data()) == CILQR_OK;
+  if (!done) { printf("stored rows: the sequence by hand failed: %s\n", cilqr_last_error()); return false; }
+  cilqr_destroy(h);
+  const int want = first_minimum(total);
+  double moved = 0.0;
+  for (size_t i = 0; i < o.U.size(); ++i) moved = std::fmax(moved, std::fabs(o.U[i] - o.U_first[i]));
+  printf("stored rows: pick by hand %d; %d of %d candidates rejected; the round moved U by up to %.3g\n", want, count_nan(total), B, moved);
+  if (want < 0 || !(moved > 1e-3) || !(o.tg[0] > 0.1)) { printf("stored rows: the scene does not exercise the tightening\n"); return false; }
+  iLQR planner(sc.params, 0, M, B);
+  planner.set_global_plan(sc.path);
+  planner.set_Obstacle(sc.obstacles);
+  planner.set_pose_noise_check(offsets, max_risk);
+  planner.set_chance_tightening(sc.sigma0, sc.W, kEps, 1, kCap);
+  const int best = planner.run_candidates(sc.egos);
+  if (best != want) { printf("stored rows: run_candidates picked %d, the sequence by hand %d\n", best, want); return false; }
+  if (!results_match("stored rows", planner, o, B, best)) return false;
+  if (!same(planner.last_risk, risk)) { printf("stored rows: last_risk differs from cilqr_score_rollouts on the final plans against the original obstacle\n"); return false; }
+  if (!planner.last_scores.empty() || !planner.last_step_hits.empty() || !planner.last_chance_risk.empty()) {
+    printf("stored rows: a field the mode does not produce is not empty\n");
+    return false;
+  }
+  return true;
+}
+
 bool run_step_case(const Scene& sc) {
   cilqr_handle* h = nullptr;
   if (cilqr_create(&sc.params, 3, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return false; }
@@ -199,17 +233,6 @@ bool run_step_case(const Scene& sc) {
   return planner.last_tighten.empty();
 }
 
-template <typename F>
-bool throws_logic_error(F&& f, const char* needle) {
-  try {
-    f();
-  } catch (const std::logic_error& e) {
-    return strstr(e.what(), needle) != nullptr;
-  } catch (...) {
-    return false;
-  }
-  return false;
-}
 }  // namespace
 
 int main() {
@@ -217,20 +240,9 @@ int main() {
   sc.params = default_parameters();
   sc.params.horizon = N;
   const int B = 16;
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
-  sc.egos.resize(4 * (size_t)B);
-  for (int b = 0; b < B; ++b) {
-    sc.egos[4 * b + 0] = 0.0;
-    sc.egos[4 * b + 1] = -3.0 + 0.5 * b;
-    sc.egos[4 * b + 2] = 5.0;
-    sc.egos[4 * b + 3] = 0.0;
-  }
-  Matrix dim(2, N), pose(4, N);
-  for (int t = 0; t < N; ++t) {
-    dim(0, t) = kDim[0]; dim(1, t) = kDim[1];
-    for (int r = 0; r < 4; ++r) pose(r, t) = kPose[r];
-  }
-  sc.obstacles = {Obstacle(sc.params, dim, pose)};
+  sc.path = straight_path();
+  sc.egos = spread_egos(B, -3.0, 0.5);
+  sc.obstacles = {standing_obstacle(sc.params, N, kPose[0], kPose[1], kPose[3], kDim[0], kDim[1])};
   sc.sigma0[0] = 0.16 * 0.16; sc.sigma0[5] = 0.16 * 0.16; sc.sigma0[15] = 0.017 * 0.017;
   sc.W[0] = 1e-4; sc.W[5] = 1e-4; sc.W[10] = 4e-4; sc.W[15] = 1e-6;
 
@@ -241,6 +253,7 @@ int main() {
   printf("off switches ok\n");
   if (!run_case(sc, "check J", B, CandidatePick::MinTrackingCost, 1, false, true)) return 1;
   if (!run_case(sc, "check total", B, CandidatePick::MinTotalCost, 2, true, true)) return 1;
+  if (!stored_rows_case(sc, B)) return 1;
   printf("composed pick ok\n");
   if (!run_step_case(sc)) return 1;
   printf("run_step ok\n");

@@ -27,7 +27,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -36,8 +36,6 @@ const int N = 40, M = 2, B = 2;
 const double kInflate = 0.2, kZ = 2.0;
 const int kWindow = 2;
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && same(a.data(), b.data(), a.size()); }
 
 struct Scene {
   Parameters params;
@@ -56,16 +54,6 @@ struct ByHand {
   int best = -1;
 };
 
-cilqr_uncertainty_map host_map(const Scene& sc, const float* layer, int64_t stride) {
-  cilqr_uncertainty_map m{};
-  m.layer = layer;
-  m.geom = sc.map.geom;
-  m.pose_x = sc.map.pose_x; m.pose_y = sc.map.pose_y; m.pose_theta = sc.map.pose_theta;
-  m.layer_stride = stride;
-  m.probes_l = sc.map.probes_l; m.probes_w = sc.map.probes_w;
-  return m;
-}
-
 // The C-ABI sequence by hand, host forms, for the candidates egos[0 .. nb): one round.
 // tighten: the composed round of set_map_tightening (Sigma0 = sigma0, W = Q).  judge: cilqr_chance_risk_cov on the final plans.
 bool by_hand(const Scene& sc, const double* egos, int nb, bool ellipses, ByHand& o, bool tighten = false, bool judge = false,
@@ -75,15 +63,13 @@ bool by_hand(const Scene& sc, const double* egos, int nb, bool ellipses, ByHand&
   if (cilqr_create(&sc.params, 64, N, M, 0, &h) != CILQR_OK) return false;
   const size_t cells = sc.map.layer.size();
   std::vector<double> pose((size_t)M * 4 * N), dim((size_t)M * 2 * N), cov((size_t)M * 3 * N), poly((size_t)nb * CILQR_POLY_COEFFS), fl((size_t)nb * 2),
-      U((size_t)nb * 2 * N), seq(2 * (size_t)N), J(nb);
+      U = default_controls(nb, N), J(nb);
   std::vector<int32_t> status(nb);
   o.X1.assign((size_t)nb * 4 * (N + 1), 0.0); o.X2 = o.X1; o.J2.assign(nb, 0.0); o.iters.assign(nb, 0);
   o.fields.assign((size_t)nb * CILQR_TRACK_MAP_FIELDS, 0.0); o.layers.assign((size_t)nb * cells, 0.0f);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < nb; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const cilqr_obstacles obs{pose.data(), dim.data(), nullptr, 0, N, 1, 0};
   const int Ms = ellipses ? M : 0;
-  const cilqr_uncertainty_map original = host_map(sc, sc.map.layer.data(), 0);
+  const cilqr_uncertainty_map original = abi_map(sc.map, sc.map.layer.data(), 0);
   bool ok = cilqr_predict_obstacles(h, 1, N, M, sc.tracks.data(), sc.dims.data(), sc.P0.data(), sc.Q.data(), pose.data(), dim.data(), cov.data(),
                                     nullptr) == CILQR_OK &&
             cilqr_set_uncertainty_map(h, &original) == CILQR_OK &&
@@ -102,12 +88,12 @@ bool by_hand(const Scene& sc, const double* egos, int nb, bool ellipses, ByHand&
   ok = ok && cilqr_rasterize_tracks(h, nb, N, M, o.X1.data(), &obs, cov.data(), kInflate, kZ, kWindow, 0u, o.layers.data(), o.fields.data()) == CILQR_OK;
   // (the host form of the setter takes one layer: each candidate is re-solved alone against its own — a solve depends on its own inputs alone)
   for (int b = 0; ok && b < nb; ++b) {
-    cilqr_uncertainty_map own = host_map(sc, &o.layers[(size_t)b * cells], 0);
+    cilqr_uncertainty_map own = abi_map(sc.map, &o.layers[(size_t)b * cells], 0);
     if (tighten) {  // the tightening reads the candidate's RASTERISED layer
       ok = cilqr_set_uncertainty_map(h, &own) == CILQR_OK &&
            cilqr_tighten_map(h, 1, N, &o.X1[(size_t)b * 4 * (N + 1)], &sigma[(size_t)b * (N + 1) * 16], cilqr_chance_kappa(kEps), kCap,
                              &tight[(size_t)b * cells], &o.tm[(size_t)b * CILQR_TIGHTEN_MAP_FIELDS]) == CILQR_OK;
-      own = host_map(sc, &tight[(size_t)b * cells], 0);
+      own = abi_map(sc.map, &tight[(size_t)b * cells], 0);
       if (!ok) break;
     }
     ok = cilqr_set_uncertainty_map(h, &own) == CILQR_OK &&
@@ -165,7 +151,7 @@ int main(int argc, char** argv) {
   sc.params.horizon = N;
   sc.params.safe_length = 1.1; sc.params.safe_width = 0.9;
   sc.params.w_uncertainty = 5.0;
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
+  sc.path = straight_path();
   for (int b = 0; b < B; ++b) { const double e[4] = {0.0, -0.4 * b, 5.0, 0.0}; sc.egos.insert(sc.egos.end(), e, e + 4); }
   const double half_pi = 1.57079632679489655800;
   sc.tracks = {20.0, -10.0, 5.0, half_pi, 0.0, 0.0, 20.0, -22.0, 5.0, half_pi, 0.0, 0.0};

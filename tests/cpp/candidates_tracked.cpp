@@ -20,21 +20,13 @@
 #include <cstring>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
 namespace {
 const int N = 30, M = 1, B = 4;
 
-bool same(const double* a, const double* b, size_t n) { return memcmp(a, b, n * sizeof(double)) == 0; }
-bool same(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && same(a.data(), b.data(), a.size()); }
-int first_minimum(const std::vector<double>& v) {
-  int best = -1;
-  for (int b = 0; b < (int)v.size(); ++b)
-    if (v[b] == v[b] && (best < 0 || v[b] < v[best])) best = b;
-  return best;
-}
 
 struct Scene {
   Parameters params;
@@ -88,7 +80,7 @@ int main(int argc, char** argv) {
   Scene sc;
   sc.params = default_parameters();
   sc.params.horizon = N;
-  for (int i = 0; i < 200; ++i) { sc.path(0, i) = 1.0 * i; sc.path(1, i) = 0.0; }
+  sc.path = straight_path();
   for (int b = 0; b < B; ++b) { const double e[4] = {0.0, 0.3 * b, 5.0, 0.0}; sc.egos.insert(sc.egos.end(), e, e + 4); }
   sc.tracks = {30.0, 3.4, 5.0, 3.14159265358979311600, 0.0, 0.0};
   sc.dims = {4.0, 2.0};
@@ -119,10 +111,8 @@ int main(int argc, char** argv) {
   // ---- 3: the sequence by hand with obs_cov, from the default warm start the planners started from
   cilqr_handle* h = nullptr;
   if (cilqr_create(&sc.params, B, N, M, 0, &h) != CILQR_OK) { printf("cilqr_create: %s\n", cilqr_last_error()); return 1; }
-  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U((size_t)B * 2 * N), X((size_t)B * 4 * (N + 1)), J(B), seq(2 * (size_t)N);
+  std::vector<double> poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2), U = default_controls(B, N), X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B), ok(B);
-  cilqr_default_control_seq(N, seq.data());
-  for (int b = 0; b < B; ++b) memcpy(&U[(size_t)b * 2 * N], seq.data(), seq.size() * sizeof(double));
   const cilqr_obstacles obs{pose.data(), dim.data(), nullptr, 0, N, 1, 0};  // one predicted set for every candidate
   std::vector<double> k((size_t)B * 2 * N), K((size_t)B * 8 * N), risk((size_t)B * CILQR_CHANCE_FIELDS), step((size_t)B * N), total(B),
       bare((size_t)B * CILQR_CHANCE_FIELDS), bare_total(B);

@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "ilqr_adapter.h"
+#include "facade_common.h"
 
 using namespace cilqr_host;
 
@@ -14,15 +14,7 @@ int main() {
   params.horizon = N;
   Matrix path(2, 200);
   for (int i = 0; i < 200; ++i) { path(0, i) = 37.25 + 1.03 * i; path(1, i) = 1.2 * std::sin(0.05 * path(0, i)); }
-  std::vector<Obstacle> obstacles;
-  for (int o = 0; o < M; ++o) {
-    Matrix dim(2, N), pose(4, N);
-    for (int t = 0; t < N; ++t) {
-      dim(0, t) = 4.79; dim(1, t) = 2.16;
-      pose(0, t) = 60 + 14 * o; pose(1, t) = (o % 2) ? -1.5 : 2.0; pose(2, t) = 0; pose(3, t) = 0.1 * o;
-    }
-    obstacles.emplace_back(params, dim, pose);
-  }
+  const std::vector<Obstacle> obstacles = staggered_obstacles(params, N, M, 60, 14, 2.0, -1.5);
   double worst = 0.0;
   int checked = 0;
   for (int k = 0; k < 24; ++k) {

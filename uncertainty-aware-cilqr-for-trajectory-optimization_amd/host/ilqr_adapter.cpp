@@ -1,5 +1,5 @@
 // ilqr_adapter.cpp — see ilqr_adapter.h.  Host C++ over the C-ABI; the HIP runtime is used for one thing only: the device block
-// and the stream of the pose-noise check (set_pose_noise_check), whose pipeline stays on the device between the C-ABI's _device calls.
+// and the stream of the checks (candidate_layout.h), whose pipeline stays on the device between the C-ABI's _device calls.
 #include "ilqr_adapter.h"
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,70 @@ namespace {
 void check(int rc, const char* what) {
   if (rc != CILQR_OK) throw std::runtime_error(std::string(what) + ": " + cilqr_last_error());
 }
+void hip_check(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+const char* const kObstacleCovarianceSize =
+    "set_obstacle_covariance: needs 3 values per obstacle of set_Obstacle, or 3 per obstacle and step";
+const char* const kStoredRowsWithSamples =
+    "the stored-rows pose-noise check has no form for sampled obstacles (set_obstacle_samples): use set_pose_noise_check_fused";
+const char* const kCovarianceWithNoise =
+    "set_pose_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
+const char* const kTighteningWithSamples =
+    "set_chance_tightening has no form for sampled obstacles (set_obstacle_samples): the sampled solve takes no inflated table";
+const char* const kMapTighteningWithSamples =
+    "set_map_tightening has no form for sampled obstacles (set_obstacle_samples), like set_chance_tightening";
+const char* const kTighteningsDisagree =
+    "set_chance_tightening and set_map_tightening are both set and must agree on Sigma0, W, lamb and rounds: one covariance chain and one "
+    "re-solve per round serve both";
+const char* const kTrackMapWithSamples =
+    "set_track_map has no form for sampled obstacles (set_obstacle_samples), like set_map_tightening";
+const char* const kTrackMapRoundsDisagree =
+    "set_track_map beside set_chance_tightening or set_map_tightening: one re-solve per round serves them all, so the round counts must agree";
+const char* const kTrackMapEllipsesOffTightened =
+    "set_track_map with ellipses = false beside set_chance_tightening: the solves read no ellipse that the tightening could inflate";
+const char* const kCovarianceWithSamples =
+    "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
+const char* const kSampleCovarianceWithNoise =
+    "set_sample_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
+const char* const kSampleCovarianceWithoutSamples =
+    "set_sample_covariance_check has effect with obstacle samples (set_obstacle_samples) only: without samples use set_pose_covariance_check";
 }  // namespace
+
+// The checks' device block and the stream everything on it goes to.  `d + at` is the array at offset `at` (in doubles).
+struct iLQR::Block {
+  double* d;
+  hipStream_t st;
+  double* operator+(size_t at) const { return d + at; }
+  int32_t* i32(size_t at) const { return (int32_t*)(d + at); }
+  void up(size_t at, const void* src, size_t doubles) const {
+    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  }
+  void down(void* dst, size_t at, size_t bytes) const {
+    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  }
+  void down_i32(int32_t* dst, size_t at, size_t index) const {
+    hip_check(hipMemcpyAsync(dst, i32(at) + index, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  }
+  template <class T>
+  void fetch(std::vector<T>& v, size_t at, size_t n) const {  // a last_* vector: sized, then filled from the block
+    v.assign(n, T(0));
+    down(v.data(), at, n * sizeof(T));
+  }
+  void wait() const { hip_check(hipStreamSynchronize(st), "hipStreamSynchronize"); }
+};
+
+struct iLQR::Candidates {
+  std::vector<double> U, poly, fl, ref;
+  std::vector<int32_t> n_ref;
+};
+
+struct iLQR::Solved {
+  Matrix X;
+  std::vector<double> U;
+  double J = 0.0;
+  int32_t iters = 0, status = 0;
+};
 
 Parameters default_parameters() {
   Parameters p;
@@ -32,11 +95,10 @@ iLQR::iLQR(const Parameters& params, int device, int max_obstacles, int max_cand
 }
 
 iLQR::~iLQR() {
-  if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);
-  if (noise_dev_) (void)hipFree(noise_dev_);
-  if (scov_dev_) (void)hipFree(scov_dev_);
+  if (block_stream_) (void)hipStreamSynchronize((hipStream_t)block_stream_);
+  if (block_dev_) (void)hipFree(block_dev_);
   if (map_dev_) (void)hipFree(map_dev_);
-  if (noise_stream_) (void)hipStreamDestroy((hipStream_t)noise_stream_);
+  if (block_stream_) (void)hipStreamDestroy((hipStream_t)block_stream_);
   cilqr_destroy(h_);
 }
 
@@ -101,7 +163,7 @@ void iLQR::install_tracked() {
 void iLQR::set_obstacle_covariance_check(bool on) {
   const bool was = obs_cov_check_;
   obs_cov_check_ = on;
-  if (was != on && cov_check_) reserve_noise_buffers();
+  if (was != on) reserve_block_if_used();
 }
 
 void iLQR::set_uncertainty_map(const Uncertainty& u) {
@@ -135,7 +197,7 @@ void iLQR::apply_map(const Uncertainty& u) {
   // (with the track map beside the map tightening a round keeps two layers per candidate: the rasterised one and the tightened one)
   const size_t cells = (size_t)u.geom.rows * u.geom.cols, need = cells * (1 + (size_t)max_candidates_ * (map_tighten_ && tm_rounds_ > 0 ? 2 : 1));
   if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error("set_uncertainty_map: hipSetDevice failed");
-  if (noise_stream_) (void)hipStreamSynchronize((hipStream_t)noise_stream_);  // nothing enqueued may still read the old block
+  if (block_stream_) (void)hipStreamSynchronize((hipStream_t)block_stream_);  // nothing enqueued may still read the old block
   if (need > map_dev_cap_) {
     if (map_dev_) (void)hipFree(map_dev_);
     map_dev_ = nullptr; map_dev_cap_ = 0;
@@ -223,7 +285,7 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
   const double fl[2] = {x_local_plan.front(), x_local_plan.back()};
-  if (tighten_ || map_tighten_ || track_map_on()) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
+  if (modes().chain() || modes().track_rounds()) { solve_tightened(x_0, U, poly_coeffs, fl); return; }
   X_result = Matrix(4, N + 1);
   int32_t iters = 0, status = 0;
   if (n_samples_) {
@@ -280,102 +342,128 @@ void iLQR::set_candidate_pick(CandidatePick pick, double max_collision) {
   max_collision_ = max_collision;
 }
 
+CandidateModes iLQR::modes() const {
+  CandidateModes m;
+  m.noise = !noise_.empty(); m.fused = noise_fused_; m.cov = cov_.on; m.scov = scov_.on; m.sampled = n_samples_ > 0;
+  m.cov_judge = obs_cov_check_; m.cmap = cmap_check_; m.map = map_check_;
+  m.tighten = tighten_; m.map_tighten = map_tighten_; m.track_map = tm_rounds_ > 0;
+  m.min_total = pick_ == CandidatePick::MinTotalCost;
+  m.map_set = map_set_; m.obstacles = !obstacles_.empty(); m.tracks = tracked_horizon_ >= 0;
+  return m;
+}
+
+CandidateSizes iLQR::sizes() const {
+  CandidateSizes z;
+  z.B = max_candidates_; z.N = params.horizon; z.M = max_obstacles_; z.S = noise_.size() / 4;
+  z.n_samples = n_samples_; z.n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
+  z.Q = cmap_weights_.size();
+  return z;
+}
+
+iLQR::Block iLQR::block() const { return Block{(double*)block_dev_, (hipStream_t)block_stream_}; }
+
+void iLQR::clear_round_fields() {
+  last_tighten.clear(); last_tighten_risk_before.clear();
+  last_tighten_map.clear(); last_tighten_map_risk_before.clear();
+  last_track_map.clear();
+}
+
+void iLQR::clear_candidate_fields() {
+  clear_round_fields();
+  last_scores.clear(); last_risk.clear(); last_step_hits.clear();
+  last_map_risk.clear(); last_map_step_hits.clear(); last_map_unknown_hits.clear();
+  last_chance_risk.clear(); last_step_risk.clear();
+  last_chance_map_risk.clear(); last_map_step_risk.clear();
+  last_chance_risk_sampled.clear();
+}
+
+// The prologue of every run_candidates: LocalPlanner pre-step for all candidates in one device launch (cilqr_local_plan_batch)
+// instead of B host fits, and the warm start replicated into [B][2N].
+iLQR::Candidates iLQR::plan_candidates(int B, const std::vector<double>& ego_states) {
+  const size_t N = params.horizon, W = params.num_of_local_wpts;
+  Candidates c;
+  c.U.resize((size_t)B * 2 * N); c.poly.resize((size_t)B * CILQR_POLY_COEFFS); c.fl.resize((size_t)B * 2);
+  c.ref.resize((size_t)B * 2 * W); c.n_ref.resize(B);
+  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), c.poly.data(), c.fl.data(),
+                               c.ref.data(), c.n_ref.data()), "cilqr_local_plan_batch");
+  for (int b = 0; b < B; ++b) memcpy(&c.U[(size_t)b * 2 * N], control_seq_.a.data(), 2 * N * sizeof(double));
+  return c;
+}
+
+// The epilogue of every solve: `U` is where the caller keeps the controls — the warm start, for run_step and run_candidates.
+void iLQR::install(const Solved& s, Matrix& U) {
+  X_result = s.X;
+  U.a = s.U;
+  U_result = U;  // I/iLQR.cpp:244
+  last_iterations = s.iters;
+  last_exit = s.status;
+  last_cost = s.J;
+}
+
+void iLQR::fetch_solved(const Block& d, int b, Solved& s) const {
+  const size_t N = params.horizon;
+  s.X = Matrix(4, (int)N + 1);
+  s.U.resize(2 * N);
+  d.down(s.X.a.data(), layout_.X + (size_t)b * 4 * (N + 1), s.X.a.size() * sizeof(double));
+  d.down(s.U.data(), layout_.U + (size_t)b * 2 * N, s.U.size() * sizeof(double));
+  d.down(&s.J, layout_.J + (size_t)b, sizeof(double));
+  d.down_i32(&s.iters, layout_.iters, b);
+  d.down_i32(&s.status, layout_.status, b);
+}
+
 int iLQR::run_candidates(const std::vector<double>& ego_states) {
   if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
-  if (scov_check_ && track_map_on())
-    throw std::logic_error("set_track_map has no form for sampled obstacles (set_obstacle_samples), like set_map_tightening");
-  if (scov_check_) return run_candidates_sample_covariance(B, ego_states);
-  if (!noise_.empty() || cov_check_ || tighten_ || map_tighten_ || track_map_on()) return run_candidates_noise_checked(B, ego_states);
-  std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
+  const CandidateModes m = modes();
+  if (m.scov && m.track_rounds()) throw std::logic_error(kTrackMapWithSamples);
+  if (m.in_block()) return run_candidates_in_block(B, ego_states, m);
+  // the unchecked path: the host-buffer forms on the handle's stream, the pick on the host
+  Candidates c = plan_candidates(B, ego_states);
   std::vector<double> X((size_t)B * 4 * (N + 1)), J(B);
   std::vector<int32_t> iters(B), status(B);
-  // LocalPlanner pre-step for all candidates in one device launch (cilqr_local_plan_batch) instead of B host fits
-  const int W = params.num_of_local_wpts;
-  std::vector<double> ref((size_t)B * 2 * W);
-  std::vector<int32_t> n_ref(B);
-  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), poly.data(), fl.data(),
-                               ref.data(), n_ref.data()), "cilqr_local_plan_batch");
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
   const cilqr_obstacles obs = obstacle_strides();  // one obstacle set for every candidate
   std::vector<double> total, nom_pose, nom_dim, samp_off;
   const int n_obs = n_samples_ ? pack_sampled(B, nom_pose, nom_dim, samp_off) : 0;
   if (n_samples_)
-    check(cilqr_solve_batch_sampled(h_, B, N, n_obs, n_samples_, ego_states.data(), U.data(), poly.data(), fl.data(), nom_pose.data(),
+    check(cilqr_solve_batch_sampled(h_, B, N, n_obs, n_samples_, ego_states.data(), c.U.data(), c.poly.data(), c.fl.data(), nom_pose.data(),
                                     nom_dim.data(), samp_off.data(), sample_weight(), X.data(), J.data(), iters.data(), status.data(),
                                     CILQR_FLAG_NONE),
           "cilqr_solve_batch_sampled");
   else
-    check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, X.data(),
+    check(cilqr_solve_batch_obstacles(h_, B, N, M, ego_states.data(), c.U.data(), c.poly.data(), c.fl.data(), M ? &obs : nullptr, X.data(),
                                       J.data(), iters.data(), status.data(), CILQR_FLAG_NONE),
           "cilqr_solve_batch_obstacles");
-  last_scores.clear();
-  if (pick_ == CandidatePick::MinTotalCost) {  // rank by everything the solve descended along, among the candidates that are safe
+  clear_candidate_fields();
+  if (m.min_total) {  // rank by everything the solve descended along, among the candidates that are safe
     last_scores.resize((size_t)B * CILQR_SCORE_FIELDS);
     total.resize(B);
     if (n_samples_)
-      check(cilqr_score_batch_sampled(h_, B, N, n_obs, n_samples_, X.data(), U.data(), poly.data(), fl.data(), nom_pose.data(),
+      check(cilqr_score_batch_sampled(h_, B, N, n_obs, n_samples_, X.data(), c.U.data(), c.poly.data(), c.fl.data(), nom_pose.data(),
                                       nom_dim.data(), samp_off.data(), sample_weight(), max_collision_, last_scores.data(), total.data()),
             "cilqr_score_batch_sampled");
     else
-      check(cilqr_score_batch(h_, B, N, M, X.data(), U.data(), poly.data(), fl.data(), M ? &obs : nullptr, max_collision_,
+      check(cilqr_score_batch(h_, B, N, M, X.data(), c.U.data(), c.poly.data(), c.fl.data(), M ? &obs : nullptr, max_collision_,
                               last_scores.data(), total.data()),
             "cilqr_score_batch");
   }
-  const std::vector<double>& rank = pick_ == CandidatePick::MinTotalCost ? total : J;
+  const std::vector<double>& rank = m.min_total ? total : J;
   int best = 0;  // strict-< first minimum, NaN never wins (the convention of cilqr_argmin_device)
   bool have = false;
   for (int b = 0; b < B; ++b)
     if (rank[b] == rank[b] && (!have || rank[b] < rank[best])) { best = b; have = true; }
-  if (pick_ == CandidatePick::MinTotalCost && !have) return -1;  // every candidate rejected: results and warm start stay
-  X_result = Matrix(4, N + 1);
-  for (int i = 0; i < 4 * (N + 1); ++i) X_result.a[i] = X[(size_t)best * 4 * (N + 1) + i];
-  for (int i = 0; i < 2 * N; ++i) control_seq_.a[i] = U[(size_t)best * 2 * N + i];
-  U_result = control_seq_;
-  ref_traj_result = Matrix(2, n_ref[best]);
-  for (int i = 0; i < 2 * n_ref[best]; ++i) ref_traj_result.a[i] = ref[(size_t)best * 2 * W + i];
-  last_iterations = iters[best];
-  last_exit = status[best];
-  last_cost = J[best];
+  if (m.min_total && !have) return -1;  // every candidate rejected: results and warm start stay
+  Solved s;
+  s.X = Matrix(4, N + 1);
+  memcpy(s.X.a.data(), &X[(size_t)best * 4 * (N + 1)], s.X.a.size() * sizeof(double));
+  s.U.assign(&c.U[(size_t)best * 2 * N], &c.U[(size_t)best * 2 * N] + 2 * N);
+  s.J = J[best]; s.iters = iters[best]; s.status = status[best];
+  install(s, control_seq_);
+  ref_traj_result = Matrix(2, c.n_ref[best]);
+  memcpy(ref_traj_result.a.data(), &c.ref[(size_t)best * 2 * params.num_of_local_wpts], ref_traj_result.a.size() * sizeof(double));
   return best;
 }
-
-namespace {
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-}  // namespace
-
-namespace {
-const char* const kObstacleCovarianceSize =
-    "set_obstacle_covariance: needs 3 values per obstacle of set_Obstacle, or 3 per obstacle and step";
-const char* const kStoredRowsWithSamples =
-    "the stored-rows pose-noise check has no form for sampled obstacles (set_obstacle_samples): use set_pose_noise_check_fused";
-const char* const kCovarianceWithNoise =
-    "set_pose_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
-const char* const kTighteningWithSamples =
-    "set_chance_tightening has no form for sampled obstacles (set_obstacle_samples): the sampled solve takes no inflated table";
-const char* const kMapTighteningWithSamples =
-    "set_map_tightening has no form for sampled obstacles (set_obstacle_samples), like set_chance_tightening";
-const char* const kTighteningsDisagree =
-    "set_chance_tightening and set_map_tightening are both set and must agree on Sigma0, W, lamb and rounds: one covariance chain and one "
-    "re-solve per round serve both";
-const char* const kTrackMapWithSamples =
-    "set_track_map has no form for sampled obstacles (set_obstacle_samples), like set_map_tightening";
-const char* const kTrackMapRoundsDisagree =
-    "set_track_map beside set_chance_tightening or set_map_tightening: one re-solve per round serves them all, so the round counts must agree";
-const char* const kTrackMapEllipsesOffTightened =
-    "set_track_map with ellipses = false beside set_chance_tightening: the solves read no ellipse that the tightening could inflate";
-const char* const kCovarianceWithSamples =
-    "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
-const char* const kSampleCovarianceWithNoise =
-    "set_sample_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
-const char* const kSampleCovarianceWithoutSamples =
-    "set_sample_covariance_check has effect with obstacle samples (set_obstacle_samples) only: without samples use set_pose_covariance_check";
-}  // namespace
 
 void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_samples) {
   if (offsets.empty()) {
@@ -385,7 +473,7 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
     if (n_samples < 2 || offsets.size() % ((size_t)3 * n_samples) != 0)
       throw std::runtime_error("set_obstacle_samples: needs n_samples >= 2 and n_obs * n_samples * 3 offsets");
     if (offsets.size() / 3 > (size_t)max_obstacles_) throw std::runtime_error("set_obstacle_samples: n_obs * n_samples above max_obstacles");
-    if (cov_check_) throw std::logic_error(kCovarianceWithSamples);
+    if (cov_.on) throw std::logic_error(kCovarianceWithSamples);
     if (tighten_) throw std::logic_error(kTighteningWithSamples);
     if (map_tighten_) throw std::logic_error(kMapTighteningWithSamples);
     samples_ = offsets;
@@ -393,7 +481,7 @@ void iLQR::set_obstacle_samples(const std::vector<double>& offsets, int n_sample
   }
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || cov_check_ || rounds_on()) reserve_noise_buffers();  // (the device block holds other arrays with samples than without)
+  reserve_block_if_used();  // (the device block holds other arrays with samples than without)
 }
 
 int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const {
@@ -424,28 +512,24 @@ int iLQR::pack_sampled(int B, std::vector<double>& pose, std::vector<double>& di
 void iLQR::set_pose_noise_check(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check: offsets must hold 4 doubles per sample");
   if (n_samples_ && !offsets.empty()) throw std::logic_error(kStoredRowsWithSamples);
-  if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
-  if (scov_check_ && !offsets.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
-  noise_ = offsets;
-  max_risk_ = max_risk;
-  noise_lamb_ = lamb;
-  noise_fused_ = false;
-  last_risk.clear();
-  last_step_hits.clear();
-  if (!noise_.empty() || rounds_on()) reserve_noise_buffers();
+  set_noise(offsets, max_risk, lamb, false);
 }
 
 void iLQR::set_pose_noise_check_fused(const std::vector<double>& offsets, double max_risk, double lamb) {
   if (offsets.size() % 4 != 0) throw std::runtime_error("set_pose_noise_check_fused: offsets must hold 4 doubles per sample");
-  if (cov_check_ && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
-  if (scov_check_ && !offsets.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
+  set_noise(offsets, max_risk, lamb, true);
+}
+
+void iLQR::set_noise(const std::vector<double>& offsets, double max_risk, double lamb, bool fused) {
+  if (cov_.on && !offsets.empty()) throw std::logic_error(kCovarianceWithNoise);
+  if (scov_.on && !offsets.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
   noise_ = offsets;
   max_risk_ = max_risk;
   noise_lamb_ = lamb;
-  noise_fused_ = true;
+  noise_fused_ = fused;
   last_risk.clear();
   last_step_hits.clear();
-  if (!noise_.empty() || rounds_on()) reserve_noise_buffers();
+  reserve_block_if_used();
 }
 
 void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits) {
@@ -459,33 +543,43 @@ void iLQR::set_map_risk_check(double occ_threshold, double max_risk, bool unknow
   last_map_unknown_hits.clear();
 }
 
+// Sigma0 == nullptr: off, and Sigma0 and W stay as they are.
+void iLQR::CovarianceParams::set(const double* Sigma0, const double* W_, double max_risk_, double lamb_, bool sum_) {
+  on = Sigma0 != nullptr;
+  has_W = on && W_ != nullptr;
+  if (on) memcpy(sigma0, Sigma0, sizeof(sigma0));
+  if (has_W) memcpy(W, W_, sizeof(W));
+  max_risk = max_risk_;
+  lamb = lamb_;
+  sum = sum_;
+}
+
+bool iLQR::CovarianceParams::same_inputs(const double* Sigma0, const double* W_, double lamb_) const {
+  return memcmp(sigma0, Sigma0, sizeof(sigma0)) == 0 && has_W == (W_ != nullptr) && (!has_W || memcmp(W, W_, sizeof(W)) == 0) && lamb == lamb_;
+}
+
+const double* iLQR::upload(const Block& d, const CovarianceParams& p, size_t s0_at, size_t W_at) const {
+  d.up(s0_at, p.sigma0, 16);
+  if (p.has_W) d.up(W_at, p.W, 16);
+  return p.has_W ? d + W_at : nullptr;
+}
+
 void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
   if (Sigma0 && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
   if (Sigma0 && n_samples_) throw std::logic_error(kCovarianceWithSamples);
   if (max_risk != max_risk) throw std::runtime_error("set_pose_covariance_check: max_risk is NaN");
-  cov_check_ = Sigma0 != nullptr;
-  cov_has_W_ = cov_check_ && W != nullptr;
-  if (cov_check_) memcpy(cov_sigma0_, Sigma0, sizeof(cov_sigma0_));
-  if (cov_has_W_) memcpy(cov_W_, W, sizeof(cov_W_));
-  cov_max_risk_ = max_risk;
-  cov_lamb_ = lamb;
-  cov_sum_ = sum_bound;
+  cov_.set(Sigma0, W, max_risk, lamb, sum_bound);
   last_chance_risk.clear();
   last_step_risk.clear();
-  if (cov_check_ || rounds_on()) reserve_noise_buffers();
+  reserve_block_if_used();
 }
 
 void iLQR::set_sample_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
   if (Sigma0 && !noise_.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
   if (max_risk != max_risk) throw std::runtime_error("set_sample_covariance_check: max_risk is NaN");
-  scov_check_ = Sigma0 != nullptr;
-  scov_has_W_ = scov_check_ && W != nullptr;
-  if (scov_check_) memcpy(scov_sigma0_, Sigma0, sizeof(scov_sigma0_));
-  if (scov_has_W_) memcpy(scov_W_, W, sizeof(scov_W_));
-  scov_max_risk_ = max_risk;
-  scov_lamb_ = lamb;
-  scov_sum_ = sum_bound;
+  scov_.set(Sigma0, W, max_risk, lamb, sum_bound);
   last_chance_risk_sampled.clear();
+  reserve_block_if_used();
 }
 
 void iLQR::set_map_covariance_check(double occ_threshold, double max_risk, int nx, int ny, int nth, bool sum_bound, bool unknown_hits) {
@@ -508,64 +602,55 @@ void iLQR::set_map_covariance_check(double occ_threshold, double max_risk, int n
   cmap_unknown_hits_ = unknown_hits;
   last_chance_map_risk.clear();
   last_map_step_risk.clear();
-  if (cov_check_) reserve_noise_buffers();  // (the device block holds Sigma_t and the nodes while this check is on)
+  reserve_block_if_used();  // (the device block holds Sigma_t and the nodes while this check is on)
 }
 
 void iLQR::set_chance_tightening(const double Sigma0[16], const double* W, double eps, int rounds, double max_inflate, double lamb) {
   const bool on = Sigma0 != nullptr && rounds != 0;
   if (on && n_samples_) throw std::logic_error(kTighteningWithSamples);
-  if (on && rounds < 0) throw std::runtime_error("set_chance_tightening: rounds is negative");
-  const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
-  if (kappa != kappa) throw std::runtime_error("set_chance_tightening: eps outside (0, 0.5]");
-  if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error("set_chance_tightening: max_inflate is negative or not finite");
+  const double kappa = tightening_kappa("set_chance_tightening", on, eps, rounds, max_inflate);
   if (on) check_tightening_agrees(map_tighten_, mt_rounds_, Sigma0, W, lamb, rounds);
   tighten_ = on;
-  if (on) {  // (Sigma0, W and lamb are the one set both tightenings read; switched off, a map tightening keeps them as they are)
-    tg_has_W_ = W != nullptr;
-    memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
-    if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
-    tg_lamb_ = lamb;
-  } else if (!map_tighten_) {
-    tg_has_W_ = false;
-  }
+  // (Sigma0, W and lamb are the one set both tightenings read; switched off, a map tightening keeps them as they are)
+  if (on) tg_.set(Sigma0, W, 1.0, lamb, false);
+  else if (!map_tighten_) tg_.has_W = false;
   tg_kappa_ = kappa;
   tg_rounds_ = on ? rounds : 0;
   tg_cap_ = max_inflate;
   last_tighten.clear();
   last_tighten_risk_before.clear();
-  if (rounds_on()) reserve_noise_buffers();
+  reserve_block_if_used();
+}
+
+// What both tightening setters check of their arguments; kappa, 0 when off.
+double iLQR::tightening_kappa(const char* setter, bool on, double eps, int rounds, double max_inflate) const {
+  const std::string name = setter;
+  if (on && rounds < 0) throw std::runtime_error(name + ": rounds is negative");
+  const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
+  if (kappa != kappa) throw std::runtime_error(name + ": eps outside (0, 0.5]");
+  if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error(name + ": max_inflate is negative or not finite");
+  return kappa;
 }
 
 void iLQR::check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const {
-  if (!other_on) return;
-  const bool same = memcmp(tg_sigma0_, Sigma0, sizeof(tg_sigma0_)) == 0 && tg_has_W_ == (W != nullptr) &&
-                    (!tg_has_W_ || memcmp(tg_W_, W, sizeof(tg_W_)) == 0) && tg_lamb_ == lamb && other_rounds == rounds;
-  if (!same) throw std::logic_error(kTighteningsDisagree);
+  if (other_on && !(tg_.same_inputs(Sigma0, W, lamb) && other_rounds == rounds)) throw std::logic_error(kTighteningsDisagree);
 }
 
 void iLQR::set_map_tightening(const double Sigma0[16], const double* W, double eps, int rounds, double max_inflate, double lamb) {
   const bool on = Sigma0 != nullptr && rounds != 0;
   if (on && n_samples_) throw std::logic_error(kMapTighteningWithSamples);
-  if (on && rounds < 0) throw std::runtime_error("set_map_tightening: rounds is negative");
-  const double kappa = on ? cilqr_chance_kappa(eps) : 0.0;
-  if (kappa != kappa) throw std::runtime_error("set_map_tightening: eps outside (0, 0.5]");
-  if (on && !(max_inflate >= 0.0 && max_inflate <= 1.7e308)) throw std::runtime_error("set_map_tightening: max_inflate is negative or not finite");
+  const double kappa = tightening_kappa("set_map_tightening", on, eps, rounds, max_inflate);
   if (on) check_tightening_agrees(tighten_, tg_rounds_, Sigma0, W, lamb, rounds);
   const bool was = map_tighten_;
   map_tighten_ = on;
-  if (on) {  // (Sigma0, W and lamb are the one set both tightenings read)
-    tg_has_W_ = W != nullptr;
-    memcpy(tg_sigma0_, Sigma0, sizeof(tg_sigma0_));
-    if (tg_has_W_) memcpy(tg_W_, W, sizeof(tg_W_));
-    tg_lamb_ = lamb;
-  }
+  if (on) tg_.set(Sigma0, W, 1.0, lamb, false);  // (Sigma0, W and lamb are the one set both tightenings read)
   mt_kappa_ = kappa;
   mt_rounds_ = on ? rounds : 0;
   mt_cap_ = max_inflate;
   last_tighten_map.clear();
   last_tighten_map_risk_before.clear();
   if (map_set_ && (was != on || map_in_block())) apply_map(unc_);  // the layer moves to this object's device block, or back to the handle's
-  if (rounds_on()) reserve_noise_buffers();
+  reserve_block_if_used();
 }
 
 void iLQR::set_track_map(double inflate, double z_max, int window, int rounds, bool ellipses) {
@@ -575,420 +660,222 @@ void iLQR::set_track_map(double inflate, double z_max, int window, int rounds, b
   tm_rounds_ = rounds; tm_window_ = window; tm_inflate_ = inflate; tm_z_max_ = z_max; tm_ellipses_ = ellipses;
   last_track_map.clear();
   if (map_set_ && (was != map_in_block() || map_in_block())) apply_map(unc_);  // the layer moves to this object's device block, or back
-  if (rounds_on()) reserve_noise_buffers();
+  reserve_block_if_used();
 }
 
 // Before anything is enqueued: what a run under set_track_map cannot be combined with.
 void iLQR::check_track_map_conflicts() const {
-  if (!track_map_on()) return;
+  const CandidateModes m = modes();
+  if (!m.track_rounds()) return;
   if (n_samples_) throw std::logic_error(kTrackMapWithSamples);
-  const bool obs_on = tighten_ && !obstacles_.empty(), map_on = map_tightened();
-  if (obs_on && !tm_ellipses_) throw std::logic_error(kTrackMapEllipsesOffTightened);
-  if ((obs_on && tg_rounds_ != tm_rounds_) || (map_on && mt_rounds_ != tm_rounds_)) throw std::logic_error(kTrackMapRoundsDisagree);
+  if (m.obstacle_rounds() && !tm_ellipses_) throw std::logic_error(kTrackMapEllipsesOffTightened);
+  if ((m.obstacle_rounds() && tg_rounds_ != tm_rounds_) || (m.map_rounds() && mt_rounds_ != tm_rounds_)) throw std::logic_error(kTrackMapRoundsDisagree);
 }
+
+int iLQR::solve_obstacles() const { return modes().track_rounds() && !tm_ellipses_ ? 0 : (int)obstacles_.size(); }
 
 void iLQR::set_obstacle_covariance(const std::vector<double>& cov) {
   obs_cov_ = cov;
   pack_obstacles();
 }
 
-// One device block for max_candidates candidates x S rollouts at the current horizon; the offsets travel here, once.  The fused
-// check stores no rollout rows: it keeps the nominal score rows, their totals and the step counts instead.
-void iLQR::reserve_noise_buffers() {
-  // (the covariance check has no draws: it keeps ONE zero offset, the plan itself, for the map risk call, and the fused check's arrays)
-  // (tightening alone, with no check behind it, keeps the fused check's score rows and totals for a MinTotalCost pick)
-  const bool fused = noise_fused_ || cov_check_ || noise_.empty();
-  const size_t B = max_candidates_, S = cov_check_ ? 1 : noise_.size() / 4, N = params.horizon, M = max_obstacles_, R = fused ? 0 : B * S;
-  // with obstacle samples: per-candidate nominal tables and offsets in place of the one shared set (n_obs * n_samples <= M)
-  const size_t n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
-  size_t o = 0;
-  const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
-  NoiseLayout& L = nl_;
-  L.x0 = take(B * 4); L.U = take(B * 2 * N); L.poly = take(B * CILQR_POLY_COEFFS); L.fl = take(B * 2);
-  L.pose = take(n_samples_ ? B * n_obs * 4 * N : M * 4 * N); L.dim = take(n_samples_ ? B * n_obs * 2 * N : M * 2 * N);
-  L.soff = take(B * samples_.size());
-  L.X = take(B * 4 * (N + 1)); L.J = take(B); L.iters = take(B); L.status = take(B);
-  L.k = take(B * 2 * N); L.K = take(B * 8 * N); L.ok = take(B);
-  L.delta = take(S * 4);
-  L.Xr = take(R * 4 * (N + 1)); L.Ur = take(R * 2 * N); L.rows = take(R * CILQR_SCORE_FIELDS);
-  L.risk = take(B * (n_samples_ ? CILQR_RRS_FIELDS : fused ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS)); L.total = take(B); L.pair = take(2);
-  L.score = take(fused ? B * CILQR_SCORE_FIELDS : 0); L.base = take(fused ? B : 0); L.hits = take(fused ? (B * N + 1) / 2 : 0);
-  // the map risk check's outputs (a few doubles per candidate: reserved with the fused check whether or not the check is on)
-  L.mrisk = take(fused ? B * CILQR_MAP_RISK_FIELDS : 0); L.mtotal = take(fused ? B : 0);
-  L.mhits = take(fused ? (B * N + 1) / 2 : 0); L.munk = take(fused ? (B * N + 1) / 2 : 0);
-  // the covariance check's inputs and outputs
-  L.s0 = take(cov_check_ ? 16 : 0); L.W = take(cov_check_ ? 16 : 0);
-  L.crisk = take(cov_check_ ? B * CILQR_CHANCE_FIELDS : 0); L.cstep = take(cov_check_ ? B * N : 0);
-  L.ccov = take(cov_check_ && obs_cov_check_ ? M * N * 3 : 0);  // the obstacles' covariance for the judge (set_obstacle_covariance_check)
-  // the map covariance check: every Sigma_t of the chance call, the nodes and weights, its outputs
-  const size_t cm = cov_check_ && cmap_check_ ? 1 : 0, Q = cmap_weights_.size();
-  L.csig = take(cm * B * (N + 1) * 16); L.qn = take(cm * Q * 3); L.qw = take(cm * Q);
-  L.cmrisk = take(cm * B * CILQR_CHANCE_MAP_FIELDS); L.cmstep = take(cm * B * N); L.cmtotal = take(cm * B);
-  // the tightening rounds: Sigma0, W, every Sigma_t, the risk row of the round's input plan, the inflated dense table, the fields, obs_cov
-  // (the map tightening shares the chain's arrays and adds its fields; its layers are floats and lie in map_dev_)
-  const size_t tg = tighten_ ? 1 : 0, chain = tighten_ || map_tighten_ ? 1 : 0;
-  L.ts0 = take(chain * 16); L.tW = take(chain * 16); L.tsig = take(chain * B * (N + 1) * 16); L.trisk = take(chain * B * CILQR_CHANCE_FIELDS);
-  L.tpose = take(tg * B * M * 4 * N); L.tdim = take(tg * B * M * 2 * N); L.tg = take(tg * B * CILQR_TIGHTEN_FIELDS); L.tcov = take(tg * M * N * 3);
-  L.tmg = take((map_tighten_ ? 1 : 0) * B * CILQR_TIGHTEN_MAP_FIELDS);
-  // the track map's rounds: the tracks' covariance by the packed obstacles' strides, the fields
-  L.tkcov = take((tm_rounds_ > 0 ? 1 : 0) * M * N * 3); L.tkf = take((tm_rounds_ > 0 ? 1 : 0) * B * CILQR_TRACK_MAP_FIELDS);
-  L.end = o;
+// One device block for max_candidates candidates at the current horizon, laid out by candidate_layout.h for the modes in force; what
+// the setters fixed travels here, once: the pose-noise offsets (the covariance check keeps ONE zero offset, the plan itself, for the
+// map risk call) and the quadrature nodes.
+void iLQR::reserve_block() {
+  const CandidateModes m = modes();
+  const CandidateLayout& L = layout_ = candidate_layout(m, sizes());
   hip_check(hipSetDevice(device_), "hipSetDevice");
-  if (!noise_stream_) {
+  if (!block_stream_) {
     hipStream_t st;
     hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-    noise_stream_ = st;
+    block_stream_ = st;
   }
-  hip_check(hipStreamSynchronize((hipStream_t)noise_stream_), "hipStreamSynchronize");
-  if (noise_dev_) hip_check(hipFree(noise_dev_), "hipFree");
-  noise_dev_ = nullptr;
-  hip_check(hipMalloc(&noise_dev_, L.end * sizeof(double)), "hipMalloc");
-  if (cov_check_) hip_check(hipMemset((double*)noise_dev_ + L.delta, 0, 4 * sizeof(double)), "hipMemset");
-  else if (!noise_.empty()) hip_check(hipMemcpy((double*)noise_dev_ + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-  if (cm) {
-    hip_check(hipMemcpy((double*)noise_dev_ + L.qn, cmap_nodes_.data(), cmap_nodes_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-    hip_check(hipMemcpy((double*)noise_dev_ + L.qw, cmap_weights_.data(), cmap_weights_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  hip_check(hipStreamSynchronize((hipStream_t)block_stream_), "hipStreamSynchronize");
+  if (block_dev_) hip_check(hipFree(block_dev_), "hipFree");
+  block_dev_ = nullptr;
+  hip_check(hipMalloc(&block_dev_, L.end * sizeof(double)), "hipMalloc");
+  double* d = (double*)block_dev_;
+  if (m.cov) hip_check(hipMemset(d + L.delta, 0, 4 * sizeof(double)), "hipMemset");
+  else if (m.noise) hip_check(hipMemcpy(d + L.delta, noise_.data(), noise_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  if (m.cmap_arrays()) {
+    hip_check(hipMemcpy(d + L.qn, cmap_nodes_.data(), cmap_nodes_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d + L.qw, cmap_weights_.data(), cmap_weights_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
   }
-  noise_horizon_ = params.horizon;
+  block_horizon_ = params.horizon;
 }
 
-int iLQR::run_candidates_noise_checked(int B, const std::vector<double>& ego_states) {
-  const int N = params.horizon, M = (int)obstacles_.size(), S = cov_check_ ? 1 : (int)(noise_.size() / 4);
-  if (cov_check_ && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
-  if (cov_check_ && n_samples_) throw std::logic_error(kCovarianceWithSamples);
-  if (tighten_ && n_samples_) throw std::logic_error(kTighteningWithSamples);
-  if (map_tighten_ && n_samples_) throw std::logic_error(kMapTighteningWithSamples);
-  if (n_samples_ && !noise_fused_) throw std::logic_error(kStoredRowsWithSamples);
-  check_track_map_conflicts();
-  if (noise_horizon_ != N) reserve_noise_buffers();  // (params is public: the horizon may have changed since the setter)
-  std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
-  const int W = params.num_of_local_wpts;
-  std::vector<double> ref((size_t)B * 2 * W);
-  std::vector<int32_t> n_ref(B);
-  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), poly.data(), fl.data(),
-                               ref.data(), n_ref.data()), "cilqr_local_plan_batch");
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
-  const cilqr_obstacles host_obs = obstacle_strides();
-  if ((tighten_ || (cov_check_ && obs_cov_check_)) && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  hipStream_t st = (hipStream_t)noise_stream_;
-  double* d = (double*)noise_dev_;
-  const NoiseLayout& L = nl_;
-  const auto up = [&](size_t at, const void* src, size_t doubles) {
-    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  };
-  const auto down = [&](void* dst, size_t at, size_t bytes) {
-    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  };
-  up(L.x0, ego_states.data(), (size_t)B * 4);
-  up(L.U, U.data(), U.size());
-  up(L.poly, poly.data(), poly.size());
-  up(L.fl, fl.data(), fl.size());
-  std::vector<double> nom_pose, nom_dim, samp_off;  // (alive until the stream has been waited for)
-  const int n_obs = n_samples_ ? pack_sampled(B, nom_pose, nom_dim, samp_off) : 0;
-  if (n_samples_) {
-    up(L.pose, nom_pose.data(), nom_pose.size());
-    up(L.dim, nom_dim.data(), nom_dim.size());
-    up(L.soff, samp_off.data(), samp_off.size());
+cilqr_obstacles iLQR::upload_obstacles(const Block& d) {
+  cilqr_obstacles obs = obstacle_strides();
+  d.up(layout_.pose, obs_pose_.data(), obs_pose_.size());
+  d.up(layout_.dim, obs_dim_.data(), obs_dim_.size());
+  obs.pose = d + layout_.pose;
+  obs.dim = d + layout_.dim;
+  return obs;
+}
+
+// Every run_candidates with a check, a tightening or the track map in force: prologue -> uploads -> solve -> rounds -> the checks, a
+// chain in which each takes the total before it as its base (NaN staying NaN) -> cilqr_argmin_device on the last total -> one wait ->
+// the pick's arrays -> one wait.  CandidateModes says which stages run; the block was laid out from the same predicates.
+int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, const CandidateModes& m) {
+  const int N = params.horizon, M = (int)obstacles_.size(), S = (int)sizes().rollouts(m);
+  if (m.scov) {
+    if (!m.sampled) throw std::logic_error(kSampleCovarianceWithoutSamples);
+    if (m.noise) throw std::logic_error(kSampleCovarianceWithNoise);
   } else {
-    up(L.pose, obs_pose_.data(), obs_pose_.size());
-    up(L.dim, obs_dim_.data(), obs_dim_.size());
+    if (m.cov && m.noise) throw std::logic_error(kCovarianceWithNoise);
+    if (m.cov && m.sampled) throw std::logic_error(kCovarianceWithSamples);
+    if (tighten_ && m.sampled) throw std::logic_error(kTighteningWithSamples);
+    if (map_tighten_ && m.sampled) throw std::logic_error(kMapTighteningWithSamples);
+    if (m.sampled && !m.fused) throw std::logic_error(kStoredRowsWithSamples);
+    check_track_map_conflicts();
   }
-  cilqr_obstacles obs = host_obs;  // the same strides over the device copies
-  obs.pose = d + L.pose;
-  obs.dim = d + L.dim;
+  if (block_horizon_ != N) reserve_block();  // (params is public: the horizon may have changed since the setter)
+  const Candidates c = plan_candidates(B, ego_states);
+  std::vector<double> nom_pose, nom_dim, samp_off;  // (alive until the stream has been waited for)
+  const int n_obs = m.sampled ? pack_sampled(B, nom_pose, nom_dim, samp_off) : 0, ns = n_samples_;
+  (void)obstacle_strides();  // (packs again when the horizon changed: the size check below reads the packed covariance)
+  const bool judge_cov = m.cov && m.cov_judge && M > 0 && !obs_cov_packed_.empty();
+  if ((tighten_ || (m.cov && m.cov_judge)) && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
+  hip_check(hipSetDevice(device_), "hipSetDevice");
+  const Block d = block();
+  const CandidateLayout& L = layout_;
+  d.up(L.x0, ego_states.data(), (size_t)B * 4);
+  d.up(L.U, c.U.data(), c.U.size());
+  d.up(L.poly, c.poly.data(), c.poly.size());
+  d.up(L.fl, c.fl.data(), c.fl.size());
+  cilqr_obstacles obs{};
+  if (m.sampled) {
+    d.up(L.pose, nom_pose.data(), nom_pose.size());
+    d.up(L.dim, nom_dim.data(), nom_dim.size());
+    d.up(L.soff, samp_off.data(), samp_off.size());
+  } else {
+    obs = upload_obstacles(d);
+  }
   const cilqr_obstacles* po = M ? &obs : nullptr;
   // under set_track_map with ellipses off the SOLVES read no ellipse: the tracks reach them through the map only; every check still sees them
-  const int Ms = track_map_on() && !tm_ellipses_ ? 0 : M;
-  const cilqr_obstacles* pos = Ms ? po : nullptr;
-  const int risk_fields = n_samples_ ? CILQR_RRS_FIELDS : noise_fused_ ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS;
-  int rc = CILQR_OK;
-  const bool plain = !cov_check_ && noise_.empty();  // tightening alone: no check behind it, the pick of run_candidates itself
-  const bool scored = cov_check_ || plain ? pick_ == CandidatePick::MinTotalCost : noise_fused_;  // last_scores is filled
-  const bool obs_tightened = tighten_ && M > 0, tightened = obs_tightened || map_tightened() || track_map_on();
-  const bool cmap_checked = cmap_check_ && map_set_ && cov_check_;
-  if (plain) {
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
-                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
-    if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, max_collision_, d + L.score, d + L.total);
-  } else if (cov_check_) {  // the analytic check: covariance chain and chance values in place of rollouts
-    up(L.s0, cov_sigma0_, 16);
-    if (cov_has_W_) up(L.W, cov_W_, 16);
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
-                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
-    if (!rc && scored) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
-    if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, cov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-    // (the judge counts the obstacles' own covariance when asked to and one is set; its entries lie by the packed obstacles' strides)
-    const bool judge_cov = obs_cov_check_ && M > 0 && !obs_cov_packed_.empty();
-    if (judge_cov) up(L.ccov, obs_cov_packed_.data(), obs_cov_packed_.size());
-    if (!rc && judge_cov)
-      rc = cilqr_chance_risk_cov_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po, d + L.ccov,
-                                        cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
-                                        d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
-    else if (!rc)
-      rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cov_has_W_ ? d + L.W : nullptr, po,
-                                    cov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, cov_max_risk_, d + (scored ? L.base : L.J), d + L.crisk,
-                                    d + L.cstep, nullptr, cmap_checked ? d + L.csig : nullptr, d + L.total);
-  } else if (n_samples_) {  // the same chain in the compact sampled form
-    const int ns = n_samples_;
-    const double w = sample_weight();
-    rc = cilqr_solve_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim, d + L.soff, w,
-                                          d + L.X, d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-    if (!rc) rc = cilqr_gains_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
-                                                   d + L.soff, w, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-    if (!rc) rc = cilqr_score_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
-                                                   d + L.soff, w, 1.0, d + L.score, d + L.base);
-    if (!rc) rc = cilqr_rollout_risk_sampled_device(h_, st, B, N, n_obs, ns, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0,
-                                                    d + L.pose, d + L.dim, d + L.soff, max_risk_, d + L.base, d + L.risk,
-                                                    (int32_t*)(d + L.hits), d + L.total);
-  } else {
-    rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, pos, d + L.X, d + L.J,
-                                            (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-    if (!rc && tightened) rc = tighten_rounds(st, d, B, po);
-    if (!rc) rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, noise_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-    if (noise_fused_) {
-      if (!rc) rc = cilqr_score_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, 1.0, d + L.score, d + L.base);
-      if (!rc) rc = cilqr_rollout_risk_device(h_, st, B, N, M, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, po, max_risk_,
-                                              d + L.base, d + L.risk, (int32_t*)(d + L.hits), d + L.total);
-    } else {
-      if (!rc) rc = cilqr_rollout_batch_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
-      if (!rc) rc = cilqr_score_rollouts_device(h_, st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, d + L.total);
-    }
-  }
-  size_t total_at = plain && !scored ? L.J : L.total;  // each check on top takes the total before it as its base, NaN staying NaN
-  if (cmap_checked && !rc) {  // the covariance against the map: Sigma_t of the chance call placed on the nodes
-    rc = cilqr_chance_risk_map_device(h_, st, B, N, (int)cmap_weights_.size(), d + L.X, d + L.csig, d + L.qn, d + L.qw, cmap_threshold_,
-                                      (cmap_sum_ ? CILQR_CHANCE_MAP_BOUND_SUM : 0u) | (cmap_unknown_hits_ ? CILQR_CHANCE_MAP_UNKNOWN_HITS : 0u),
-                                      cmap_max_risk_, d + total_at, d + L.cmrisk, d + L.cmstep, nullptr, nullptr, d + L.cmtotal);
-    total_at = L.cmtotal;
-  }
-  const bool map_checked = map_check_ && map_set_ && (noise_fused_ || cov_check_);
-  if (map_checked && !rc) {  // the map's say on top of the obstacles': base = their total
-    rc = cilqr_rollout_risk_map_device(h_, st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
-                                       map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, d + total_at, d + L.mrisk,
-                                       (int32_t*)(d + L.mhits), (int32_t*)(d + L.munk), d + L.mtotal);
-    total_at = L.mtotal;
-  }
-  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + total_at, d + L.pair);
-  if (rc) {
-    const std::string msg = cilqr_last_error();
-    (void)hipStreamSynchronize(st);
-    throw std::runtime_error((plain ? "run_candidates (chance tightening): " : "run_candidates (pose-noise check): ") + msg);
-  }
-  double pair[2] = {0.0, -1.0};
-  last_scores.clear();
-  last_step_hits.clear();
-  last_risk.clear();
-  last_chance_risk.clear();
-  last_step_risk.clear();
-  down(pair, L.pair, sizeof(pair));
-  if (cov_check_) {
-    last_chance_risk.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0);
-    last_step_risk.assign((size_t)B * N, 0.0);
-    down(last_chance_risk.data(), L.crisk, last_chance_risk.size() * sizeof(double));
-    down(last_step_risk.data(), L.cstep, last_step_risk.size() * sizeof(double));
-  } else if (!plain) {
-    last_risk.assign((size_t)B * risk_fields, 0.0);
-    down(last_risk.data(), L.risk, last_risk.size() * sizeof(double));
-  }
-  std::vector<double> tg_rows;
-  last_tighten.clear();
-  last_tighten_risk_before.clear();
-  last_tighten_map.clear();
-  last_tighten_map_risk_before.clear();
-  last_track_map.clear();
-  if (tightened) fetch_tighten(st, d, B, tg_rows);
-  if (scored) {
-    last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
-    down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
-  }
-  if (noise_fused_ && !cov_check_) {
-    last_step_hits.assign((size_t)B * N, 0);
-    down(last_step_hits.data(), L.hits, last_step_hits.size() * sizeof(int32_t));
-  }
-  last_chance_map_risk.clear();
-  last_map_step_risk.clear();
-  if (cmap_checked) {
-    last_chance_map_risk.assign((size_t)B * CILQR_CHANCE_MAP_FIELDS, 0.0);
-    last_map_step_risk.assign((size_t)B * N, 0.0);
-    down(last_chance_map_risk.data(), L.cmrisk, last_chance_map_risk.size() * sizeof(double));
-    down(last_map_step_risk.data(), L.cmstep, last_map_step_risk.size() * sizeof(double));
-  }
-  last_map_risk.clear();
-  last_map_step_hits.clear();
-  last_map_unknown_hits.clear();
-  if (map_checked) {
-    last_map_risk.assign((size_t)B * CILQR_MAP_RISK_FIELDS, 0.0);
-    last_map_step_hits.assign((size_t)B * N, 0);
-    last_map_unknown_hits.assign((size_t)B * N, 0);
-    down(last_map_risk.data(), L.mrisk, last_map_risk.size() * sizeof(double));
-    down(last_map_step_hits.data(), L.mhits, last_map_step_hits.size() * sizeof(int32_t));
-    down(last_map_unknown_hits.data(), L.munk, last_map_unknown_hits.size() * sizeof(int32_t));
-  }
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-  if (tightened) keep_tighten_risk(B, tg_rows);
-  const int best = (int)pair[1];
-  if (best < 0) return -1;  // every candidate rejected: results and warm start stay
-  Matrix Xb(4, N + 1);
-  int32_t iters = 0, status = 0;
-  double J = 0.0;
-  down(Xb.a.data(), L.X + (size_t)best * 4 * (N + 1), Xb.a.size() * sizeof(double));
-  std::vector<double> Ub((size_t)2 * N);
-  down(Ub.data(), L.U + (size_t)best * 2 * N, Ub.size() * sizeof(double));
-  down(&J, L.J + (size_t)best, sizeof(double));
-  hip_check(hipMemcpyAsync(&iters, (int32_t*)(d + L.iters) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  hip_check(hipMemcpyAsync(&status, (int32_t*)(d + L.status) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-  X_result = Xb;
-  control_seq_.a = Ub;
-  U_result = control_seq_;
-  ref_traj_result = Matrix(2, n_ref[best]);
-  for (int i = 0; i < 2 * n_ref[best]; ++i) ref_traj_result.a[i] = ref[(size_t)best * 2 * W + i];
-  last_iterations = iters;
-  last_exit = status;
-  last_cost = J;
-  return best;
-}
+  const int Ms = solve_obstacles();
+  const CovarianceParams& cp = m.scov ? scov_ : cov_;
+  const double* cW = m.chance() ? upload(d, cp, L.s0, L.W) : nullptr;
+  // (the judge counts the obstacles' own covariance when asked to and one is set; its entries lie by the packed obstacles' strides)
+  if (judge_cov) d.up(L.ccov, obs_cov_packed_.data(), obs_cov_packed_.size());
+  const double w = m.sampled ? sample_weight() : 0.0, lamb = m.noise ? noise_lamb_ : cp.lamb;
+  double* const sigma_out = m.scov || m.map_covariance() ? d + L.csig : nullptr;
 
-// run_candidates under set_sample_covariance_check: the analytic chain in the compact sampled form, in a device block of its own
-// (grown when a call needs more), on the checks' stream.
-int iLQR::run_candidates_sample_covariance(int B, const std::vector<double>& ego_states) {
-  const int N = params.horizon;
-  if (!n_samples_) throw std::logic_error(kSampleCovarianceWithoutSamples);
-  if (!noise_.empty()) throw std::logic_error(kSampleCovarianceWithNoise);
-  std::vector<double> U((size_t)B * 2 * N), poly((size_t)B * CILQR_POLY_COEFFS), fl((size_t)B * 2);
-  const int W = params.num_of_local_wpts;
-  std::vector<double> ref((size_t)B * 2 * W);
-  std::vector<int32_t> n_ref(B);
-  check(cilqr_local_plan_batch(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), poly.data(), fl.data(),
-                               ref.data(), n_ref.data()), "cilqr_local_plan_batch");
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < 2 * N; ++i) U[(size_t)b * 2 * N + i] = control_seq_.a[i];
-  std::vector<double> nom_pose, nom_dim, samp_off;  // (alive until the stream has been waited for)
-  const int n_obs = pack_sampled(B, nom_pose, nom_dim, samp_off), ns = n_samples_;
-  const bool cmap_checked = cmap_check_ && map_set_;
-  const size_t Q = cmap_checked ? cmap_weights_.size() : 0;
-  struct { size_t x0, U, poly, fl, pose, dim, soff, X, J, iters, status, k, K, ok, score, base, s0, W, crisk, ctotal, csig, srisk, stotal, qn, qw, cmrisk, cmtotal, pair, end; } L;
-  size_t o = 0;
-  const auto take = [&o](size_t doubles) { const size_t at = o; o += (doubles + 1) & ~(size_t)1; return at; };
-  L.x0 = take((size_t)B * 4); L.U = take(U.size()); L.poly = take(poly.size()); L.fl = take(fl.size());
-  L.pose = take(nom_pose.size()); L.dim = take(nom_dim.size()); L.soff = take(samp_off.size());
-  L.X = take((size_t)B * 4 * (N + 1)); L.J = take(B); L.iters = take(B); L.status = take(B);
-  L.k = take((size_t)B * 2 * N); L.K = take((size_t)B * 8 * N); L.ok = take(B);
-  L.score = take((size_t)B * CILQR_SCORE_FIELDS); L.base = take(B);
-  L.s0 = take(16); L.W = take(16); L.crisk = take((size_t)B * CILQR_CHANCE_FIELDS); L.ctotal = take(B);
-  L.csig = take((size_t)B * (N + 1) * 16); L.srisk = take((size_t)B * CILQR_CRS_FIELDS); L.stotal = take(B);
-  L.qn = take(Q * 3); L.qw = take(Q); L.cmrisk = take(cmap_checked ? (size_t)B * CILQR_CHANCE_MAP_FIELDS : 0); L.cmtotal = take(cmap_checked ? B : 0);
-  L.pair = take(2);
-  L.end = o;
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  if (!noise_stream_) {
-    hipStream_t created;
-    hip_check(hipStreamCreateWithFlags(&created, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-    noise_stream_ = created;
-  }
-  hipStream_t st = (hipStream_t)noise_stream_;
-  if (L.end > scov_cap_) {
-    hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (scov_dev_) hip_check(hipFree(scov_dev_), "hipFree");
-    scov_dev_ = nullptr; scov_cap_ = 0;
-    hip_check(hipMalloc(&scov_dev_, L.end * sizeof(double)), "hipMalloc");
-    scov_cap_ = L.end;
-  }
-  double* d = (double*)scov_dev_;
-  const auto up = [&](size_t at, const void* src, size_t doubles) {
-    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  int rc = CILQR_OK;
+  size_t total_at = L.J;  // each check takes the total before it as its base and leaves its own
+  const auto step = [&](bool runs, auto&& call) { if (runs && !rc) rc = call(); };
+  const auto stage = [&](bool runs, size_t out, auto&& call) {
+    if (runs && !rc) { rc = call(d + total_at, d + out); total_at = out; }
   };
-  const auto down = [&](void* dst, size_t at, size_t bytes) {
-    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  const auto score = [&](const double*, double* total) {
+    return m.sampled ? cilqr_score_batch_sampled_device(h_, d.st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                        d + L.soff, w, 1.0, d + L.score, total)
+                     : cilqr_score_batch_device(h_, d.st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, m.plain() ? max_collision_ : 1.0,
+                                                d + L.score, total);
   };
-  up(L.x0, ego_states.data(), (size_t)B * 4);
-  up(L.U, U.data(), U.size());
-  up(L.poly, poly.data(), poly.size());
-  up(L.fl, fl.data(), fl.size());
-  up(L.pose, nom_pose.data(), nom_pose.size());
-  up(L.dim, nom_dim.data(), nom_dim.size());
-  up(L.soff, samp_off.data(), samp_off.size());
-  up(L.s0, scov_sigma0_, 16);
-  if (scov_has_W_) up(L.W, scov_W_, 16);
-  if (cmap_checked) { up(L.qn, cmap_nodes_.data(), cmap_nodes_.size()); up(L.qw, cmap_weights_.data(), cmap_weights_.size()); }
-  const double w = sample_weight();
-  int rc = cilqr_solve_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim, d + L.soff, w,
-                                            d + L.X, d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-  if (!rc) rc = cilqr_gains_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
-                                                 d + L.soff, w, scov_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-  if (!rc) rc = cilqr_score_batch_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
-                                                 d + L.soff, w, 1.0, d + L.score, d + L.base);
-  // the chain alone (M = 0): every Sigma_t, and the steps whose U_t or K_t is not finite marked in its total
-  if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, 0, d + L.X, d + L.U, d + L.K, d + L.s0, 0, scov_has_W_ ? d + L.W : nullptr, nullptr,
-                                         scov_sum_ ? CILQR_CHANCE_BOUND_SUM : 0u, scov_max_risk_, d + L.base, d + L.crisk, nullptr, nullptr,
-                                         d + L.csig, d + L.ctotal);
-  if (!rc) rc = cilqr_chance_risk_sampled_device(h_, st, B, N, n_obs, ns, d + L.X, d + L.csig, d + L.pose, d + L.dim, d + L.soff,
-                                                 scov_sum_ ? CILQR_CHANCE_SAMPLED_BOUND_SUM : 0u, scov_max_risk_, d + L.ctotal, d + L.srisk,
-                                                 nullptr, nullptr, nullptr, d + L.stotal);
-  size_t total_at = L.stotal;
-  if (cmap_checked && !rc) {
-    rc = cilqr_chance_risk_map_device(h_, st, B, N, (int)Q, d + L.X, d + L.csig, d + L.qn, d + L.qw, cmap_threshold_,
-                                      (cmap_sum_ ? CILQR_CHANCE_MAP_BOUND_SUM : 0u) | (cmap_unknown_hits_ ? CILQR_CHANCE_MAP_UNKNOWN_HITS : 0u),
-                                      cmap_max_risk_, d + total_at, d + L.cmrisk, nullptr, nullptr, nullptr, d + L.cmtotal);
-    total_at = L.cmtotal;
-  }
-  if (!rc) rc = cilqr_argmin_device(h_, st, B, d + total_at, d + L.pair);
+  const size_t score_out = m.plain() ? L.total : L.base;  // (a check behind it reads the nominal totals as its base)
+  step(true, [&] {
+    return m.sampled ? cilqr_solve_batch_sampled_device(h_, d.st, B, N, n_obs, ns, d + L.x0, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                        d + L.soff, w, d + L.X, d + L.J, d.i32(L.iters), d.i32(L.status), CILQR_FLAG_NONE)
+                     : cilqr_solve_batch_obstacles_device(h_, d.st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, Ms ? po : nullptr, d + L.X,
+                                                          d + L.J, d.i32(L.iters), d.i32(L.status), CILQR_FLAG_NONE);
+  });
+  step(m.rounds(), [&] { return tighten_rounds(d, B, po); });
+  stage(m.scored() && m.score_before_gains(), score_out, score);
+  step(m.gains(), [&] {
+    return m.sampled ? cilqr_gains_batch_sampled_device(h_, d.st, B, N, n_obs, ns, d + L.X, d + L.U, d + L.poly, d + L.fl, d + L.pose, d + L.dim,
+                                                        d + L.soff, w, lamb, d + L.k, d + L.K, d.i32(L.ok))
+                     : cilqr_gains_batch_device(h_, d.st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, lamb, d + L.k, d + L.K, d.i32(L.ok));
+  });
+  stage(m.scored() && !m.score_before_gains(), score_out, score);
+  stage(m.stored_rows_risk(), L.total, [&](const double*, double* total) {  // (ranks by the mean total over its rollouts: no base)
+    const int r = cilqr_rollout_batch_device(h_, d.st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.Xr, d + L.Ur);
+    return r ? r : cilqr_score_rollouts_device(h_, d.st, B, N, M, S, d + L.Xr, d + L.Ur, d + L.poly, d + L.fl, po, max_risk_, d + L.rows, d + L.risk, total);
+  });
+  stage(m.fused_risk(), L.total, [&](const double* base, double* total) {
+    return cilqr_rollout_risk_device(h_, d.st, B, N, M, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, po, max_risk_, base, d + L.risk,
+                                     d.i32(L.hits), total);
+  });
+  stage(m.fused_sampled_risk(), L.total, [&](const double* base, double* total) {
+    return cilqr_rollout_risk_sampled_device(h_, d.st, B, N, n_obs, ns, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, d + L.pose,
+                                             d + L.dim, d + L.soff, max_risk_, base, d + L.risk, d.i32(L.hits), total);
+  });
+  // (under the sample covariance check the chance call runs with M = 0, for every Sigma_t and the steps that are not finite alone)
+  stage(m.chance() && !judge_cov, L.total, [&](const double* base, double* total) {
+    return cilqr_chance_risk_device(h_, d.st, B, N, m.scov ? 0 : M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cW, m.scov ? nullptr : po,
+                                    cp.sum ? CILQR_CHANCE_BOUND_SUM : 0u, cp.max_risk, base, d + L.crisk, m.scov ? nullptr : d + L.cstep, nullptr,
+                                    sigma_out, total);
+  });
+  stage(m.chance() && judge_cov, L.total, [&](const double* base, double* total) {
+    return cilqr_chance_risk_cov_device(h_, d.st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.s0, 0, cW, po, d + L.ccov,
+                                        cp.sum ? CILQR_CHANCE_BOUND_SUM : 0u, cp.max_risk, base, d + L.crisk, d + L.cstep, nullptr, sigma_out, total);
+  });
+  stage(m.chance_sampled(), L.stotal, [&](const double* base, double* total) {
+    return cilqr_chance_risk_sampled_device(h_, d.st, B, N, n_obs, ns, d + L.X, d + L.csig, d + L.pose, d + L.dim, d + L.soff,
+                                            cp.sum ? CILQR_CHANCE_SAMPLED_BOUND_SUM : 0u, cp.max_risk, base, d + L.srisk, nullptr, nullptr, nullptr, total);
+  });
+  stage(m.map_covariance(), L.cmtotal, [&](const double* base, double* total) {  // Sigma_t of the chance call placed on the nodes
+    return cilqr_chance_risk_map_device(h_, d.st, B, N, (int)cmap_weights_.size(), d + L.X, d + L.csig, d + L.qn, d + L.qw, cmap_threshold_,
+                                        (cmap_sum_ ? CILQR_CHANCE_MAP_BOUND_SUM : 0u) | (cmap_unknown_hits_ ? CILQR_CHANCE_MAP_UNKNOWN_HITS : 0u),
+                                        cmap_max_risk_, base, d + L.cmrisk, m.scov ? nullptr : d + L.cmstep, nullptr, nullptr, total);
+  });
+  stage(m.map_rollout_risk(), L.mtotal, [&](const double* base, double* total) {  // the map's say on top of the obstacles'
+    return cilqr_rollout_risk_map_device(h_, d.st, B, N, S, d + L.X, d + L.U, d + L.k, d + L.K, d + L.delta, 0, 0.0, map_threshold_,
+                                         map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, base, d + L.mrisk, d.i32(L.mhits),
+                                         d.i32(L.munk), total);
+  });
+  step(true, [&] { return cilqr_argmin_device(h_, d.st, B, d + total_at, d + L.pair); });
   if (rc) {
     const std::string msg = cilqr_last_error();
-    (void)hipStreamSynchronize(st);
-    throw std::runtime_error("run_candidates (sample covariance check): " + msg);
+    (void)hipStreamSynchronize(d.st);
+    throw std::runtime_error((m.scov ? "run_candidates (sample covariance check): " : m.plain() ? "run_candidates (chance tightening): "
+                                                                                                 : "run_candidates (pose-noise check): ") + msg);
   }
+  // every last_* vector is reset here; the stages that ran fill theirs
+  clear_candidate_fields();
   double pair[2] = {0.0, -1.0};
-  down(pair, L.pair, sizeof(pair));
-  last_scores.assign((size_t)B * CILQR_SCORE_FIELDS, 0.0);
-  down(last_scores.data(), L.score, last_scores.size() * sizeof(double));
-  last_chance_risk_sampled.assign((size_t)B * CILQR_CRS_FIELDS, 0.0);
-  down(last_chance_risk_sampled.data(), L.srisk, last_chance_risk_sampled.size() * sizeof(double));
-  last_chance_map_risk.clear();
-  if (cmap_checked) {
-    last_chance_map_risk.assign((size_t)B * CILQR_CHANCE_MAP_FIELDS, 0.0);
-    down(last_chance_map_risk.data(), L.cmrisk, last_chance_map_risk.size() * sizeof(double));
+  d.down(pair, L.pair, sizeof(pair));
+  if (m.cov && !m.scov) {
+    d.fetch(last_chance_risk, L.crisk, (size_t)B * CILQR_CHANCE_FIELDS);
+    d.fetch(last_step_risk, L.cstep, (size_t)B * N);
   }
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (m.noise) d.fetch(last_risk, L.risk, (size_t)B * (m.sampled ? CILQR_RRS_FIELDS : m.fused ? CILQR_ROLLOUT_RISK_FIELDS : CILQR_RISK_FIELDS));
+  std::vector<double> tg_rows;
+  if (m.rounds()) fetch_tighten(d, B, tg_rows);
+  if (m.scored()) d.fetch(last_scores, L.score, (size_t)B * CILQR_SCORE_FIELDS);
+  if (m.fused_check()) d.fetch(last_step_hits, L.hits, (size_t)B * N);
+  if (m.chance_sampled()) d.fetch(last_chance_risk_sampled, L.srisk, (size_t)B * CILQR_CRS_FIELDS);
+  if (m.map_covariance()) {
+    d.fetch(last_chance_map_risk, L.cmrisk, (size_t)B * CILQR_CHANCE_MAP_FIELDS);
+    if (!m.scov) d.fetch(last_map_step_risk, L.cmstep, (size_t)B * N);
+  }
+  if (m.map_rollout_risk()) {
+    d.fetch(last_map_risk, L.mrisk, (size_t)B * CILQR_MAP_RISK_FIELDS);
+    d.fetch(last_map_step_hits, L.mhits, (size_t)B * N);
+    d.fetch(last_map_unknown_hits, L.munk, (size_t)B * N);
+  }
+  d.wait();
+  if (m.rounds()) keep_tighten_risk(B, tg_rows);
   const int best = (int)pair[1];
   if (best < 0) return -1;  // every candidate rejected: results and warm start stay
-  Matrix Xb(4, N + 1);
-  std::vector<double> Ub((size_t)2 * N);
-  int32_t iters = 0, status = 0;
-  double J = 0.0;
-  down(Xb.a.data(), L.X + (size_t)best * 4 * (N + 1), Xb.a.size() * sizeof(double));
-  down(Ub.data(), L.U + (size_t)best * 2 * N, Ub.size() * sizeof(double));
-  down(&J, L.J + (size_t)best, sizeof(double));
-  hip_check(hipMemcpyAsync(&iters, (int32_t*)(d + L.iters) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  hip_check(hipMemcpyAsync(&status, (int32_t*)(d + L.status) + best, sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-  X_result = Xb;
-  control_seq_.a = Ub;
-  U_result = control_seq_;
-  ref_traj_result = Matrix(2, n_ref[best]);
-  for (int i = 0; i < 2 * n_ref[best]; ++i) ref_traj_result.a[i] = ref[(size_t)best * 2 * W + i];
-  last_iterations = iters;
-  last_exit = status;
-  last_cost = J;
+  Solved s;
+  fetch_solved(d, best, s);
+  d.wait();
+  install(s, control_seq_);
+  ref_traj_result = Matrix(2, c.n_ref[best]);
+  memcpy(ref_traj_result.a.data(), &c.ref[(size_t)best * 2 * params.num_of_local_wpts], ref_traj_result.a.size() * sizeof(double));
   return best;
 }
 
 // The rounds behind a solve whose arrays lie in the device block: gains and covariance chain of the current plan against the ORIGINAL
 // obstacles `po`, the inflated dense table, the re-solve on it from the U the solve before left.  Sigma0, W and obs_cov travel here.
-int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* po) {
+int iLQR::tighten_rounds(const Block& d, int B, const cilqr_obstacles* po) {
   const int N = params.horizon, M = (int)obstacles_.size();
-  hipStream_t st = (hipStream_t)stream;
-  const NoiseLayout& L = nl_;
-  const auto up = [&](size_t at, const void* src, size_t doubles) {
-    hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  };
-  if (tighten_ || map_tighten_) up(L.ts0, tg_sigma0_, 16);
-  if ((tighten_ || map_tighten_) && tg_has_W_) up(L.tW, tg_W_, 16);
-  if (tighten_ && !obs_cov_packed_.empty()) up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
+  const CandidateModes m = modes();
+  const CandidateLayout& L = layout_;
+  const double* tW = m.chain() ? upload(d, tg_, L.ts0, L.tW) : nullptr;
+  if (tighten_ && !obs_cov_packed_.empty()) d.up(L.tcov, obs_cov_packed_.data(), obs_cov_packed_.size());
   cilqr_obstacles inflated{};
   inflated.pose = d + L.tpose;
   inflated.dim = d + L.tdim;
@@ -997,10 +884,9 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   inflated.step_stride = 1;
   // with both tightenings on one round serves both and re-solves once (the setters made the two round counts agree); so it is with the
   // track map beside them: rasterise along the plan, tighten the RASTERISED layers, one re-solve
-  const bool trk_on = track_map_on();
-  const int Ms = trk_on && !tm_ellipses_ ? 0 : M;  // what the solves read
+  const bool trk_on = m.track_rounds(), obs_on = m.obstacle_rounds(), map_on = m.map_rounds(), chain = obs_on || map_on;
+  const int Ms = solve_obstacles();  // what the solves read
   const cilqr_obstacles* pos = Ms ? po : nullptr;
-  const bool obs_on = tighten_ && M > 0, map_on = map_tightened(), chain = obs_on || map_on;
   const int rounds = obs_on ? tg_rounds_ : map_on ? mt_rounds_ : tm_rounds_;
   const bool layers_on = map_on || trk_on;
   const size_t cells = layers_on ? (size_t)unc_.geom.rows * unc_.geom.cols : 0;
@@ -1012,26 +898,26 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   cilqr_uncertainty_map layers = rastered;  // what the re-solve reads
   if (map_on && trk_on) layers.layer = second_layers;
   const bool trk_cov = trk_on && !obs_cov_packed_.empty();
-  if (trk_cov) up(L.tkcov, obs_cov_packed_.data(), obs_cov_packed_.size());
+  if (trk_cov) d.up(L.tkcov, obs_cov_packed_.data(), obs_cov_packed_.size());
   int rc = CILQR_OK;
   for (int r = 0; r < rounds && !rc; ++r) {
     if (chain) {
-      rc = cilqr_gains_batch_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_lamb_, d + L.k, d + L.K, (int32_t*)(d + L.ok));
-      if (!rc) rc = cilqr_chance_risk_device(h_, st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tg_has_W_ ? d + L.tW : nullptr, po, 0u, 1.0,
+      rc = cilqr_gains_batch_device(h_, d.st, B, N, M, d + L.X, d + L.U, d + L.poly, d + L.fl, po, tg_.lamb, d + L.k, d + L.K, d.i32(L.ok));
+      if (!rc) rc = cilqr_chance_risk_device(h_, d.st, B, N, M, d + L.X, d + L.U, d + L.K, d + L.ts0, 0, tW, po, 0u, 1.0,
                                              nullptr, d + L.trisk, nullptr, nullptr, d + L.tsig, nullptr);
     }
     if (!rc && obs_on)
-      rc = cilqr_tighten_obstacles_device(h_, st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
+      rc = cilqr_tighten_obstacles_device(h_, d.st, B, N, M, d + L.X, d + L.tsig, po, obs_cov_packed_.empty() ? nullptr : d + L.tcov, tg_kappa_,
                                           tg_cap_, d + L.tpose, d + L.tdim, d + L.tg);
     // the ORIGINAL layer is the one on the handle here: neither the rasterisation nor the inflation compounds over rounds
     if (!rc && trk_on)
-      rc = cilqr_rasterize_tracks_device(h_, st, B, N, M, d + L.X, po, trk_cov ? d + L.tkcov : nullptr, tm_inflate_, tm_z_max_, tm_window_, 0u,
+      rc = cilqr_rasterize_tracks_device(h_, d.st, B, N, M, d + L.X, po, trk_cov ? d + L.tkcov : nullptr, tm_inflate_, tm_z_max_, tm_window_, 0u,
                                          first_layers, d + L.tkf);
     if (!rc && map_on && trk_on) rc = cilqr_set_uncertainty_map_device(h_, &rastered);  // the tightening reads the rasterised layers
-    if (!rc && map_on) rc = cilqr_tighten_map_device(h_, st, B, N, d + L.X, d + L.tsig, mt_kappa_, mt_cap_, trk_on ? second_layers : first_layers, d + L.tmg);
+    if (!rc && map_on) rc = cilqr_tighten_map_device(h_, d.st, B, N, d + L.X, d + L.tsig, mt_kappa_, mt_cap_, trk_on ? second_layers : first_layers, d + L.tmg);
     if (!rc && layers_on) rc = cilqr_set_uncertainty_map_device(h_, &layers);
-    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, obs_on ? &inflated : pos, d + L.X,
-                                                     d + L.J, (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
+    if (!rc) rc = cilqr_solve_batch_obstacles_device(h_, d.st, B, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, obs_on ? &inflated : pos, d + L.X,
+                                                     d + L.J, d.i32(L.iters), d.i32(L.status), CILQR_FLAG_NONE);
     if (layers_on) {  // the original map is back on the handle whatever happened: what follows judges the plan against it
       const int back = cilqr_set_uncertainty_map_device(h_, &original);  // (a success leaves cilqr_last_error as it is)
       if (!rc) rc = back;
@@ -1040,91 +926,58 @@ int iLQR::tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* 
   return rc;
 }
 
-void iLQR::fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows) {
+void iLQR::fetch_tighten(const Block& d, int B, std::vector<double>& risk_rows) {
+  const CandidateModes m = modes();
   risk_rows.assign((size_t)B * CILQR_CHANCE_FIELDS, 0.0);
-  if (map_tightened()) {
-    last_tighten_map.assign((size_t)B * CILQR_TIGHTEN_MAP_FIELDS, 0.0);
-    hip_check(hipMemcpyAsync(last_tighten_map.data(), d + nl_.tmg, last_tighten_map.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
-  }
-  if (tighten_ && !obstacles_.empty()) {
-    last_tighten.assign((size_t)B * CILQR_TIGHTEN_FIELDS, 0.0);
-    hip_check(hipMemcpyAsync(last_tighten.data(), d + nl_.tg, last_tighten.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
-  }
-  if (track_map_on()) {
-    last_track_map.assign((size_t)B * CILQR_TRACK_MAP_FIELDS, 0.0);
-    hip_check(hipMemcpyAsync(last_track_map.data(), d + nl_.tkf, last_track_map.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
-  }
-  if (tighten_ || map_tighten_)  // (the chain ran: the risk row of the plan the last round started from)
-    hip_check(hipMemcpyAsync(risk_rows.data(), d + nl_.trisk, risk_rows.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync");
+  if (m.map_rounds()) d.fetch(last_tighten_map, layout_.tmg, (size_t)B * CILQR_TIGHTEN_MAP_FIELDS);
+  if (m.obstacle_rounds()) d.fetch(last_tighten, layout_.tg, (size_t)B * CILQR_TIGHTEN_FIELDS);
+  if (m.track_rounds()) d.fetch(last_track_map, layout_.tkf, (size_t)B * CILQR_TRACK_MAP_FIELDS);
+  if (m.chain()) d.down(risk_rows.data(), layout_.trisk, risk_rows.size() * sizeof(double));  // (of the plan the last round started from)
 }
 
 void iLQR::keep_tighten_risk(int B, const std::vector<double>& risk_rows) {
   std::vector<double> before(B);
   for (int b = 0; b < B; ++b) before[b] = risk_rows[(size_t)b * CILQR_CHANCE_FIELDS + CILQR_CR_STEP_RISK];
   if (tighten_ && !obstacles_.empty()) last_tighten_risk_before = before;
-  if (map_tightened()) last_tighten_map_risk_before = before;
+  if (map_tighten_ && map_set_) last_tighten_map_risk_before = before;
 }
 
-// get_optimal_control_seq under set_chance_tightening: the B = 1 solve and its rounds in the device block, one wait.
+// get_optimal_control_seq under a tightening or the track map: the B = 1 solve and its rounds in the device block, one wait.
 void iLQR::solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]) {
   const int N = params.horizon, M = (int)obstacles_.size();
   check_track_map_conflicts();
   if (n_samples_ && (tighten_ || map_tighten_)) throw std::logic_error(tighten_ ? kTighteningWithSamples : kMapTighteningWithSamples);
-  if (noise_horizon_ != N) reserve_noise_buffers();
-  const cilqr_obstacles host_obs = obstacle_strides();
+  if (block_horizon_ != N) reserve_block();
+  (void)obstacle_strides();
   if (tighten_ && M && !obs_cov_.empty() && obs_cov_packed_.empty()) throw std::runtime_error(kObstacleCovarianceSize);
   hip_check(hipSetDevice(device_), "hipSetDevice");
-  hipStream_t st = (hipStream_t)noise_stream_;
-  double* d = (double*)noise_dev_;
-  const NoiseLayout& L = nl_;
-  const auto up = [&](size_t at, const void* src, size_t doubles) {
-    if (doubles) hip_check(hipMemcpyAsync(d + at, src, doubles * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  };
-  const auto down = [&](void* dst, size_t at, size_t bytes) {
-    hip_check(hipMemcpyAsync(dst, d + at, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-  };
-  up(L.x0, x_0, 4);
-  up(L.U, U.a.data(), U.a.size());
-  up(L.poly, poly_coeffs, CILQR_POLY_COEFFS);
-  up(L.fl, fl, 2);
-  up(L.pose, obs_pose_.data(), obs_pose_.size());
-  up(L.dim, obs_dim_.data(), obs_dim_.size());
-  cilqr_obstacles obs = host_obs;  // the same strides over the device copies
-  obs.pose = d + L.pose;
-  obs.dim = d + L.dim;
+  const Block d = block();
+  const CandidateLayout& L = layout_;
+  d.up(L.x0, x_0, 4);
+  d.up(L.U, U.a.data(), U.a.size());
+  d.up(L.poly, poly_coeffs, CILQR_POLY_COEFFS);
+  d.up(L.fl, fl, 2);
+  const cilqr_obstacles obs = upload_obstacles(d);
   const cilqr_obstacles* po = M ? &obs : nullptr;
-  const int Ms = track_map_on() && !tm_ellipses_ ? 0 : M;  // (ellipses off: the tracks reach the solve through the map only)
-  int rc = cilqr_solve_batch_obstacles_device(h_, st, 1, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, Ms ? po : nullptr, d + L.X, d + L.J,
-                                              (int32_t*)(d + L.iters), (int32_t*)(d + L.status), CILQR_FLAG_NONE);
-  const bool tightened = (tighten_ && M > 0) || map_tightened() || track_map_on();
-  if (!rc && tightened) rc = tighten_rounds(st, d, 1, po);
+  const int Ms = solve_obstacles();  // (ellipses off: the tracks reach the solve through the map only)
+  int rc = cilqr_solve_batch_obstacles_device(h_, d.st, 1, N, Ms, d + L.x0, d + L.U, d + L.poly, d + L.fl, Ms ? po : nullptr, d + L.X, d + L.J,
+                                              d.i32(L.iters), d.i32(L.status), CILQR_FLAG_NONE);
+  const bool tightened = modes().rounds();
+  if (!rc && tightened) rc = tighten_rounds(d, 1, po);
   if (rc) {
     const std::string msg = cilqr_last_error();
-    (void)hipStreamSynchronize(st);
+    (void)hipStreamSynchronize(d.st);
     throw std::runtime_error("run_step (chance tightening): " + msg);
   }
-  Matrix Xb(4, N + 1);
-  int32_t iters = 0, status = 0;
-  double J = 0.0;
+  Solved s;
   std::vector<double> tg_rows;
-  last_tighten.clear();
-  last_tighten_risk_before.clear();
-  last_tighten_map.clear();
-  last_tighten_map_risk_before.clear();
-  last_track_map.clear();
-  down(Xb.a.data(), L.X, Xb.a.size() * sizeof(double));
-  down(U.a.data(), L.U, U.a.size() * sizeof(double));
-  down(&J, L.J, sizeof(double));
-  down(&iters, L.iters, sizeof(int32_t));
-  down(&status, L.status, sizeof(int32_t));
-  if (tightened) fetch_tighten(st, d, 1, tg_rows);
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  clear_round_fields();
+  fetch_solved(d, 0, s);
+  if (tightened) fetch_tighten(d, 1, tg_rows);
+  d.wait();
   if (tightened) keep_tighten_risk(1, tg_rows);
-  X_result = Xb;
-  last_iterations = iters;
-  last_exit = status;
-  last_cost = J;
-  U_result = U;  // I/iLQR.cpp:244
+  install(s, U);
 }
 
 }  // namespace cilqr_host
+

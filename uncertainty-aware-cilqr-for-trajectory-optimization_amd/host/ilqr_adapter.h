@@ -20,6 +20,7 @@
 
 #include <vector>
 
+#include "candidate_layout.h"
 #include "cilqr.h"
 
 namespace cilqr_host {
@@ -316,12 +317,6 @@ class iLQR {
   bool held_ = false;
   int packed_horizon_ = -1;  // the horizon obs_pose_ / obs_dim_ were packed for
   std::vector<double> obs_pose_, obs_dim_;  // packed ONCE: [obstacle][4N] / [2N], or [obstacle][4] / [2] when held_
-  // pose-noise check: the offsets, and one device block (offsets in doubles below) with a stream of its own; both opaque here
-  // so that this header needs no HIP
-  struct NoiseLayout {
-    size_t x0, U, poly, fl, pose, dim, X, J, iters, status, k, K, ok, delta, Xr, Ur, rows, risk, total, pair, score, base, hits, soff, mrisk, mtotal, mhits, munk, s0, W, crisk, cstep,
-        csig, qn, qw, cmrisk, cmstep, cmtotal, ts0, tW, tsig, trisk, tpose, tdim, tg, tcov, tmg, ccov, tkcov, tkf, end;
-  };
   // tracked obstacles (set_tracked_obstacles): the inputs as given, and the horizon they were last predicted over (-1: none set)
   std::vector<double> tracks_, track_dims_, track_cov_, track_Q_;
   int tracked_horizon_ = -1;
@@ -334,40 +329,60 @@ class iLQR {
   // returns n_obs
   int pack_sampled(int B, std::vector<double>& pose, std::vector<double>& dim, std::vector<double>& off) const;
   double sample_weight() const { return params.w_obstacle / n_samples_; }
-  int run_candidates_noise_checked(int B, const std::vector<double>& ego_states);
+  // The checks' pipeline ("The facade's candidate pipeline"): every run_candidates but the unchecked one, and run_step under
+  // a tightening, runs in ONE device block on a stream of its own.  candidate_layout.h says, from modes() and sizes(), where the
+  // block's arrays lie and which stages a run enqueues; Block (the pointer, the stream, up / down) is opaque here so that this header
+  // needs no HIP.
+  struct Block;
+  struct Candidates;  // what the prologue makes: the local plans and the replicated warm start
+  struct Solved;      // one solve's X, U, J, iterations and exit
+  CandidateModes modes() const;
+  CandidateSizes sizes() const;
+  Block block() const;
+  void reserve_block();  // lays the block out for modes() and sizes(), allocates it and uploads what the setters fixed
+  void reserve_block_if_used() { if (modes().block_used()) reserve_block(); }
+  Candidates plan_candidates(int B, const std::vector<double>& ego_states);
+  int run_candidates_in_block(int B, const std::vector<double>& ego_states, const CandidateModes& m);
+  cilqr_obstacles upload_obstacles(const Block& d);  // the packed set into the block: the same strides over the device copies
+  void fetch_solved(const Block& d, int b, Solved& s) const;  // enqueues
+  void install(const Solved& s, Matrix& U);                  // after the wait: X_result, U (the warm start) and U_result, last_*
+  void clear_round_fields();      // last_tighten*, last_track_map
+  void clear_candidate_fields();  // every last_* vector run_candidates owns
+  CandidateLayout layout_{};
+  int block_horizon_ = -1;  // the horizon the block was laid out for
+  void* block_dev_ = nullptr;
+  void* block_stream_ = nullptr;
+  // Sigma0, W, the bound and lamb of a covariance setter; Sigma0 and W travel with every call (32 doubles)
+  struct CovarianceParams {
+    bool on = false, has_W = false, sum = false;
+    double sigma0[16] = {}, W[16] = {}, max_risk = 1.0, lamb = 1.0;
+    void set(const double* Sigma0, const double* W_, double max_risk_, double lamb_, bool sum_);
+    bool same_inputs(const double* Sigma0, const double* W_, double lamb_) const;
+  };
+  const double* upload(const Block& d, const CovarianceParams& p, size_t s0_at, size_t W_at) const;  // returns W in the block, or null
+  CovarianceParams cov_, scov_;  // set_pose_covariance_check, set_sample_covariance_check
+  CovarianceParams tg_;          // the one set both tightenings read (on, sum and max_risk unused)
+  // pose-noise check: the offsets as given
   bool noise_fused_ = false;  // set_pose_noise_check_fused was the last setter
-  void reserve_noise_buffers();
+  void set_noise(const std::vector<double>& offsets, double max_risk, double lamb, bool fused);
   std::vector<double> noise_;
   double max_risk_ = 1.0, noise_lamb_ = 1.0;
-  NoiseLayout nl_{};
-  int noise_horizon_ = -1;
-  void* noise_dev_ = nullptr;
-  void* noise_stream_ = nullptr;
-  // map risk check: in effect when map_check_ (set_map_risk_check), map_set_ (an uncertainty map is set) and noise_fused_
+  // map risk check: in effect when map_check_ (set_map_risk_check), map_set_ (an uncertainty map is set) and a fused or covariance check
   bool map_check_ = false, map_set_ = false, map_unknown_hits_ = false;
   double map_threshold_ = 0.0, map_max_risk_ = 1.0;
-  // pose-covariance check (set_pose_covariance_check): Sigma0 and W travel with every call (32 doubles)
-  bool cov_check_ = false, cov_has_W_ = false, cov_sum_ = false;
-  double cov_sigma0_[16] = {}, cov_W_[16] = {}, cov_max_risk_ = 1.0, cov_lamb_ = 1.0;
-  // sample covariance check (set_sample_covariance_check): a device block of its own, grown on demand (scov_cap_ doubles)
-  bool scov_check_ = false, scov_has_W_ = false, scov_sum_ = false;
-  double scov_sigma0_[16] = {}, scov_W_[16] = {}, scov_max_risk_ = 1.0, scov_lamb_ = 1.0;
-  void* scov_dev_ = nullptr;
-  size_t scov_cap_ = 0;
-  int run_candidates_sample_covariance(int B, const std::vector<double>& ego_states);
-  // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and cov_check_; the nodes as built
+  // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and a covariance check; the nodes as built
   bool cmap_check_ = false, cmap_sum_ = false, cmap_unknown_hits_ = false;
   double cmap_threshold_ = 0.0, cmap_max_risk_ = 1.0;
   std::vector<double> cmap_nodes_, cmap_weights_;
   // chance-constraint tightening (set_chance_tightening, set_obstacle_covariance)
-  bool tighten_ = false, tg_has_W_ = false;
+  bool tighten_ = false;
   int tg_rounds_ = 0;
-  double tg_sigma0_[16] = {}, tg_W_[16] = {}, tg_kappa_ = 0.0, tg_cap_ = 2.0, tg_lamb_ = 1.0;
+  double tg_kappa_ = 0.0, tg_cap_ = 2.0;
   std::vector<double> obs_cov_, obs_cov_packed_;  // as given; and addressed by the packed obstacles' strides, 3 per entry
-  // `rounds` rounds behind a solve of B plans in the device block `d` (x0, U, poly, fl, X, J, iters, status in place); returns a C-ABI code
-  int tighten_rounds(void* stream, double* d, int B, const cilqr_obstacles* po);
-  void fetch_tighten(void* stream, double* d, int B, std::vector<double>& risk_rows);  // enqueues last_tighten and the round's risk rows
-  void keep_tighten_risk(int B, const std::vector<double>& risk_rows);                 // after the wait: their CR_STEP_RISK column
+  // `rounds` rounds behind a solve of B plans in the block (x0, U, poly, fl, X, J, iters, status in place); returns a C-ABI code
+  int tighten_rounds(const Block& d, int B, const cilqr_obstacles* po);
+  void fetch_tighten(const Block& d, int B, std::vector<double>& risk_rows);  // enqueues last_tighten and the round's risk rows
+  void keep_tighten_risk(int B, const std::vector<double>& risk_rows);       // after the wait: their CR_STEP_RISK column
   void solve_tightened(const double x_0[4], Matrix& U, const double poly_coeffs[6], const double fl[2]);  // run_step's solve
   // map tightening (set_map_tightening): Sigma0, W and lamb are the tightening's above (the setters agree on them).  The map as it was
   // set, and, while the tightening is on, one device block of floats: the original layer, then a tightened layer per candidate
@@ -379,16 +394,15 @@ class iLQR {
   size_t map_dev_cap_ = 0;
   void apply_map(const Uncertainty& u);  // puts `u` on the handle: through map_dev_ while the map tightening is on
   cilqr_uncertainty_map device_map(bool tightened) const;  // the original in map_dev_, or the per-solve layers behind it
-  bool map_tightened() const { return map_tighten_ && map_set_; }
+  double tightening_kappa(const char* setter, bool on, double eps, int rounds, double max_inflate) const;
   void check_tightening_agrees(bool other_on, int other_rounds, const double Sigma0[16], const double* W, double lamb, int rounds) const;
   // track map (set_track_map): its rounds run in tighten_rounds, its layers lie in map_dev_ behind the original
   int tm_rounds_ = 0, tm_window_ = 0;
   double tm_inflate_ = 0.0, tm_z_max_ = 0.0;
   bool tm_ellipses_ = true;
-  bool track_map_on() const { return tm_rounds_ > 0 && tracked_horizon_ >= 0 && map_set_; }
+  int solve_obstacles() const;  // the M the SOLVES read: 0 under the track map with ellipses off
   void check_track_map_conflicts() const;  // throws std::logic_error, before a run enqueues anything
   bool map_in_block() const { return map_tighten_ || tm_rounds_ > 0; }  // the map lives in map_dev_
-  bool rounds_on() const { return tighten_ || map_tighten_ || tm_rounds_ > 0; }  // solves run in the checks' device block
 };
 
 }  // namespace cilqr_host
