@@ -1408,6 +1408,85 @@ int cilqr_costmap_frame_polygons_device(cilqr_handle* h, void* stream, const flo
                                         float* vehicle_layer, float* uncertainty_layer, int8_t* occupancy_out,
                                         int64_t* n_out_of_range_dev);
 
+/* --- exact footprint check: the vehicle's rectangle against obstacle rectangles and map cells (new) -------------------------------
+ * Every other judge of a plan (cilqr_score_batch, the rollout and chance risks, both tightenings) decides "collision" with the
+ * solver's surrogates: against obstacles c = 1 - d'Pd > 0, an ego circle CENTRE inside an ellipse of semi-axes dim/2 + ego_rad (+ 1
+ * along); against the map the probes_l x probes_w probes on safe_length x safe_width.  cilqr_footprint_check(_device) answers
+ * whether the vehicle's RECTANGLE touches anything — the separating-axis test of the reference's isCollision (I/Experiment.cpp) and,
+ * where separated, the exact distance; against the map Polygon::isInside of every cell centre.  Geometry only: no speed inflation,
+ * no s_safe, no weights (obs->weight is not read).
+ * X [B*S][4*(N+1)]: rows.  Row r belongs to solve b = r / S and reads the obstacles, the layer and the map pose of solve b, indexed as
+ * the solve and score kernels index them.  S = 1: a solved batch; S > 1: stored rollouts (X_roll of cilqr_rollout_batch).  obs by
+ * strides as everywhere, NULL only when M == 0.  Steps t = 0 ... N-1 are paired with obstacle column t (the score call's
+ * convention); x_N is not visited.
+ *
+ * Definitions.
+ *   ego rectangle       centred on the state's (x, y), turned by its theta (X_t[3]); half-extents hl = length/2 + margin and
+ *                       hw = width/2 + margin from cilqr_params.  (The ego circles lie symmetric about (x, y): it is the body's centre.)
+ *   obstacle rectangle  centre (pose x, y), heading pose theta (pose[3]), half-extents dim/2.  The pose's speed is not read.
+ *   clearance of an entry   over the four axes u (two of each rectangle, a = (cos, sin), b = (-sin, cos)):
+ *                       gap_u = |u . (centre_O - centre_E)| - (r_E(u) + r_O(u)),  r_R(u) = hl_R |u . a_R| + hw_R |u . b_R|,  g = max_u gap_u.
+ *                       g > 0: separated, and the clearance is the least of the eight vertex-to-rectangle distances
+ *                       hypot(max(|a| - hl, 0), max(|b| - hw, 0)), each vertex in the other rectangle's body frame (exact for
+ *                       disjoint convex polygons).  Otherwise the clearance is g <= 0: minus the least overlap, 0 when touching.
+ *   HIT                 clearance <= 0 (isCollision's max1 < min2 is strict: touching collides).  An entry whose pose x, y, theta
+ *                       or dimension is not finite, or whose dimension is negative, is a hit with no clearance value.
+ *   map test            runs when a map is set on the handle and CILQR_FOOTPRINT_SKIP_MAP is not given.  The four ego corners in
+ *                       bondingBoxHandle's order (hl, hw), (hl, -hw), (-hl, -hw), (-hl, hw) go into the map frame by the probes'
+ *                       rigid transform (cilqr_rollout_risk_map).  Cell (i, j) of the VIRTUAL grid — centre (x_first - i*res,
+ *                       y_first - j*res) for every integer i, j, in the map or not — is covered when Polygon::isInside(centre)
+ *                       holds for that 4-gon, by the statements of cilqr_rasterize_polygons: the covered cells inside the map are
+ *                       the cells that call marks for those vertices.  A covered cell is UNKNOWN when it is outside the map or
+ *                       NaN.  A step HITS the map when a covered in-map cell is > occ_threshold (strict) or, under
+ *                       CILQR_FOOTPRINT_UNKNOWN_HITS, when a covered cell is unknown.
+ *   lost step           a state whose x, y or theta is not finite: an obstacle hit (whatever M is) and, where the map test runs, a
+ *                       map hit and unknown; it covers no cell and adds no clearance value.  For the map test alone, so is a state
+ *                       whose footprint's virtual index range (one cell wider than the corners' extremes) leaves +-2^30.
+ * fp [B*S][CILQR_FOOTPRINT_FIELDS] (required): see the enum; doubles that hold a value's bits, a count or an index.
+ * step_clearance [B*S][N] (double): the min over m at step t; +HUGE_VAL when no entry has a value (M == 0), -HUGE_VAL at a lost step.
+ * step_occ [B*S][N] (float): the step's largest finite occupancy under the footprint, NaN when none (or no map test).  total [B*S]:
+ * total[r] = base[r] when base[r] is finite, FP_HIT_STEPS == 0, FP_CLEARANCE >= min_clearance and FP_MAP_HIT_STEPS == 0; otherwise
+ * NaN — the convention of cilqr_rollout_risk_map, so the call composes through base and feeds cilqr_argmin_device.  Each of the
+ * three may be NULL; total without base is CILQR_ERR_ARG.  With M == 0 and no map the call succeeds and returns the empty values.
+ *   Determinism: minima and maxima are lexicographic (value, then lowest index) and everything else is an integer count, so nothing
+ *   depends on an order of evaluation: a row's bits depend on that row's inputs alone, whatever B, S, its place in the batch and
+ *   the obstacles' strides are.  (A per-solve map pose's cosine and sine are formed on the device, the shared pose's on the host:
+ *   equal poses given the two ways may differ in the last bit, as for every call that reads the map.)
+ * Mapping: one workgroup per row over the M*N entries; wavefront = (row, step), four steps per workgroup, over the cells of the
+ * footprint's bounding box; one wavefront per row for the fold.  Three launches (two without a map test), no global atomics.  The
+ * virtual index range is formed in doubles and compared with +-2^30 before any conversion; every load of the layer is guarded by the
+ * in-map test of its own cell.  Nothing is allocated per call: the per-step records live in device memory reserved at cilqr_create
+ * (7*max_batch*max_horizon + 2*max_batch doubles) — two footprint checks on DIFFERENT streams of one handle must not overlap.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X or fp; obs (or its pose or dim) NULL with M > 0; total without
+ * base; S < 1; a negative stride; margin negative or not finite; a NaN min_clearance or occ_threshold; unknown flag bits.  Then the
+ * cilqr_create limits: B*S <= max_batch, N, M; M*N and the map's cells below 2^31.  CILQR_ERR_UNSUPPORTED where a map test would run
+ * and ceil(2*hypot(hl, hw)/res) + 2 > 1024: a footprint of more than about a million cells per step.  The host-buffer form's arrays —
+ * X, the obstacles' span (6 doubles per entry), base and the outputs — must fit the arena reserved at create: B*S*(6*N + 18) + 6*span
+ * doubles with every output, against max_batch*(28*max_horizon + 6*max_obstacles*max_horizon + 50) at least; every B*S <= max_batch fits. */
+#define CILQR_FOOTPRINT_FIELDS 12
+typedef enum cilqr_footprint_field {
+  CILQR_FP_CLEARANCE = 0,          /* min signed clearance over (m, t); +HUGE_VAL when no entry has a value */
+  CILQR_FP_CLEARANCE_ENTRY = 1,    /* m*N + t of it, lowest on equal values; -1 */
+  CILQR_FP_HIT_STEPS = 2,          /* steps with an obstacle hit */
+  CILQR_FP_FIRST_HIT = 3,          /* lowest such t; -1 */
+  CILQR_FP_MAP_OCC = 4,            /* largest finite occupancy under the footprint; -HUGE_VAL when none */
+  CILQR_FP_MAP_OCC_STEP = 5,       /* its step, lowest on equal; -1 */
+  CILQR_FP_MAP_OCC_CELL = 6,       /* i + j*rows of it within that step, lowest on equal; -1 */
+  CILQR_FP_MAP_HIT_STEPS = 7,      /* steps that hit the map */
+  CILQR_FP_MAP_FIRST_HIT = 8,      /* lowest such t; -1 */
+  CILQR_FP_MAP_HIT_CELLS = 9,      /* largest per-step count of covered cells above the threshold */
+  CILQR_FP_MAP_UNKNOWN_STEPS = 10, /* steps with an unknown covered cell */
+  CILQR_FP_MAP_CELLS = 11          /* covered cells over all steps, in the map or not */
+} cilqr_footprint_field;
+#define CILQR_FOOTPRINT_UNKNOWN_HITS 1u /* flags: a covered cell that is unknown counts as a map hit */
+#define CILQR_FOOTPRINT_SKIP_MAP 2u     /* flags: no map test, whatever is set on the handle */
+int cilqr_footprint_check_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X, const cilqr_obstacles* obs,
+                                 double margin, double min_clearance, double occ_threshold, uint32_t flags, const double* base,
+                                 double* fp, double* step_clearance, float* step_occ, double* total);
+int cilqr_footprint_check(cilqr_handle* h, int B, int N, int M, int S, const double* X, const cilqr_obstacles* obs, double margin,
+                          double min_clearance, double occ_threshold, uint32_t flags, const double* base, double* fp,
+                          double* step_clearance, float* step_occ, double* total);
+
 /* setGeometry(Length(lx,ly), res, Position(px,py)) size/length rule (G/grid_map_core/src/GridMap.cpp:45-62). */
 int cilqr_map_geom_set(cilqr_map_geom* g, double len_x, double len_y, double res, double pos_x, double pos_y);
 

@@ -60,6 +60,11 @@ CRS_FIELDS = 8
 (CRS_STEP_RISK, CRS_WORST_STEP, CRS_SUM_RISK, CRS_MAX_PAIR_P, CRS_MAX_PAIR, CRS_MAX_ENTRY_P, CRS_MAX_ENTRY,
  CRS_NOMINAL_SHARE) = range(CRS_FIELDS)
 CHANCE_SAMPLED_BOUND_SUM = 1  # flags of `chance_risk_sampled`: max_risk bounds CRS_SUM_RISK instead of CRS_STEP_RISK
+# `cilqr_footprint_field`: the columns of a footprint row (`Solver.footprint_check`)
+FOOTPRINT_FIELDS = 12
+(FP_CLEARANCE, FP_CLEARANCE_ENTRY, FP_HIT_STEPS, FP_FIRST_HIT, FP_MAP_OCC, FP_MAP_OCC_STEP, FP_MAP_OCC_CELL, FP_MAP_HIT_STEPS,
+ FP_MAP_FIRST_HIT, FP_MAP_HIT_CELLS, FP_MAP_UNKNOWN_STEPS, FP_MAP_CELLS) = range(FOOTPRINT_FIELDS)
+FOOTPRINT_UNKNOWN_HITS, FOOTPRINT_SKIP_MAP = 1, 2  # flags of `footprint_check`
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -87,6 +92,7 @@ ABI_SYMBOLS = (
     "cilqr_chance_risk_map", "cilqr_chance_risk_map_device", "cilqr_pose_quadrature",
     "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
     "cilqr_predict_obstacles", "cilqr_predict_obstacles_device", "cilqr_chance_risk_cov", "cilqr_chance_risk_cov_device",
+    "cilqr_footprint_check", "cilqr_footprint_check_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -970,6 +976,41 @@ class Solver:
         _check(lib().cilqr_rasterize_tracks_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(X), C.byref(obs), _vp(obs_cov),
                                                    C.c_double(inflate), C.c_double(z_max), int(window), C.c_uint32(int(flags)),
                                                    _vp(layer_out), _vp(fields)))
+
+    def footprint_check(self, N, X, obs_pose=None, obs_dim=None, S=1, margin=0.0, min_clearance=0.0, occ_threshold=float("inf"),
+                        base=None, unknown_hits=False, skip_map=False, steps=True):
+        """`cilqr_footprint_check`: X (B*S, 4(N+1)) rows, row r of solve r // S; obstacles in any shape of `obstacle_strides` for the B
+        solves, or None.  Returns dict(fp (B*S, FOOTPRINT_FIELDS), step_clearance (B*S, N), step_occ (B*S, N) float32 — both None
+        with steps=False — and total (B*S,), None without base)."""
+        X = _np64(X)
+        R = X.size // (4 * (N + 1))
+        X = X.reshape(R, 4 * (N + 1))
+        S = int(S)
+        if S < 1 or R % S:
+            raise CilqrError("footprint_check: %d rows are no multiple of S = %d" % (R, S))
+        B = R // S
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        base = None if base is None else _np64(base).reshape(R)
+        fp = np.zeros((R, FOOTPRINT_FIELDS))
+        step_clearance = np.zeros((R, N)) if steps else None
+        step_occ = np.zeros((R, N), dtype=np.float32) if steps else None
+        total = None if base is None else np.zeros(R)
+        flags = (FOOTPRINT_UNKNOWN_HITS if unknown_hits else 0) | (FOOTPRINT_SKIP_MAP if skip_map else 0)
+        _check(lib().cilqr_footprint_check(self._h, B, int(N), int(M), S, _p(X), None if obs is None else C.byref(obs),
+                                           C.c_double(margin), C.c_double(min_clearance), C.c_double(occ_threshold),
+                                           C.c_uint32(flags), _p(base), _p(fp), _p(step_clearance), _p(step_occ, _fp), _p(total)))
+        return dict(fp=fp, step_clearance=step_clearance, step_occ=step_occ, total=total)
+
+    def footprint_check_device(self, stream, B, N, M, S, X, obs_pose, obs_dim, strides, fp, margin=0.0, min_clearance=0.0,
+                               occ_threshold=float("inf"), flags=0, base=0, step_clearance=0, step_occ=0, total=0):
+        """`cilqr_footprint_check_device`: device addresses; strides (batch, obstacle, step, weight batch) as `score_batch_device`;
+        the map is the one set by `set_uncertainty_map(_device)`."""
+        bs, ms, ts, wbs = (int(v) for v in strides)
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, wbs)
+        _check(lib().cilqr_footprint_check_device(self._h, _vp(stream), int(B), int(N), int(M), int(S), _vp(X),
+                                                  C.byref(obs) if M else None, C.c_double(margin), C.c_double(min_clearance),
+                                                  C.c_double(occ_threshold), C.c_uint32(int(flags)), _vp(base), _vp(fp),
+                                                  _vp(step_clearance), _vp(step_occ), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -278,6 +278,7 @@ int cilqr_create(const cilqr_params* p, int max_batch, int max_horizon, int max_
   if (err == hipSuccess) err = dmalloc(&h->d_risk_part, B * h->risk_part_stride);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_map_steps, 3 * B * N);
   if (err == hipSuccess) err = dmalloc(&h->d_chance_sampled_steps, cilqr::CHANCE_SAMPLED_REC * B * N);
+  if (err == hipSuccess) err = dmalloc(&h->d_footprint_steps, cilqr::footprint_scratch_doubles(B, N));
   if (err == hipSuccess) err = dmalloc(&h->d_tighten_map_part, (size_t)cilqr::TIGHTEN_MAP_REC * cilqr::TIGHTEN_MAP_MAX_G * B);
   if (err == hipSuccess) err = dmalloc(&h->d_track_map_rec, (size_t)cilqr::TRACK_MAP_ENTRY * B * M * N);
   if (err == hipSuccess) err = dmalloc(&h->d_track_map_part, (size_t)cilqr::TRACK_MAP_REC * cilqr::TRACK_MAP_MAX_G * B);
@@ -312,7 +313,7 @@ int cilqr_destroy(cilqr_handle* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   for (void* p : h->scratch)
     if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_tighten_map_part, h->d_track_map_rec, h->d_track_map_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
+  void* ptrs[] = {h->d_poses, h->d_polys, h->d_unc_layer, h->d_triple, h->d_gather, h->d_arena, h->d_obs_tab, h->d_ws, h->d_redo, h->d_hint_passes, h->d_order, h->d_pair, h->d_risk_part, h->d_chance_map_steps, h->d_chance_sampled_steps, h->d_footprint_steps, h->d_tighten_map_part, h->d_track_map_rec, h->d_track_map_part, h->d_src, h->d_dst, h->d_bbox, h->d_oob, h->d_occ_steps};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1589,6 +1590,90 @@ int cilqr_chance_risk_map(cilqr_handle* h, int B, int N, int Q, const double* X,
   return cilqr::host_call(h, p, [&] {
     return cilqr_chance_risk_map_device(h, h->stream, B, N, Q, X, sigma, nodes, weights, occ_threshold, flags, max_risk, base, risk,
                                         step_risk, step_occ, step_unknown, total);
+  });
+}
+
+// ---- exact footprint check (cilqr_footprint.hip) ------------------------------------------------------------------------------------------
+namespace {
+// what needs no handle
+int footprint_args_check(int M, int S, const double* X, const cilqr_obstacles* obs, double margin, double min_clearance,
+                         double occ_threshold, uint32_t flags, const double* base, const double* fp, const double* total) {
+  if (!X || !fp) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: null required pointer");
+  if (M > 0 && (!obs || !obs->pose || !obs->dim)) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: M = %d but obs, its pose or its dim is null", M);
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: total needs base");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: S = %d, must be at least 1", S);
+  if (M > 0 && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0 || obs->weight_batch_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_footprint_check: negative stride");
+  if (!(margin >= 0.0 && margin <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: margin is negative or not finite");
+  if (min_clearance != min_clearance || occ_threshold != occ_threshold)
+    return fail(CILQR_ERR_ARG, "cilqr_footprint_check: min_clearance or occ_threshold is NaN");
+  if (flags & ~(CILQR_FOOTPRINT_UNKNOWN_HITS | CILQR_FOOTPRINT_SKIP_MAP))
+    return fail(CILQR_ERR_ARG, "cilqr_footprint_check: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int footprint_handle_check(const cilqr_handle* h, int B, int N, int M, int S, const cilqr_obstacles* obs, double margin, uint32_t flags,
+                           size_t* span) {
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (B < 0 || (int64_t)B * S > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: B*S = %lld outside [0,%d]", (long long)B * S, h->max_batch);
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = check_obstacles(B, N, M, obs, span, nullptr);
+  if (rc) return rc;
+  if ((int64_t)M * N > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: M * N beyond 2^31 - 1 entries");
+  if (h->unc.layer && !(flags & CILQR_FOOTPRINT_SKIP_MAP)) {
+    if ((int64_t)h->unc.rows * h->unc.cols > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_footprint_check: the map has 2^31 cells or more");
+    const double hl = 0.5 * h->params.length + margin, hw = 0.5 * h->params.width + margin;
+    if (!(ceil(2.0 * hypot(hl, hw) / h->unc_res) + 2.0 <= 1024.0))
+      return fail(CILQR_ERR_UNSUPPORTED, "cilqr_footprint_check: the footprint spans more than 1024 cells of %g m", h->unc_res);
+  }
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_footprint_check_device(cilqr_handle* h, void* stream, int B, int N, int M, int S, const double* X, const cilqr_obstacles* obs,
+                                 double margin, double min_clearance, double occ_threshold, uint32_t flags, const double* base,
+                                 double* fp, double* step_clearance, float* step_occ, double* total) {
+  int rc = footprint_args_check(M, S, X, obs, margin, min_clearance, occ_threshold, flags, base, fp, total);
+  if (rc) return rc;
+  rc = footprint_handle_check(h, B, N, M, S, obs, margin, flags, nullptr);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::FootprintArgs a = {};
+  a.s = handle_args(h, B, N, M, 0);
+  set_obstacles(a.s, M, obs);
+  a.X = X;
+  a.hl = 0.5 * h->params.length + margin; a.hw = 0.5 * h->params.width + margin;
+  a.min_clearance = min_clearance; a.occ_threshold = occ_threshold; a.res = h->unc_res;
+  a.base = base; a.fp = fp; a.step_occ = step_occ; a.total = total;
+  a.rows = B * S; a.S = S; a.flags = flags;
+  a.map_on = h->unc.layer && !(flags & CILQR_FOOTPRINT_SKIP_MAP) ? 1 : 0;
+  // reserved at create: max_batch·max_horizon step records, max_batch row records, max_batch·max_horizon stand-in step clearances
+  const size_t slab = (size_t)h->max_batch * h->max_horizon;
+  a.steps = h->d_footprint_steps;
+  a.row_rec = a.steps + slab * cilqr::FOOTPRINT_STEP_REC;
+  a.step_clearance = step_clearance ? step_clearance : a.row_rec + (size_t)h->max_batch * cilqr::FOOTPRINT_ROW_REC;
+  if ((int64_t)a.rows * ((N + cilqr::FOOTPRINT_WAVES - 1) / cilqr::FOOTPRINT_WAVES) > 0x7fffffff)
+    return fail(CILQR_ERR_ARG, "cilqr_footprint_check: B * S * ceil(N / 4) workgroups beyond 2^31 - 1");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_footprint_check(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_footprint_check(cilqr_handle* h, int B, int N, int M, int S, const double* X, const cilqr_obstacles* obs, double margin,
+                          double min_clearance, double occ_threshold, uint32_t flags, const double* base, double* fp,
+                          double* step_clearance, float* step_occ, double* total) {
+  int rc = footprint_args_check(M, S, X, obs, margin, min_clearance, occ_threshold, flags, base, fp, total);
+  if (rc) return rc;
+  size_t span = 0;
+  rc = footprint_handle_check(h, B, N, M, S, obs, margin, flags, &span);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr_obstacles o = M > 0 ? *obs : cilqr_obstacles{};
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_footprint(p, (size_t)B * S, N, M, X, o, span, base, fp, step_clearance, step_occ, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_footprint_check_device(h, h->stream, B, N, M, S, X, &o, margin, min_clearance, occ_threshold, flags, base, fp,
+                                        step_clearance, step_occ, total);
   });
 }
 

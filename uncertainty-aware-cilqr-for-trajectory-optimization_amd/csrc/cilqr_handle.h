@@ -86,6 +86,7 @@ struct cilqr_handle {
   double* d_tighten_map_part;  // workgroup records of cilqr_tighten_map: max_batch x TIGHTEN_MAP_MAX_G x TIGHTEN_MAP_REC doubles
   double* d_track_map_rec;   // entry records of cilqr_rasterize_tracks: max_batch x max_obstacles x max_horizon x TRACK_MAP_ENTRY doubles
   double* d_track_map_part;  // its workgroup records: max_batch x TRACK_MAP_MAX_G x TRACK_MAP_REC doubles
+  double* d_footprint_steps;  // step and row records of cilqr_footprint_check: footprint_scratch_doubles(max_batch, max_horizon)
   double* d_chance_sampled_steps;  // step records of cilqr_chance_risk_sampled: CHANCE_SAMPLED_REC x max_batch x max_horizon doubles
   // warp staging (grown on demand by the host-pointer warp entry point only)
   float *d_src, *d_dst, *d_bbox;

@@ -349,6 +349,22 @@ inline void plan_chance_sampled(HostPlan& p, size_t B, size_t N, size_t M, size_
   p.out(total, B);
 }
 
+// cilqr_footprint_check: 8 arrays; R = B·S rows; obstacle weights are not read and do not travel.  Per row 5.5·N + 18 doubles with
+// every output — X, base, the fp row, step_clearance, step_occ (N floats), total — and the obstacles are 6 doubles per entry of the
+// span: R·(6·N + 18) + 6·span at most, against the 28·N + 6·M·N + M + 50 per unit of max_batch that host_arena_bytes reserves below:
+// every R <= max_batch fits with a span within the B·M·N of dense tables, and the 8 roundings stay within its 32 x 16 bytes.
+inline void plan_footprint(HostPlan& p, size_t R, size_t N, size_t M, const double*& X, cilqr_obstacles& o, size_t span, const double*& base,
+                           double*& fp, double*& step_clearance, float*& step_occ, double*& total) {
+  p.in(X, R * 4 * (N + 1));
+  o.weight = nullptr;
+  plan_obstacles(p, M, o, span, 0);
+  p.in(base, R);
+  p.out(fp, R * CILQR_FOOTPRINT_FIELDS);
+  p.out(step_clearance, R * N);
+  p.out(step_occ, R * N);
+  p.out(total, R);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

@@ -360,6 +360,42 @@ struct TrackMapArgs {
 hipError_t launch_rasterize_tracks(const TrackMapArgs& a, hipStream_t stream);
 size_t track_map_lds_bytes(int N);
 
+// Exact footprint check (cilqr_footprint.hip; cilqr_footprint_check*): the vehicle's rectangle against the obstacle rectangles and
+// against the cells of the map set on the handle.  Three launches:
+//   boxes  one workgroup of FOOTPRINT_THREADS lanes per row; lanes stride over the entries e = m·N + t
+//   map    wavefront = (row, step), FOOTPRINT_WAVES steps per workgroup, rows·ceil(N / FOOTPRINT_WAVES) workgroups; lanes stride
+//          over the virtual cells of the footprint's bounding box, i fastest (only when a map is set and not skipped)
+//   merge  one wavefront per row folds the N step records and the boxes' record into fp and total
+// `s` carries B (SOLVES), N, M, the strided obstacle fields and unc; row r = b·S + s reads X at r and everything else of solve b.
+// `steps`: the handle's, one record of FOOTPRINT_STEP_REC doubles per (row, step) — boxes writes field 0, map fields 1..5 — then,
+// behind rows·N records, FOOTPRINT_ROW_REC doubles per row (the boxes' smallest clearance and its entry) and, behind those, rows·N
+// doubles that stand in for a step_clearance the caller did not ask for.
+constexpr int FOOTPRINT_THREADS = 256;
+constexpr int FOOTPRINT_WAVES = 4;
+constexpr int FOOTPRINT_STEP_REC = 6;  // box hit, largest occupancy (-inf: none), its cell, cells above the threshold, hit | unknown << 1, covered cells
+constexpr int FOOTPRINT_ROW_REC = 2;
+constexpr size_t FOOTPRINT_LDS_MAX = 64 * 1024;
+struct FootprintArgs {
+  SolveArgs s;
+  const double* X;         // [rows][4(N + 1)]
+  double hl, hw;           // half-extents of the ego rectangle, the margin included
+  double min_clearance, occ_threshold;
+  double res;              // the map's resolution as it was set
+  const double* base;      // [rows] or null (then total is null)
+  double* fp;              // [rows][CILQR_FOOTPRINT_FIELDS]
+  double* step_clearance;  // [rows][N]: the caller's, or the handle's
+  float* step_occ;         // [rows][N] or null
+  double* total;           // [rows] or null
+  double *steps, *row_rec;
+  int32_t rows, S, map_on;
+  uint32_t flags;          // CILQR_FOOTPRINT_*
+};
+hipError_t launch_footprint_check(const FootprintArgs& a, hipStream_t stream);
+size_t footprint_lds_bytes(int N);
+inline size_t footprint_scratch_doubles(size_t max_batch, size_t max_horizon) {
+  return max_batch * max_horizon * (FOOTPRINT_STEP_REC + 1) + max_batch * FOOTPRINT_ROW_REC;
+}
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

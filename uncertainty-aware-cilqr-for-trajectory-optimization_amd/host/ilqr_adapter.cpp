@@ -39,6 +39,8 @@ const char* const kTrackMapEllipsesOffTightened =
     "set_track_map with ellipses = false beside set_chance_tightening: the solves read no ellipse that the tightening could inflate";
 const char* const kCovarianceWithSamples =
     "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
+const char* const kFootprintWithSamples =
+    "set_footprint_check has no form for sampled obstacles (set_obstacle_samples): it judges rectangles, and a sample has none";
 const char* const kSampleCovarianceWithNoise =
     "set_sample_covariance_check and set_pose_noise_check(_fused) are both set: the pose noise is given either as a covariance or as draws";
 const char* const kSampleCovarianceWithoutSamples =
@@ -348,6 +350,7 @@ CandidateModes iLQR::modes() const {
   m.cov_judge = obs_cov_check_; m.cmap = cmap_check_; m.map = map_check_;
   m.tighten = tighten_; m.map_tighten = map_tighten_; m.track_map = tm_rounds_ > 0;
   m.min_total = pick_ == CandidatePick::MinTotalCost;
+  m.footprint = fp_check_;
   m.map_set = map_set_; m.obstacles = !obstacles_.empty(); m.tracks = tracked_horizon_ >= 0;
   return m;
 }
@@ -375,6 +378,7 @@ void iLQR::clear_candidate_fields() {
   last_chance_risk.clear(); last_step_risk.clear();
   last_chance_map_risk.clear(); last_map_step_risk.clear();
   last_chance_risk_sampled.clear();
+  last_footprint.clear(); last_footprint_clearance.clear();
 }
 
 // The prologue of every run_candidates: LocalPlanner pre-step for all candidates in one device launch (cilqr_local_plan_batch)
@@ -564,6 +568,19 @@ const double* iLQR::upload(const Block& d, const CovarianceParams& p, size_t s0_
   return p.has_W ? d + W_at : nullptr;
 }
 
+void iLQR::set_footprint_check(double min_clearance, double occ_threshold, double margin, bool unknown_hits, bool on) {
+  if (on && (min_clearance != min_clearance || occ_threshold != occ_threshold)) throw std::runtime_error("set_footprint_check: min_clearance or occ_threshold is NaN");
+  if (on && !(margin >= 0.0 && margin <= 1.7e308)) throw std::runtime_error("set_footprint_check: margin is negative or not finite");
+  fp_check_ = on;
+  fp_min_clearance_ = min_clearance;
+  fp_threshold_ = occ_threshold;
+  fp_margin_ = margin;
+  fp_unknown_hits_ = unknown_hits;
+  last_footprint.clear();
+  last_footprint_clearance.clear();
+  reserve_block_if_used();  // (the device block holds the check's rows while it is on)
+}
+
 void iLQR::set_pose_covariance_check(const double Sigma0[16], const double* W, double max_risk, double lamb, bool sum_bound) {
   if (Sigma0 && !noise_.empty()) throw std::logic_error(kCovarianceWithNoise);
   if (Sigma0 && n_samples_) throw std::logic_error(kCovarianceWithSamples);
@@ -719,6 +736,7 @@ cilqr_obstacles iLQR::upload_obstacles(const Block& d) {
 // the pick's arrays -> one wait.  CandidateModes says which stages run; the block was laid out from the same predicates.
 int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, const CandidateModes& m) {
   const int N = params.horizon, M = (int)obstacles_.size(), S = (int)sizes().rollouts(m);
+  if (m.footprint && m.sampled) throw std::logic_error(kFootprintWithSamples);
   if (m.scov) {
     if (!m.sampled) throw std::logic_error(kSampleCovarianceWithoutSamples);
     if (m.noise) throw std::logic_error(kSampleCovarianceWithNoise);
@@ -825,11 +843,16 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
                                          map_unknown_hits_ ? CILQR_MAP_RISK_UNKNOWN_HITS : 0u, map_max_risk_, base, d + L.mrisk, d.i32(L.mhits),
                                          d.i32(L.munk), total);
   });
+  // the last gate: the final plan's rectangle against the ORIGINAL obstacles and the map on the handle (the original: the rounds put it back)
+  stage(m.footprint_check(), L.fptotal, [&](const double* base, double* total) {
+    return cilqr_footprint_check_device(h_, d.st, B, N, M, 1, d + L.X, po, fp_margin_, fp_min_clearance_, fp_threshold_,
+                                        fp_unknown_hits_ ? CILQR_FOOTPRINT_UNKNOWN_HITS : 0u, base, d + L.fprow, d + L.fpstep, nullptr, total);
+  });
   step(true, [&] { return cilqr_argmin_device(h_, d.st, B, d + total_at, d + L.pair); });
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(d.st);
-    throw std::runtime_error((m.scov ? "run_candidates (sample covariance check): " : m.plain() ? "run_candidates (chance tightening): "
+    throw std::runtime_error((m.scov ? "run_candidates (sample covariance check): " : m.plain() && !m.rounds() ? "run_candidates (footprint check): " : m.plain() ? "run_candidates (chance tightening): "
                                                                                                  : "run_candidates (pose-noise check): ") + msg);
   }
   // every last_* vector is reset here; the stages that ran fill theirs
@@ -854,6 +877,10 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
     d.fetch(last_map_risk, L.mrisk, (size_t)B * CILQR_MAP_RISK_FIELDS);
     d.fetch(last_map_step_hits, L.mhits, (size_t)B * N);
     d.fetch(last_map_unknown_hits, L.munk, (size_t)B * N);
+  }
+  if (m.footprint_check()) {
+    d.fetch(last_footprint, L.fprow, (size_t)B * CILQR_FOOTPRINT_FIELDS);
+    d.fetch(last_footprint_clearance, L.fpstep, (size_t)B * N);
   }
   d.wait();
   if (m.rounds()) keep_tighten_risk(B, tg_rows);

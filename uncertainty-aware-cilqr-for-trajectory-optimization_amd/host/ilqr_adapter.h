@@ -136,6 +136,18 @@ class iLQR {
   // per candidate.  With no map set, or under any other pick, behaviour is what it is without this call and the three fields are
   // empty.  An occ_threshold that is NaN switches the check off (the default).
   void set_map_risk_check(double occ_threshold, double max_risk, bool unknown_hits = false);
+  // Footprint check: the last gate in front of the pick.  Every check above judges a plan by the solver's surrogates (an ego circle's
+  // centre inside an inflated ellipse; probes on safe_length x safe_width); this one asks whether the vehicle's length x width
+  // rectangle, grown by `margin`, touches an obstacle's rectangle or covers a map cell above occ_threshold
+  // (cilqr_footprint_check_device).  run_candidates then enqueues it as the LAST stage in front of cilqr_argmin_device, on the final
+  // plan, against the ORIGINAL obstacles and the original map, whatever else is in force: its base is the total before it, or J where
+  // no check ran, and a candidate with an obstacle hit, a clearance below min_clearance or a map hit is rejected (its total is NaN;
+  // -1 when all are).  It needs no other setter: alone it is a valid configuration (solve -> (score under MinTotalCost) -> footprint
+  // -> pick).  occ_threshold = +infinity leaves the map out of the decision; unknown_hits: a covered cell outside the map or NaN
+  // rejects.  last_footprint holds CILQR_FOOTPRINT_FIELDS per candidate (cilqr_footprint_field), last_footprint_clearance the
+  // smallest clearance per step, horizon per candidate.  With set_obstacle_samples the run throws std::logic_error (the check has no
+  // sampled form).  on = false switches it off (the default).
+  void set_footprint_check(double min_clearance, double occ_threshold, double margin = 0.0, bool unknown_hits = false, bool on = true);
   // Pose-covariance check: the analytic counterpart of the fused pose-noise check.  Instead of S draws of the pose noise the node
   // hands over its covariance: Sigma0, 4 x 4 column-major over (x, y, v, theta) (only row <= column is read), and the process noise
   // W added per step (nullable: none).  run_candidates then enqueues, on the check's stream: solve -> (under MinTotalCost
@@ -289,6 +301,8 @@ class iLQR {
   // run_candidates with the map risk check in effect (set_map_risk_check); empty otherwise
   std::vector<double> last_map_risk;               // CILQR_MAP_RISK_FIELDS per candidate
   std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
+  // run_candidates under set_footprint_check; empty otherwise
+  std::vector<double> last_footprint, last_footprint_clearance;  // CILQR_FOOTPRINT_FIELDS per candidate; horizon per candidate
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
   // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
@@ -370,6 +384,9 @@ class iLQR {
   // map risk check: in effect when map_check_ (set_map_risk_check), map_set_ (an uncertainty map is set) and a fused or covariance check
   bool map_check_ = false, map_set_ = false, map_unknown_hits_ = false;
   double map_threshold_ = 0.0, map_max_risk_ = 1.0;
+  // footprint check (set_footprint_check)
+  bool fp_check_ = false, fp_unknown_hits_ = false;
+  double fp_min_clearance_ = 0.0, fp_threshold_ = 0.0, fp_margin_ = 0.0;
   // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and a covariance check; the nodes as built
   bool cmap_check_ = false, cmap_sum_ = false, cmap_unknown_hits_ = false;
   double cmap_threshold_ = 0.0, cmap_max_risk_ = 1.0;
