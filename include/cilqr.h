@@ -1487,6 +1487,110 @@ int cilqr_footprint_check(cilqr_handle* h, int B, int N, int M, int S, const dou
                           double min_clearance, double occ_threshold, uint32_t flags, const double* base, double* fp,
                           double* step_clearance, float* step_occ, double* total);
 
+/* --- distance to the occupied cells of a layer: exact distance field and inflation (new) -------------------------------------------
+ * Every other map product raises cells (cilqr_tighten_map, cilqr_rasterize_tracks) or tests overlap (cilqr_footprint_check); these
+ * two say how FAR the nearest occupied cell is — the quantity of grid_map_sdf and of costmap_2d's inflation layer.
+ * Layers are float32, column-major (i + j*rows), geometry g (only rows, cols and res are read); layer l starts at layer +
+ * l*layer_stride, layer_stride 0 (one shared layer, its result written L times) or >= rows*cols.  Outputs are dense, rows*cols apart.
+ *
+ * Definitions.
+ *   seed      a cell whose value is finite and > occ_threshold (strict, as in cilqr_footprint_check).  Under
+ *             CILQR_MAP_DISTANCE_UNKNOWN_SEEDS a NaN cell is a seed too.  Under CILQR_MAP_DISTANCE_TO_FREE the predicate — the
+ *             unknown-seeds rule included — is complemented: the result is the distance to the nearest cell that is NOT a seed, and
+ *             two calls give the signed field of grid_map_sdf.
+ *   d2_out    [L][rows*cols] int32 (required): min over the seeds (i', j') of layer l of (i - i')^2 + (j - j')^2, in cells, an exact
+ *             integer, 0 on a seed; INT32_MAX when the layer has no seed.
+ *   dist_out  [L][rows*cols] float, or NULL: (float)(res * sqrt((double)d2)) — one correctly rounded square root, one multiply and
+ *             one conversion, so it is bit-defined; +INFINITY when the layer has no seed.
+ *   Determinism: everything is an integer minimum, so a layer's bits depend on that layer alone, whatever L and its place are.
+ * Mapping: two launches.  Lane = row i walks the columns forward and back carrying the distance to the last seed of its row and
+ * writes it into d2_out; then one workgroup per (layer, column) takes the column's rows values, squared, into LDS (4*rows bytes) and
+ * lane = i searches outward over min(G[i - d], G[i + d]) + d^2 until d^2 reaches the best so far; the result replaces the column in
+ * place.  Both launches are coalesced; no atomics, no scratch memory, nothing allocated per call.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL layer, g or d2_out; L < 1; rows or cols < 1 or a res that is not
+ * positive and finite; a layer_stride that is negative or between 1 and rows*cols - 1; a NaN occ_threshold; unknown flag bits; L
+ * beyond 2^31 - 1 workgroups (L * max(cols, ceil(rows*cols/256))).  CILQR_ERR_UNSUPPORTED for rows or cols > 8192 (d2 <= 2*8192^2
+ * < 2^31, and a column of int32 is 32 KiB of LDS).  The host-buffer form's arrays — the layers' span, d2_out and dist_out, 4 bytes a
+ * cell each — must fit the device arena reserved at create (CILQR_ERR_ARG otherwise, as for every host form; this call adds nothing
+ * to it): large maps and batches take the device form. */
+#define CILQR_MAP_DISTANCE_UNKNOWN_SEEDS 1u /* flags: NaN cells are seeds */
+#define CILQR_MAP_DISTANCE_TO_FREE 2u       /* flags: the seed predicate is complemented */
+int cilqr_map_distance_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                              double occ_threshold, uint32_t flags, int32_t* d2_out, float* dist_out);
+int cilqr_map_distance(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, double occ_threshold,
+                       uint32_t flags, int32_t* d2_out, float* dist_out);
+
+/* cilqr_inflate_map(_device): the layers inflated from the field d2 [L][rows*cols] of cilqr_map_distance, for the solve to read.
+ * Per cell, with d = res * sqrt((double)d2) evaluated in double, in this order:
+ *   v = peak                                          where d <= inscribed;
+ *   v = 0                                             where d >= radius or d2 == INT32_MAX;
+ *   v = peak * (radius - d) / (radius - inscribed)    otherwise (the product first, then the quotient).
+ * A cell o that is not NaN becomes max(o, (float)v).  A NaN cell becomes (float)v where v > 0 and stays NaN elsewhere — the convention
+ * of cilqr_rasterize_tracks: unknown stays unknown where nothing reaches it.  layer_out [L][rows*cols] goes where tightened layers go:
+ * cilqr_set_uncertainty_map_device with layer_stride = rows*cols (or 0), followed by a solve.  The inflation is soft: judge the final
+ * plan against the ORIGINAL map.  layer_out may be the very buffer `layer` when L == 1 or layer_stride == rows*cols; any other
+ * overlap of the two ranges is CILQR_ERR_ARG (device form).  One launch, lane = cell; nothing is allocated per call.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL layer, g, d2 or layer_out; L, geometry and layer_stride as above;
+ * inscribed or radius not finite, inscribed < 0 or radius <= inscribed; a peak that is not finite or not > 0.  CILQR_ERR_UNSUPPORTED
+ * for rows or cols > 8192.  Host-buffer form: the layers' span, d2 and layer_out must fit the arena, as above. */
+int cilqr_inflate_map_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                             const int32_t* d2, double inscribed, double radius, double peak, float* layer_out);
+int cilqr_inflate_map(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* d2,
+                      double inscribed, double radius, double peak, float* layer_out);
+
+/* --- exact clearance of the ego rectangle to the occupied cells of the map (new) -----------------------------------------------------
+ * The map counterpart of CILQR_FP_CLEARANCE: cilqr_footprint_check reports only whether the rectangle covers a cell above the
+ * threshold; this call returns how far the nearest such cell is, so that min_clearance has something to act on where the map is
+ * the only obstacle information (M = 0).  Rows, steps t = 0 ... N-1, the map set on the handle, the rigid transform into the map
+ * frame, the layer and pose of solve b = r / S and the half-extents hl = length/2 + margin, hw = width/2 + margin are exactly those of
+ * cilqr_footprint_check.
+ *
+ * Definitions.
+ *   seed          an in-map cell whose value is finite and > occ_threshold (strict); under CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS an
+ *                 in-map NaN cell too.  Cells outside the map are never seeds.
+ *   s of a seed   with (a, b) the body-frame coordinates of the cell's centre (x_first - i*res, y_first - j*res): where |a| > hl or
+ *                 |b| > hw, s = hypot(max(|a| - hl, 0), max(|b| - hw, 0)); otherwise s = -min(hl - |a|, hw - |b|): minus the
+ *                 penetration depth, 0 on the boundary — the obstacle clearance's "minus the least overlap".  This inside test,
+ *                 |a| <= hl && |b| <= hw, is this call's own: for a centre within rounding of the boundary it may differ from
+ *                 Polygon::isInside, so CILQR_MC_TOUCH_STEPS is not promised to equal CILQR_FP_MAP_HIT_STEPS there.
+ *   step          its clearance is the minimum of s over the seeds with s <= reach, lexicographic: the value first, then the lowest
+ *                 i + j*rows; +HUGE_VAL when there is none.  Seeds with s > reach never count, so the answer does not depend on
+ *                 the shape of the search WINDOW: the range of virtual cell indices, one cell wider on every side than the
+ *                 extremes of the four corners of the rectangle grown by reach (half-extents hl + reach, hw + reach), formed as
+ *                 cilqr_footprint_check forms its range.  A step whose window leaves [0, rows) x [0, cols) is counted.
+ *   lost step     a state whose x, y or theta is not finite, or whose window leaves +-2^30: clearance -HUGE_VAL, no cell; it is
+ *                 below every min_clearance and counts among the steps <= 0.
+ * mc [B*S][CILQR_MAP_CLEARANCE_FIELDS] (required): see the enum; doubles that hold a value's bits, a count or an index.
+ * step_clearance [B*S][N] or NULL.  total [B*S] or NULL: total[r] = base[r] when base[r] is finite, there is no lost step and
+ * MC_CLEARANCE >= min_clearance; otherwise NaN — the base convention, so the call composes (behind cilqr_footprint_check, say) and
+ * feeds cilqr_argmin_device.  total without base is CILQR_ERR_ARG.
+ *   Determinism: lexicographic minima and integer counts; a row's bits depend on that row's inputs alone.
+ * Mapping: wavefront = (row, step), four steps per workgroup, lanes over the cells of the window clipped to the map, every load of
+ * the layer guarded by the in-map test of its own cell; then one wavefront per row for the fold.  Two launches, no global atomics.
+ * Nothing is allocated per call: the per-step records live in the region reserved at cilqr_create for cilqr_footprint_check — this
+ * call and a footprint check, or two of these, on DIFFERENT streams of one handle must not overlap.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X or mc; total without base; S < 1; margin or reach negative or not
+ * finite; a NaN min_clearance or occ_threshold; unknown flag bits.  Then the cilqr_create limits (B*S <= max_batch, N), no map set on
+ * the handle, a map of 2^31 cells or more.  CILQR_ERR_UNSUPPORTED where ceil(2*(hypot(hl, hw) + reach)/res) + 2 > 1024.  The host-buffer
+ * form's arrays — B*S*(5*N + 14) doubles with every output — fit the arena reserved at create for every B*S <= max_batch. */
+#define CILQR_MAP_CLEARANCE_FIELDS 8
+typedef enum cilqr_map_clearance_field {
+  CILQR_MC_CLEARANCE = 0,     /* min clearance over t; +HUGE_VAL when no step has a seed within reach; -HUGE_VAL with a lost step */
+  CILQR_MC_STEP = 1,          /* its step, lowest on equal values; -1 */
+  CILQR_MC_CELL = 2,          /* i + j*rows of it within that step, lowest on equal values; -1 */
+  CILQR_MC_BELOW_STEPS = 3,   /* steps with clearance < min_clearance */
+  CILQR_MC_FIRST_BELOW = 4,   /* lowest such t; -1 */
+  CILQR_MC_TOUCH_STEPS = 5,   /* steps with clearance <= 0 */
+  CILQR_MC_OFF_MAP_STEPS = 6, /* steps whose window leaves the map */
+  CILQR_MC_LOST_STEPS = 7     /* lost steps */
+} cilqr_map_clearance_field;
+#define CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS 1u /* flags: in-map NaN cells are seeds */
+int cilqr_map_clearance_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, double margin, double occ_threshold,
+                               double reach, double min_clearance, uint32_t flags, const double* base, double* mc,
+                               double* step_clearance, double* total);
+int cilqr_map_clearance(cilqr_handle* h, int B, int N, int S, const double* X, double margin, double occ_threshold, double reach,
+                        double min_clearance, uint32_t flags, const double* base, double* mc, double* step_clearance, double* total);
+
 /* setGeometry(Length(lx,ly), res, Position(px,py)) size/length rule (G/grid_map_core/src/GridMap.cpp:45-62). */
 int cilqr_map_geom_set(cilqr_map_geom* g, double len_x, double len_y, double res, double pos_x, double pos_y);
 

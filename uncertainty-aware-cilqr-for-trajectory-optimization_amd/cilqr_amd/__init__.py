@@ -65,6 +65,13 @@ FOOTPRINT_FIELDS = 12
 (FP_CLEARANCE, FP_CLEARANCE_ENTRY, FP_HIT_STEPS, FP_FIRST_HIT, FP_MAP_OCC, FP_MAP_OCC_STEP, FP_MAP_OCC_CELL, FP_MAP_HIT_STEPS,
  FP_MAP_FIRST_HIT, FP_MAP_HIT_CELLS, FP_MAP_UNKNOWN_STEPS, FP_MAP_CELLS) = range(FOOTPRINT_FIELDS)
 FOOTPRINT_UNKNOWN_HITS, FOOTPRINT_SKIP_MAP = 1, 2  # flags of `footprint_check`
+MAP_DISTANCE_UNKNOWN_SEEDS, MAP_DISTANCE_TO_FREE = 1, 2  # flags of `map_distance`
+MAP_DISTANCE_NONE = 2 ** 31 - 1  # d2 of a layer without a seed
+# `cilqr_map_clearance_field`: the columns of a map clearance row (`Solver.map_clearance`)
+MAP_CLEARANCE_FIELDS = 8
+(MC_CLEARANCE, MC_STEP, MC_CELL, MC_BELOW_STEPS, MC_FIRST_BELOW, MC_TOUCH_STEPS, MC_OFF_MAP_STEPS,
+ MC_LOST_STEPS) = range(MAP_CLEARANCE_FIELDS)
+MAP_CLEARANCE_UNKNOWN_SEEDS = 1  # flags of `map_clearance`
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -93,6 +100,8 @@ ABI_SYMBOLS = (
     "cilqr_chance_risk_sampled", "cilqr_chance_risk_sampled_device",
     "cilqr_predict_obstacles", "cilqr_predict_obstacles_device", "cilqr_chance_risk_cov", "cilqr_chance_risk_cov_device",
     "cilqr_footprint_check", "cilqr_footprint_check_device",
+    "cilqr_map_distance", "cilqr_map_distance_device", "cilqr_inflate_map", "cilqr_inflate_map_device",
+    "cilqr_map_clearance", "cilqr_map_clearance_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -1011,6 +1020,95 @@ class Solver:
                                                   C.byref(obs) if M else None, C.c_double(margin), C.c_double(min_clearance),
                                                   C.c_double(occ_threshold), C.c_uint32(int(flags)), _vp(base), _vp(fp),
                                                   _vp(step_clearance), _vp(step_occ), _vp(total)))
+
+    # ---- distance to the occupied cells of a layer: exact field, inflation, clearance of the ego rectangle ----
+    @staticmethod
+    def _layers(layers, geom):
+        """(rows, cols) or (L, rows, cols) float32 -> (flat (L, rows*cols) column-major per layer, L)."""
+        a = np.asarray(layers, dtype=np.float32)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != (geom.rows, geom.cols):
+            raise CilqrError("layers %s are not (L, %d, %d)" % (a.shape, geom.rows, geom.cols))
+        return np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(a.shape[0], -1), int(a.shape[0])
+
+    def map_distance(self, layers, geom, occ_threshold, unknown_seeds=False, to_free=False, L=None, want_dist=True):
+        """`cilqr_map_distance`: layers (rows, cols) or (L, rows, cols) float32; one (rows, cols) layer with L given: the shared layer
+        (layer_stride 0), its result written L times.  Returns dict(d2 (L, rows, cols) int32 — MAP_DISTANCE_NONE where the layer has
+        no seed — and dist (L, rows, cols) float32 in metres, None with want_dist=False).  The layers travel through the device
+        arena: large maps and batches take the device form."""
+        flat, n = self._layers(layers, geom)
+        stride = flat.shape[1]
+        if L is not None:
+            if n != 1:
+                raise CilqrError("map_distance: L is given for ONE shared layer, not %d" % n)
+            n, stride = int(L), 0
+        d2 = np.zeros((n, flat.shape[1]), dtype=np.int32)
+        dist = np.zeros((n, flat.shape[1]), dtype=np.float32) if want_dist else None
+        flags = (MAP_DISTANCE_UNKNOWN_SEEDS if unknown_seeds else 0) | (MAP_DISTANCE_TO_FREE if to_free else 0)
+        _check(lib().cilqr_map_distance(self._h, n, _p(flat, _fp), C.c_int64(stride), C.byref(geom), C.c_double(occ_threshold),
+                                        C.c_uint32(flags), _p(d2, _ip), _p(dist, _fp)))
+        shape = lambda a: None if a is None else a.reshape(n, geom.cols, geom.rows).transpose(0, 2, 1)
+        return dict(d2=shape(d2), dist=shape(dist))
+
+    def map_distance_device(self, stream, L, layer, layer_stride, geom, occ_threshold, d2_out, dist_out=0, flags=0):
+        """`cilqr_map_distance_device`: device addresses; d2_out (L, rows*cols) int32, dist_out (L, rows*cols) float32 or 0."""
+        _check(lib().cilqr_map_distance_device(self._h, _vp(stream), int(L), _vp(layer), C.c_int64(int(layer_stride)), C.byref(geom),
+                                               C.c_double(occ_threshold), C.c_uint32(int(flags)), _vp(d2_out), _vp(dist_out)))
+
+    def inflate_map(self, layers, geom, d2, inscribed, radius, peak=100.0, L=None):
+        """`cilqr_inflate_map`: layers as `map_distance` takes them, d2 (L, rows, cols) int32 as it returns it.  Returns the inflated
+        layers (L, rows, cols) float32."""
+        flat, n = self._layers(layers, geom)
+        stride = flat.shape[1]
+        if L is not None:
+            if n != 1:
+                raise CilqrError("inflate_map: L is given for ONE shared layer, not %d" % n)
+            n, stride = int(L), 0
+        d2 = np.asarray(d2, dtype=np.int32)
+        if d2.ndim == 2:
+            d2 = d2[None]
+        if d2.shape != (n, geom.rows, geom.cols):
+            raise CilqrError("inflate_map: d2 %s is not (%d, %d, %d)" % (d2.shape, n, geom.rows, geom.cols))
+        d2 = np.ascontiguousarray(d2.transpose(0, 2, 1)).reshape(n, -1)
+        out = np.zeros((n, flat.shape[1]), dtype=np.float32)
+        _check(lib().cilqr_inflate_map(self._h, n, _p(flat, _fp), C.c_int64(stride), C.byref(geom), _p(d2, _ip), C.c_double(inscribed),
+                                       C.c_double(radius), C.c_double(peak), _p(out, _fp)))
+        return out.reshape(n, geom.cols, geom.rows).transpose(0, 2, 1)
+
+    def inflate_map_device(self, stream, L, layer, layer_stride, geom, d2, inscribed, radius, peak, layer_out):
+        """`cilqr_inflate_map_device`: device addresses; layer_out (L, rows*cols) float32 feeds `set_uncertainty_map_device` with
+        layer_stride = rows*cols."""
+        _check(lib().cilqr_inflate_map_device(self._h, _vp(stream), int(L), _vp(layer), C.c_int64(int(layer_stride)), C.byref(geom),
+                                              _vp(d2), C.c_double(inscribed), C.c_double(radius), C.c_double(peak), _vp(layer_out)))
+
+    def map_clearance(self, N, X, reach, S=1, margin=0.0, occ_threshold=float("inf"), min_clearance=0.0, base=None,
+                      unknown_seeds=False, steps=True):
+        """`cilqr_map_clearance`: X (B*S, 4(N+1)) rows, row r of solve r // S, against the map set by `set_uncertainty_map(_device)`.
+        Returns dict(mc (B*S, MAP_CLEARANCE_FIELDS), step_clearance (B*S, N) — None with steps=False — and total (B*S,), None
+        without base)."""
+        X = _np64(X)
+        R = X.size // (4 * (N + 1))
+        X = X.reshape(R, 4 * (N + 1))
+        S = int(S)
+        if S < 1 or R % S:
+            raise CilqrError("map_clearance: %d rows are no multiple of S = %d" % (R, S))
+        base = None if base is None else _np64(base).reshape(R)
+        mc = np.zeros((R, MAP_CLEARANCE_FIELDS))
+        step_clearance = np.zeros((R, N)) if steps else None
+        total = None if base is None else np.zeros(R)
+        _check(lib().cilqr_map_clearance(self._h, R // S, int(N), S, _p(X), C.c_double(margin), C.c_double(occ_threshold),
+                                         C.c_double(reach), C.c_double(min_clearance),
+                                         C.c_uint32(MAP_CLEARANCE_UNKNOWN_SEEDS if unknown_seeds else 0), _p(base), _p(mc),
+                                         _p(step_clearance), _p(total)))
+        return dict(mc=mc, step_clearance=step_clearance, total=total)
+
+    def map_clearance_device(self, stream, B, N, S, X, mc, reach, margin=0.0, occ_threshold=float("inf"), min_clearance=0.0, flags=0,
+                             base=0, step_clearance=0, total=0):
+        """`cilqr_map_clearance_device`: device addresses; the map is the one set by `set_uncertainty_map(_device)`."""
+        _check(lib().cilqr_map_clearance_device(self._h, _vp(stream), int(B), int(N), int(S), _vp(X), C.c_double(margin),
+                                                C.c_double(occ_threshold), C.c_double(reach), C.c_double(min_clearance),
+                                                C.c_uint32(int(flags)), _vp(base), _vp(mc), _vp(step_clearance), _vp(total)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

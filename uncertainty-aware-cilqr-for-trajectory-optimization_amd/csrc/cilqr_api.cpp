@@ -1677,6 +1677,170 @@ int cilqr_footprint_check(cilqr_handle* h, int B, int N, int M, int S, const dou
   });
 }
 
+// ---- distance to the occupied cells of a layer: exact field and inflation (costmap_distance.hip) -------------------------------------------
+namespace {
+// what needs no handle: L, the geometry and the stride of cilqr_map_distance and cilqr_inflate_map; *cells and *span (floats the
+// layers' stride addresses) on success
+int map_layers_check(const char* name, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, size_t* cells, size_t* span) {
+  if (!layer || !g) return fail(CILQR_ERR_ARG, "%s: null layer or geometry", name);
+  if (L < 1) return fail(CILQR_ERR_ARG, "%s: L = %d, must be at least 1", name, L);
+  if (g->rows < 1 || g->cols < 1 || !(g->res > 0.0 && g->res <= 1.7e308)) return fail(CILQR_ERR_ARG, "%s: bad geometry", name);
+  if (g->rows > cilqr::MAP_DISTANCE_MAX_SIDE || g->cols > cilqr::MAP_DISTANCE_MAX_SIDE)
+    return fail(CILQR_ERR_UNSUPPORTED, "%s: %d x %d cells, more than %d along a side", name, g->rows, g->cols, cilqr::MAP_DISTANCE_MAX_SIDE);
+  const int64_t n = (int64_t)g->rows * g->cols;
+  if (layer_stride < 0 || (layer_stride > 0 && layer_stride < n)) return fail(CILQR_ERR_ARG, "%s: layer_stride smaller than one layer", name);
+  if (layer_stride > ((int64_t)1 << 40)) return fail(CILQR_ERR_ARG, "%s: layer_stride beyond 2^40", name);
+  const int64_t tiles = (n + cilqr::MAP_DISTANCE_THREADS - 1) / cilqr::MAP_DISTANCE_THREADS;
+  if ((int64_t)L * (tiles > g->cols ? tiles : g->cols) > 0x7fffffff) return fail(CILQR_ERR_ARG, "%s: L = %d layers beyond 2^31 - 1 workgroups", name, L);
+  *cells = (size_t)n;
+  *span = (size_t)((int64_t)(L - 1) * layer_stride + n);
+  return CILQR_OK;
+}
+int map_distance_args_check(int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, double occ_threshold, uint32_t flags,
+                            const int32_t* d2_out, size_t* cells, size_t* span) {
+  if (!d2_out) return fail(CILQR_ERR_ARG, "cilqr_map_distance: null d2_out");
+  int rc = map_layers_check("cilqr_map_distance", L, layer, layer_stride, g, cells, span);
+  if (rc) return rc;
+  if (occ_threshold != occ_threshold) return fail(CILQR_ERR_ARG, "cilqr_map_distance: occ_threshold is NaN");
+  if (flags & ~(CILQR_MAP_DISTANCE_UNKNOWN_SEEDS | CILQR_MAP_DISTANCE_TO_FREE)) return fail(CILQR_ERR_ARG, "cilqr_map_distance: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int inflate_map_args_check(int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* d2, double inscribed,
+                           double radius, double peak, const float* layer_out, size_t* cells, size_t* span) {
+  if (!d2 || !layer_out) return fail(CILQR_ERR_ARG, "cilqr_inflate_map: null d2 or layer_out");
+  int rc = map_layers_check("cilqr_inflate_map", L, layer, layer_stride, g, cells, span);
+  if (rc) return rc;
+  if (!(inscribed >= 0.0 && radius <= 1.7e308 && inscribed < radius)) return fail(CILQR_ERR_ARG, "cilqr_inflate_map: needs 0 <= inscribed < radius, both finite");
+  if (!(peak > 0.0 && peak <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_inflate_map: peak is not finite and > 0");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_map_distance_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                              double occ_threshold, uint32_t flags, int32_t* d2_out, float* dist_out) {
+  size_t cells = 0, span = 0;
+  int rc = map_distance_args_check(L, layer, layer_stride, g, occ_threshold, flags, d2_out, &cells, &span);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::MapDistanceArgs a = {};
+  a.layer = layer; a.layer_stride = layer_stride; a.d2_out = d2_out; a.dist_out = dist_out;
+  a.occ_threshold = occ_threshold; a.res = g->res;
+  a.L = L; a.rows = g->rows; a.cols = g->cols; a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_map_distance(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_map_distance(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, double occ_threshold,
+                       uint32_t flags, int32_t* d2_out, float* dist_out) {
+  size_t cells = 0, span = 0;
+  int rc = map_distance_args_check(L, layer, layer_stride, g, occ_threshold, flags, d2_out, &cells, &span);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_map_distance(p, L, cells, span, layer, d2_out, dist_out);
+  return cilqr::host_call(h, p, [&] { return cilqr_map_distance_device(h, h->stream, L, layer, layer_stride, g, occ_threshold, flags, d2_out, dist_out); });
+}
+
+int cilqr_inflate_map_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                             const int32_t* d2, double inscribed, double radius, double peak, float* layer_out) {
+  size_t cells = 0, span = 0;
+  int rc = inflate_map_args_check(L, layer, layer_stride, g, d2, inscribed, radius, peak, layer_out, &cells, &span);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  // lane = cell reads its own cell and writes it: in place is fine where layer l of the output IS layer l of the input
+  const bool same = layer_out == layer && (L == 1 || (size_t)layer_stride == cells);
+  if (!same && layer_out < layer + span && layer < layer_out + (size_t)L * cells)
+    return fail(CILQR_ERR_ARG, "cilqr_inflate_map: layer_out overlaps layer without being the same layers");
+  cilqr::InflateMapArgs a = {};
+  a.layer = layer; a.layer_stride = layer_stride; a.d2 = d2; a.layer_out = layer_out;
+  a.res = g->res; a.inscribed = inscribed; a.radius = radius; a.peak = peak;
+  a.L = L; a.rows = g->rows; a.cols = g->cols;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_inflate_map(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_inflate_map(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* d2,
+                      double inscribed, double radius, double peak, float* layer_out) {
+  size_t cells = 0, span = 0;
+  int rc = inflate_map_args_check(L, layer, layer_stride, g, d2, inscribed, radius, peak, layer_out, &cells, &span);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_inflate_map(p, L, cells, span, layer, d2, layer_out);
+  return cilqr::host_call(h, p, [&] { return cilqr_inflate_map_device(h, h->stream, L, layer, layer_stride, g, d2, inscribed, radius, peak, layer_out); });
+}
+
+// ---- exact clearance of the ego rectangle to the occupied cells of the map (cilqr_map_clearance.hip) ---------------------------------------
+namespace {
+// what needs no handle
+int map_clearance_args_check(int S, const double* X, double margin, double occ_threshold, double reach, double min_clearance, uint32_t flags,
+                             const double* base, const double* mc, const double* total) {
+  if (!X || !mc) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: null required pointer");
+  if (total && !base) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: total needs base");
+  if (S < 1) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: S = %d, must be at least 1", S);
+  if (!(margin >= 0.0 && margin <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: margin is negative or not finite");
+  if (!(reach >= 0.0 && reach <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: reach is negative or not finite");
+  if (min_clearance != min_clearance || occ_threshold != occ_threshold)
+    return fail(CILQR_ERR_ARG, "cilqr_map_clearance: min_clearance or occ_threshold is NaN");
+  if (flags & ~CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+int map_clearance_handle_check(const cilqr_handle* h, int B, int N, int S, double margin, double reach) {
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (B < 0 || (int64_t)B * S > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: B*S = %lld outside [0,%d]", (long long)B * S, h->max_batch);
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  if (!h->unc.layer) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: no uncertainty map is set on the handle");
+  if ((int64_t)h->unc.rows * h->unc.cols > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_map_clearance: the map has 2^31 cells or more");
+  const double hl = 0.5 * h->params.length + margin, hw = 0.5 * h->params.width + margin;
+  if (!(ceil(2.0 * (hypot(hl, hw) + reach) / h->unc_res) + 2.0 <= 1024.0))
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_map_clearance: the search window spans more than 1024 cells of %g m", h->unc_res);
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_map_clearance_device(cilqr_handle* h, void* stream, int B, int N, int S, const double* X, double margin, double occ_threshold,
+                               double reach, double min_clearance, uint32_t flags, const double* base, double* mc,
+                               double* step_clearance, double* total) {
+  int rc = map_clearance_args_check(S, X, margin, occ_threshold, reach, min_clearance, flags, base, mc, total);
+  if (rc) return rc;
+  rc = map_clearance_handle_check(h, B, N, S, margin, reach);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::MapClearanceArgs a = {};
+  a.s = handle_args(h, B, N, 0, 0);
+  a.X = X;
+  a.hl = 0.5 * h->params.length + margin; a.hw = 0.5 * h->params.width + margin;
+  a.reach = reach; a.min_clearance = min_clearance; a.occ_threshold = occ_threshold; a.res = h->unc_res;
+  a.base = base; a.mc = mc; a.total = total;
+  a.rows = B * S; a.S = S; a.flags = flags;
+  // the footprint check's region, reserved at create: max_batch·max_horizon step records, then stand-in step clearances
+  const size_t slab = (size_t)h->max_batch * h->max_horizon;
+  a.steps = h->d_footprint_steps;
+  a.step_clearance = step_clearance ? step_clearance : a.steps + slab * cilqr::MAP_CLEARANCE_STEP_REC;
+  if ((int64_t)a.rows * ((N + cilqr::FOOTPRINT_WAVES - 1) / cilqr::FOOTPRINT_WAVES) > 0x7fffffff)
+    return fail(CILQR_ERR_ARG, "cilqr_map_clearance: B * S * ceil(N / 4) workgroups beyond 2^31 - 1");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_map_clearance(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_map_clearance(cilqr_handle* h, int B, int N, int S, const double* X, double margin, double occ_threshold, double reach,
+                        double min_clearance, uint32_t flags, const double* base, double* mc, double* step_clearance, double* total) {
+  int rc = map_clearance_args_check(S, X, margin, occ_threshold, reach, min_clearance, flags, base, mc, total);
+  if (rc) return rc;
+  rc = map_clearance_handle_check(h, B, N, S, margin, reach);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_map_clearance(p, (size_t)B * S, N, X, base, mc, step_clearance, total);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_map_clearance_device(h, h->stream, B, N, S, X, margin, occ_threshold, reach, min_clearance, flags, base, mc, step_clearance, total);
+  });
+}
+
 // ---- analytic chance risk against sampled obstacles in compact form (cilqr_chance_sampled.hip) ----------------------------------------
 namespace {
 // what needs no handle

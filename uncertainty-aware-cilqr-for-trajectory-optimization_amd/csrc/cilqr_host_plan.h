@@ -365,6 +365,35 @@ inline void plan_footprint(HostPlan& p, size_t R, size_t N, size_t M, const doub
   p.out(total, R);
 }
 
+// cilqr_map_distance: 3 arrays of 4 bytes a cell: the layers' span in, d2_out and dist_out out.  The arena is sized by the solves,
+// not by maps: the call fits where (span + 2·L·cells)/2 doubles do — the node's 150 x 100 map with both outputs takes 22 500 doubles
+// a layer against the 28·N + 6·M·N + M + 50 per unit of max_batch that host_arena_bytes reserves below — and returns the transport's
+// error where it does not.
+inline void plan_map_distance(HostPlan& p, size_t L, size_t cells, size_t span, const float*& layer, int32_t*& d2_out, float*& dist_out) {
+  p.in(layer, span);
+  p.out(d2_out, L * cells);
+  p.out(dist_out, L * cells);
+}
+
+// cilqr_inflate_map: 3 arrays of 4 bytes a cell: the layers' span and d2 in, layer_out out; fits as plan_map_distance does.
+inline void plan_inflate_map(HostPlan& p, size_t L, size_t cells, size_t span, const float*& layer, const int32_t*& d2, float*& layer_out) {
+  p.in(layer, span);
+  p.in(d2, L * cells);
+  p.out(layer_out, L * cells);
+}
+
+// cilqr_map_clearance: 5 arrays; R = B·S rows; the map is the handle's.  Per row 5·N + 14 doubles with every output — X, base, the mc
+// row, step_clearance, total — against the 28·N + 50 per unit of max_batch that host_arena_bytes reserves below: every R <= max_batch
+// fits, and the 5 roundings stay within its 32 x 16 bytes.
+inline void plan_map_clearance(HostPlan& p, size_t R, size_t N, const double*& X, const double*& base, double*& mc, double*& step_clearance,
+                               double*& total) {
+  p.in(X, R * 4 * (N + 1));
+  p.in(base, R);
+  p.out(mc, R * CILQR_MAP_CLEARANCE_FIELDS);
+  p.out(step_clearance, R * N);
+  p.out(total, R);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

@@ -396,6 +396,54 @@ inline size_t footprint_scratch_doubles(size_t max_batch, size_t max_horizon) {
   return max_batch * max_horizon * (FOOTPRINT_STEP_REC + 1) + max_batch * FOOTPRINT_ROW_REC;
 }
 
+// Distance to the occupied cells of a layer (costmap_distance.hip; cilqr_map_distance*, cilqr_inflate_map*).  Two launches for the
+// field — lane = row, walking the columns; then one workgroup per (layer, column) with the column in LDS — and one, lane = cell,
+// for the inflated layer.  Layers are `layer_stride` floats apart (0: one shared layer); outputs are dense, rows·cols apart.
+constexpr int MAP_DISTANCE_THREADS = 256;
+constexpr int MAP_DISTANCE_MAX_SIDE = 8192;  // rows, cols at most: d2 <= 2·8192² < 2^31, and a column of int32 is 32 KiB of LDS
+struct MapDistanceArgs {
+  const float* layer;
+  long long layer_stride;
+  int32_t* d2_out;   // [L][rows·cols]
+  float* dist_out;   // [L][rows·cols] or null
+  double occ_threshold, res;
+  int32_t L, rows, cols;
+  uint32_t flags;    // CILQR_MAP_DISTANCE_*
+};
+hipError_t launch_map_distance(const MapDistanceArgs& a, hipStream_t stream);
+struct InflateMapArgs {
+  const float* layer;
+  long long layer_stride;
+  const int32_t* d2;  // [L][rows·cols]
+  float* layer_out;   // [L][rows·cols]
+  double res, inscribed, radius, peak;
+  int32_t L, rows, cols;
+};
+hipError_t launch_inflate_map(const InflateMapArgs& a, hipStream_t stream);
+
+// Exact clearance of the ego rectangle to the occupied cells of the map set on the handle (cilqr_map_clearance.hip;
+// cilqr_map_clearance*).  Two launches: wavefront = (row, step), FOOTPRINT_WAVES steps per workgroup, lanes over the cells of the
+// window; then one wavefront per row for the fold.  `s` carries B (SOLVES), N and unc; row r = b·S + s reads X at r and the layer and
+// pose of solve b.  `steps`: the handle's footprint region (footprint_scratch_doubles), here one record of MAP_CLEARANCE_STEP_REC
+// doubles per (row, step) and, behind max_batch·max_horizon of them, rows·N doubles that stand in for a step_clearance the caller
+// did not ask for.
+constexpr int MAP_CLEARANCE_STEP_REC = 2;  // the step's nearest cell (-1: none), window leaves the map | lost << 1
+struct MapClearanceArgs {
+  SolveArgs s;
+  const double* X;         // [rows][4(N + 1)]
+  double hl, hw;           // half-extents of the ego rectangle, the margin included
+  double reach, min_clearance, occ_threshold;
+  double res;              // the map's resolution as it was set
+  const double* base;      // [rows] or null (then total is null)
+  double* mc;              // [rows][CILQR_MAP_CLEARANCE_FIELDS]
+  double* step_clearance;  // [rows][N]: the caller's, or the handle's
+  double* total;           // [rows] or null
+  double* steps;
+  int32_t rows, S;
+  uint32_t flags;          // CILQR_MAP_CLEARANCE_*
+};
+hipError_t launch_map_clearance(const MapClearanceArgs& a, hipStream_t stream);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

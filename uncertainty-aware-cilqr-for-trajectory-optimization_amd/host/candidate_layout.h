@@ -25,6 +25,7 @@ struct CandidateModes {
   bool track_map = false;      // set_track_map with rounds > 0
   bool min_total = false;      // set_candidate_pick(MinTotalCost)
   bool footprint = false;      // set_footprint_check
+  bool map_clearance = false;  // set_map_clearance_check
   // the scene at the time of the run: no setter reserves by these, so the layout never reads them
   bool map_set = false;        // an uncertainty map is set
   bool obstacles = false;      // M > 0
@@ -37,11 +38,11 @@ struct CandidateModes {
   bool cmap_arrays() const { return chance_inputs() && cmap; }    // the nodes and the map covariance check's outputs
   bool sigma_kept() const { return cmap_arrays() || scov; }       // every Sigma_t of the chance call
   bool chain() const { return tighten || map_tighten; }           // the rounds' gains and covariance chain
-  bool block_used() const { return noise || cov || scov || chain() || track_map || footprint; }  // a setter that is on keeps the block reserved
+  bool block_used() const { return noise || cov || scov || chain() || track_map || footprint || map_clearance; }  // a setter that is on keeps the block reserved
 
   // ---- which stages a run enqueues --------------------------------------------------------------------------------------------
   bool track_rounds() const { return track_map && tracks && map_set; }
-  bool in_block() const { return noise || cov || scov || tighten || map_tighten || track_rounds() || footprint; }  // else: the host-buffer forms
+  bool in_block() const { return noise || cov || scov || tighten || map_tighten || track_rounds() || footprint || map_clearance_check(); }  // else: the host-buffer forms
   bool plain() const { return !noise && !cov && !scov; }  // no check behind the solve: the pick of run_candidates itself
   bool sampled_solve() const { return sampled; }
   bool obstacle_rounds() const { return tighten && obstacles; }
@@ -58,7 +59,8 @@ struct CandidateModes {
   bool chance_sampled() const { return scov; }
   bool map_covariance() const { return cmap && map_set && chance(); }
   bool map_rollout_risk() const { return map && map_set && (fused_check() || cov); }
-  bool footprint_check() const { return footprint; }  // the last check in front of the pick, whatever else is in force
+  bool footprint_check() const { return footprint; }  // the last check but one in front of the pick, whatever else is in force
+  bool map_clearance_check() const { return map_clearance && map_set; }  // behind it: the last stage in front of the pick, while a map is set
 };
 
 struct CandidateSizes {
@@ -78,7 +80,7 @@ struct CandidateSizes {
   F(x0) F(U) F(poly) F(fl) F(pose) F(dim) F(soff) F(X) F(J) F(iters) F(status) F(k) F(K) F(ok) F(delta) F(Xr) F(Ur) F(rows) F(risk) \
   F(total) F(pair) F(score) F(base) F(hits) F(mrisk) F(mtotal) F(mhits) F(munk) F(s0) F(W) F(crisk) F(cstep) F(ccov) F(csig) F(qn)  \
   F(qw) F(cmrisk) F(cmstep) F(cmtotal) F(ts0) F(tW) F(tsig) F(trisk) F(tpose) F(tdim) F(tg) F(tcov) F(tmg) F(tkcov) F(tkf) F(srisk) \
-  F(stotal) F(fprow) F(fpstep) F(fptotal)
+  F(stotal) F(mcrow) F(mcstep) F(mctotal) F(fprow) F(fpstep) F(fptotal)
 
 struct CandidateLayout {  // offsets in doubles (from candidate_layout) or sizes in doubles (from candidate_sizes)
 #define F(name) size_t name = 0;
@@ -119,6 +121,9 @@ inline CandidateLayout candidate_sizes(const CandidateModes& m, const CandidateS
   s.tkcov = trk * M * N * 3; s.tkf = trk * B * CILQR_TRACK_MAP_FIELDS;
   // the sample covariance check's rows and total
   s.srisk = m.scov ? B * CILQR_CRS_FIELDS : 0; s.stotal = m.scov ? B : 0;
+  // the map clearance check's rows, its per-step clearances and its total: empty with the flag off, so that every offset is what it was
+  // (in FRONT of the footprint check's, which tests/test_footprint.py pins as the last three)
+  s.mcrow = m.map_clearance ? B * CILQR_MAP_CLEARANCE_FIELDS : 0; s.mcstep = m.map_clearance ? B * N : 0; s.mctotal = m.map_clearance ? B : 0;
   // the footprint check's rows, its per-step clearances and its total: at the END, so that every earlier offset is what it was
   s.fprow = m.footprint ? B * CILQR_FOOTPRINT_FIELDS : 0; s.fpstep = m.footprint ? B * N : 0; s.fptotal = m.footprint ? B : 0;
   return s;

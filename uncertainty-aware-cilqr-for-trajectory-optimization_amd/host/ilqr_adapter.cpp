@@ -351,6 +351,7 @@ CandidateModes iLQR::modes() const {
   m.tighten = tighten_; m.map_tighten = map_tighten_; m.track_map = tm_rounds_ > 0;
   m.min_total = pick_ == CandidatePick::MinTotalCost;
   m.footprint = fp_check_;
+  m.map_clearance = mc_check_;
   m.map_set = map_set_; m.obstacles = !obstacles_.empty(); m.tracks = tracked_horizon_ >= 0;
   return m;
 }
@@ -379,6 +380,7 @@ void iLQR::clear_candidate_fields() {
   last_chance_map_risk.clear(); last_map_step_risk.clear();
   last_chance_risk_sampled.clear();
   last_footprint.clear(); last_footprint_clearance.clear();
+  last_map_clearance.clear(); last_map_step_clearance.clear();
 }
 
 // The prologue of every run_candidates: LocalPlanner pre-step for all candidates in one device launch (cilqr_local_plan_batch)
@@ -578,6 +580,21 @@ void iLQR::set_footprint_check(double min_clearance, double occ_threshold, doubl
   fp_unknown_hits_ = unknown_hits;
   last_footprint.clear();
   last_footprint_clearance.clear();
+  reserve_block_if_used();  // (the device block holds the check's rows while it is on)
+}
+
+void iLQR::set_map_clearance_check(double min_clearance, double reach, double occ_threshold, double margin, bool unknown_seeds, bool on) {
+  if (on && (min_clearance != min_clearance || occ_threshold != occ_threshold)) throw std::runtime_error("set_map_clearance_check: min_clearance or occ_threshold is NaN");
+  if (on && !(reach >= 0.0 && reach <= 1.7e308)) throw std::runtime_error("set_map_clearance_check: reach is negative or not finite");
+  if (on && !(margin >= 0.0 && margin <= 1.7e308)) throw std::runtime_error("set_map_clearance_check: margin is negative or not finite");
+  mc_check_ = on;
+  mc_min_clearance_ = min_clearance;
+  mc_reach_ = reach;
+  mc_threshold_ = occ_threshold;
+  mc_margin_ = margin;
+  mc_unknown_seeds_ = unknown_seeds;
+  last_map_clearance.clear();
+  last_map_step_clearance.clear();
   reserve_block_if_used();  // (the device block holds the check's rows while it is on)
 }
 
@@ -848,11 +865,16 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
     return cilqr_footprint_check_device(h_, d.st, B, N, M, 1, d + L.X, po, fp_margin_, fp_min_clearance_, fp_threshold_,
                                         fp_unknown_hits_ ? CILQR_FOOTPRINT_UNKNOWN_HITS : 0u, base, d + L.fprow, d + L.fpstep, nullptr, total);
   });
+  // behind it, while a map is set: how far the rectangle stays from the ORIGINAL map's occupied cells (the map half of min_clearance)
+  stage(m.map_clearance_check(), L.mctotal, [&](const double* base, double* total) {
+    return cilqr_map_clearance_device(h_, d.st, B, N, 1, d + L.X, mc_margin_, mc_threshold_, mc_reach_, mc_min_clearance_,
+                                      mc_unknown_seeds_ ? CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS : 0u, base, d + L.mcrow, d + L.mcstep, total);
+  });
   step(true, [&] { return cilqr_argmin_device(h_, d.st, B, d + total_at, d + L.pair); });
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(d.st);
-    throw std::runtime_error((m.scov ? "run_candidates (sample covariance check): " : m.plain() && !m.rounds() ? "run_candidates (footprint check): " : m.plain() ? "run_candidates (chance tightening): "
+    throw std::runtime_error((m.scov ? "run_candidates (sample covariance check): " : m.plain() && !m.rounds() ? (m.footprint ? "run_candidates (footprint check): " : "run_candidates (map clearance check): ") : m.plain() ? "run_candidates (chance tightening): "
                                                                                                  : "run_candidates (pose-noise check): ") + msg);
   }
   // every last_* vector is reset here; the stages that ran fill theirs
@@ -881,6 +903,10 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
   if (m.footprint_check()) {
     d.fetch(last_footprint, L.fprow, (size_t)B * CILQR_FOOTPRINT_FIELDS);
     d.fetch(last_footprint_clearance, L.fpstep, (size_t)B * N);
+  }
+  if (m.map_clearance_check()) {
+    d.fetch(last_map_clearance, L.mcrow, (size_t)B * CILQR_MAP_CLEARANCE_FIELDS);
+    d.fetch(last_map_step_clearance, L.mcstep, (size_t)B * N);
   }
   d.wait();
   if (m.rounds()) keep_tighten_risk(B, tg_rows);

@@ -148,6 +148,17 @@ class iLQR {
   // smallest clearance per step, horizon per candidate.  With set_obstacle_samples the run throws std::logic_error (the check has no
   // sampled form).  on = false switches it off (the default).
   void set_footprint_check(double min_clearance, double occ_threshold, double margin = 0.0, bool unknown_hits = false, bool on = true);
+  // Map clearance check: the map half of min_clearance.  The footprint check measures distance to obstacle rectangles only; against
+  // the map it knows overlap alone.  This check asks how far the vehicle's rectangle, grown by `margin`, stays from the nearest
+  // occupied cell (value > occ_threshold; unknown_seeds: NaN cells too) within `reach` metres (cilqr_map_clearance_device).  It runs
+  // while a map is set: run_candidates enqueues it as the LAST stage in front of cilqr_argmin_device, behind the footprint check when
+  // both are on, on the final plan against the ORIGINAL map; its base is the total before it, or J where no check ran, and a
+  // candidate that comes closer than min_clearance, or has a step that is not finite, is rejected (its total is NaN; -1 when all
+  // are).  It needs no other setter.  last_map_clearance holds CILQR_MAP_CLEARANCE_FIELDS per candidate (cilqr_map_clearance_field),
+  // last_map_step_clearance the clearance per step, horizon per candidate; both are empty when no map was set.  on = false switches
+  // it off (the default).
+  void set_map_clearance_check(double min_clearance, double reach, double occ_threshold, double margin = 0.0, bool unknown_seeds = false,
+                               bool on = true);
   // Pose-covariance check: the analytic counterpart of the fused pose-noise check.  Instead of S draws of the pose noise the node
   // hands over its covariance: Sigma0, 4 x 4 column-major over (x, y, v, theta) (only row <= column is read), and the process noise
   // W added per step (nullable: none).  run_candidates then enqueues, on the check's stream: solve -> (under MinTotalCost
@@ -303,6 +314,8 @@ class iLQR {
   std::vector<int32_t> last_map_step_hits, last_map_unknown_hits;  // horizon per candidate
   // run_candidates under set_footprint_check; empty otherwise
   std::vector<double> last_footprint, last_footprint_clearance;  // CILQR_FOOTPRINT_FIELDS per candidate; horizon per candidate
+  // run_candidates under set_map_clearance_check with a map set; empty otherwise
+  std::vector<double> last_map_clearance, last_map_step_clearance;  // CILQR_MAP_CLEARANCE_FIELDS per candidate; horizon per candidate
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
   // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
@@ -387,6 +400,9 @@ class iLQR {
   // footprint check (set_footprint_check)
   bool fp_check_ = false, fp_unknown_hits_ = false;
   double fp_min_clearance_ = 0.0, fp_threshold_ = 0.0, fp_margin_ = 0.0;
+  // map clearance check (set_map_clearance_check)
+  bool mc_check_ = false, mc_unknown_seeds_ = false;
+  double mc_min_clearance_ = 0.0, mc_reach_ = 0.0, mc_threshold_ = 0.0, mc_margin_ = 0.0;
   // map covariance check: in effect when cmap_check_ (set_map_covariance_check), map_set_ and a covariance check; the nodes as built
   bool cmap_check_ = false, cmap_sum_ = false, cmap_unknown_hits_ = false;
   double cmap_threshold_ = 0.0, cmap_max_risk_ = 1.0;
