@@ -1591,6 +1591,74 @@ int cilqr_map_clearance_device(cilqr_handle* h, void* stream, int B, int N, int 
 int cilqr_map_clearance(cilqr_handle* h, int B, int N, int S, const double* X, double margin, double occ_threshold, double reach,
                         double min_clearance, uint32_t flags, const double* base, double* mc, double* step_clearance, double* total);
 
+/* --- stop plans: a solved plan's geometry under a braking speed profile (new) ----------------------------------------------------------
+ * Every check above can only reject; when all candidates are rejected there is no plan.  This call produces the usual fallback: for
+ * each of B solved plans (X [B][4*(N+1)], U [B][2*N]) and each of D braking levels decel[l] > 0 (m/s^2) one row that follows the
+ * plan's own path while braking.  Row r = b*D + l is plan b at level l — the row order of X_roll — so cilqr_footprint_check and
+ * cilqr_map_clearance with S = D read X_stop as it lies, pair a row's step t with obstacle column t, and take `cost` as `base`.
+ * The call generates; it judges nothing beyond the three conditions of `cost`.  A row is as safe as those checks say, no more.
+ *
+ * Definitions (dt = timestep; fs = Model::forward_simulate, I/Model.cpp:17-30; P = (x, y) of a state).
+ *   path          the plan's monotone polyline: adv_t = max((P_{t+1} - P_t).(cos th_t, sin th_t), 0) for t < N; V_0 = P_0,
+ *                 V_{t+1} = V_t + adv_t (cos th_t, sin th_t); s_0 = 0, s_{t+1} = s_t + adv_t.  (The clamp: the model steps backwards by
+ *                 a*dt^2/2 when v = 0 and a < 0; such segments get length 0.)  The three running sums are formed on a tree fixed
+ *                 by N alone: element t = 0 ... N (element N adds nothing) belongs to chunk t / ceil((N+1)/64); a chunk is summed in
+ *                 order, the 64 chunk totals are scanned by doubling (offsets 1, 2, 4 ... 32), and a chunk's elements are then added
+ *                 in order onto the total before it; V_t = P_0 + the sum before element t.
+ *   Q(sigma)      for sigma < s_N: V_t + (sigma - s_t)(cos th_t, sin th_t) with t = max{t <= N-1 : s_t <= sigma} (a segment of length 0
+ *                 is never the one chosen).  For sigma >= s_N: V_N + (sigma - s_N)(cos th_N, sin th_N), the ray that continues the
+ *                 plan — an OVERRUN: the row travels farther than the plan did.
+ *   acceleration  x'_0 = X_0, sigma_0 = 0.  Step j < hold: the plan's own U_j, both components, stored unchanged.  Otherwise
+ *                 a'_j = -min(decel[l], v'_j/dt); on the step where decel[l] >= v'_j/dt, v'_{j+1} is exactly 0 (a stopping vehicle
+ *                 stops and does not reverse); where v'_j == 0, a'_j = w'_j = 0 and the state is held.
+ *   advance       adv'_j = v'_j*dt + a*dt^2/2 with a the model's clamp of a'_j: what fs moves the row by; sigma_{j+1} = sigma_j +
+ *                 max(adv'_j, 0).
+ *   yaw rate      steps j >= hold: pursuit of the path by arc length.  With P'_{j+1} the position fs gives and adv'_{j+1} the advance
+ *                 the NEXT step will make (its speed and acceleration are decided already), the heading wanted is the direction
+ *                 atan2 from P'_{j+1} to Q(sigma_{j+1} + adv'_{j+1}), and w'_j = wrap(wanted - th'_j)/dt with wrap(d) =
+ *                 d - 2 pi ceil((d - pi)/(2 pi)), into (-pi, pi].  Where adv'_{j+1} < CILQR_STOP_MIN_ADVANCE, and on the last step,
+ *                 w'_j = 0.  w'_j then takes the model's clamp, v'_j*tan(steer_angle_min)/wheelbase ... v'_j*tan(steer_angle_max)/
+ *                 wheelbase, and U_stop holds the clamped value.  With hold >= N the row's U is the plan's U bit for bit.
+ *   X_stop        exactly the chain of fs over U_stop from X_0 (up to the speed of the stopping step, which is 0, not its rounding).
+ * sp [B*D][CILQR_STOP_FIELDS] (required): see the enum; doubles that hold a value's bits, a count or an index.  A LOST row — any
+ * state or control of plan b is not finite, or a heading of the plan is 1e6 rad or more in magnitude (the range of the kernel's
+ * sincos) — has NaN in every element of its X_stop and U_stop rows and in its values, -1 for its indices, 0 for its counts and
+ * CILQR_SP_LOST = 1.  The same range holds for a row's OWN heading th'_j: only a start speed no vehicle has (the yaw clamp grows
+ * with v'_0) can carry it beyond 1e6 rad, and from there on the kernel takes cos th' = 1, sin th' = 0 without marking the row.
+ * cost [B*D] or NULL: decel_weight*decel[l] + (plan_cost ? plan_cost[b] : 0), or NaN where the row is lost, where CILQR_SP_DEVIATION >
+ * max_deviation (+HUGE_VAL disables this), or where the row is not at rest by step N-1 (CILQR_SP_STOP_STEP < 0 or > N-1: the footprint
+ * check visits steps 0 ... N-1, and a stop it never sees finished is not a verified stop; CILQR_STOP_ALLOW_MOVING drops this
+ * condition).  As `base` of cilqr_footprint_check it makes the gentlest clear row win cilqr_argmin_device.
+ *   Determinism: nothing is summed across rows or plans; a row's bits depend on plan b, level l, hold and the parameters alone,
+ * whatever B, D and the row's place in the batch.
+ * Mapping: a workgroup holds up to four plans and up to 64 rows; each of its four wavefronts forms the path of one plan in LDS, then
+ * lane = row runs the chain with two segment pointers that only move forward; rows leave through LDS as whole row segments.  One
+ * launch, no atomics, nothing allocated per call.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL X, U, decel, X_stop, U_stop or sp; D < 1; hold < 0; a NaN or negative
+ * max_deviation; a decel_weight that is not finite; unknown flag bits; in the host-buffer form a level that is not finite or not > 0.
+ * Then the cilqr_create limits (B*D <= max_batch, N <= max_horizon; every such N fits the kernel's LDS) and, in the host-buffer form, a level above -acc_min (the model
+ * would clamp it).  The device form cannot read decel on the host: there a row of a level outside (0, -acc_min] is lost.  The
+ * host-buffer form's arrays — at most B*D*(12*N + 19) doubles — fit the arena reserved at create for every B*D <= max_batch. */
+#define CILQR_STOP_FIELDS 8
+typedef enum cilqr_stop_field {
+  CILQR_SP_STOP_STEP = 0,      /* lowest j in 0 ... N with v'_j == 0; -1 when none */
+  CILQR_SP_DISTANCE = 1,       /* sigma_N */
+  CILQR_SP_END_SPEED = 2,      /* v'_N */
+  CILQR_SP_DEVIATION = 3,      /* max over j = 0 ... N of |P'_j - Q(sigma_j)| */
+  CILQR_SP_DEVIATION_STEP = 4, /* its step, lowest on equal values */
+  CILQR_SP_CLAMPED_STEPS = 5,  /* steps j >= hold whose yaw rate the model's clamp changed */
+  CILQR_SP_OVERRUN_STEPS = 6,  /* steps whose pursuit target lay at or beyond s_N */
+  CILQR_SP_LOST = 7            /* 1: a state or control of plan b (or the level, device form) is not usable */
+} cilqr_stop_field;
+#define CILQR_STOP_ALLOW_MOVING 1u    /* flags: a row still moving at step N-1 keeps its cost */
+#define CILQR_STOP_MIN_ADVANCE 1.0e-3 /* metres: below this advance of the next step the row does not steer */
+int cilqr_stop_plans_device(cilqr_handle* h, void* stream, int B, int N, int D, const double* X, const double* U, const double* decel,
+                            int hold, double max_deviation, const double* plan_cost, double decel_weight, uint32_t flags,
+                            double* X_stop, double* U_stop, double* sp, double* cost);
+int cilqr_stop_plans(cilqr_handle* h, int B, int N, int D, const double* X, const double* U, const double* decel, int hold,
+                     double max_deviation, const double* plan_cost, double decel_weight, uint32_t flags, double* X_stop, double* U_stop,
+                     double* sp, double* cost);
+
 /* setGeometry(Length(lx,ly), res, Position(px,py)) size/length rule (G/grid_map_core/src/GridMap.cpp:45-62). */
 int cilqr_map_geom_set(cilqr_map_geom* g, double len_x, double len_y, double res, double pos_x, double pos_y);
 

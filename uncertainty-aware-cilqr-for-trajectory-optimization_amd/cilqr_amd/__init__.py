@@ -72,6 +72,12 @@ MAP_CLEARANCE_FIELDS = 8
 (MC_CLEARANCE, MC_STEP, MC_CELL, MC_BELOW_STEPS, MC_FIRST_BELOW, MC_TOUCH_STEPS, MC_OFF_MAP_STEPS,
  MC_LOST_STEPS) = range(MAP_CLEARANCE_FIELDS)
 MAP_CLEARANCE_UNKNOWN_SEEDS = 1  # flags of `map_clearance`
+# `cilqr_stop_field`: the columns of a stop-plan row (`Solver.stop_plans`)
+STOP_FIELDS = 8
+(SP_STOP_STEP, SP_DISTANCE, SP_END_SPEED, SP_DEVIATION, SP_DEVIATION_STEP, SP_CLAMPED_STEPS, SP_OVERRUN_STEPS,
+ SP_LOST) = range(STOP_FIELDS)
+STOP_ALLOW_MOVING = 1  # flags of `stop_plans`: a row still moving at step N-1 keeps its cost
+STOP_MIN_ADVANCE = 1.0e-3  # metres: below this advance of the next step a row does not steer
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
@@ -102,6 +108,7 @@ ABI_SYMBOLS = (
     "cilqr_footprint_check", "cilqr_footprint_check_device",
     "cilqr_map_distance", "cilqr_map_distance_device", "cilqr_inflate_map", "cilqr_inflate_map_device",
     "cilqr_map_clearance", "cilqr_map_clearance_device",
+    "cilqr_stop_plans", "cilqr_stop_plans_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -1109,6 +1116,32 @@ class Solver:
         _check(lib().cilqr_map_clearance_device(self._h, _vp(stream), int(B), int(N), int(S), _vp(X), C.c_double(margin),
                                                 C.c_double(occ_threshold), C.c_double(reach), C.c_double(min_clearance),
                                                 C.c_uint32(int(flags)), _vp(base), _vp(mc), _vp(step_clearance), _vp(total)))
+
+    # ---- stop plans: a solved plan's path under a braking profile ----
+    def stop_plans(self, N, X, U, decel, hold=1, max_deviation=float("inf"), plan_cost=None, decel_weight=0.0, allow_moving=False,
+                   want_cost=True):
+        """`cilqr_stop_plans`: X (B, 4(N+1)), U (B, 2N) solved plans, decel (D,) braking levels in m/s^2.  Returns dict(X (B*D, 4(N+1)),
+        U (B*D, 2N), sp (B*D, STOP_FIELDS) and cost (B*D,), None with want_cost=False); row b*D + l is plan b at level l, the row
+        order `footprint_check` and `map_clearance` take with S = D.  B*D must not exceed max_batch."""
+        X = _np64(X)
+        B = X.size // (4 * (N + 1))
+        X, U = X.reshape(B, 4 * (N + 1)), _np64(U).reshape(B, 2 * N)
+        decel = _np64(decel).reshape(-1)
+        D = decel.size
+        plan_cost = None if plan_cost is None else _np64(plan_cost).reshape(B)
+        Xs, Us, sp = np.zeros((B * D, 4 * (N + 1))), np.zeros((B * D, 2 * N)), np.zeros((B * D, STOP_FIELDS))
+        cost = np.zeros(B * D) if want_cost else None
+        _check(lib().cilqr_stop_plans(self._h, B, int(N), int(D), _p(X), _p(U), _p(decel), int(hold), C.c_double(max_deviation),
+                                      _p(plan_cost), C.c_double(decel_weight), C.c_uint32(STOP_ALLOW_MOVING if allow_moving else 0),
+                                      _p(Xs), _p(Us), _p(sp), _p(cost)))
+        return dict(X=Xs, U=Us, sp=sp, cost=cost)
+
+    def stop_plans_device(self, stream, B, N, D, X, U, decel, X_stop, U_stop, sp, hold=1, max_deviation=float("inf"), plan_cost=0,
+                          decel_weight=0.0, flags=0, cost=0):
+        """`cilqr_stop_plans_device`: device addresses; X_stop (B*D, 4(N+1)), U_stop (B*D, 2N), sp (B*D, STOP_FIELDS), cost (B*D,) or 0."""
+        _check(lib().cilqr_stop_plans_device(self._h, _vp(stream), int(B), int(N), int(D), _vp(X), _vp(U), _vp(decel), int(hold),
+                                             C.c_double(max_deviation), _vp(plan_cost), C.c_double(decel_weight), C.c_uint32(int(flags)),
+                                             _vp(X_stop), _vp(U_stop), _vp(sp), _vp(cost)))
 
     # ---- batched LocalPlanner pre-step on the device ----
     def local_plan_batch(self, path, ego):

@@ -1841,6 +1841,75 @@ int cilqr_map_clearance(cilqr_handle* h, int B, int N, int S, const double* X, d
   });
 }
 
+// ---- stop plans: a solved plan's geometry under a braking profile (cilqr_stop.hip) ------------------------------------------------------
+namespace {
+// what needs no handle
+int stop_args_check(int D, const double* X, const double* U, const double* decel, int hold, double max_deviation, double decel_weight,
+                    uint32_t flags, const double* X_stop, const double* U_stop, const double* sp) {
+  if (!X || !U || !decel || !X_stop || !U_stop || !sp) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: null required pointer");
+  if (D < 1) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: D = %d, must be at least 1", D);
+  if (hold < 0) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: hold = %d is negative", hold);
+  if (!(max_deviation >= 0.0)) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: max_deviation is negative or NaN");
+  if (!(fabs(decel_weight) <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: decel_weight is not finite");
+  if (flags & ~CILQR_STOP_ALLOW_MOVING) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: unknown flag bits 0x%x", flags);
+  return CILQR_OK;
+}
+// the levels of the host-buffer form, which it can read
+int stop_levels_check(int D, const double* decel) {
+  for (int l = 0; l < D; ++l)
+    if (!(decel[l] > 0.0 && decel[l] <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: decel[%d] is not finite or not positive", l);
+  return CILQR_OK;
+}
+int stop_handle_check(const cilqr_handle* h, int B, int N, int D) {
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (B < 0 || (int64_t)B * D > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_stop_plans: B*D = %lld outside [0,%d]", (long long)B * D, h->max_batch);
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  return CILQR_OK;  // (every horizon a handle accepts fits the kernel's LDS: a static_assert in cilqr_stop.hip)
+}
+}  // namespace
+
+int cilqr_stop_plans_device(cilqr_handle* h, void* stream, int B, int N, int D, const double* X, const double* U, const double* decel,
+                            int hold, double max_deviation, const double* plan_cost, double decel_weight, uint32_t flags,
+                            double* X_stop, double* U_stop, double* sp, double* cost) {
+  int rc = stop_args_check(D, X, U, decel, hold, max_deviation, decel_weight, flags, X_stop, U_stop, sp);
+  if (rc) return rc;
+  rc = stop_handle_check(h, B, N, D);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::StopArgs a = {};
+  a.X = X; a.U = U; a.decel = decel; a.plan_cost = plan_cost;
+  a.X_stop = X_stop; a.U_stop = U_stop; a.sp = sp; a.cost = cost;
+  a.max_deviation = max_deviation; a.decel_weight = decel_weight;
+  a.B = B; a.N = N; a.D = D; a.hold = hold; a.flags = flags;
+  a.plans = cilqr::stop_plans_per_group(N, D);
+  a.dt = h->kp.dt; a.half_dt2 = h->kp.half_dt2; a.acc_max = h->kp.acc_max; a.acc_min = h->kp.acc_min;
+  a.yaw_hi = h->kp.yaw_hi; a.yaw_lo = h->kp.yaw_lo; a.speed_max = h->kp.speed_max;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_stop_plans(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_stop_plans(cilqr_handle* h, int B, int N, int D, const double* X, const double* U, const double* decel, int hold,
+                     double max_deviation, const double* plan_cost, double decel_weight, uint32_t flags, double* X_stop, double* U_stop,
+                     double* sp, double* cost) {
+  int rc = stop_args_check(D, X, U, decel, hold, max_deviation, decel_weight, flags, X_stop, U_stop, sp);
+  if (rc) return rc;
+  rc = stop_levels_check(D, decel);
+  if (rc) return rc;
+  rc = stop_handle_check(h, B, N, D);
+  if (rc) return rc;
+  for (int l = 0; l < D; ++l)
+    if (decel[l] > -h->params.acc_min)
+      return fail(CILQR_ERR_ARG, "cilqr_stop_plans: decel[%d] = %g is above -acc_min = %g, the model would clamp it", l, decel[l], -h->params.acc_min);
+  if (B == 0) return CILQR_OK;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_stop_plans(p, B, N, D, X, U, decel, plan_cost, X_stop, U_stop, sp, cost);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_stop_plans_device(h, h->stream, B, N, D, X, U, decel, hold, max_deviation, plan_cost, decel_weight, flags, X_stop, U_stop, sp, cost);
+  });
+}
+
 // ---- analytic chance risk against sampled obstacles in compact form (cilqr_chance_sampled.hip) ----------------------------------------
 namespace {
 // what needs no handle

@@ -394,6 +394,22 @@ inline void plan_map_clearance(HostPlan& p, size_t R, size_t N, const double*& X
   p.out(total, R);
 }
 
+// cilqr_stop_plans: 8 arrays; B plans, R = B·D rows.  In: X, U, the D levels, plan_cost; out: X_stop, U_stop, the sp row, cost.  With
+// B <= R and D <= R that is R·(12·N + 19) doubles at most, against the 22·N + 34 per unit of max_batch that host_arena_bytes reserves
+// below: every R <= max_batch fits, and the 8 roundings stay within its 32 x 16 bytes.
+inline void plan_stop_plans(HostPlan& p, size_t B, size_t N, size_t D, const double*& X, const double*& U, const double*& decel,
+                            const double*& plan_cost, double*& X_stop, double*& U_stop, double*& sp, double*& cost) {
+  const size_t R = B * D;
+  p.in(X, B * 4 * (N + 1));
+  p.in(U, B * 2 * N);
+  p.in(decel, D);
+  p.in(plan_cost, B);
+  p.out(X_stop, R * 4 * (N + 1));
+  p.out(U_stop, R * 2 * N);
+  p.out(sp, R * CILQR_STOP_FIELDS);
+  p.out(cost, R);
+}
+
 // Bytes of the arena cilqr_create reserves for a handle of max_batch B, max_horizon N, max_obstacles M.  What include/cilqr.h
 // promises about "the buffers reserved at create" is a statement about this number: it does not change.
 inline size_t host_arena_bytes(size_t B, size_t N, size_t M) {

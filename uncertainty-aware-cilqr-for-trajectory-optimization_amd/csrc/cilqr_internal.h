@@ -444,6 +444,29 @@ struct MapClearanceArgs {
 };
 hipError_t launch_map_clearance(const MapClearanceArgs& a, hipStream_t stream);
 
+// Stop plans (cilqr_stop.hip; cilqr_stop_plans*): row r = b·D + l is plan b braked at level l.  One launch of STOP_THREADS lanes per
+// workgroup; a workgroup holds `plans` plans (stop_plans_per_group) and the rows of up to 64 levels of each.
+constexpr int STOP_THREADS = 256;
+constexpr int STOP_WAVES = 4;
+constexpr size_t STOP_LDS_MAX = 64 * 1024;
+struct StopArgs {
+  const double* X;          // [B][4(N + 1)]
+  const double* U;          // [B][2N]
+  const double* decel;      // [D]
+  const double* plan_cost;  // [B] or null
+  double* X_stop;           // [B·D][4(N + 1)]
+  double* U_stop;           // [B·D][2N]
+  double* sp;               // [B·D][CILQR_STOP_FIELDS]
+  double* cost;             // [B·D] or null
+  double max_deviation, decel_weight;
+  int32_t B, N, D, hold;
+  int32_t plans;            // plans per workgroup
+  uint32_t flags;           // CILQR_STOP_*
+  double dt, half_dt2, acc_max, acc_min, yaw_hi, yaw_lo, speed_max;  // the model's constants (KParams)
+};
+int stop_plans_per_group(int N, int D);  // at least 1 for every N <= CILQR_MAX_HORIZON
+hipError_t launch_stop_plans(const StopArgs& a, hipStream_t stream);
+
 // Batched LocalPlanner (local_plan.hip): one lane per candidate.
 struct LocalPlanArgs {
   const double* path;      // 2×P column-major; candidate b reads path + b*path_stride (0: one shared path)

@@ -26,6 +26,7 @@ struct CandidateModes {
   bool min_total = false;      // set_candidate_pick(MinTotalCost)
   bool footprint = false;      // set_footprint_check
   bool map_clearance = false;  // set_map_clearance_check
+  bool stop_fallback = false;  // set_stop_fallback
   // the scene at the time of the run: no setter reserves by these, so the layout never reads them
   bool map_set = false;        // an uncertainty map is set
   bool obstacles = false;      // M > 0
@@ -61,6 +62,7 @@ struct CandidateModes {
   bool map_rollout_risk() const { return map && map_set && (fused_check() || cov); }
   bool footprint_check() const { return footprint; }  // the last check but one in front of the pick, whatever else is in force
   bool map_clearance_check() const { return map_clearance && map_set; }  // behind it: the last stage in front of the pick, while a map is set
+  bool stop_fallback_check() const { return stop_fallback && footprint; }  // behind the pick: stop plans, their checks and a second pick
 };
 
 struct CandidateSizes {
@@ -71,6 +73,7 @@ struct CandidateSizes {
   size_t n_obs = 0;      // nominal obstacles under set_obstacle_samples
   size_t n_samples = 0;  // ... and samples of each
   size_t Q = 0;          // quadrature nodes of set_map_covariance_check
+  size_t D = 0;          // braking levels of set_stop_fallback
   // rollouts per candidate: the covariance check has no draws and keeps ONE zero offset, the plan itself, for the map risk call
   size_t rollouts(const CandidateModes& m) const { return m.cov ? 1 : S; }
 };
@@ -82,9 +85,14 @@ struct CandidateSizes {
   F(qw) F(cmrisk) F(cmstep) F(cmtotal) F(ts0) F(tW) F(tsig) F(trisk) F(tpose) F(tdim) F(tg) F(tcov) F(tmg) F(tkcov) F(tkf) F(srisk) \
   F(stotal) F(mcrow) F(mcstep) F(mctotal) F(fprow) F(fpstep) F(fptotal)
 
+// The stop fallback's arrays, behind every array above: the levels, the stop rows (at most B of them: floor(B / D) candidates at D
+// levels), their sp rows and costs, the S = D footprint check's rows and totals, the map clearance check's, the second pick.
+#define CILQR_CANDIDATE_STOP_ARRAYS(F) F(stlv) F(stX) F(stU) F(stsp) F(stcost) F(stfp) F(stfptotal) F(stmc) F(stmctotal) F(stpair)
+
 struct CandidateLayout {  // offsets in doubles (from candidate_layout) or sizes in doubles (from candidate_sizes)
 #define F(name) size_t name = 0;
   CILQR_CANDIDATE_ARRAYS(F)
+  CILQR_CANDIDATE_STOP_ARRAYS(F)
 #undef F
   size_t end = 0;
 };
@@ -126,6 +134,11 @@ inline CandidateLayout candidate_sizes(const CandidateModes& m, const CandidateS
   s.mcrow = m.map_clearance ? B * CILQR_MAP_CLEARANCE_FIELDS : 0; s.mcstep = m.map_clearance ? B * N : 0; s.mctotal = m.map_clearance ? B : 0;
   // the footprint check's rows, its per-step clearances and its total: at the END, so that every earlier offset is what it was
   s.fprow = m.footprint ? B * CILQR_FOOTPRINT_FIELDS : 0; s.fpstep = m.footprint ? B * N : 0; s.fptotal = m.footprint ? B : 0;
+  // the stop fallback: empty with the flag off, so that every offset and `end` are what they were
+  const size_t st = m.stop_fallback;
+  s.stlv = st * z.D; s.stX = st * B * 4 * (N + 1); s.stU = st * B * 2 * N; s.stsp = st * B * CILQR_STOP_FIELDS; s.stcost = st * B;
+  s.stfp = st * B * CILQR_FOOTPRINT_FIELDS; s.stfptotal = st * B; s.stmc = st * B * CILQR_MAP_CLEARANCE_FIELDS; s.stmctotal = st * B;
+  s.stpair = st * 2;
   return s;
 }
 
@@ -136,6 +149,7 @@ inline CandidateLayout candidate_layout(const CandidateModes& m, const Candidate
   size_t o = 0;
 #define F(name) L.name = o; o += (s.name + 1) & ~(size_t)1;
   CILQR_CANDIDATE_ARRAYS(F)
+  CILQR_CANDIDATE_STOP_ARRAYS(F)
 #undef F
   L.end = o;
   return L;

@@ -39,6 +39,8 @@ const char* const kTrackMapEllipsesOffTightened =
     "set_track_map with ellipses = false beside set_chance_tightening: the solves read no ellipse that the tightening could inflate";
 const char* const kCovarianceWithSamples =
     "set_pose_covariance_check has no form for sampled obstacles (set_obstacle_samples): use set_sample_covariance_check";
+const char* const kStopFallbackWithoutFootprint =
+    "set_stop_fallback needs set_footprint_check: a stop row that no exact check judged is no fallback";
 const char* const kFootprintWithSamples =
     "set_footprint_check has no form for sampled obstacles (set_obstacle_samples): it judges rectangles, and a sample has none";
 const char* const kSampleCovarianceWithNoise =
@@ -352,6 +354,7 @@ CandidateModes iLQR::modes() const {
   m.min_total = pick_ == CandidatePick::MinTotalCost;
   m.footprint = fp_check_;
   m.map_clearance = mc_check_;
+  m.stop_fallback = stop_on_;
   m.map_set = map_set_; m.obstacles = !obstacles_.empty(); m.tracks = tracked_horizon_ >= 0;
   return m;
 }
@@ -361,6 +364,7 @@ CandidateSizes iLQR::sizes() const {
   z.B = max_candidates_; z.N = params.horizon; z.M = max_obstacles_; z.S = noise_.size() / 4;
   z.n_samples = n_samples_; z.n_obs = n_samples_ ? samples_.size() / 3 / n_samples_ : 0;
   z.Q = cmap_weights_.size();
+  z.D = stop_decel_.size();
   return z;
 }
 
@@ -381,6 +385,8 @@ void iLQR::clear_candidate_fields() {
   last_chance_risk_sampled.clear();
   last_footprint.clear(); last_footprint_clearance.clear();
   last_map_clearance.clear(); last_map_step_clearance.clear();
+  last_stop.clear(); last_stop_footprint.clear();
+  last_stop_pick = -1; last_stop_level = -1;
 }
 
 // The prologue of every run_candidates: LocalPlanner pre-step for all candidates in one device launch (cilqr_local_plan_batch)
@@ -424,6 +430,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");
   const CandidateModes m = modes();
   if (m.scov && m.track_rounds()) throw std::logic_error(kTrackMapWithSamples);
+  if (m.stop_fallback && !m.footprint) throw std::logic_error(kStopFallbackWithoutFootprint);
   if (m.in_block()) return run_candidates_in_block(B, ego_states, m);
   // the unchecked path: the host-buffer forms on the handle's stream, the pick on the host
   Candidates c = plan_candidates(B, ego_states);
@@ -583,6 +590,24 @@ void iLQR::set_footprint_check(double min_clearance, double occ_threshold, doubl
   reserve_block_if_used();  // (the device block holds the check's rows while it is on)
 }
 
+void iLQR::set_stop_fallback(const std::vector<double>& decels, int hold, double max_deviation, bool on) {
+  if (on) {
+    if (decels.empty()) throw std::runtime_error("set_stop_fallback: no braking level");
+    for (double d : decels)
+      if (!(d > 0.0 && d <= -params.acc_min)) throw std::runtime_error("set_stop_fallback: a level is not in (0, -acc_min]");
+    if ((int)decels.size() > max_candidates_) throw std::runtime_error("set_stop_fallback: more levels than max_candidates rows");
+    if (hold < 0) throw std::runtime_error("set_stop_fallback: hold is negative");
+    if (!(max_deviation >= 0.0)) throw std::runtime_error("set_stop_fallback: max_deviation is negative or NaN");
+  }
+  stop_on_ = on;
+  stop_decel_ = on ? decels : std::vector<double>();
+  stop_hold_ = hold;
+  stop_max_deviation_ = max_deviation;
+  last_stop.clear(); last_stop_footprint.clear();
+  last_stop_pick = -1; last_stop_level = -1;
+  reserve_block_if_used();  // (the device block holds the levels and the stop rows while it is on)
+}
+
 void iLQR::set_map_clearance_check(double min_clearance, double reach, double occ_threshold, double margin, bool unknown_seeds, bool on) {
   if (on && (min_clearance != min_clearance || occ_threshold != occ_threshold)) throw std::runtime_error("set_map_clearance_check: min_clearance or occ_threshold is NaN");
   if (on && !(reach >= 0.0 && reach <= 1.7e308)) throw std::runtime_error("set_map_clearance_check: reach is negative or not finite");
@@ -736,6 +761,7 @@ void iLQR::reserve_block() {
     hip_check(hipMemcpy(d + L.qn, cmap_nodes_.data(), cmap_nodes_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
     hip_check(hipMemcpy(d + L.qw, cmap_weights_.data(), cmap_weights_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
   }
+  if (m.stop_fallback) hip_check(hipMemcpy(d + L.stlv, stop_decel_.data(), stop_decel_.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
   block_horizon_ = params.horizon;
 }
 
@@ -754,6 +780,9 @@ cilqr_obstacles iLQR::upload_obstacles(const Block& d) {
 int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, const CandidateModes& m) {
   const int N = params.horizon, M = (int)obstacles_.size(), S = (int)sizes().rollouts(m);
   if (m.footprint && m.sampled) throw std::logic_error(kFootprintWithSamples);
+  const int D = (int)stop_decel_.size();
+  if (m.stop_fallback_check() && B > max_candidates_ / D)
+    throw std::runtime_error("run_candidates (stop fallback): more than floor(max_candidates / levels) candidates: the handle holds max_candidates rows");
   if (m.scov) {
     if (!m.sampled) throw std::logic_error(kSampleCovarianceWithoutSamples);
     if (m.noise) throw std::logic_error(kSampleCovarianceWithNoise);
@@ -871,6 +900,24 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
                                       mc_unknown_seeds_ ? CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS : 0u, base, d + L.mcrow, d + L.mcstep, total);
   });
   step(true, [&] { return cilqr_argmin_device(h_, d.st, B, d + total_at, d + L.pair); });
+  // behind the pick, always: the B final plans braked at every level, judged by the same exact gates with S = D, and a second pick
+  if (m.stop_fallback_check()) {
+    step(true, [&] {
+      return cilqr_stop_plans_device(h_, d.st, B, N, D, d + L.X, d + L.U, d + L.stlv, stop_hold_, stop_max_deviation_, d + L.J, 1.0e6, 0u, d + L.stX,
+                                     d + L.stU, d + L.stsp, d + L.stcost);
+    });
+    size_t stop_total = L.stfptotal;
+    step(true, [&] {
+      return cilqr_footprint_check_device(h_, d.st, B, N, M, D, d + L.stX, po, fp_margin_, fp_min_clearance_, fp_threshold_,
+                                          fp_unknown_hits_ ? CILQR_FOOTPRINT_UNKNOWN_HITS : 0u, d + L.stcost, d + L.stfp, nullptr, nullptr, d + L.stfptotal);
+    });
+    step(m.map_clearance_check(), [&] {
+      stop_total = L.stmctotal;
+      return cilqr_map_clearance_device(h_, d.st, B, N, D, d + L.stX, mc_margin_, mc_threshold_, mc_reach_, mc_min_clearance_,
+                                        mc_unknown_seeds_ ? CILQR_MAP_CLEARANCE_UNKNOWN_SEEDS : 0u, d + L.stfptotal, d + L.stmc, nullptr, d + L.stmctotal);
+    });
+    step(true, [&] { return cilqr_argmin_device(h_, d.st, B * D, d + stop_total, d + L.stpair); });
+  }
   if (rc) {
     const std::string msg = cilqr_last_error();
     (void)hipStreamSynchronize(d.st);
@@ -908,10 +955,31 @@ int iLQR::run_candidates_in_block(int B, const std::vector<double>& ego_states, 
     d.fetch(last_map_clearance, L.mcrow, (size_t)B * CILQR_MAP_CLEARANCE_FIELDS);
     d.fetch(last_map_step_clearance, L.mcstep, (size_t)B * N);
   }
+  double stop_pair[2] = {0.0, -1.0};
+  if (m.stop_fallback_check()) {
+    d.down(stop_pair, L.stpair, sizeof(stop_pair));
+    d.fetch(last_stop, L.stsp, (size_t)B * D * CILQR_STOP_FIELDS);
+    d.fetch(last_stop_footprint, L.stfp, (size_t)B * D * CILQR_FOOTPRINT_FIELDS);
+  }
   d.wait();
   if (m.rounds()) keep_tighten_risk(B, tg_rows);
   const int best = (int)pair[1];
-  if (best < 0) return -1;  // every candidate rejected: results and warm start stay
+  if (m.stop_fallback_check()) last_stop_pick = (int)stop_pair[1];
+  if (best < 0 && last_stop_pick >= 0) {  // every candidate rejected, a stop row is clear: publish it; the warm start stays (not a solve)
+    const size_t row = (size_t)last_stop_pick;
+    Matrix Xs(4, N + 1), Us(2, N);
+    d.down(Xs.a.data(), L.stX + row * 4 * ((size_t)N + 1), Xs.a.size() * sizeof(double));
+    d.down(Us.a.data(), L.stU + row * 2 * (size_t)N, Us.a.size() * sizeof(double));
+    d.wait();
+    X_result = Xs;
+    U_result = Us;
+    last_stop_level = last_stop_pick % D;
+    const int cand = last_stop_pick / D;
+    ref_traj_result = Matrix(2, c.n_ref[cand]);
+    memcpy(ref_traj_result.a.data(), &c.ref[(size_t)cand * 2 * params.num_of_local_wpts], ref_traj_result.a.size() * sizeof(double));
+    return cand;
+  }
+  if (best < 0) return -1;  // every candidate rejected (and no stop row clear): results and warm start stay
   Solved s;
   fetch_solved(d, best, s);
   d.wait();

@@ -159,6 +159,22 @@ class iLQR {
   // it off (the default).
   void set_map_clearance_check(double min_clearance, double reach, double occ_threshold, double margin = 0.0, bool unknown_seeds = false,
                                bool on = true);
+  // Stop fallback: a plan for the tick on which every candidate is rejected.  While it is on run_candidates enqueues, behind its normal
+  // pipeline and pick, on the same stream with nothing coming back in between: cilqr_stop_plans_device on the B final plans (D =
+  // decels.size() braking levels, gentlest first by convention, plan_cost = J, decel_weight 1e6) -> cilqr_footprint_check_device with
+  // S = D on the stop rows, against the ORIGINAL obstacles and map, with the margin, min_clearance and threshold of set_footprint_check
+  // -> cilqr_map_clearance_device with S = D when that check is on and a map is set -> a second cilqr_argmin_device over the B*D
+  // totals.  It is always enqueued: the fallback costs a fixed latency per tick, not a second round trip on the tick that needs it.
+  // Where the normal pick is >= 0 the return value, X_result, U_result, the warm start and every other last_* field are bit for bit
+  // what they are without this setter, and last_stop_level is -1.  Where it is -1 and a stop row is clear, the call returns that row's
+  // candidate, X_result / U_result are the stop row, last_stop_level is its level index, and the warm start stays as it was (a stop
+  // plan is not a solve); where no stop row is clear either the call returns -1.  last_stop holds CILQR_STOP_FIELDS per row
+  // (row = candidate * D + level), last_stop_footprint CILQR_FOOTPRINT_FIELDS per row, last_stop_pick the second pick's row or -1.
+  // It needs set_footprint_check: without it run_candidates throws std::logic_error (a stop row nobody judged is no fallback), and
+  // with set_obstacle_samples it throws as the footprint check does.  The handle holds max_candidates rows: under the fallback
+  // run_candidates takes at most floor(max_candidates / D) candidates and throws std::runtime_error beyond.  on = false switches it
+  // off (the default).
+  void set_stop_fallback(const std::vector<double>& decels, int hold = 1, double max_deviation = 0.5, bool on = true);
   // Pose-covariance check: the analytic counterpart of the fused pose-noise check.  Instead of S draws of the pose noise the node
   // hands over its covariance: Sigma0, 4 x 4 column-major over (x, y, v, theta) (only row <= column is read), and the process noise
   // W added per step (nullable: none).  run_candidates then enqueues, on the check's stream: solve -> (under MinTotalCost
@@ -316,6 +332,9 @@ class iLQR {
   std::vector<double> last_footprint, last_footprint_clearance;  // CILQR_FOOTPRINT_FIELDS per candidate; horizon per candidate
   // run_candidates under set_map_clearance_check with a map set; empty otherwise
   std::vector<double> last_map_clearance, last_map_step_clearance;  // CILQR_MAP_CLEARANCE_FIELDS per candidate; horizon per candidate
+  // run_candidates under set_stop_fallback; empty otherwise (last_stop_level: -1 whenever the published plan is a solved one)
+  std::vector<double> last_stop, last_stop_footprint;  // CILQR_STOP_FIELDS / CILQR_FOOTPRINT_FIELDS per row = candidate * D + level
+  int last_stop_pick = -1, last_stop_level = -1;
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
   // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
@@ -400,6 +419,11 @@ class iLQR {
   // footprint check (set_footprint_check)
   bool fp_check_ = false, fp_unknown_hits_ = false;
   double fp_min_clearance_ = 0.0, fp_threshold_ = 0.0, fp_margin_ = 0.0;
+  // stop fallback (set_stop_fallback)
+  bool stop_on_ = false;
+  std::vector<double> stop_decel_;
+  int stop_hold_ = 1;
+  double stop_max_deviation_ = 0.5;
   // map clearance check (set_map_clearance_check)
   bool mc_check_ = false, mc_unknown_seeds_ = false;
   double mc_min_clearance_ = 0.0, mc_reach_ = 0.0, mc_threshold_ = 0.0, mc_margin_ = 0.0;

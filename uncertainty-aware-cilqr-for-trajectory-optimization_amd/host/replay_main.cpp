@@ -2,12 +2,17 @@
 // odomCallback does per odometry message (I/ilqr_uncertainty_node.cpp:111-130: set_global_plan → set_Obstacle → run_step →
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
-//   cilqr_replay <log> [device] [--tighten eps[,rounds]]     → one line per tick on stdout
+//   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]]     → one line per tick on stdout
 //
 // --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
 // (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
 // 0.017^2) and no process noise; the line then ends with " tighten <max da> <max db> <entry> <capped> <CR_STEP_RISK before>" when
 // the tick has obstacles.
+//
+// --stop-fallback: every tick runs as ONE candidate of iLQR::run_candidates under set_footprint_check(0, +inf) — the exact rectangle
+// test against the tick's obstacles — and set_stop_fallback with the braking levels d1, d2 ... (m/s^2) and `hold` (default 1); the line
+// then ends with " stop <plan> <level> <pick>": plan 1 when the published plan is a stop plan, 0 when it is the solved one, -1 when the
+// tick has no plan at all (X and U are then the tick's before); level its level index or -1; pick the stop pick's row or -1.
 //
 // Log (whitespace-separated, '#' starts a comment line):
 //   cilqr-replay 1
@@ -20,6 +25,7 @@
 // Output per tick: "experiment <start_pos 4> <planning_time> <iterations> <exit> <J> X <4(N+1) values> U <2N values>" —
 // X and U in the vehiclepub/Experiment flattening (:243-284).
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -65,14 +71,15 @@ struct Tokens {
 
 int main(int argc, char** argv) {
   std::vector<const char*> pos;  // the log and the device; options may stand anywhere
-  const char* tighten = nullptr;
+  const char *tighten = nullptr, *stop = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
+    else if (strcmp(argv[i], "--stop-fallback") == 0 && i + 1 < argc) stop = argv[++i];
     else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
     else pos.push_back(argv[i]);
   }
   if (pos.empty() || pos.size() > 2) {
-    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]]\n", argv[0]);
     return 2;
   }
   try {
@@ -91,7 +98,27 @@ int main(int argc, char** argv) {
 
     Parameters params = default_parameters();
     params.horizon = N;
-    iLQR planner(params, pos.size() > 1 ? atoi(pos[1]) : 0, 64, 1);
+    std::vector<double> levels;
+    int hold = 1;
+    if (stop) {
+      const char* q = stop;
+      for (;;) {
+        char* rest = nullptr;
+        const double d = strtod(q, &rest);
+        if (rest == q) throw std::runtime_error("--stop-fallback takes d1[,d2...][:hold]");
+        levels.push_back(d);
+        q = rest;
+        if (*q != ',') break;
+        ++q;
+      }
+      if (*q == ':') hold = atoi(q + 1);
+      else if (*q != 0) throw std::runtime_error("--stop-fallback takes d1[,d2...][:hold]");
+    }
+    iLQR planner(params, pos.size() > 1 ? atoi(pos[1]) : 0, 64, stop ? (int)levels.size() : 1);
+    if (stop) {
+      planner.set_footprint_check(0.0, INFINITY);
+      planner.set_stop_fallback(levels, hold);
+    }
     if (tighten) {
       char* rest = nullptr;
       const double eps = strtod(tighten, &rest);
@@ -124,7 +151,9 @@ int main(int argc, char** argv) {
       planner.set_global_plan(path);
       if (M) planner.set_Obstacle(obstacles); else planner.clear_Obstacle();
       const auto t0 = std::chrono::high_resolution_clock::now();
-      planner.run_step(ego);
+      int picked = 0;
+      if (stop) picked = planner.run_candidates(std::vector<double>(ego, ego + 4));
+      else planner.run_step(ego);
       const double secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
       const Experiment e = flatten_experiment(ego, secs, planner.X_result, planner.U_result);
       printf("experiment %.17g %.17g %.17g %.17g %.9g %d %d %.17g X", e.start_pos[0], e.start_pos[1], e.start_pos[2], e.start_pos[3],
@@ -135,6 +164,7 @@ int main(int argc, char** argv) {
       if (!planner.last_tighten.empty())
         printf(" tighten %.17g %.17g %d %d %.17g", planner.last_tighten[CILQR_TG_MAX_DA], planner.last_tighten[CILQR_TG_MAX_DB],
                (int)planner.last_tighten[CILQR_TG_MAX_ENTRY], (int)planner.last_tighten[CILQR_TG_CAPPED], planner.last_tighten_risk_before[0]);
+      if (stop) printf(" stop %d %d %d", picked < 0 ? -1 : planner.last_stop_level >= 0 ? 1 : 0, planner.last_stop_level, planner.last_stop_pick);
       printf("\n");
     }
   } catch (const std::exception& ex) {
