@@ -194,23 +194,30 @@ __device__ __forceinline__ void sincos_loop(double x, double& sn, double& cs) {
 // which evaluates sincos of every heading — if a turn was larger (above 8 m/s at full lock with the reference's parameters); a
 // first heading beyond MAX_HEADING0 goes there too, so that |theta| stays in the range of sincos_loop over any horizon.
 constexpr double MAX_TURN = 0.25, MAX_HEADING0 = 9.99e5;
-__device__ __forceinline__ void rotate_heading(const FwdConst& k, double delta, double& sn, double& cs) {
+struct PlainPins {
+  template <int J> __device__ __forceinline__ void pin(double& ps, double& pc) const { CILQR_PIN2(ps, pc); }
+};
+// PINS: pins.pin<J>(ps, pc) is pin J (0..3) of the chains.  hipcc pads a pin with an s_nop where it finds nothing independent
+// to put behind it, and a lone wavefront pays the s_nop like any instruction (tools/ubench_slot.hip): a caller with loop
+// bookkeeping to do (forward_smem) hangs it on a pin, where it costs nothing.
+template <class PINS = PlainPins>
+__device__ __forceinline__ void rotate_heading(const FwdConst& k, double delta, double& sn, double& cs, const PINS& pins = PINS()) {
   const double z = delta * delta;
   // sin d = d (1 - z/3! + z²/5! - z³/7! + z⁴/9! - z⁵/11!);  cos d - 1 = z (-1/2 + z/4! - z²/6! + z³/8! - z⁴/10! + z⁵/12!).
   // The two Horner chains are written interleaved and pinned that way: a dependent fp64 instruction issues every 8.5 ticks,
   // an independent one every 5.2 (tools/ubench_exec.hip), and hipcc emits the chains one after the other otherwise.
   double ps = fma(z, k.sn5, k.sn4);
   double pc = fma(z, k.cs6, k.cs5);
-  CILQR_PIN2(ps, pc);
+  pins.template pin<0>(ps, pc);
   pc = fma(pc, z, k.cs4);
   ps = fma(ps, z, k.sn3);
-  CILQR_PIN2(ps, pc);
+  pins.template pin<1>(ps, pc);
   pc = fma(pc, z, k.cs3);
   ps = fma(ps, z, k.sn2);
-  CILQR_PIN2(ps, pc);
+  pins.template pin<2>(ps, pc);
   pc = fma(pc, z, k.cs2);
   ps = fma(ps, z, k.sn1);
-  CILQR_PIN2(ps, pc);
+  pins.template pin<3>(ps, pc);
   pc = fma(pc, z, k.cs1);
   const double sd = fma(delta * z, ps, delta);
   const double cdm1 = pc * z;

@@ -602,6 +602,7 @@ __device__ __forceinline__ bool riccati_mfma(int N, const double* rec, double* k
     if (FSMEM) {
       *reinterpret_cast<double*>(gbase + goff) = Dk;
       goff -= gstride;
+      asm volatile("" : "+v"(goff));  // (one subtraction per step: hipcc formed every second offset a second time otherwise)
     } else {
       *gp = Dk;
       gp -= RECF;
@@ -614,15 +615,23 @@ __device__ __forceinline__ bool riccati_mfma(int N, const double* rec, double* k
   };
   // two steps per trip: the lower step's operands are read while the upper one computes, the next trip's upper operands while
   // the lower one computes; the last one or two steps are peeled so that no read reaches below the first record
-  int j = N - 1;
-  for (; j >= 2; j -= 2) {
+  auto trip = [&] {
     cur.lower(ob);
     step(oa);
     cur.back();
     cur.upper(oa);
     step(ob);
+  };
+  bool two_left;
+  if (FSMEM) {  // one counter, of trips: counting steps down by two, hipcc keeps a second copy of the step for the test behind the loop
+    two_left = ((N - 1) & 1) != 0;
+    for (int trips = (N - 1) >> 1; trips > 0; --trips) trip();
+  } else {  // (the LDS form as it was: with the counter above config 3 ran 2.85–2.91 ms per step against 2.83–2.90, no gain)
+    int j = N - 1;
+    for (; j >= 2; j -= 2) trip();
+    two_left = j == 1;
   }
-  if (j == 1) {
+  if (two_left) {
     cur.lower(ob);
     step(oa);
     step(ob);
@@ -665,6 +674,36 @@ __device__ __forceinline__ void fwd_step_store(const FwdConst& k, const FwdIn& c
 // for the scalar cache; the ≈ 250 ticks between a request and its wait cover that (one-dword loads two to five steps ahead, to
 // warm the cache, made the step slower: 430 ticks against 400).  hipcc does not see these loads: every use lies behind f_swait,
 // which carries the registers as in/out operands of the s_waitcnt that makes them valid.
+typedef double d2_t __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) d2_t lds_d2;  // through a 32-bit LDS address (one vector register, pinned as such): one ds_write_b128
+constexpr int FSTEP = FREC * 8;  // bytes per forward record
+static_assert(XR % 2 == 0, "state records are whole 16-byte pairs");
+// The once-per-trip bookkeeping of forward_smem on rotate_heading's pins: record offset, control address, state address, each
+// moved on by the two steps of a trip with one instruction, which stands between the pin and the chain's next instruction.
+// (The chain's pin reads the position, a pin of its own behind the bump defines it anew: the bump stands between the two.  As an
+// in/out operand of the chain's pin the position would make hipcc pad the bump itself.)
+struct FwdBump {
+  unsigned& off;
+  lds_d2*& un;
+  lds_d2*& xn;
+  template <int J> __device__ __forceinline__ void pin(double& ps, double& pc) const {
+    if (J == 0) {
+      asm volatile("" : "+v"(ps), "+v"(pc) : "v"(un));
+      un += 2;
+      asm volatile("" : "+v"(un));
+    } else if (J == 1) {
+      asm volatile("" : "+v"(ps), "+v"(pc) : "v"(xn));
+      xn += XR;
+      asm volatile("" : "+v"(xn));
+    } else if (J == 2) {  // (the offset last: the loop's compare then falls behind the last pin)
+      asm volatile("" : "+v"(ps), "+v"(pc) : "s"(off));
+      off += 2 * FSTEP;
+      asm volatile("" : "+s"(off));
+    } else {
+      CILQR_PIN2(ps, pc);
+    }
+  }
+};
 typedef double d8_t __attribute__((ext_vector_type(8)));
 struct FwdS { d8_t lo, hi; };  // lo = {k0, k1, K00..K03, K10, K11}, hi = {K12, K13, x, y, v, theta, u0, u1}
 __device__ __forceinline__ void f_sload_first(FwdS& r, const double* p) {
@@ -672,8 +711,12 @@ __device__ __forceinline__ void f_sload_first(FwdS& r, const double* p) {
 }
 // The next record into the SAME registers: as in/out operands, so that every use of the old values lies before this point and
 // one set of 32 scalar registers serves the whole pass (two sets alive at once do not fit beside the kernel's other scalars).
-__device__ __forceinline__ void f_sload_next(FwdS& r, const double* p) {
-  asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40" : "+s"(r.lo), "+s"(r.hi) : "s"(p) : "memory");
+// The record lies AHEAD bytes behind byte offset `off` of the pass's records: base, offset register and immediate all go into
+// the load itself, so a step forms no address (as `fwd + min(i + 1, N) * FREC` it was five scalar instructions per step).
+template <int AHEAD>
+__device__ __forceinline__ void f_sload_next(FwdS& r, const double* fwd, unsigned off) {
+  asm volatile("s_load_dwordx16 %0, %2, %3 offset:%4\n\ts_load_dwordx16 %1, %2, %3 offset:%5"
+               : "+s"(r.lo), "+s"(r.hi) : "s"(fwd), "s"(off), "n"(AHEAD), "n"(AHEAD + 64) : "memory");
 }
 // The wait is the compiler's own s_waitcnt (the builtin), not text inside the assembly statement: hipcc's wait-count pass then
 // KNOWS that no LDS store of an earlier step is pending behind this point.  With the wait hidden in assembly text it protected the
@@ -708,34 +751,50 @@ __device__ __forceinline__ bool forward_smem(const KParams& kp, int N, const dou
   s.x = X[0]; s.y = X[1]; s.v = X[2]; s.th = X[3]; s.c = X[4]; s.s = X[5];
   store_state(Xn, 0, s);
   double max_turn = 0.0;  // (the first heading was checked by the rollout)
-  auto recp = [&](int j) { return fwd + (size_t)(j < N ? j : N) * FREC; };  // (past the end: the dump record)
+  // A lone wavefront pays an issue slot (4 ticks, tools/ubench_slot.hip) for every instruction of the loop, address arithmetic
+  // included, so a trip keeps three positions and nothing else: `off`, the byte offset of the trip's first record in a scalar
+  // register — it is the offset register of the record loads and the trip counter at once — and the LDS addresses of the
+  // trip's first control and first new state in two vector registers; the second step of a trip lies at immediate offsets from
+  // all three.  They are pinned, or hipcc re-derives each address from scalar counters of its own, and each is bumped once per
+  // trip, behind a pin of the second step's rotation (FwdBump), where an s_nop would stand otherwise.
   FwdS r;
   FwdIn c;
-  f_sload_first(r, recp(0));
-  auto step = [&](int i) {
+  f_sload_first(r, fwd);
+  unsigned off = 0;
+  lds_d2* un = (lds_d2*)Un;
+  lds_d2* xn = (lds_d2*)(Xn + XR);  // (cos/sin columns: filled by the next phase L)
+  asm volatile("" : "+s"(off), "+v"(un), "+v"(xn));
+  const FwdBump bump{off, un, xn};
+  // AHEAD: where the step's NEXT record lies behind `off`; SLOT: 0 or 1, the step's place in its trip.
+  // The request of step N - 1 goes to index N, the dump record behind the last one: still inside the (N + 1) * FREC doubles
+  // a solve's `fwd` has, and never beyond — step i asks for i + 1 ≤ N, so no clamp is needed.
+  auto step = [&](auto ahead, auto slot, const auto& pins) {
+    constexpr int AHEAD = decltype(ahead)::value, SLOT = decltype(slot)::value;
     f_swait(r);
     f_sunpack(c, r);
     double u0, u1;
     forward_controls_scalar(c, s, u0, u1, ihd);
-    f_sload_next(r, recp(i + 1));
-    Un[2 * i] = u0; Un[2 * i + 1] = u1;
+    f_sload_next<AHEAD>(r, fwd, off);
+    un[SLOT] = d2_t{u0, u1};
     const double delta = dyn_pose_loop(k, s, u0, u1, max_turn);
-    double* xo = Xn + (i + 1) * XR;  // (cos/sin columns: filled by the next phase L)
-    xo[0] = s.x; xo[1] = s.y;
+    lds_d2* xo = xn + SLOT * (XR / 2);
+    xo[0] = d2_t{s.x, s.y};
     if (PUBLISH) asm volatile("" ::: "memory");  // (compiler order only: the LDS executes one wavefront's stores in order)
-    xo[2] = s.v; xo[3] = s.th;
+    xo[1] = d2_t{s.v, s.th};
     // the rotation last: its ≈ 100 ticks cover the latency of the stores above, which the next step's s_waitcnt lgkmcnt(0) —
     // the only safe wait with scalar loads in flight — would otherwise pay
-    rotate_heading(k, delta, s.s, s.c);
+    rotate_heading(k, delta, s.s, s.c, pins);
     CILQR_PIN2(s.s, s.c);
   };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
   // two steps per trip: the rotated (cos, sin) of one step are the inputs of the next in other registers, no copies at the back edge
-  int i = 0;
-  for (; i + 1 < N; i += 2) {
-    step(i);
-    step(i + 1);
+  const unsigned end = (unsigned)N * FSTEP, last = N > 0 ? end - FSTEP : 0;
+  while (off < last) {  // steps i = off / FSTEP and i + 1, both below N
+    step(std::integral_constant<int, FSTEP>(), I0(), PlainPins());
+    step(std::integral_constant<int, 2 * FSTEP>(), I1(), bump);  // (all three positions move on behind its last request and store)
   }
-  if (i < N) step(i);
+  if (off < end) step(std::integral_constant<int, FSTEP>(), I0(), PlainPins());
   f_swait(r);  // (the request of the last step: the dump record)
   return max_turn <= MAX_TURN;
 }
