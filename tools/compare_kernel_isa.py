@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Are the kernels of one object file still, instruction for instruction, those of an earlier build?
 
-    python tools/compare_kernel_isa.py OLD.o NEW.o        exit code 1 and a listing when a kernel of OLD.o differs or is gone
+    python tools/compare_kernel_isa.py OLD.o NEW.o [NAME ...]     exit code 1 and a listing when a kernel of OLD.o differs or is gone
+    NAME: compare only the kernels whose name contains one of these strings; a leading `!` excludes instead, e.g.
+          '!share_kernel' '!pair_kernel' '!cilqr_solve_kernel<false, 1' '!cilqr_solve_kernel<true, 1' for everything but the kernels that
+          run the scalar-path form of the solve's serial loops
 
 Both objects' gfx950 code objects are disassembled (llvm-objdump -d, no raw bytes), addresses and the padding behind the last
 s_endpgm dropped, and every kernel of OLD.o compared with its namesake in NEW.o.  A kernel that has since gained a trailing
@@ -50,8 +53,12 @@ def successors(name):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    want = [a for a in sys.argv[3:] if not a.startswith("!")]
+    skip = [a[1:] for a in sys.argv[3:] if a.startswith("!")]
     bad = 0
     for name, body in sorted(old.items()):
+        if (want and not any(w in name for w in want)) or any(w in name for w in skip):
+            continue
         match = next((n for n in successors(name) if n in new), None)
         same = match is not None and new[match] == body
         bad += not same

@@ -4,6 +4,8 @@
 // measured for independent v_fma_f64 only.  Here: a stream of independent v_fma_f64 (four accumulators, round robin), and the
 // same stream with ONE filler behind every v_fma_f64: s_add_i32, v_mov_b32 (from a scalar register, as the LDS store addresses
 // of forward_smem are formed), v_add_u32 (a cursor bump), s_nop 0.  Ticks per added instruction = (variant - base) / fillers.
+// Then the price of a pad by its length: s_nop N for N = 1 … 7 (N + 1 wait states) in the same place — does a shorter pad cost
+// less than a longer one, or does only removing it count?
 // One wavefront per SIMD (1024 blocks of 64 lanes on 256 CUs), s_memtime around 256 trips of 16 pairs.
 //   hipcc -O3 --offload-arch=gfx950 -o tools/ubench_slot tools/ubench_slot.hip && tools/ubench_slot
 #include <hip/hip_runtime.h>
@@ -27,6 +29,13 @@ __global__ __launch_bounds__(64) void k(double* out, unsigned long long* cyc, do
     if (KIND == 2) { R4(FMA4("v_mov_b32 %5, %4\n")) }
     if (KIND == 3) { R4(FMA4("v_add_u32 %6, 16, %6\n")) }
     if (KIND == 4) { R4(FMA4("s_nop 0\n")) }
+    if (KIND == 5) { R4(FMA4("s_nop 1\n")) }
+    if (KIND == 6) { R4(FMA4("s_nop 2\n")) }
+    if (KIND == 7) { R4(FMA4("s_nop 3\n")) }
+    if (KIND == 8) { R4(FMA4("s_nop 4\n")) }
+    if (KIND == 9) { R4(FMA4("s_nop 5\n")) }
+    if (KIND == 10) { R4(FMA4("s_nop 6\n")) }
+    if (KIND == 11) { R4(FMA4("s_nop 7\n")) }
   }
   const unsigned long long t1 = __builtin_readcyclecounter();
   out[threadIdx.x + blockIdx.x * 64] = x0 + x1 + x2 + x4 + x5 + x6 + x7 + sc + vm + va;
@@ -55,5 +64,12 @@ int main() {
   run<2>("  + v_mov_b32 (from SGPR) behind each", base);
   run<3>("  + v_add_u32 behind each", base);
   run<4>("  + s_nop 0 behind each", base);
+  run<5>("  + s_nop 1 behind each", base);
+  run<6>("  + s_nop 2 behind each", base);
+  run<7>("  + s_nop 3 behind each", base);
+  run<8>("  + s_nop 4 behind each", base);
+  run<9>("  + s_nop 5 behind each", base);
+  run<10>("  + s_nop 6 behind each", base);
+  run<11>("  + s_nop 7 behind each", base);
   return 0;
 }

@@ -528,6 +528,9 @@ __device__ __forceinline__ void mfma_place(const double*& ptr, int& stride, int 
   stride = slot >= 0 ? 2 * RECF : 0;
 }
 
+// Both forms with the PSD test on the chain.  FSMEM = false, the LDS form (split kernels, and wherever a table is streamed from the
+// workspace): gains over the step's record in LDS.  FSMEM = true, gains to the forward records: the share kernel with three wavefronts
+// per solve; the other scalar-path callers use riccati_mfma_smem below.
 // DIAG: sub[5..7] += ticks of {the three products up to a, b, d in scalar registers; determinant and reciprocal; the rest of the step}.
 template <bool FSMEM, bool DIAG>
 __device__ __forceinline__ bool riccati_mfma(int N, const double* rec, double* kK, double* fwd, const double* cst, double inv_half_dt, double lamb_in,
@@ -639,6 +642,176 @@ __device__ __forceinline__ bool riccati_mfma(int N, const double* rec, double* k
     step(oa);
   }
   return __builtin_amdgcn_ballot_w64((signs_v | signs_s) < 0 || !(det0 == det0)) == 0;
+}
+
+// MfmaCursor through 32-bit LDS addresses: riccati_mfma_smem pins its cursors in vector registers, and a pinned generic pointer is a
+// 64-bit one that hipcc reads with flat_load.
+typedef __attribute__((address_space(3))) double lds_f64;
+struct MfmaLdsCursor {
+  const lds_f64 *AB, *AA, *BB, *Ca, *Cb;
+  int sAB, sAA, sBB, sCa, sCb;
+  __device__ __forceinline__ void upper(MfmaOperands& o) const { o.AB = AB[RECF]; o.AA = AA[RECF]; o.BB = BB[RECF]; o.Ca = Ca[RECF]; o.Cb = Cb[RECF]; }
+  __device__ __forceinline__ void lower(MfmaOperands& o) const { o.AB = AB[0]; o.AA = AA[0]; o.BB = BB[0]; o.Ca = Ca[0]; o.Cb = Cb[0]; }
+};
+__device__ __forceinline__ void mfma_place(const lds_f64*& ptr, int& stride, int slot, const lds_f64* low, const lds_f64* cst) {
+  ptr = slot >= 0 ? low + slot : cst + (-1 - slot);
+  stride = slot >= 0 ? 2 * RECF : 0;
+}
+
+// The scalar-path form (two-wavefront share kernel, pair kernel, one-wavefront kernel with its table in LDS): the gains go to the forward records in
+// global memory, where phase F reads them through the scalar path (forward_smem).  Same arithmetic as the LDS form, instruction for
+// instruction; what differs is where everything that is not arithmetic stands.  A lone wavefront pays 4 ticks for every issued
+// instruction and for every wait state of an s_nop (tools/ubench_slot.hip), a matrix instruction keeps the vector pipe for 16 ticks
+// and its dependants wait six states, so a step costs its chain plus the chain's wait states, and everything else is free exactly
+// where it stands in those states — memory and scalar instructions in a matrix instruction's first three, vector ones behind them:
+//   * the PSD test is not made on the chain (it was a v_mov_b64, a v_fma_f64, a v_or_b32 and 1.25 s_or per step): every lane stores
+//     its Db, lanes 4, 5 and 21 hold a, b, d, and the test is made by lanes behind the loop;
+//   * the next step's five operand reads stand together behind the second and third product, with one wait;
+//   * the reciprocal's Newton steps stand behind the fourth product, not before it, the store of Db in its first states;
+//   * the gain store stands alone behind the fifth product, its offset and the cursors move on in front of and behind the copies.
+template <bool DIAG>
+__device__ __forceinline__ bool riccati_mfma_smem(int N, const double* rec, double* fwd, const double* cst, double inv_half_dt, double lamb_in,
+                                                  unsigned long long* sub) {
+  constexpr int C0 = -1, C1 = -2, CDT = -3, CW = -4, C2 = -5;
+  const int lane = threadIdx.x;
+  const int e = ((lane >> 4) << 2) | (lane & 3);  // 4·r + c of this lane's entry
+  const bool odd = (lane & 4) != 0;               // block 1 (or 3)
+  // record slots, masks and lamb·I: as in riccati_mfma above (restated here: that function's text is held still)
+  const int slotA = e == 0 || e == 5 || e == 10 || e == 15 ? C1 : e == 2 ? 10 : e == 6 ? 11 : e == 3 ? 12 : e == 7 ? 13 : C0;
+  const int slotB = e == 0 ? 10 : e == 4 ? 11 : e == 8 ? C2 : e == 13 ? CDT : C0;
+  const int slotXX = e == 0 ? 3 : e == 1 || e == 4 ? 4 : e == 5 ? 5 : e == 10 ? CW : C0;
+  const int slotX = e == 2 ? 0 : e == 6 ? 1 : e == 10 ? 2 : C0;
+  const int slotUU = e == 0 ? 8 : e == 5 ? 9 : e == 2 ? 6 : e == 6 ? 7 : C0;
+  // the cursors as 32-bit LDS addresses: they are pinned in vector registers below, and a pinned generic pointer is a 64-bit one
+  using PTR = const lds_f64*;
+  const PTR low = (PTR)rec + (N - 2) * RECF;  // (N = 1: the record "below" is never read)
+  const PTR cstp = (PTR)cst;
+  MfmaLdsCursor cur;
+  mfma_place(cur.AB, cur.sAB, odd ? slotB : slotA, low, cstp);
+  mfma_place(cur.AA, cur.sAA, slotA, low, cstp);
+  mfma_place(cur.BB, cur.sBB, slotB, low, cstp);
+  mfma_place(cur.Ca, cur.sCa, odd ? slotX : slotXX, low, cstp);
+  mfma_place(cur.Cb, cur.sCb, odd ? slotUU : C0, low, cstp);
+  double m00 = e == 0 ? 1.0 : 0.0, m01 = e == 1 || e == 4 ? 1.0 : 0.0, m11 = e == 5 ? 1.0 : 0.0;
+  double mvc = odd && (lane & 3) == 2 ? 1.0 : 0.0;
+  double lamb = lamb_in, lamb0 = lamb_in * (inv_half_dt * inv_half_dt);
+  double lamb_row = (lane >> 4) == 0 ? lamb0 : lamb;
+  CILQR_PIN(m00); CILQR_PIN(m01); CILQR_PIN(m11); CILQR_PIN(mvc); CILQR_PIN(lamb); CILQR_PIN(lamb0); CILQR_PIN(lamb_row);
+  // gains in Dk: K(0, c) in lanes 0-3, K(1, c) in lanes 16-19 (block 0); k(0), k(1) in lanes 6, 22 (column 2 of block 1).  They go
+  // to the forward records, the lanes that hold no gain write into the dump record behind the last.  Every lane stores: no EXEC change.
+  const bool stores = lane == 6 || lane == 22 || lane < 4 || (lane >= 16 && lane < 20);
+  const int gslot = lane == 6 ? 0 : lane == 22 ? 1 : lane < 4 ? 2 + lane : 6 + (lane & 3);
+  unsigned goff = stores ? (unsigned)(((N - 1) * FREC + gslot) * 8) : (unsigned)((N * FREC + (lane & 15)) * 8);
+  const unsigned gstride = stores ? FREC * 8 : 0;
+  char* const gbase = reinterpret_cast<char*>(fwd);
+  // Where a, b, d go: every lane stores its Db into the LDS record of the step it computes, lanes 4, 5 and 21 into slots 0-2 and the
+  // others into slots 3-13 (no EXEC change).  The record of step t is dead by then and cannot be read late: its five operands were
+  // fetched while step t + 1 computed — the reads run one step ahead of the computation, they stand before this store in program
+  // order, and one wavefront's LDS instructions execute in order — the gains of this form do not go to LDS, phase L rewrites all 14
+  // slots of every record before they are read again, and no other wavefront touches the records during phase R (the aux
+  // wavefronts of the share kernels sleep at their barrier).  Like the cursors, the position is that of the LOWER step of a pair.
+  // (N = 1: qp and the cursors are formed as rec - RECF and only [RECF] of them is touched; a 32-bit LDS address must not wrap
+  //  below 0 on the way, which holds because path samples and trajectories lie in front of the records in every kernel's LDS)
+  lds_f64* qp = (lds_f64*)rec + (N - 2) * RECF + (lane == 4 ? 0 : lane == 5 ? 1 : lane == 21 ? 2 : 3 + lane % 11);
+
+  MfmaOperands oa, ob;
+  cur.upper(oa);
+  // :108-113: terminal value = stage N-1: V = l_xx in both blocks, vc = l_x in column 2 of block 1
+  double V = odd_blocks_from_even(oa.Ca), vc = oa.Ca * mvc;
+  // KIND: 0 / 1 the upper / lower step of a trip, 2 a peeled upper step with a lower one behind it, 3 a peeled step with none.
+  // The bookkeeping hangs on the chain where hipcc would pad: behind an empty statement that carries the chain's value, with no
+  // statement of its own behind it (hipcc counts a copy's or a matrix instruction's wait states from the last assembly statement).
+  auto step = [&](const MfmaOperands& o, auto kind, auto upper_step) {
+    constexpr int KIND = decltype(kind)::value, QOFF = decltype(upper_step)::value ? RECF : 0;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    if (DIAG) stamp_request(s0, V);
+    const double P = CILQR_MFMA(V, o.AB, vc);
+    double Db = CILQR_MFMA(o.BB, P, o.Cb);
+    const double Da = CILQR_MFMA(o.AA, P, o.Ca);
+    if (KIND != 3) {  // the next step's five operands in one group: one wait
+      asm volatile("" : "+v"(Db) : "v"(cur.AB), "v"(cur.AA), "v"(cur.BB), "v"(cur.Ca), "v"(cur.Cb));
+      if (KIND == 1) cur.upper(oa); else cur.lower(ob);
+      asm volatile("");
+    }
+    const double a = readlane_f64(Db, 4), b = readlane_f64(Db, 5), d = readlane_f64(Db, 21);
+    if (DIAG) stamp_request(s1, a + b + d);
+    const double bb = b * b;
+    const double ar = a + lamb0, dr = d + lamb;
+    const double den = fma(ar, dr, -bb);
+    const double adj = fma(ar, m11, fma(-b, m01, dr * m00));
+    double Dkr = CILQR_MFMA(adj, Db, 0.0);
+    // rcp_newton, with the store of Db between the reciprocal and its first use
+    double r = __builtin_amdgcn_rcp(den);
+    asm volatile("" : "+v"(Dkr), "+v"(r), "+v"(goff) : "v"(qp));  // (the offset: pinned as the one value it is, far from any copy)
+    qp[QOFF] = Db;
+    asm volatile("");
+    r = fma(fma(-den, r, 1.0), r, r);
+    r = fma(fma(-den, r, 1.0), r, r);
+    const double nr = -r;
+    if (DIAG) stamp_request(s2, nr);
+    const double Dk = Dkr * nr;
+    double H0 = fma(lamb_row, Dk, Db);
+    if (KIND == 0) {  // four cursors move on behind the upper step's reads: two here, two behind the copy
+      asm volatile("" : "+v"(H0) : "v"(cur.AB), "v"(cur.AA));
+      cur.AB -= cur.sAB; cur.AA -= cur.sAA;
+    }
+    if (KIND == 1) {  // (behind the lower step's store)
+      asm volatile("" : "+v"(H0) : "v"(qp));
+      qp -= 2 * RECF;
+    }
+    double H = odd_blocks_from_even(H0);
+    if (KIND == 0) {
+      asm volatile("" : "+v"(H) : "v"(cur.BB), "v"(cur.Ca));
+      cur.BB -= cur.sBB; cur.Ca -= cur.sCa;
+    }
+    double Dv = CILQR_MFMA(H, Dk, Da);
+    asm volatile("" : "+v"(Dv) : "v"(goff));  // the gain store alone in the product's first wait states
+    *reinterpret_cast<double*>(gbase + goff) = Dk;
+    asm volatile("" : "+v"(Dv) : : "memory");
+    vc = Dv * mvc;
+    CILQR_PIN(vc);  // (the product before the copy below, so that the copy can be made in place)
+    asm volatile("" : "+v"(Dv) : "v"(goff), "v"(cur.Cb));  // the store's offset and the fifth cursor: between the product and the copy
+    goff -= gstride;
+    if (KIND == 0) cur.Cb -= cur.sCb;
+    V = odd_blocks_from_even(Dv);
+    if (DIAG) {
+      stamp_request(s3, V);
+      stamps_collect(s0, s1, s2, s3);
+      sub[5] += s1 - s0; sub[6] += s2 - s1; sub[7] += s3 - s2;
+    }
+  };
+  using Upper = std::true_type;
+  using Lower = std::false_type;
+  using K0 = std::integral_constant<int, 0>;
+  using K1 = std::integral_constant<int, 1>;
+  using K2 = std::integral_constant<int, 2>;
+  using K3 = std::integral_constant<int, 3>;
+  // two steps per trip, the last one or two peeled so that no read reaches below the first record; one counter, of trips (counting
+  // steps down by two, hipcc keeps a second copy of the step for the test behind the loop)
+  for (int trips = (N - 1) >> 1; trips > 0; --trips) {
+    step(oa, K0(), Upper());
+    step(ob, K1(), Lower());
+  }
+  if (((N - 1) & 1) != 0) {
+    step(oa, K2(), Upper());
+    step(ob, K3(), Lower());
+  } else {
+    step(oa, K3(), Upper());
+  }
+  // The PSD test of riccati_step<FAST> by lanes: lane l of a round looks at step t = base + l (one round up to N = 64), with the two
+  // instructions the chain had.  The predicate is the chain's, bit for bit: a sign bit in det0, a or d of any step (-0.0 counts as
+  // negative), or a NaN in step 0's det0 (a NaN anywhere in the recursion stays in V_xx down to step 0).
+  bool bad = false;
+  for (int base = 0; base < N; base += WAVE) {
+    const int t = base + lane;
+    const double* q = rec + (t < N ? t : N - 1) * RECF;
+    const double a = q[0], b = q[1], d = q[2];
+    const double bb = b * b;
+    const double det0 = fma(a, d, -bb);
+    const int signs = __double2hiint(det0) | __double2hiint(a) | __double2hiint(d);
+    bad |= t < N && (signs < 0 || (t == 0 && !(det0 == det0)));
+  }
+  return __builtin_amdgcn_ballot_w64(bad) == 0;
 }
 
 template <int KS>
@@ -1038,7 +1211,7 @@ __global__ __launch_bounds__(WAVE, UNC ? 1 : 2) void cilqr_solve_kernel(SolveArg
       }
       break;
     }
-    if (!(GENERAL ? riccati<true>(kp, N, rec, kK, lamb) : riccati_mfma<FSMEM, DIAG>(N, rec, kK, fwd, cst, 2.0 / kp.dt, lamb, sub))) {
+    if (!(GENERAL ? riccati<true>(kp, N, rec, kK, lamb) : (FSMEM ? riccati_mfma_smem<DIAG>(N, rec, fwd, cst, 2.0 / kp.dt, lamb, sub) : riccati_mfma<false, DIAG>(N, rec, kK, fwd, cst, 2.0 / kp.dt, lamb, sub)))) {
       if (GENERAL) { status = CILQR_EXIT_NUMERIC; break; }
       handover = true;
       break;
@@ -1408,7 +1581,7 @@ __global__ __launch_bounds__(2 * WAVE) void cilqr_solve_pair_kernel(SolveArgs a)
     }
     mark_pending(Xa, N, lane, WAVE);  // the forward pass below rewrites states 1..N; the aux wavefront sleeps at B1 meanwhile
     CILQR_STAMP(c_L)
-    if (!riccati_mfma<true, DIAG>(N, rec, rec, fwd, cst, 2.0 / kp.dt, lamb, sub)) { handover = true; break; }
+    if (!riccati_mfma_smem<DIAG>(N, rec, fwd, cst, 2.0 / kp.dt, lamb, sub)) { handover = true; break; }
     if (lane == 0) *reinterpret_cast<volatile int*>(cmd) = CMD_GO;
     __syncthreads();  // B1
     CILQR_STAMP(c_R)
@@ -1974,7 +2147,10 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
       stop = true;
     } else {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wavefront's record slots are in LDS (the aux wavefront's: barrier A)
-      if (!riccati_mfma<true, false>(N, rec, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr)) {
+      // (three wavefronts per solve keep the form with the PSD test on the chain: there the new one stamped R 363 -> 365 and
+      //  F 340 -> 347 ticks per step, the slowest solve +1.2 %, profiles/r26_riccati_chain.txt)
+      if (!(W == 3 ? riccati_mfma<true, false>(N, rec, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr)
+                   : riccati_mfma_smem<false>(N, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr))) {
         handover = true;
         stop = true;
       } else {
