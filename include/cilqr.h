@@ -129,7 +129,8 @@ typedef enum cilqr_status {
   CILQR_ERR_NO_DEVICE = -2,  /* no usable gfx950 device / HIP runtime error at create */
   CILQR_ERR_HIP = -3,        /* HIP runtime error during a call */
   CILQR_ERR_UNSUPPORTED = -4,/* parameter combination the kernels do not implement (e.g. num_states != 4) */
-  CILQR_ERR_COMM = -5        /* RCCL error in the cross-GPU exchange step */
+  CILQR_ERR_COMM = -5,       /* RCCL error in the cross-GPU exchange step */
+  CILQR_ERR_INTERNAL = -6    /* a kernel's loop bound ran out: a defect of this library, reported instead of a hang */
 } cilqr_status;
 
 /* Per-solve exit reason written to status_out (I/iLQR.cpp:211-239). */
@@ -1537,6 +1538,92 @@ int cilqr_inflate_map_device(cilqr_handle* h, void* stream, int L, const float* 
                              const int32_t* d2, double inscribed, double radius, double peak, float* layer_out);
 int cilqr_inflate_map(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* d2,
                       double inscribed, double radius, double peak, float* layer_out);
+
+/* --- obstacles from the map: connected components of occupied cells as boxes (new) ---------------------------------------------------
+ * Every map call above takes boxes, tracks or covariances and raises cells; this one goes the other way.  Where the occupied cells
+ * of a layer are the only obstacle information (M = 0), it labels them and returns one rectangle per component in the formats the
+ * obstacle channel reads: cilqr_boxes_to_polygons rows and cilqr_obstacles pose / dim tables.
+ * L layers per call, column-major (i + j*rows), geometry g as cilqr_map_distance reads it (rows, cols, res) plus its position
+ * (pos_x, pos_y, len_x, len_y) for the cell centres.
+ *
+ * Definitions.
+ *   d2          [L][rows*cols] int32 (required): the output of cilqr_map_distance for the layer, so the seed predicate (threshold,
+ *               NaN flag, complement) is that call's.  A cell is a SEED where d2 == 0 and LINKED where d2 <= gap2, gap2 >= 0 an
+ *               integer in cells^2; INT32_MAX (no seed in the layer) is never linked.  With gap2 = 0 the linked cells are the
+ *               seeds; a larger gap2 bridges gaps between returns (the Eps of DBSCAN).
+ *   component   a maximal set of linked cells connected through neighbours: 8 neighbours, or 4 under CILQR_MAP_OBSTACLES_FOUR.
+ *               Every component holds at least one seed.
+ *   label_out   [L][rows*cols] int32 (required): for a linked cell the lowest linear index among the linked cells of its
+ *               component, -1 elsewhere.  The value is canonical: it does not depend on any order of evaluation.
+ *   comp        [L][K][CILQR_MAP_OBSTACLE_FIELDS] doubles (required), see the enum: every field but FILL holds an exact integer.
+ *               CELLS, the index extremes and the index sums run over the SEEDS of the component; LINKED counts its linked cells.
+ *   n_out       [L][4] int32 (required): the components found; those with CELLS >= min_cells; the rows written; the seeds.
+ *   rows        the components with CELLS >= min_cells, in ascending label order; the first K of them get slots; of these, the ones
+ *               whose larger box size exceeds max_size (metres; HUGE_VAL: no limit — walls and buildings stay with the map channel)
+ *               are dropped; the rest are compacted in order.  K CAPS THE SLOTS BEFORE THE SIZE FILTER: with more than K components
+ *               of min_cells, a small one behind K large ones is not returned, and n_out[l][1] > K says that this happened.
+ *   filler      rows at and beyond n_out[l][2], up to K: pose (FAR, FAR, 0, 0) with FAR = CILQR_MAP_OBSTACLES_FAR, dim (0, 0), box
+ *               (FAR, FAR, 0, 0, 0), every comp field -1.  A filler row's barrier term underflows to exactly 0, so a solve with a
+ *               fixed M = K needs no read-back of the count.
+ *   boxes       [L][K][5] = (x, y, yaw, size_x, size_y) in the planning frame, the input of cilqr_boxes_to_polygons; pose_out
+ *               [L][K][4] = (x, y, 0, yaw) and dim_out [L][K][2] = (size_x, size_y), read by cilqr_obstacles strides (K, 1, 0) — one
+ *               set per layer, constant over the horizon — or (0, 1, 0) with L = 1.  Each of the three may be NULL.
+ *   pose        [L or 1][3] = (x, y, theta) with pose_stride 3 or 0, or NULL for the identity: the layer's pose in the planning
+ *               frame.  A point m of the map frame goes to w = (pose.x + (c*m.x - s*m.y), pose.y + (s*m.x + c*m.y)) with c, s the
+ *               cosine and sine of theta, exactly as cilqr_rasterize_tracks takes a cell centre there.
+ *   work        [L][rows*cols] int32 (required): scratch, contents unspecified afterwards.  Nothing is allocated per call.
+ *
+ * Box of a component, evaluated in double as written, no fused multiply-add.  Over the seeds (i, j) of the component: c = CELLS,
+ * Si, Sj, Sii, Sij, Sjj the index sums; a = c*Sii - Si*Si, b = c*Sij - Si*Sj, d = c*Sjj - Sj*Sj in 64-bit integers, exact because
+ * rows and cols <= 1024 keeps every term within 2^60.
+ *   phi = 0.5*atan2(2*(double)b, (double)a - (double)d);   co = cos phi, so = sin phi;   mi = (double)Si/(double)c, mj likewise;
+ *   per seed   p = (i - mi)*co + (j - mj)*so,   q = (j - mj)*co - (i - mi)*so;
+ *   h = 0.5*(|co| + |so|) (the half-extent of a unit cell along either axis);  p0 = min p - h, p1 = max p + h, q0, q1 likewise;
+ *   centre, in index coordinates   ci = mi + pc*co - qc*so,  cj = mj + pc*so + qc*co  with pc = 0.5*(p0 + p1), qc = 0.5*(q0 + q1);
+ *   in the map frame m = (x_first - ci*res, y_first - cj*res), x_first = pos_x + (len_x/2 - res/2) and y_first likewise, then the
+ *   planning frame as above;  yaw = phi + theta (both index axes are flipped against the map's: a half turn, which a rectangle
+ *   does not see);  size_x = (p1 - p0)*res + 2*pad,  size_y = (q1 - q0)*res + 2*pad;  FILL = c/((p1 - p0)*(q1 - q0)).
+ * The box contains the whole square of every seed of its component.  size_x lies along the axis of largest variance; it is not
+ * promised to be the larger size.  A principal-axis box is NOT the minimum-area box: an L-shaped wall gets a large box with a low
+ * FILL, and the caller can leave such components to the map channel.
+ *   Determinism: labels are minima of indices, counts and moments integer sums, extents minima and maxima, rows ordered by label: a
+ * layer's bits depend on that layer alone, whatever L and its place in the batch are.
+ * Mapping: union-find per 64 x 16 tile in LDS, lane along i; a seam launch that unites across tile borders by atomic minima;
+ * flatten and count the seeds at each root; one workgroup per layer ranks the roots by ballot prefix; lane = linked cell adds its
+ * moments into its slot by 64-bit integer atomics; one workgroup per slot scans the slot's index window for the extents; one
+ * workgroup per layer filters, compacts and writes the filler rows.  Seven launches and one 16*L-byte clear.  Every find and union
+ * loop is bounded by rows*cols; should a bound ever run out, every value of n_out[l] is -1 and every row of layer l is filler, and
+ * the host-buffer form returns CILQR_ERR_INTERNAL (the device form cannot read n_out without a wait; its caller sees the -1).
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL d2, g, work, label_out, n_out or comp; L < 1; a geometry
+ * cilqr_map_distance rejects; gap2 < 0; K outside 1 ... CILQR_MAX_POLYGONS; min_cells < 1; max_size not > 0 (NaN included); pad
+ * negative or not finite; a pose_stride other than 0 or 3; unknown flag bits; L*K or L*ceil(rows*cols/256) beyond 2^31 - 1
+ * workgroups.  CILQR_ERR_UNSUPPORTED for rows or cols > 1024.  The host-buffer form's arrays — d2, work and label_out, 4 bytes a cell
+ * each, and 24 doubles a row with every output — must fit the device arena reserved at create (CILQR_ERR_ARG otherwise, as for every
+ * host form; this call adds nothing to it). */
+#define CILQR_MAP_OBSTACLE_FIELDS 13
+typedef enum cilqr_map_obstacle_field {
+  CILQR_MO_LABEL = 0,   /* the component's label: its lowest linked cell, i + j*rows */
+  CILQR_MO_CELLS = 1,   /* its seeds */
+  CILQR_MO_LINKED = 2,  /* its linked cells */
+  CILQR_MO_I_MIN = 3,   /* extremes of i and j over its seeds */
+  CILQR_MO_I_MAX = 4,
+  CILQR_MO_J_MIN = 5,
+  CILQR_MO_J_MAX = 6,
+  CILQR_MO_SUM_I = 7,   /* sums of i, j, i*i, i*j, j*j over its seeds */
+  CILQR_MO_SUM_J = 8,
+  CILQR_MO_SUM_II = 9,
+  CILQR_MO_SUM_IJ = 10,
+  CILQR_MO_SUM_JJ = 11,
+  CILQR_MO_FILL = 12    /* seeds per cell of the box's area, in (0, 1] */
+} cilqr_map_obstacle_field;
+#define CILQR_MAP_OBSTACLES_FOUR 1u     /* flags: 4-connectivity (default 8) */
+#define CILQR_MAP_OBSTACLES_FAR 1.0e6   /* metres: where the filler rows stand */
+int cilqr_map_obstacles_device(cilqr_handle* h, void* stream, int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags,
+                               const double* pose, int pose_stride, int K, int min_cells, double max_size, double pad, int32_t* work,
+                               int32_t* label_out, int32_t* n_out, double* comp, double* boxes, double* pose_out, double* dim_out);
+int cilqr_map_obstacles(cilqr_handle* h, int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags, const double* pose,
+                        int pose_stride, int K, int min_cells, double max_size, double pad, int32_t* work, int32_t* label_out,
+                        int32_t* n_out, double* comp, double* boxes, double* pose_out, double* dim_out);
 
 /* --- exact clearance of the ego rectangle to the occupied cells of the map (new) -----------------------------------------------------
  * The map counterpart of CILQR_FP_CLEARANCE: cilqr_footprint_check reports only whether the rectangle covers a cell above the

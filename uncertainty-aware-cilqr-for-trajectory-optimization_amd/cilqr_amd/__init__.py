@@ -67,6 +67,14 @@ FOOTPRINT_FIELDS = 12
 FOOTPRINT_UNKNOWN_HITS, FOOTPRINT_SKIP_MAP = 1, 2  # flags of `footprint_check`
 MAP_DISTANCE_UNKNOWN_SEEDS, MAP_DISTANCE_TO_FREE = 1, 2  # flags of `map_distance`
 MAP_DISTANCE_NONE = 2 ** 31 - 1  # d2 of a layer without a seed
+# `cilqr_map_obstacle_field`: the columns of a component row (`Solver.map_obstacles`)
+MAP_OBSTACLE_FIELDS = 13
+(MO_LABEL, MO_CELLS, MO_LINKED, MO_I_MIN, MO_I_MAX, MO_J_MIN, MO_J_MAX, MO_SUM_I, MO_SUM_J, MO_SUM_II, MO_SUM_IJ, MO_SUM_JJ,
+ MO_FILL) = range(MAP_OBSTACLE_FIELDS)
+MAP_OBSTACLES_FOUR = 1  # flags of `map_obstacles`: 4-connectivity
+MAP_OBSTACLES_FAR = 1.0e6  # metres: where the filler rows stand
+MAX_POLYGONS = 1024
+ERR_INTERNAL = -6
 # `cilqr_map_clearance_field`: the columns of a map clearance row (`Solver.map_clearance`)
 MAP_CLEARANCE_FIELDS = 8
 (MC_CLEARANCE, MC_STEP, MC_CELL, MC_BELOW_STEPS, MC_FIRST_BELOW, MC_TOUCH_STEPS, MC_OFF_MAP_STEPS,
@@ -107,6 +115,7 @@ ABI_SYMBOLS = (
     "cilqr_predict_obstacles", "cilqr_predict_obstacles_device", "cilqr_chance_risk_cov", "cilqr_chance_risk_cov_device",
     "cilqr_footprint_check", "cilqr_footprint_check_device",
     "cilqr_map_distance", "cilqr_map_distance_device", "cilqr_inflate_map", "cilqr_inflate_map_device",
+    "cilqr_map_obstacles", "cilqr_map_obstacles_device",
     "cilqr_map_clearance", "cilqr_map_clearance_device",
     "cilqr_stop_plans", "cilqr_stop_plans_device",
 )
@@ -1088,6 +1097,44 @@ class Solver:
         layer_stride = rows*cols."""
         _check(lib().cilqr_inflate_map_device(self._h, _vp(stream), int(L), _vp(layer), C.c_int64(int(layer_stride)), C.byref(geom),
                                               _vp(d2), C.c_double(inscribed), C.c_double(radius), C.c_double(peak), _vp(layer_out)))
+
+    def map_obstacles(self, d2, geom, K, gap2=0, four=False, pose=None, min_cells=1, max_size=float("inf"), pad=0.0, tables=True):
+        """`cilqr_map_obstacles`: d2 (rows, cols) or (L, rows, cols) int32 as `map_distance` returns it; pose None, (3,) for every
+        layer or (L, 3).  Returns dict(label (L, rows, cols) int32, n (L, 4) int32 = found, of min_cells, rows written, seeds; comp
+        (L, K, MAP_OBSTACLE_FIELDS); boxes (L, K, 5), pose (L, K, 4) and dim (L, K, 2), None with tables=False).  Rows at and beyond
+        n[l, 2] are filler.  The arrays travel through the device arena: large maps and batches take the device form."""
+        d2 = np.asarray(d2, dtype=np.int32)
+        if d2.ndim == 2:
+            d2 = d2[None]
+        if d2.ndim != 3 or d2.shape[1:] != (geom.rows, geom.cols):
+            raise CilqrError("map_obstacles: d2 %s is not (L, %d, %d)" % (d2.shape, geom.rows, geom.cols))
+        n, K = int(d2.shape[0]), int(K)
+        flat = np.ascontiguousarray(d2.transpose(0, 2, 1)).reshape(n, -1)
+        stride = 0
+        if pose is not None:
+            pose = _np64(pose)
+            if pose.shape not in ((3,), (n, 3)):
+                raise CilqrError("map_obstacles: pose %s is neither (3,) nor (%d, 3)" % (pose.shape, n))
+            stride = 3 if pose.ndim == 2 else 0
+        work, label = np.zeros_like(flat), np.zeros_like(flat)
+        counts = np.zeros((n, 4), dtype=np.int32)
+        rows = max(K, 1)
+        comp = np.zeros((n, rows, MAP_OBSTACLE_FIELDS))
+        boxes, pose_out, dim_out = (np.zeros((n, rows, w)) if tables else None for w in (5, 4, 2))
+        _check(lib().cilqr_map_obstacles(self._h, n, _p(flat, _ip), C.byref(geom), int(gap2), C.c_uint32(MAP_OBSTACLES_FOUR if four else 0),
+                                         _p(pose), stride, K, int(min_cells), C.c_double(max_size), C.c_double(pad), _p(work, _ip),
+                                         _p(label, _ip), _p(counts, _ip), _p(comp), _p(boxes), _p(pose_out), _p(dim_out)))
+        return dict(label=label.reshape(n, geom.cols, geom.rows).transpose(0, 2, 1), n=counts, comp=comp, boxes=boxes, pose=pose_out,
+                    dim=dim_out)
+
+    def map_obstacles_device(self, stream, L, d2, geom, K, work, label_out, n_out, comp, boxes=0, pose_out=0, dim_out=0, gap2=0, flags=0,
+                             pose=0, pose_stride=0, min_cells=1, max_size=float("inf"), pad=0.0):
+        """`cilqr_map_obstacles_device`: device addresses; d2, work and label_out (L, rows*cols) int32, n_out (L, 4) int32, comp
+        (L, K, MAP_OBSTACLE_FIELDS), boxes (L, K, 5), pose_out (L, K, 4) and dim_out (L, K, 2) float64 or 0; pose (L or 1, 3) or 0.
+        pose_out / dim_out feed `solve_batch_obstacles_device` with strides (K, 1, 0, 0), M = K."""
+        _check(lib().cilqr_map_obstacles_device(self._h, _vp(stream), int(L), _vp(d2), C.byref(geom), int(gap2), C.c_uint32(int(flags)),
+                                                _vp(pose), int(pose_stride), int(K), int(min_cells), C.c_double(max_size), C.c_double(pad),
+                                                _vp(work), _vp(label_out), _vp(n_out), _vp(comp), _vp(boxes), _vp(pose_out), _vp(dim_out)))
 
     def map_clearance(self, N, X, reach, S=1, margin=0.0, occ_threshold=float("inf"), min_clearance=0.0, base=None,
                       unknown_seeds=False, steps=True):

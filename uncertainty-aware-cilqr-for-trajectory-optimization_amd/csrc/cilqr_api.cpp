@@ -13,6 +13,7 @@
 #include "cilqr_internal.h"
 
 #include "cilqr_handle.h"
+#include "costmap_components.hpp"
 
 namespace cilqr {
 thread_local std::string g_last_error;
@@ -1770,6 +1771,74 @@ int cilqr_inflate_map(cilqr_handle* h, int L, const float* layer, int64_t layer_
   cilqr::HostPlan p(h->d_arena);
   cilqr::plan_inflate_map(p, L, cells, span, layer, d2, layer_out);
   return cilqr::host_call(h, p, [&] { return cilqr_inflate_map_device(h, h->stream, L, layer, layer_stride, g, d2, inscribed, radius, peak, layer_out); });
+}
+
+// ---- obstacles from the map: connected components of occupied cells as boxes (costmap_components.hip) ---------------------------------------
+namespace {
+// what needs no handle; *cells on success
+int map_obstacles_args_check(int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags, int pose_stride, int K,
+                             int min_cells, double max_size, double pad, const int32_t* work, const int32_t* label_out,
+                             const int32_t* n_out, const double* comp, size_t* cells) {
+  if (!d2 || !g || !work || !label_out || !n_out || !comp) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: null required pointer");
+  if (g->rows > cilqr::MAP_OBSTACLES_MAX_SIDE || g->cols > cilqr::MAP_OBSTACLES_MAX_SIDE)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_map_obstacles: %d x %d cells, more than %d along a side", g->rows, g->cols,
+                cilqr::MAP_OBSTACLES_MAX_SIDE);
+  size_t span = 0;
+  // (the geometry and L as cilqr_map_distance takes them: d2 stands in for its layers, dense)
+  int rc = map_layers_check("cilqr_map_obstacles", L, (const float*)d2, 0, g, cells, &span);
+  if (rc) return rc;
+  if (gap2 < 0) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: gap2 = %d is negative", gap2);
+  if (flags & ~CILQR_MAP_OBSTACLES_FOUR) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: unknown flag bits 0x%x", flags);
+  if (pose_stride != 0 && pose_stride != 3) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: pose_stride = %d, must be 0 or 3", pose_stride);
+  if (K < 1 || K > CILQR_MAX_POLYGONS) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: K = %d outside [1,%d]", K, CILQR_MAX_POLYGONS);
+  if (min_cells < 1) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: min_cells = %d, must be at least 1", min_cells);
+  if (!(max_size > 0.0)) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: max_size is not > 0");
+  if (!(pad >= 0.0 && pad <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: pad is negative or not finite");
+  const int64_t tiles = (int64_t)((g->rows + cilqr::CC_TILE_I - 1) / cilqr::CC_TILE_I) * ((g->cols + cilqr::CC_TILE_J - 1) / cilqr::CC_TILE_J);
+  if ((int64_t)L * (tiles > K ? tiles : K) > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_map_obstacles: L = %d layers beyond 2^31 - 1 workgroups", L);
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_map_obstacles_device(cilqr_handle* h, void* stream, int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags,
+                               const double* pose, int pose_stride, int K, int min_cells, double max_size, double pad, int32_t* work,
+                               int32_t* label_out, int32_t* n_out, double* comp, double* boxes, double* pose_out, double* dim_out) {
+  size_t cells = 0;
+  int rc = map_obstacles_args_check(L, d2, g, gap2, flags, pose_stride, K, min_cells, max_size, pad, work, label_out, n_out, comp, &cells);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::MapObstaclesArgs a = {};
+  a.d2 = d2; a.pose = pose; a.work = work; a.label_out = label_out; a.n_out = n_out; a.comp = comp;
+  a.boxes = boxes; a.pose_out = pose_out; a.dim_out = dim_out;
+  a.res = g->res;
+  a.x_first = g->pos_x + (0.5 * g->len_x - 0.5 * g->res);  // cell (0,0) centre, as the uncertainty map forms it
+  a.y_first = g->pos_y + (0.5 * g->len_y - 0.5 * g->res);
+  a.max_size = max_size; a.pad = pad;
+  a.L = L; a.rows = g->rows; a.cols = g->cols; a.gap2 = gap2; a.K = K; a.min_cells = min_cells; a.pose_stride = pose_stride;
+  a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_map_obstacles(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_map_obstacles(cilqr_handle* h, int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags, const double* pose,
+                        int pose_stride, int K, int min_cells, double max_size, double pad, int32_t* work, int32_t* label_out,
+                        int32_t* n_out, double* comp, double* boxes, double* pose_out, double* dim_out) {
+  size_t cells = 0;
+  int rc = map_obstacles_args_check(L, d2, g, gap2, flags, pose_stride, K, min_cells, max_size, pad, work, label_out, n_out, comp, &cells);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  const int32_t* counts = n_out;  // the caller's, read once the results are back
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_map_obstacles(p, L, cells, K, pose ? (pose_stride ? L : 1) : 0, d2, pose, work, label_out, n_out, comp, boxes, pose_out, dim_out);
+  rc = cilqr::host_call(h, p, [&] {
+    return cilqr_map_obstacles_device(h, h->stream, L, d2, g, gap2, flags, pose, pose_stride, K, min_cells, max_size, pad, work, label_out,
+                                      n_out, comp, boxes, pose_out, dim_out);
+  });
+  if (rc) return rc;
+  for (int l = 0; l < L; ++l)
+    if (counts[4 * l + 2] < 0) return fail(CILQR_ERR_INTERNAL, "cilqr_map_obstacles: a loop bound ran out in layer %d", l);
+  return CILQR_OK;
 }
 
 // ---- exact clearance of the ego rectangle to the occupied cells of the map (cilqr_map_clearance.hip) ---------------------------------------

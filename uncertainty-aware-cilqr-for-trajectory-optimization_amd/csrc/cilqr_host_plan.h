@@ -382,6 +382,24 @@ inline void plan_inflate_map(HostPlan& p, size_t L, size_t cells, size_t span, c
   p.out(layer_out, L * cells);
 }
 
+// cilqr_map_obstacles: 9 arrays.  In: d2 and the poses; then `work`, scratch that travels neither way (a place and no host
+// address); out: label_out, n_out, comp and the three optional tables.  Three arrays of 4 bytes a cell and 24 doubles a row; fits
+// as plan_map_distance does.
+inline void plan_map_obstacles(HostPlan& p, size_t L, size_t cells, size_t K, size_t poses, const int32_t*& d2, const double*& pose,
+                               int32_t*& work, int32_t*& label_out, int32_t*& n_out, double*& comp, double*& boxes, double*& pose_out,
+                               double*& dim_out) {
+  p.in(d2, L * cells);
+  p.in(pose, poses * 3);
+  work = nullptr;
+  p.out(work, L * cells, true);
+  p.out(label_out, L * cells);
+  p.out(n_out, L * 4);
+  p.out(comp, L * K * CILQR_MAP_OBSTACLE_FIELDS);
+  p.out(boxes, L * K * 5);
+  p.out(pose_out, L * K * 4);
+  p.out(dim_out, L * K * 2);
+}
+
 // cilqr_map_clearance: 5 arrays; R = B·S rows; the map is the handle's.  Per row 5·N + 14 doubles with every output — X, base, the mc
 // row, step_clearance, total — against the 28·N + 50 per unit of max_batch that host_arena_bytes reserves below: every R <= max_batch
 // fits, and the 5 roundings stay within its 32 x 16 bytes.

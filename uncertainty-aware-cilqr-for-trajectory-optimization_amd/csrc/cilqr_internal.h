@@ -421,6 +421,29 @@ struct InflateMapArgs {
 };
 hipError_t launch_inflate_map(const InflateMapArgs& a, hipStream_t stream);
 
+// Connected components of the linked cells of L distance fields, and their boxes (costmap_components.hip; cilqr_map_obstacles*).
+// Seven launches behind one 16·L-byte clear of n_out: tiles (union-find in LDS), seams (global atomic minima), flatten + count,
+// rank (one workgroup per layer), moments (lane = linked cell, integer atomics into the slot's row of comp), extents (one workgroup
+// per slot), finish (one workgroup per layer: filter, compact, filler rows).  Everything is dense, rows·cols or K rows apart.
+constexpr int MAP_OBSTACLES_THREADS = 256;
+constexpr int MAP_OBSTACLES_RANK_THREADS = 1024;
+constexpr int MAP_OBSTACLES_MAX_SIDE = 1024;  // rows, cols at most: every term of c·Sii - Si² stays within 2^60
+struct MapObstaclesArgs {
+  const int32_t* d2;   // [L][rows·cols]
+  const double* pose;  // [L or 1][3] or null
+  int32_t* work;       // [L][rows·cols]
+  int32_t* label_out;  // [L][rows·cols]
+  int32_t* n_out;      // [L][4]
+  double* comp;        // [L][K][CILQR_MAP_OBSTACLE_FIELDS]
+  double* boxes;       // [L][K][5] or null
+  double* pose_out;    // [L][K][4] or null
+  double* dim_out;     // [L][K][2] or null
+  double res, x_first, y_first, max_size, pad;
+  int32_t L, rows, cols, gap2, K, min_cells, pose_stride;
+  uint32_t flags;      // CILQR_MAP_OBSTACLES_*
+};
+hipError_t launch_map_obstacles(const MapObstaclesArgs& a, hipStream_t stream);
+
 // Exact clearance of the ego rectangle to the occupied cells of the map set on the handle (cilqr_map_clearance.hip;
 // cilqr_map_clearance*).  Two launches: wavefront = (row, step), FOOTPRINT_WAVES steps per workgroup, lanes over the cells of the
 // window; then one wavefront per row for the fold.  `s` carries B (SOLVES), N and unc; row r = b·S + s reads X at r and the layer and

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <string.h>
 
 #include <stdexcept>
@@ -102,6 +103,7 @@ iLQR::~iLQR() {
   if (block_stream_) (void)hipStreamSynchronize((hipStream_t)block_stream_);
   if (block_dev_) (void)hipFree(block_dev_);
   if (map_dev_) (void)hipFree(map_dev_);
+  if (mo_dev_) (void)hipFree(mo_dev_);
   if (block_stream_) (void)hipStreamDestroy((hipStream_t)block_stream_);
   cilqr_destroy(h_);
 }
@@ -115,7 +117,8 @@ void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
   if (tracked_horizon_ >= 0) obs_cov_.clear();  // (the covariance the prediction installed goes with its obstacles)
   tracked_horizon_ = -1;
   obstacles_ = obstacles;
-  pack_obstacles();
+  map_rows_ = 0;
+  append_map_rows();  // (the rows of set_map_obstacles stay behind the new set; packs)
 }
 
 void iLQR::clear_Obstacle() {
@@ -123,7 +126,8 @@ void iLQR::clear_Obstacle() {
   tracked_horizon_ = -1;
   tracks_.clear(); track_dims_.clear(); track_cov_.clear(); track_Q_.clear();
   obstacles_.clear();
-  pack_obstacles();
+  map_rows_ = 0;
+  append_map_rows();
 }
 
 void iLQR::set_tracked_obstacles(const std::vector<double>& tracks, const std::vector<double>& dims, const std::vector<double>& cov,
@@ -153,6 +157,7 @@ void iLQR::install_tracked() {
     m += n;
   }
   obstacles_.clear();
+  map_rows_ = 0;  // (a run under set_map_obstacles throws while tracks are set: its rows are not kept behind them)
   for (int m = 0; m < M; ++m) {
     Matrix d(2, N), r(4, N);
     memcpy(d.a.data(), &dim[(size_t)m * 2 * N], (size_t)2 * N * sizeof(double));   // (column-major 2 x N is the table's [2N] row)
@@ -175,6 +180,83 @@ void iLQR::set_uncertainty_map(const Uncertainty& u) {
   apply_map(u);
   unc_ = u;  // (kept: set_map_tightening moves the layer between the handle's device copy and this object's)
   map_set_ = true;
+  if (mo_on_) { extract_map_obstacles(); append_map_rows(); }
+}
+
+void iLQR::set_map_obstacles(double occ_threshold, double gap, int min_cells, double max_size, double pad, int K, bool on) {
+  if (on && (occ_threshold != occ_threshold || !(gap >= 0.0 && gap <= 1.7e308) || min_cells < 1 || !(max_size > 0.0) ||
+             !(pad >= 0.0 && pad <= 1.7e308) || K < 1 || K > CILQR_MAX_POLYGONS))
+    throw std::runtime_error("set_map_obstacles: needs a threshold that is not NaN, gap and pad >= 0 and finite, min_cells >= 1, max_size > 0 and K in 1 ... CILQR_MAX_POLYGONS");
+  mo_on_ = on;
+  if (on) { mo_threshold_ = occ_threshold; mo_gap_ = gap; mo_min_cells_ = min_cells; mo_max_size_ = max_size; mo_pad_ = pad; mo_K_ = K; }
+  if (on && map_set_) extract_map_obstacles();
+  if (!on) { last_map_obstacles.clear(); memset(last_map_obstacle_counts, 0, sizeof(last_map_obstacle_counts)); }
+  if (on ? map_set_ : map_rows_ > 0) append_map_rows();
+}
+
+// The device forms on a block of this object's own (the layer, d2, work, label_out, then n_out, comp, boxes and the pose), grown when a
+// larger map or K comes: a map's three arrays of 4 bytes a cell do not fit the arena of a handle made for a few candidates, which is
+// sized by solves.  The results are those of the host forms, bit for bit.
+void iLQR::extract_map_obstacles() {
+  const cilqr_map_geom& g = unc_.geom;
+  const size_t cells = (size_t)g.rows * g.cols, ints = (4 * cells + 4 + 1) / 2 * 2, K = (size_t)mo_K_;
+  const size_t doubles = K * (CILQR_MAP_OBSTACLE_FIELDS + 5) + 3, need = ints * sizeof(int32_t) + doubles * sizeof(double);
+  const char* what = "set_map_obstacles: HIP runtime call failed";
+  if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error(what);
+  if (need > mo_dev_cap_) {
+    if (mo_dev_) (void)hipFree(mo_dev_);
+    mo_dev_ = nullptr; mo_dev_cap_ = 0;
+    if (hipMalloc(&mo_dev_, need) != hipSuccess) throw std::runtime_error("set_map_obstacles: hipMalloc failed");
+    mo_dev_cap_ = need;
+  }
+  float* layer = (float*)mo_dev_;
+  int32_t *d2 = (int32_t*)mo_dev_ + cells, *work = d2 + cells, *label = work + cells, *n_out = label + cells;
+  double *comp = (double*)((int32_t*)mo_dev_ + ints), *boxes = comp + K * CILQR_MAP_OBSTACLE_FIELDS, *pose_dev = boxes + K * 5;
+  const double r = mo_gap_ / g.res, r2 = floor(r * r);
+  const int gap2 = r2 < 2147483646.0 ? (int)r2 : 2147483646;
+  const double pose[3] = {unc_.pose_x, unc_.pose_y, unc_.pose_theta};
+  // (the null stream: each copy below waits for what was enqueued before it)
+  if (hipMemcpy(layer, unc_.layer.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(pose_dev, pose, sizeof(pose), hipMemcpyHostToDevice) != hipSuccess)
+    throw std::runtime_error(what);
+  check(cilqr_map_distance_device(h_, nullptr, 1, layer, 0, &g, mo_threshold_, 0u, d2, nullptr), "cilqr_map_distance_device");
+  check(cilqr_map_obstacles_device(h_, nullptr, 1, d2, &g, gap2, 0u, pose_dev, 0, mo_K_, mo_min_cells_, mo_max_size_, mo_pad_, work, label, n_out,
+                                   comp, boxes, nullptr, nullptr),
+        "cilqr_map_obstacles_device");
+  std::vector<double> rows(K * 5);
+  if (hipMemcpy(last_map_obstacle_counts, n_out, 4 * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(rows.data(), boxes, rows.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error(what);
+  if (last_map_obstacle_counts[2] < 0) throw std::runtime_error("set_map_obstacles: cilqr_map_obstacles ran out of a loop bound (CILQR_ERR_INTERNAL)");
+  last_map_obstacles.assign(rows.begin(), rows.begin() + (size_t)5 * last_map_obstacle_counts[2]);
+}
+
+void iLQR::append_map_rows() {
+  obstacles_.erase(obstacles_.end() - map_rows_, obstacles_.end());
+  map_rows_ = 0;
+  const int N = params.horizon, n = (int)(last_map_obstacles.size() / 5);
+  if ((int)obstacles_.size() + n > max_obstacles_) {
+    pack_obstacles();
+    throw std::runtime_error("set_map_obstacles: the obstacles of set_Obstacle and the rows from the map exceed max_obstacles");
+  }
+  for (int k = 0; k < n; ++k) {
+    const double* b = &last_map_obstacles[(size_t)5 * k];
+    Matrix d(2, N), r(4, N);
+    for (int t = 0; t < N; ++t) {
+      d(0, t) = b[3]; d(1, t) = b[4];
+      r(0, t) = b[0]; r(1, t) = b[1]; r(2, t) = 0.0; r(3, t) = b[2];
+    }
+    obstacles_.emplace_back(params, d, r);
+  }
+  map_rows_ = n;
+  map_rows_horizon_ = N;
+  pack_obstacles();
+}
+
+void iLQR::check_map_obstacle_conflicts() const {
+  if (mo_on_ && (n_samples_ > 0 || tracked_horizon_ >= 0 || !obs_cov_.empty()))
+    throw std::logic_error("set_map_obstacles: the rows from the map have neither samples nor a covariance: not with set_obstacle_samples, "
+                           "set_tracked_obstacles or set_obstacle_covariance");
 }
 
 namespace {
@@ -229,6 +311,9 @@ cilqr_uncertainty_map iLQR::device_map(bool tightened) const {
 void iLQR::clear_uncertainty_map() {
   check(cilqr_clear_uncertainty_map(h_), "cilqr_clear_uncertainty_map");
   map_set_ = false;
+  last_map_obstacles.clear();
+  memset(last_map_obstacle_counts, 0, sizeof(last_map_obstacle_counts));
+  if (map_rows_ > 0) append_map_rows();  // (the rows go with their map)
 }
 
 void iLQR::set_global_plan(const Matrix& global_plan) {
@@ -270,6 +355,7 @@ void iLQR::pack_obstacles() {
 
 cilqr_obstacles iLQR::obstacle_strides() {
   if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();  // (the horizon changed: predict again)
+  refresh_map_rows();
   if (packed_horizon_ != params.horizon) pack_obstacles();  // (params is public: the horizon may have changed since set_Obstacle)
   cilqr_obstacles o{};
   o.pose = obs_pose_.data();
@@ -285,6 +371,8 @@ cilqr_obstacles iLQR::obstacle_strides() {
 void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double poly_coeffs[6],
                                    const std::vector<double>& x_local_plan) {
   if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
+  check_map_obstacle_conflicts();
+  refresh_map_rows();
   const int N = params.horizon, M = (int)obstacles_.size();
   if (U.rows != 2 || U.cols != N) throw std::runtime_error("get_optimal_control_seq: U must be 2×horizon");
   if (x_local_plan.empty()) throw std::runtime_error("get_optimal_control_seq: empty x_local_plan");
@@ -425,6 +513,8 @@ void iLQR::fetch_solved(const Block& d, int b, Solved& s) const {
 
 int iLQR::run_candidates(const std::vector<double>& ego_states) {
   if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
+  check_map_obstacle_conflicts();
+  refresh_map_rows();
   const int B = (int)(ego_states.size() / 4), N = params.horizon, M = (int)obstacles_.size();
   if (B < 1 || B > max_candidates_) throw std::runtime_error("run_candidates: candidate count outside [1, max_candidates]");
   if (global_plan_.cols < 1) throw std::runtime_error("run_candidates: set_global_plan was not called");

@@ -281,6 +281,20 @@ class iLQR {
   // rounds == 0 switches it off (the default: nothing changes for existing callers).  A negative rounds or window, or an inflate or
   // z_max that is negative or not finite, throws std::runtime_error.
   void set_track_map(double inflate, double z_max, int window, int rounds = 1, bool ellipses = true);
+  // Map obstacles: the other direction of the map channel.  In the live node's configuration the occupied cells of the layer are all
+  // the planner knows of obstacles, and the barrier, CILQR_FP_CLEARANCE and the chance risk have no rectangle to act on.  While this
+  // setter is on, every set_uncertainty_map runs, on that layer and pose, cilqr_map_distance_device(occ_threshold) ->
+  // cilqr_map_obstacles_device(gap2 = floor((gap/res)^2), 8-connectivity, min_cells, max_size, pad, K) and installs the rows written BEHIND
+  // the obstacles of set_Obstacle, constant over the horizon: the solve, and every later score and check, sees them as if set_Obstacle
+  // had been given them too.  last_map_obstacles holds the rows, 5 values each — (x, y, yaw, size_x, size_y), the boxes of
+  // cilqr_map_obstacles — and last_map_obstacle_counts its n_out.  set_Obstacle and clear_Obstacle replace the obstacles in front of
+  // the rows and keep the rows; clear_uncertainty_map, or on = false, removes them.  The rows count against max_obstacles
+  // (std::runtime_error beyond).  The two calls run in a device block of this object's own — a map's arrays, three of 4 bytes a cell,
+  // do not fit the arena of a handle made for a few candidates — grown when a larger map or K comes, never per call; their results are
+  // those of the host forms, bit for bit.  With
+  // set_obstacle_samples, set_tracked_obstacles or set_obstacle_covariance in force a run throws std::logic_error: the rows have
+  // neither samples nor a covariance.  Off (the default): nothing changes for existing callers.
+  void set_map_obstacles(double occ_threshold, double gap, int min_cells, double max_size, double pad, int K, bool on = true);
   // Test hook: cilqr_debug_uncertainty_cost on the map this object's handle holds right now, at n = states.size() / 4 states
   // (x, y, v, theta) -> n costs, then 2n of vx, then 3n of mx.  Throws std::runtime_error when no map is set.
   std::vector<double> debug_map_cost(const std::vector<double>& states) const;
@@ -347,6 +361,9 @@ class iLQR {
   std::vector<double> last_tighten_map, last_tighten_map_risk_before;  // CILQR_TIGHTEN_MAP_FIELDS per solve; CR_STEP_RISK per solve
   // run_step / run_candidates under set_track_map with tracks and an uncertainty map set; empty otherwise
   std::vector<double> last_track_map;  // CILQR_TRACK_MAP_FIELDS per solve
+  // set_uncertainty_map under set_map_obstacles; empty / zero otherwise
+  std::vector<double> last_map_obstacles;  // 5 per row: (x, y, yaw, size_x, size_y)
+  int32_t last_map_obstacle_counts[4] = {0, 0, 0, 0};  // n_out of cilqr_map_obstacles
 
  private:
   void pack_obstacles();
@@ -460,6 +477,16 @@ class iLQR {
   int solve_obstacles() const;  // the M the SOLVES read: 0 under the track map with ellipses off
   void check_track_map_conflicts() const;  // throws std::logic_error, before a run enqueues anything
   bool map_in_block() const { return map_tighten_ || tm_rounds_ > 0; }  // the map lives in map_dev_
+  // map obstacles (set_map_obstacles): the last map_rows_ entries of obstacles_ are last_map_obstacles over map_rows_horizon_ steps
+  bool mo_on_ = false;
+  double mo_threshold_ = 0.0, mo_gap_ = 0.0, mo_max_size_ = 0.0, mo_pad_ = 0.0;
+  int mo_min_cells_ = 1, mo_K_ = 1, map_rows_ = 0, map_rows_horizon_ = -1;
+  void* mo_dev_ = nullptr;
+  size_t mo_dev_cap_ = 0;
+  void extract_map_obstacles();                // unc_ -> last_map_obstacles, last_map_obstacle_counts
+  void append_map_rows();                      // replaces the map's entries of obstacles_ by last_map_obstacles, packs
+  void refresh_map_rows() { if (map_rows_ && map_rows_horizon_ != params.horizon) append_map_rows(); }  // (the horizon changed)
+  void check_map_obstacle_conflicts() const;   // throws std::logic_error, before a run enqueues anything
 };
 
 }  // namespace cilqr_host

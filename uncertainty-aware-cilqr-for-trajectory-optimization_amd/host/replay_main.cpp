@@ -2,7 +2,8 @@
 // odomCallback does per odometry message (I/ilqr_uncertainty_node.cpp:111-130: set_global_plan → set_Obstacle → run_step →
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
-//   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]]     → one line per tick on stdout
+//   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]
+//                                                                                             → one line per tick on stdout
 //
 // --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
 // (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
@@ -14,6 +15,10 @@
 // then ends with " stop <plan> <level> <pick>": plan 1 when the published plan is a stop plan, 0 when it is the solved one, -1 when the
 // tick has no plan at all (X and U are then the tick's before); level its level index or -1; pick the stop pick's row or -1.
 //
+// --map-obstacles: iLQR::set_map_obstacles(thr, gap, min_cells, max_size, pad 0, K = 16): on every tick that carries a `map` record
+// the occupied cells of its layer (value > thr) are clustered into boxes, which are installed behind the tick's obstacles; the line
+// then ends with " map_obstacles <installed> <components>".  A tick without a map record clears the map (0 0).
+//
 // Log (whitespace-separated, '#' starts a comment line):
 //   cilqr-replay 1
 //   horizon <N>
@@ -22,6 +27,8 @@
 //   ego <x> <y> <v> <theta>
 //   obstacles <M>       followed by M lines "x y v theta length width" (held over the horizon, as the node's static-obstacle
 //                       callback replicates them, I/ilqr_uncertainty_node.cpp:175-185)
+//   map <len_x> <len_y> <res> <pos_x> <pos_y> <pose_x> <pose_y> <pose_theta> <n>      optional; followed by n lines "i j value": the cells
+//                       of the layer that are not 0 (the lidar layer of the map node, vehicle frame geometry, the pose it was made at)
 // Output per tick: "experiment <start_pos 4> <planning_time> <iterations> <exit> <J> X <4(N+1) values> U <2N values>" —
 // X and U in the vehiclepub/Experiment flattening (:243-284).
 #include <chrono>
@@ -71,15 +78,16 @@ struct Tokens {
 
 int main(int argc, char** argv) {
   std::vector<const char*> pos;  // the log and the device; options may stand anywhere
-  const char *tighten = nullptr, *stop = nullptr;
+  const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
     else if (strcmp(argv[i], "--stop-fallback") == 0 && i + 1 < argc) stop = argv[++i];
+    else if (strcmp(argv[i], "--map-obstacles") == 0 && i + 1 < argc) map_obstacles = argv[++i];
     else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
     else pos.push_back(argv[i]);
   }
   if (pos.empty() || pos.size() > 2) {
-    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]\n", argv[0]);
     return 2;
   }
   try {
@@ -114,7 +122,7 @@ int main(int argc, char** argv) {
       if (*q == ':') hold = atoi(q + 1);
       else if (*q != 0) throw std::runtime_error("--stop-fallback takes d1[,d2...][:hold]");
     }
-    iLQR planner(params, pos.size() > 1 ? atoi(pos[1]) : 0, 64, stop ? (int)levels.size() : 1);
+    iLQR planner(params, pos.size() > 1 ? atoi(pos[1]) : 0, map_obstacles ? 64 + 16 : 64, stop ? (int)levels.size() : 1);
     if (stop) {
       planner.set_footprint_check(0.0, INFINITY);
       planner.set_stop_fallback(levels, hold);
@@ -129,6 +137,13 @@ int main(int argc, char** argv) {
       Sigma0[15] = 0.017 * 0.017;
       planner.set_chance_tightening(Sigma0, nullptr, eps, rounds);
     }
+    if (map_obstacles) {
+      double thr = 0.0, gap = 0.0, max_size = 0.0;
+      int min_cells = 0;
+      if (sscanf(map_obstacles, "%lf,%lf,%d,%lf", &thr, &gap, &min_cells, &max_size) != 4) throw std::runtime_error("--map-obstacles takes thr,gap,min_cells,max_size");
+      planner.set_map_obstacles(thr, gap, min_cells, max_size, 0.0, 16);
+    }
+    bool map_on = false;
     while (!in.done()) {
       in.expect("tick");
       in.expect("ego");
@@ -150,6 +165,26 @@ int main(int argc, char** argv) {
       }
       planner.set_global_plan(path);
       if (M) planner.set_Obstacle(obstacles); else planner.clear_Obstacle();
+      if (!in.done() && in.t[in.at] == "map") {
+        in.expect("map");
+        double v[8];
+        for (double& x : v) x = in.num();
+        Uncertainty um;
+        if (cilqr_map_geom_set(&um.geom, v[0], v[1], v[2], v[3], v[4]) != CILQR_OK) throw std::runtime_error(std::string("replay log: map: ") + cilqr_last_error());
+        um.pose_x = v[5]; um.pose_y = v[6]; um.pose_theta = v[7];
+        um.layer.assign((size_t)um.geom.rows * um.geom.cols, 0.0f);
+        for (int n = in.integer(); n > 0; --n) {
+          const int i = in.integer(), j = in.integer();
+          const double value = in.num();
+          if (i < 0 || i >= um.geom.rows || j < 0 || j >= um.geom.cols) throw std::runtime_error("replay log: map cell outside the layer");
+          um.layer[(size_t)j * um.geom.rows + i] = (float)value;
+        }
+        planner.set_uncertainty_map(um);
+        map_on = true;
+      } else if (map_on) {
+        planner.clear_uncertainty_map();
+        map_on = false;
+      }
       const auto t0 = std::chrono::high_resolution_clock::now();
       int picked = 0;
       if (stop) picked = planner.run_candidates(std::vector<double>(ego, ego + 4));
@@ -164,6 +199,7 @@ int main(int argc, char** argv) {
       if (!planner.last_tighten.empty())
         printf(" tighten %.17g %.17g %d %d %.17g", planner.last_tighten[CILQR_TG_MAX_DA], planner.last_tighten[CILQR_TG_MAX_DB],
                (int)planner.last_tighten[CILQR_TG_MAX_ENTRY], (int)planner.last_tighten[CILQR_TG_CAPPED], planner.last_tighten_risk_before[0]);
+      if (map_obstacles) printf(" map_obstacles %d %d", planner.last_map_obstacle_counts[2], planner.last_map_obstacle_counts[0]);
       if (stop) printf(" stop %d %d %d", picked < 0 ? -1 : planner.last_stop_level >= 0 ? 1 : 0, planner.last_stop_level, planner.last_stop_pick);
       printf("\n");
     }
