@@ -45,12 +45,26 @@ print("R per call: %.0f -> %.0f per step" % ((d[m, 2] / nR[m]).mean(), (d[m, 2] 
 print("F per call: %.0f -> %.0f per step" % ((d[m, 3] / nR[m]).mean(), (d[m, 3] / nR[m]).mean() / N))
 w = int(np.argmax(d[:, 7]))
 print("slowest solve %d: pro %d L %d R %d F %d epi %d nL %d nR %d total %d" % ((w,) + tuple(int(v) for v in d[w][:8])))
+for q in [int(v) for v in os.environ.get("SOLVES", "").split(",") if v]:  # named solves, e.g. another build's slowest one
+    print("solve %d: pro %d L %d R %d F %d epi %d nL %d nR %d total %d | wait at A %d | R %.1f F %.1f ticks per step"
+          % ((q,) + tuple(int(v) for v in d[q][:8]) + (int(d[q, 10]), d[q, 2] / max(nR[q], 1) / N, d[q, 3] / max(nR[q], 1) / N)))
 if os.environ.get("SHARE"):  # shared-phase-L kernel: slots 8..10 = aux busy ticks, aux calls, main's wait at barrier A
     k = np.maximum(d[:, 9], 1)
     print("aux wavefront: %.0f ticks per linearisation (calls mean %.1f) | second aux wavefront %.0f | main waits %.0f ticks per linearisation at barrier A"
           % ((d[:, 8] / k).mean(), d[:, 9].mean(), (d[:, 11] / k).mean(), (d[:, 10] / nL).mean()))
     w = int(np.argmax(d[:, 7]))
     print("slowest solve %d: aux %.0f / %.0f ticks per linearisation, main waits %.0f" % (w, d[w, 8] / k[w], d[w, 11] / k[w], d[w, 10] / nL[w]))
+    if s.solve_wavefronts(B, N, M) == 2 and N <= 64 and d[:, 14].sum() > 0:
+        # two wavefronts, one step per lane: phase L's aux share in two rounds — slot 11 = aux busy ticks in round 1 (not a second aux
+        # wavefront's), 14 = in round 2, 15 = main's wait at barrier A2 inside phase R (counted in R)
+        print("two rounds: aux round 1 %.0f | round 2 %.0f ticks per linearisation | main waits %.0f ticks per pass at barrier A2"
+              % ((d[:, 11] / k).mean(), (d[:, 14] / k).mean(), (d[m, 15] / nR[m]).mean()))
+        print("slowest solve %d: L %.0f per linearisation (wait at A %.0f) | aux round 1 %.0f, round 2 %.0f | wait at A2 %.0f per pass | R %.1f F %.1f ticks per step | total %d"
+              % (w, d[w, 1] / nL[w], d[w, 10] / nL[w], d[w, 11] / k[w], d[w, 14] / k[w], d[w, 15] / max(nR[w], 1), d[w, 2] / max(nR[w], 1) / N,
+                 d[w, 3] / max(nR[w], 1) / N, d[w, 7]))
+    else:
+        print("slowest solve %d: L %.0f per linearisation (wait at A %.0f) | R %.1f F %.1f ticks per step | total %d"
+              % (w, d[w, 1] / nL[w], d[w, 10] / nL[w], d[w, 2] / max(nR[w], 1) / N, d[w, 3] / max(nR[w], 1) / N, d[w, 7]))
 elif os.environ.get("PAIR"):  # two-wavefront kernel: slots 8..11 are the aux wavefront's account
     k = d[:, 11]
     print("aux wavefront, ticks per linearisation: waiting for states %.0f | chunk work %.0f | from the last state's arrival to its barrier %.0f  (calls mean %.1f)"

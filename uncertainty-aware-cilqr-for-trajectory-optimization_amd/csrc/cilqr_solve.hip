@@ -669,9 +669,16 @@ __device__ __forceinline__ void mfma_place(const lds_f64*& ptr, int& stride, int
 //   * the next step's five operand reads stand together behind the second and third product, with one wait;
 //   * the reciprocal's Newton steps stand behind the fourth product, not before it, the store of Db in its first states;
 //   * the gain store stands alone behind the fifth product, its offset and the cursors move on in front of and behind the copies.
-template <bool DIAG>
+// SEG (the two-wavefront share kernel's short form; 0 everywhere else, which compiles to the unsegmented loop): the trips run in two
+// segments, `seg_trips` of them, then a workgroup barrier (A2 of that kernel), then the rest, everything in the same registers.
+// The reads run one step ahead, so after k trips the records N - 1 … N - 1 - 2k have been read and the steps N - 1 … N - 2k
+// computed: the caller chooses k with N - 1 - 2k at or above the lowest record that is finished when R starts.  The barrier
+// waits for LDS only (lgkmcnt), not for the gains' global stores.  SEG = 2: *seg_wait += the ticks spent at that barrier.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <bool DIAG, int SEG = 0>
 __device__ __forceinline__ bool riccati_mfma_smem(int N, const double* rec, double* fwd, const double* cst, double inv_half_dt, double lamb_in,
-                                                  unsigned long long* sub) {
+                                                  unsigned long long* sub, int seg_trips = 0, unsigned long long* seg_wait = nullptr) {
   constexpr int C0 = -1, C1 = -2, CDT = -3, CW = -4, C2 = -5;
   const int lane = threadIdx.x;
   const int e = ((lane >> 4) << 2) | (lane & 3);  // 4·r + c of this lane's entry
@@ -709,7 +716,10 @@ __device__ __forceinline__ bool riccati_mfma_smem(int N, const double* rec, doub
   // fetched while step t + 1 computed — the reads run one step ahead of the computation, they stand before this store in program
   // order, and one wavefront's LDS instructions execute in order — the gains of this form do not go to LDS, phase L rewrites all 14
   // slots of every record before they are read again, and no other wavefront touches the records during phase R (the aux
-  // wavefronts of the share kernels sleep at their barrier).  Like the cursors, the position is that of the LOWER step of a pair.
+  // wavefronts of the share kernels sleep at their barrier).  SEG: the aux wavefront does work during the first segment — it
+  // finishes the records of the steps below the split, slots 0-5 and 10-13 — and that segment computes, and so stores into, the
+  // steps N - 1 … N - 2·seg_trips only, all above the split: the two sets of records are disjoint, and behind the barrier the aux
+  // wavefront sleeps as before.  Like the cursors, the position is that of the LOWER step of a pair.
   // (N = 1: qp and the cursors are formed as rec - RECF and only [RECF] of them is touched; a 32-bit LDS address must not wrap
   //  below 0 on the way, which holds because path samples and trajectories lie in front of the records in every kernel's LDS)
   lds_f64* qp = (lds_f64*)rec + (N - 2) * RECF + (lane == 4 ? 0 : lane == 5 ? 1 : lane == 21 ? 2 : 3 + lane % 11);
@@ -788,9 +798,24 @@ __device__ __forceinline__ bool riccati_mfma_smem(int N, const double* rec, doub
   using K3 = std::integral_constant<int, 3>;
   // two steps per trip, the last one or two peeled so that no read reaches below the first record; one counter, of trips (counting
   // steps down by two, hipcc keeps a second copy of the step for the test behind the loop)
-  for (int trips = (N - 1) >> 1; trips > 0; --trips) {
-    step(oa, K0(), Upper());
-    step(ob, K1(), Lower());
+  if (SEG) {  // the trips above the split, then the barrier in front of the first read of a record below it, then the others
+    for (int trips = seg_trips; trips > 0; --trips) {
+      step(oa, K0(), Upper());
+      step(ob, K1(), Lower());
+    }
+    unsigned long long w0 = 0;
+    if (SEG == 2) w0 = stamp_after(V);
+    lds_barrier();
+    if (SEG == 2) *seg_wait += __builtin_readcyclecounter() - w0;
+    for (int trips = ((N - 1) >> 1) - seg_trips; trips > 0; --trips) {
+      step(oa, K0(), Upper());
+      step(ob, K1(), Lower());
+    }
+  } else {
+    for (int trips = (N - 1) >> 1; trips > 0; --trips) {
+      step(oa, K0(), Upper());
+      step(ob, K1(), Lower());
+    }
   }
   if (((N - 1) & 1) != 0) {
     step(oa, K2(), Upper());
@@ -1888,8 +1913,33 @@ __global__ __launch_bounds__(W * WAVE, 2) void cilqr_solve_split_kernel(SolveArg
 // not depend on which wavefront formed which slot — results are bit-identical to cilqr_solve_kernel's (tests/test_gpu_parity.py,
 // test_share_kernel_changes_no_bit).  Horizons up to 64 on one step per lane, up to 127 on two (LONG); obstacle table in LDS; with or
 // without an uncertainty map (UNC); early-exit mode.
+// TWO ROUNDS (W = 2, one step per lane, no map — the production form of config 2): phase R runs backward, so its first half reads
+// only the records of the upper half of the horizon, and the aux wavefront, which used to sleep through R, finishes the lower half's
+// records meanwhile.  The horizon is split at h = N / 2 (share_split); the aux wavefront's lanes are (step, chain) pairs, 2·(N − h)
+// then 2·h ≤ 64 of them: the even lane sums the entries 0, 2, …, the odd lane 1, 3, …, each ONE chain in order (obstacle_loop with
+// SPLIT = false, as with three wavefronts), the odd lane also forms the Jacobians, the even lane adds odd sums onto even sums —
+// two entries of latency per linearisation where one lane per step took four.  Each lane evaluates one heading (its step's, or
+// the next one for the Jacobians), so no state is left without a lane.
+//   round 1, beside main's closest-sample search: steps [h, N) — sums to `part`, Jacobians to the records; main, meanwhile, leaves
+//            dx, dy and the finished l_x(2) of the steps below h in their record slots 0-2;
+//   barrier A; main combines the steps [h, N) as ever, decides, enters phase R;
+//   round 2, beside R's first (N − 1 − h) / 2 trips: steps [0, h) — Jacobians, sums, and state_terms from the dx, dy in the record
+//            (the same statement on the same operands, whoever executes it: the same bits);
+//   barrier A2 inside riccati_mfma_smem (SEG), in front of its first read of a record below h.
+// N < 24 (SHARE_SPLIT_MIN): h = 0, one round over all steps (2·N ≤ 46 lanes) and an empty second one; the barriers stay the same.
+// A round lasts as long as one lane's chain, ≈ 3 k ticks however few steps it covers, and R's upper segment hides 2 · 352 ticks per
+// trip: from N = 24 on it has five trips or more (≈ 3.5 k ticks), below it main would wait at A2 for what the split was to hide.
+// Every pass has the same three barriers on both wavefronts, whatever main decides (s_barrier counts arrivals, not places):
+//   main's pass                                         A    A2                      B     then
+//   accept, R and F succeed                             L    inside R                end   next pass (or exit: tolerance, last iteration)
+//   accept, R hands over (PSD test behind R's loop)     L    inside R                end   CMD_EXIT, hand-over
+//   accept, F hands over (turn beyond the bound)        L    inside R                end   CMD_EXIT, hand-over
+//   reject / NaN cost / lambda beyond its maximum       L    in the reject branch    end   CMD_EXIT
+//   aux's pass (CMD_EXIT is looked at only behind B)    behind round 1, behind round 2, then B
+// A hand-over out of the rollout sets CMD_EXIT before the prologue's last barrier: no pass begins on either wavefront.
 // DIAG: a.diag[b] = {prologue, L (main's share + the wait at barrier A + the combine), R, F, epilogue, #L, #R, total, aux: busy
-// ticks, aux: calls, main: ticks waiting at barrier A, 0…}.
+// ticks, aux: calls, main: ticks waiting at barrier A, second aux wavefront: busy ticks, placement ×3, 0}; TWO ROUNDS: slot 11 =
+// aux busy ticks in round 1, 14 = in round 2 (8 = both), 15 = main's ticks waiting at barrier A2.
 // LONG: horizons 65 … 127, two steps per lane (two wavefronts only: the registers of a second step do not fit three wavefronts per SIMD).
 // UNC: an uncertainty map is set (cilqr_set_uncertainty_map*) — the reference's own mode of operation.  The map term (footprint probes,
 // bilinear lookups, one exponential each: ≈ 4 k ticks per call, as much as all obstacles of config 2) goes to the LAST aux wavefront,
@@ -1897,11 +1947,17 @@ __global__ __launch_bounds__(W * WAVE, 2) void cilqr_solve_split_kernel(SolveArg
 // wavefront 1.  It leaves its five scaled sums per step in LDS and main adds them to l_x / l_xx behind the obstacle sums, the order of
 // the one-wavefront kernel (unc_cost_add adds w·vx, w·mx to the finished record, I/Constraints.cpp:188-201).  Two wavefronts per SIMD
 // (the map code needs more than 168 registers), so three wavefronts per solve up to half a solve per SIMD.
+constexpr int SHARE_SPLIT_MIN = 24;  // shortest horizon whose phase L the two-wavefront short form deals in two rounds
+__device__ __forceinline__ int share_split(int N) { return N >= SHARE_SPLIT_MIN ? N >> 1 : 0; }  // first step of round 1 (0: one round)
+// trips of phase R that read no record below the split: after k trips the records N - 1 … N - 1 - 2k have been read (riccati_mfma_smem, SEG)
+__device__ __forceinline__ int share_seg_trips(int N) { return N >= SHARE_SPLIT_MIN ? (N - 1 - (N >> 1)) >> 1 : 0; }
+
 template <int W, bool LONG, bool DIAG, bool UNC = false>
 __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kernel(SolveArgs a) {  // (W wavefronts per SIMD: ≤ 256 / 168 vector registers)
   static_assert(!(LONG && W != 2), "the long-horizon form is built for two wavefronts");
   constexpr int STEPS = LONG ? 2 : 1;  // steps per lane
-  unsigned long long tk0 = 0, tk = 0, c_pro = 0, c_L = 0, c_R = 0, c_F = 0, n_L = 0, n_R = 0, c_wait = 0;
+  constexpr bool TWO_ROUNDS = W == 2 && !LONG && !UNC;  // the production short form: phase L's aux share in two rounds (above)
+  unsigned long long tk0 = 0, tk = 0, c_pro = 0, c_L = 0, c_R = 0, c_F = 0, n_L = 0, n_R = 0, c_wait = 0, c_wait2 = 0;
   if (DIAG) tk0 = tk = __builtin_readcyclecounter();
 #define CILQR_STAMP(acc)                                 \
   if (DIAG) {                                            \
@@ -1979,7 +2035,7 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
 
   if (wave != 0) {
     // ---- the aux wavefront: cos / sin, obstacle sums, control barrier, Jacobians — pass after pass -------------------------------------
-    unsigned long long busy = 0, calls = 0;
+    unsigned long long busy = 0, calls = 0, busy1 = 0, busy2 = 0;  // (busy1, busy2: the two rounds of TWO_ROUNDS)
     for (;;) {
       if (*reinterpret_cast<volatile int*>(cmd) == CMD_EXIT) break;
       unsigned long long t0 = 0;
@@ -2026,6 +2082,56 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
         }
       };
       double cn = 0.0;
+      if (TWO_ROUNDS) {
+        // lanes = (step, chain) pairs of steps [t0, t0 + cnt): the even lane sums the entries 0, 2, …, the odd lane 1, 3, … — each one
+        // chain, in order — and the odd lane forms the Jacobians.  Every lane evaluates one heading: the even lane the step's own,
+        // the odd lane the next one (the same call on the same input as with one state per lane: the same bits).  The even lane then
+        // adds the odd sums onto the even ones (obstacle_loop's last statement) and either leaves the sums in `part` (round 1: main
+        // goes on from there as ever) or finishes the record with state_terms from the dx, dy main left in its slots 0, 1 (round 2).
+        auto round = [&](int t0, int cnt, bool finish) {
+          const int t = t0 + (lane >> 1), chain = lane & 1;
+          const bool on = lane < 2 * cnt;
+          double so = 0.0, co = 1.0;
+          if (on) sincos_loop(Xa[(t + chain) * XR + 3], so, co);  // (headings within sincos_loop's range: rollout_fast, MAX_TURN)
+          const double cA = dpp_f64<0xA0>(co), sA = dpp_f64<0xA0>(so);  // quad_perm [0, 0, 2, 2]: the step's own heading
+          StepSums s5{0.0, 0.0, 0.0, 0.0, 0.0};
+          if (on) {
+            const double* xr = Xa + t * XR;
+            obstacle_loop<true, false, true, false>(make_obs_consts(kpl, xr[0], xr[1], cA, sA), (M - chain + 1) / 2,
+                                                    TabObstaclesStrided{tab + (size_t)t * TABF, wts, N, chain, 2, kpl.w_obstacle}, s5);
+            if (chain) {
+              Rec c;
+              ab_terms(kpl, Ua[2 * t], Xa[(t + 1) * XR + 2], co, so, c);
+              double* r = rec + t * RECF;
+              r[10] = c.al; r[11] = c.be; r[12] = c.ga; r[13] = c.de;
+            }
+          }
+          const StepSums odd{dpp_f64<0xF5>(s5.lx0), dpp_f64<0xF5>(s5.lx1), dpp_f64<0xF5>(s5.h00), dpp_f64<0xF5>(s5.h01), dpp_f64<0xF5>(s5.h11)};  // quad_perm [1, 1, 3, 3]
+          if (on && !chain) {
+            s5.lx0 += odd.lx0; s5.lx1 += odd.lx1; s5.h00 += odd.h00; s5.h01 += odd.h01; s5.h11 += odd.h11;
+            if (!finish) {
+              double* q = part + (size_t)t * 5;
+              q[0] = s5.lx0; q[1] = s5.lx1; q[2] = s5.h00; q[3] = s5.h01; q[4] = s5.h11;
+            } else {
+              double* r = rec + t * RECF;
+              double lx0, lx1, l00, l01, l11;
+              state_terms(kpl, r[0], r[1], s5, lx0, lx1, l00, l01, l11);
+              r[0] = lx0; r[1] = lx1; r[3] = l00; r[4] = l01; r[5] = l11;
+            }
+          }
+          cn = co;
+        };
+        const int h = share_split(N);
+        round(h, N - h, false);
+        if (DIAG) busy1 += stamp_after(cn) - t0;
+        __syncthreads();  // A: the upper steps' sums and Jacobians, and main's dx, dy of the lower steps, are in LDS
+        if (DIAG) t0 = __builtin_readcyclecounter();
+        if (h > 0) round(0, h, true);
+        if (DIAG) { busy2 += stamp_after(cn) - t0; ++calls; }
+        __syncthreads();  // A2: every record is finished
+        __syncthreads();  // B: main has decided, and, going on, has written the next trajectory
+        continue;
+      }
       if (!LONG) {  // one state per lane: a step's next heading comes from the lane above
         double sA = 0.0, cA = 1.0;
         if (lane <= N) sincos_loop(Xa[lane * XR + 3], sA, cA);  // (headings within sincos_loop's range: rollout_fast, MAX_TURN)
@@ -2048,7 +2154,8 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
     }
     if (DIAG && lane == 0 && a.diag && wave == 1) {
       unsigned long long* o = a.diag + (size_t)b * DIAG_SLOTS;
-      o[8] = busy; o[9] = calls;
+      o[8] = TWO_ROUNDS ? busy1 + busy2 : busy; o[9] = calls;
+      if (TWO_ROUNDS) { o[11] = busy1; o[14] = busy2; }
     }
     // where this wavefront ran: HW_ID (wave slot, SIMD, CU, shader array, shader engine) | XCC_ID << 32 (tools/wave_placement.py)
     if (DIAG && lane == 0 && a.diag)
@@ -2068,6 +2175,10 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
     ++iters;
     {  // phase L: forward-pass rows, closest sample, tracking terms, J; then the aux wavefront's sums on top
       const KParams kpl = phase_params();
+      // TWO_ROUNDS: steps [split, N) are finished at barrier A, steps [0, split) at barrier A2 (formed from the
+      // argument block where it is used: kept in a scalar register across the pass, it made hipcc's backend give up on this kernel
+      // with "illegal VGPR to SGPR copy")
+      const int split = TWO_ROUNDS ? __builtin_amdgcn_readfirstlane(share_split(phase_args().N)) : 0;  // (wave-uniform: R's trip counter stays scalar)
       double dx[STEPS], dy[STEPS], lx2[STEPS], Jt = 0.0;  // (LONG: steps lane and lane + 64)
 #pragma unroll
       for (int c2 = 0; c2 < STEPS; ++c2) {
@@ -2087,6 +2198,10 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
           const double dv = v - kpl.desired_speed;
           lx2[c2] = (2 * kpl.w_vel) * dv;
           Jt += stage_cost(kpl, dx[c2], dy[c2], dv, u0, u1);
+          if (TWO_ROUNDS && t < split) {  // a step of round 2: dx, dy for the aux wavefront's state_terms, and l_x(2) as it stays
+            double* r = rec + t * RECF;
+            r[0] = dx[c2]; r[1] = dy[c2]; r[2] = lx2[c2];
+          }
           if (W == 2) {  // control barrier (I/Constraints.cpp:110-131); with three wavefronts: on the last one
             Rec c;
             double a1, a2, a3, a4;
@@ -2110,7 +2225,7 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
 #pragma unroll
       for (int c2 = 0; c2 < STEPS; ++c2) {
         const int t = lane + c2 * WAVE;
-        if (t < N) {
+        if (t < N && (!TWO_ROUNDS || t >= split)) {  // (TWO_ROUNDS: the steps of round 1; the others' records are finished by the aux wavefront)
           const double* q = part + (size_t)t * 5;
           StepSums s5{q[0], q[1], q[2], q[3], q[4]};
           if (W == 3 && !UNC) {  // odd sums onto even sums: obstacle_loop's last statement
@@ -2145,11 +2260,13 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
         }
       }
       stop = true;
+      if (TWO_ROUNDS) lds_barrier();  // A2 (no phase R to stand in: the solve ends here, behind the aux wavefront's second round)
     } else {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wavefront's record slots are in LDS (the aux wavefront's: barrier A)
       // (three wavefronts per solve keep the form with the PSD test on the chain: there the new one stamped R 363 -> 365 and
       //  F 340 -> 347 ticks per step, the slowest solve +1.2 %, profiles/r26_riccati_chain.txt)
       if (!(W == 3 ? riccati_mfma<true, false>(N, rec, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr)
+            : TWO_ROUNDS ? riccati_mfma_smem<false, DIAG ? 2 : 1>(N, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr, __builtin_amdgcn_readfirstlane(share_seg_trips(phase_args().N)), &c_wait2)  // (barrier A2 inside)
                    : riccati_mfma_smem<false>(N, rec, fwd, cst, 2.0 / kp.dt, lamb, nullptr))) {
         handover = true;
         stop = true;
@@ -2205,8 +2322,8 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
     o[10] = c_wait;
     o[12] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
             ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)) << 32);
-    if (W == 2) { o[11] = 0; o[14] = 0; }
-    o[15] = 0;
+    if (W == 2 && !TWO_ROUNDS) { o[11] = 0; o[14] = 0; }  // (TWO_ROUNDS: the aux wavefront's two rounds, written by it)
+    o[15] = TWO_ROUNDS ? c_wait2 : 0;
   }
 #undef CILQR_STAMP
 }
