@@ -46,6 +46,9 @@
  *                                                                cilqr_tighten_obstacles(_device): obstacles inflated by that
  *                                                                covariance for a warm-started re-solve; cilqr_chance_kappa
  *                                                                cilqr_tighten_map(_device): the costmap dilated by it instead
+ *   LocalCostmap's cv::KalmanFilter on ONE bounding box  M/src/local_costmap.cpp:138-158, 351-380
+ *                                                                cilqr_track_update(_device): the boxes of cilqr_map_obstacles
+ *                                                                followed across ticks — association, birth and death of tracks
  *
  * Conventions
  *   - fp64 everywhere in the solver; float32 map payloads in the warp.
@@ -1624,6 +1627,126 @@ int cilqr_map_obstacles_device(cilqr_handle* h, void* stream, int L, const int32
 int cilqr_map_obstacles(cilqr_handle* h, int L, const int32_t* d2, const cilqr_map_geom* g, int gap2, uint32_t flags, const double* pose,
                         int pose_stride, int K, int min_cells, double max_size, double pad, int32_t* work, int32_t* label_out,
                         int32_t* n_out, double* comp, double* boxes, double* pose_out, double* dim_out);
+
+/* --- map obstacles tracked across ticks: association and Kalman update (new) ---------------------------------------------------------
+ * cilqr_map_obstacles returns this tick's boxes in label order, without velocity or covariance; cilqr_predict_obstacles wants what a
+ * tracker hands over.  cilqr_track_update(_device) is that tracker, one tick per call: predict, gate, associate, update, retire,
+ * start new tracks, and write the track / track_dim / track_cov arrays of cilqr_predict_obstacles, slot-ordered, so that an
+ * obstacle keeps its index over the ticks and nothing is read back between the map and the solve.
+ *
+ * Definitions.  W worlds (independent trackers; W = 1 is the node, W is the T of cilqr_predict_obstacles), M slots per world
+ * (1 ... CILQR_TRACK_MAX_SLOTS, the M of cilqr_predict_obstacles), D detections per world (0 ... CILQR_TRACK_MAX_DETECTIONS).
+ *   det        [W][D][5] = (x, y, yaw, size_x, size_y) in the planning frame: the `boxes` rows of cilqr_map_obstacles.  NULL is
+ *              allowed when D = 0.
+ *   n_det      int32 count of world w at n_det[w*n_det_stride] (n_det_stride >= 0), clamped to [0, D]; NULL: all D rows count.
+ *              With n_det = n_out + 2 and n_det_stride = 4 the call reads the "rows written" of cilqr_map_obstacles where it lies.
+ *              A detection below the count whose x or y is not finite is INVALID: it takes part in nothing and is counted.
+ *   f          the filter, copied at the call.  dt > 0 is the time between ticks in seconds (not Parameters::timestep).  Q and
+ *              P_birth are 4 x 4 for the state order (x, y, vx, vy), R is 2 x 2; all column-major, only row <= column read (the
+ *              convention of sigma0); Q is the process noise of one tick of this dt.  gate2 >= 0 bounds the squared Mahalanobis
+ *              distance, HUGE_VAL: no gate.  min_hits >= 1, max_misses >= 0, v_min >= 0, theta_var_slow >= 0.
+ *   state      [W][M][CILQR_TRACK_STATE] doubles, see the enum; integers are stored as exact doubles.  state_in and state_out
+ *              may be the same address (the call then updates in place) and may not overlap otherwise.  A slot whose ID is
+ *              not >= 0 is FREE; the call writes a free slot as ID = -1 and every other value 0.  Of P only row <= column is
+ *              read; what is written is exactly symmetric.
+ *   world      [W][CILQR_TRACK_WORLD_FIELDS] doubles, in and out, exact integers, see the enum: NEXT_ID and TICKS are carried
+ *              over the ticks, the others are counts of this tick.
+ *   flags      CILQR_TRACK_RESET: every slot is free on entry and NEXT_ID = TICKS = 0; state_in (which may then be NULL) and the
+ *              incoming world are not read, so a first tick needs no initialised memory.
+ *   assign     [W][D] int32 or NULL: the slot the detection was matched to or born into, -1 when dropped, -2 when invalid or at
+ *              or beyond the count.
+ *   track_out  [W][M][6], dim_out [W][M][2], cov_out [W][M][16]: required; the track, track_dim and track_cov of
+ *              cilqr_predict_obstacles.
+ * One tick of one world, evaluated in double as written, no fused multiply-add:
+ *   1 predict  every slot live on entry: x += dt*vx, y += dt*vy; P- = F P F' + Q with F = I + dt*{(0,2), (1,3)}, entries with
+ *              row <= column computed and mirrored; AGE += 1.
+ *   2 gate     S = P-[0:2, 0:2] + R, det = S00*S11 - S01*S01, nu = (det.x - x, det.y - y),
+ *              d2 = (S11*nu_x^2 - 2*S01*nu_x*nu_y + S00*nu_y^2) / det.  A pair (slot m, detection d) is ADMISSIBLE when m is live
+ *              on entry, d is valid and d2 <= gate2; a NaN d2 fails, and a det that is not > 0 admits nothing.
+ *   3 associate  greedy global nearest neighbour: repeatedly the smallest (d2, m, d), compared in that order (-0 equals +0), among
+ *              the admissible pairs whose m and d are both unassigned is assigned, until none is left.  This is NOT the optimal
+ *              assignment: it can match fewer pairs, or at a larger summed d2, than the Hungarian method would.
+ *   4 update   matched slots: K = P- H' S^-1 (H = [I2 0]), (x, y, vx, vy) += K nu; Joseph form
+ *              P = (I - K H) P- (I - K H)' + K R K', upper triangle mirrored; SIZE_X, SIZE_Y, YAW become a bit copy of the
+ *              detection; HITS += 1, MISSES = 0, DET = d.
+ *   5 miss     unmatched live slots: MISSES += 1, DET = -1, the predicted state and P- stay.  A slot with MISSES > max_misses is
+ *              freed; a slot freed this tick takes no birth this tick.
+ *   6 birth    the unassigned valid detections in ascending d take the slots free on entry in ascending m: state
+ *              (det.x, det.y, 0, 0), P = P_birth (mirrored), box copied, ID = NEXT_ID++ in that order, HITS = 1, MISSES = 0, AGE = 0,
+ *              DET = d.  Those that find no slot are DROPPED.  Then TICKS += 1.
+ *   7 output   row of slot m.  CONFIRMED (live after the tick and HITS >= min_hits): with v = hypot(vx, vy), if v >= v_min the row is
+ *              (x, y, v, theta = atan2(vy, vx), 0, 0), its covariance J P J' with J = diag(1, 1) (+) [[vx/v, vy/v],
+ *              [-vy/v^2, vx/v^2]] (upper triangle mirrored) and its dimensions (SIZE_X, SIZE_Y) when |cos(theta - YAW)| >=
+ *              |sin(theta - YAW)|, else (SIZE_Y, SIZE_X): the box's principal axis knows nothing of the direction of travel.
+ *              Otherwise the track is reported as standing: (x, y, 0, YAW, 0, 0), the position block of P bit-copied, speed
+ *              variance P(2,2) + P(3,3), heading variance theta_var_slow, every cross term 0, dimensions as stored.  With
+ *              v_min = 0 a track at rest (every newborn) divides by v = 0 and its row is not finite: choose v_min > 0.
+ *              Every other slot is filler: (FAR, FAR, 0, 0, 0, 0) with FAR = CILQR_MAP_OBSTACLES_FAR, dimensions 0, covariance 0 —
+ *              the filler of cilqr_map_obstacles, whose barrier term is exactly 0, so predict and solve run at a fixed M.
+ *   The model is constant velocity: a and omega of every row are 0.  A turning or braking vehicle is followed only through Q, its
+ *   predicted path is a straight line at its last estimated velocity, and the yaw of its box does not enter the filter.
+ *   Determinism: values are not checked beyond what is said above; a NaN stays in its own slot.  A world's outputs depend on that
+ *   world's inputs, f, M and D alone: the same bits whatever W is and wherever the world sits.
+ * Mapping: one wavefront per world, W workgroups, one launch, nothing allocated per call.  Lane = slot for predict, gate and
+ * update; each lane walks the detections in LDS for its best one; the greedy rounds are wavefront-wide minima of (d2, m, d) by DPP
+ * and v_readlane, after which only the lanes that lost their detection scan again; births meet their slots through ballot ranks.
+ * LDS: the detections, three 64-word lists and one [64][33] staging block through which the state rows are loaded and every output
+ * is stored, coalesced.
+ * CILQR_ERR_ARG, decided before the handle is looked at where no handle is needed: NULL f, state_out, world, track_out, dim_out or
+ * cov_out; NULL state_in without CILQR_TRACK_RESET; NULL det with D > 0; W < 1, M < 1, D < 0, n_det_stride < 0; dt not > 0 or not
+ * finite; gate2, v_min or theta_var_slow negative or NaN; min_hits < 1; max_misses < 0; unknown flag bits; then W beyond max_batch
+ * or M beyond max_obstacles.  CILQR_ERR_UNSUPPORTED for M above CILQR_TRACK_MAX_SLOTS or D above CILQR_TRACK_MAX_DETECTIONS.
+ * The host-buffer form's arrays must fit the device arena reserved at create (CILQR_ERR_ARG otherwise; this call adds nothing to
+ * it): W*(56*M + 5.5*D + 9) doubles in place, 32*W*M more with a separate state_out, and the counts.  On a handle with
+ * max_horizon >= 15 every W <= max_batch fits, whatever M <= max_obstacles and D are. */
+#define CILQR_TRACK_MAX_SLOTS 64
+#define CILQR_TRACK_MAX_DETECTIONS 64
+#define CILQR_TRACK_STATE 32
+typedef enum cilqr_track_state_field {
+  CILQR_TS_X = 0,
+  CILQR_TS_Y = 1,
+  CILQR_TS_VX = 2,
+  CILQR_TS_VY = 3,
+  CILQR_TS_P = 4,        /* 4 ... 19: the covariance, column-major */
+  CILQR_TS_SIZE_X = 20,  /* 20 ... 22: a bit copy of the last matched detection */
+  CILQR_TS_SIZE_Y = 21,
+  CILQR_TS_YAW = 22,
+  CILQR_TS_ID = 23,      /* -1: the slot is free */
+  CILQR_TS_HITS = 24,
+  CILQR_TS_MISSES = 25,  /* consecutive */
+  CILQR_TS_AGE = 26,     /* ticks since birth */
+  CILQR_TS_DET = 27      /* the detection matched or born from this tick, -1 for a miss; 28 ... 31 are zero */
+} cilqr_track_state_field;
+#define CILQR_TRACK_WORLD_FIELDS 9
+typedef enum cilqr_track_world_field {
+  CILQR_TW_NEXT_ID = 0,
+  CILQR_TW_TICKS = 1,
+  CILQR_TW_LIVE = 2,       /* live slots after the tick */
+  CILQR_TW_CONFIRMED = 3,  /* of these, HITS >= min_hits */
+  CILQR_TW_MATCHED = 4,
+  CILQR_TW_BORN = 5,
+  CILQR_TW_DIED = 6,
+  CILQR_TW_DROPPED = 7,    /* unassigned valid detections that found no free slot */
+  CILQR_TW_INVALID = 8
+} cilqr_track_world_field;
+#define CILQR_TRACK_RESET 1u /* flags: every slot is free on entry, NEXT_ID = TICKS = 0 */
+typedef struct cilqr_track_filter {
+  double dt;
+  double Q[16];
+  double R[4];
+  double P_birth[16];
+  double gate2;
+  double v_min;
+  double theta_var_slow;
+  int32_t min_hits;
+  int32_t max_misses;
+} cilqr_track_filter;
+int cilqr_track_update_device(cilqr_handle* h, void* stream, int W, int M, int D, const double* det, const int32_t* n_det,
+                              int64_t n_det_stride, const cilqr_track_filter* f, const double* state_in, double* state_out,
+                              double* world, uint32_t flags, int32_t* assign, double* track_out, double* dim_out, double* cov_out);
+int cilqr_track_update(cilqr_handle* h, int W, int M, int D, const double* det, const int32_t* n_det, int64_t n_det_stride,
+                       const cilqr_track_filter* f, const double* state_in, double* state_out, double* world, uint32_t flags,
+                       int32_t* assign, double* track_out, double* dim_out, double* cov_out);
 
 /* --- exact clearance of the ego rectangle to the occupied cells of the map (new) -----------------------------------------------------
  * The map counterpart of CILQR_FP_CLEARANCE: cilqr_footprint_check reports only whether the rectangle covers a cell above the

@@ -75,6 +75,15 @@ MAP_OBSTACLES_FOUR = 1  # flags of `map_obstacles`: 4-connectivity
 MAP_OBSTACLES_FAR = 1.0e6  # metres: where the filler rows stand
 MAX_POLYGONS = 1024
 ERR_INTERNAL = -6
+# `cilqr_track_state_field` / `cilqr_track_world_field`: a slot's row and a world's record (`Solver.track_update`)
+TRACK_STATE = 32
+TRACK_MAX_SLOTS = TRACK_MAX_DETECTIONS = 64
+TS_X, TS_Y, TS_VX, TS_VY, TS_P = 0, 1, 2, 3, 4
+TS_SIZE_X, TS_SIZE_Y, TS_YAW, TS_ID, TS_HITS, TS_MISSES, TS_AGE, TS_DET = range(20, 28)
+TRACK_WORLD_FIELDS = 9
+(TW_NEXT_ID, TW_TICKS, TW_LIVE, TW_CONFIRMED, TW_MATCHED, TW_BORN, TW_DIED, TW_DROPPED,
+ TW_INVALID) = range(TRACK_WORLD_FIELDS)
+TRACK_RESET = 1  # flags of `track_update`: every slot is free on entry
 # `cilqr_map_clearance_field`: the columns of a map clearance row (`Solver.map_clearance`)
 MAP_CLEARANCE_FIELDS = 8
 (MC_CLEARANCE, MC_STEP, MC_CELL, MC_BELOW_STEPS, MC_FIRST_BELOW, MC_TOUCH_STEPS, MC_OFF_MAP_STEPS,
@@ -116,6 +125,7 @@ ABI_SYMBOLS = (
     "cilqr_footprint_check", "cilqr_footprint_check_device",
     "cilqr_map_distance", "cilqr_map_distance_device", "cilqr_inflate_map", "cilqr_inflate_map_device",
     "cilqr_map_obstacles", "cilqr_map_obstacles_device",
+    "cilqr_track_update", "cilqr_track_update_device",
     "cilqr_map_clearance", "cilqr_map_clearance_device",
     "cilqr_stop_plans", "cilqr_stop_plans_device",
 )
@@ -159,6 +169,33 @@ class Obstacles(C.Structure):
     solve b at step t is entry b*batch_stride + m*obstacle_stride + t*step_stride; weight[b*weight_batch_stride + m]."""
     _fields_ = [("pose", C.c_void_p), ("dim", C.c_void_p), ("weight", C.c_void_p), ("batch_stride", C.c_int64),
                 ("obstacle_stride", C.c_int64), ("step_stride", C.c_int64), ("weight_batch_stride", C.c_int64)]
+
+
+class TrackFilter(C.Structure):
+    """`cilqr_track_filter` — the constant-velocity Kalman filter and the track life cycle of `Solver.track_update`.  Q and P_birth
+    are 4 x 4 over (x, y, vx, vy), R is 2 x 2, column-major, only row <= column read."""
+    _fields_ = [("dt", C.c_double), ("Q", C.c_double * 16), ("R", C.c_double * 4), ("P_birth", C.c_double * 16),
+                ("gate2", C.c_double), ("v_min", C.c_double), ("theta_var_slow", C.c_double), ("min_hits", C.c_int32),
+                ("max_misses", C.c_int32)]
+
+
+def track_filter(dt, Q, R, P_birth, gate2=float("inf"), min_hits=1, max_misses=0, v_min=0.5, theta_var_slow=1.0):
+    """A `TrackFilter` from (4, 4), (2, 2) and (4, 4) arrays (symmetric: the upper triangles are what is read)."""
+    f = TrackFilter()
+    f.dt, f.gate2, f.v_min, f.theta_var_slow = float(dt), float(gate2), float(v_min), float(theta_var_slow)
+    f.min_hits, f.max_misses = int(min_hits), int(max_misses)
+    for name, a, n in (("Q", Q, 4), ("R", R, 2), ("P_birth", P_birth, 4)):
+        a = np.asarray(a, dtype=np.float64).reshape(n, n)
+        getattr(f, name)[:] = a.T.reshape(-1).tolist()  # column-major
+    return f
+
+
+def white_acceleration_noise(q, dt):
+    """Q of one tick for white acceleration of intensity q on each axis: q*dt^3/3, q*dt^2/2, q*dt."""
+    Q = np.zeros((4, 4))
+    for a in (0, 1):
+        Q[a, a], Q[a, a + 2], Q[a + 2, a], Q[a + 2, a + 2] = q * dt ** 3 / 3, q * dt ** 2 / 2, q * dt ** 2 / 2, q * dt
+    return Q
 
 
 class CilqrError(RuntimeError):
@@ -1135,6 +1172,54 @@ class Solver:
         _check(lib().cilqr_map_obstacles_device(self._h, _vp(stream), int(L), _vp(d2), C.byref(geom), int(gap2), C.c_uint32(int(flags)),
                                                 _vp(pose), int(pose_stride), int(K), int(min_cells), C.c_double(max_size), C.c_double(pad),
                                                 _vp(work), _vp(label_out), _vp(n_out), _vp(comp), _vp(boxes), _vp(pose_out), _vp(dim_out)))
+
+    # ---- map obstacles tracked across ticks ----
+    def track_update(self, det, filt, state=None, world=None, n_det=None, reset=False, M=None):
+        """`cilqr_track_update`: det (D, 5) or (W, D, 5) rows (x, y, yaw, size_x, size_y), as `map_obstacles` returns `boxes`; filt a
+        `TrackFilter`; state (…, M, TRACK_STATE) and world (…, TRACK_WORLD_FIELDS) as the last call returned them, or reset=True with M
+        slots for a first tick; n_det None or one count per world.  Returns dict(state, world, assign (…, D) int32, track (…, M, 6),
+        dim (…, M, 2), cov (…, M, 16)): track, dim and cov are what `predict_obstacles` takes."""
+        det = _np64(det)
+        if det.ndim not in (2, 3) or det.shape[-1] != 5:
+            raise CilqrError("track_update: det %s is not (D, 5) or (W, D, 5)" % (det.shape,))
+        lead = det.shape[:-2]
+        W, D = (1 if not lead else lead[0]), det.shape[-2]
+        if reset:
+            if M is None and state is not None:
+                M = np.asarray(state).shape[-2]
+            if M is None:
+                raise CilqrError("track_update: reset needs the number of slots M")
+            state, world = np.zeros(lead + (int(M), TRACK_STATE)), np.zeros(lead + (TRACK_WORLD_FIELDS,))
+        else:
+            if state is None or world is None:
+                raise CilqrError("track_update: state and world are needed without reset")
+            state, world = _np64(state).copy(), _np64(world).copy()
+            if state.ndim != len(lead) + 2 or state.shape[-1] != TRACK_STATE or state.shape[:-2] != lead:
+                raise CilqrError("track_update: state %s is not %s + (M, %d)" % (state.shape, lead, TRACK_STATE))
+            if world.shape != lead + (TRACK_WORLD_FIELDS,):
+                raise CilqrError("track_update: world %s is not %s" % (world.shape, lead + (TRACK_WORLD_FIELDS,)))
+        M = state.shape[-2]
+        counts = None
+        if n_det is not None:
+            counts = np.ascontiguousarray(n_det, dtype=np.int32).reshape(-1)
+            if counts.size != W:
+                raise CilqrError("track_update: n_det holds %d counts for %d worlds" % (counts.size, W))
+        assign = np.zeros(lead + (D,), dtype=np.int32)
+        track, dim, cov = np.zeros(lead + (M, 6)), np.zeros(lead + (M, 2)), np.zeros(lead + (M, 16))
+        _check(lib().cilqr_track_update(self._h, int(W), int(M), int(D), _p(det) if D else None, _p(counts, _ip), C.c_int64(1),
+                                        C.byref(filt), _p(state), _p(state), _p(world), C.c_uint32(TRACK_RESET if reset else 0),
+                                        _p(assign, _ip) if D else None, _p(track), _p(dim), _p(cov)))
+        return dict(state=state, world=world, assign=assign, track=track, dim=dim, cov=cov)
+
+    def track_update_device(self, stream, W, M, D, det, filt, state_in, state_out, world, track_out, dim_out, cov_out, n_det=0,
+                            n_det_stride=1, assign=0, flags=0):
+        """`cilqr_track_update_device`: device addresses; det (W, D, 5), state (W, M, TRACK_STATE) — state_in may equal state_out —,
+        world (W, TRACK_WORLD_FIELDS), track_out (W, M, 6), dim_out (W, M, 2), cov_out (W, M, 16) float64; n_det int32 read at
+        n_det[w*n_det_stride] or 0; assign (W, D) int32 or 0.  With n_det = n_out + 8 bytes and n_det_stride = 4 the counts are the
+        "rows written" of `map_obstacles_device`."""
+        _check(lib().cilqr_track_update_device(self._h, _vp(stream), int(W), int(M), int(D), _vp(det), _vp(n_det), C.c_int64(int(n_det_stride)),
+                                               C.byref(filt), _vp(state_in), _vp(state_out), _vp(world), C.c_uint32(int(flags)),
+                                               _vp(assign), _vp(track_out), _vp(dim_out), _vp(cov_out)))
 
     def map_clearance(self, N, X, reach, S=1, margin=0.0, occ_threshold=float("inf"), min_clearance=0.0, base=None,
                       unknown_seeds=False, steps=True):

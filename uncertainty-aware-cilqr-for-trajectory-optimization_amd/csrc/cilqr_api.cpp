@@ -1253,6 +1253,62 @@ int cilqr_predict_obstacles(cilqr_handle* h, int T, int N, int M, const double* 
   });
 }
 
+// ---- map obstacles tracked across ticks (cilqr_track.hip) ------------------------------------------------------------------------------
+namespace {
+int track_update_check(const cilqr_handle* h, int W, int M, int D, const double* det, int64_t n_det_stride, const cilqr_track_filter* f,
+                       const double* state_in, const double* state_out, const double* world, uint32_t flags, const double* track_out,
+                       const double* dim_out, const double* cov_out) {
+  if (!f || !state_out || !world || !track_out || !dim_out || !cov_out)
+    return fail(CILQR_ERR_ARG, "cilqr_track_update: null required pointer");
+  if (flags & ~CILQR_TRACK_RESET) return fail(CILQR_ERR_ARG, "cilqr_track_update: unknown flag bits 0x%x", flags);
+  if (!state_in && !(flags & CILQR_TRACK_RESET)) return fail(CILQR_ERR_ARG, "cilqr_track_update: null state_in without CILQR_TRACK_RESET");
+  if (W < 1 || M < 1 || D < 0) return fail(CILQR_ERR_ARG, "cilqr_track_update: W = %d, M = %d, D = %d: W and M must be at least 1, D at least 0", W, M, D);
+  if (D > 0 && !det) return fail(CILQR_ERR_ARG, "cilqr_track_update: D = %d but det is null", D);
+  if (n_det_stride < 0) return fail(CILQR_ERR_ARG, "cilqr_track_update: negative n_det_stride");
+  if (!(f->dt > 0.0 && f->dt <= 1.7e308)) return fail(CILQR_ERR_ARG, "cilqr_track_update: dt is not > 0 or not finite");
+  if (!(f->gate2 >= 0.0)) return fail(CILQR_ERR_ARG, "cilqr_track_update: gate2 is negative or NaN");
+  if (!(f->v_min >= 0.0)) return fail(CILQR_ERR_ARG, "cilqr_track_update: v_min is negative or NaN");
+  if (!(f->theta_var_slow >= 0.0)) return fail(CILQR_ERR_ARG, "cilqr_track_update: theta_var_slow is negative or NaN");
+  if (f->min_hits < 1) return fail(CILQR_ERR_ARG, "cilqr_track_update: min_hits = %d, must be at least 1", f->min_hits);
+  if (f->max_misses < 0) return fail(CILQR_ERR_ARG, "cilqr_track_update: max_misses = %d is negative", f->max_misses);
+  if (M > CILQR_TRACK_MAX_SLOTS || D > CILQR_TRACK_MAX_DETECTIONS)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_track_update: M = %d slots, D = %d detections: at most %d and %d", M, D, CILQR_TRACK_MAX_SLOTS,
+                CILQR_TRACK_MAX_DETECTIONS);
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (W > h->max_batch) return fail(CILQR_ERR_ARG, "W=%d outside [1,%d]", W, h->max_batch);
+  if (M > h->max_obstacles) return fail(CILQR_ERR_ARG, "M=%d outside [1,%d]", M, h->max_obstacles);
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_track_update_device(cilqr_handle* h, void* stream, int W, int M, int D, const double* det, const int32_t* n_det,
+                              int64_t n_det_stride, const cilqr_track_filter* f, const double* state_in, double* state_out,
+                              double* world, uint32_t flags, int32_t* assign, double* track_out, double* dim_out, double* cov_out) {
+  int rc = track_update_check(h, W, M, D, det, n_det_stride, f, state_in, state_out, world, flags, track_out, dim_out, cov_out);
+  if (rc) return rc;
+  cilqr::TrackArgs a = {};
+  a.det = det; a.n_det = n_det; a.state_in = state_in; a.state_out = state_out; a.world = world; a.assign = assign;
+  a.track_out = track_out; a.dim_out = dim_out; a.cov_out = cov_out;
+  a.n_det_stride = n_det_stride; a.f = *f; a.W = W; a.M = M; a.D = D; a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_track_update(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_track_update(cilqr_handle* h, int W, int M, int D, const double* det, const int32_t* n_det, int64_t n_det_stride,
+                       const cilqr_track_filter* f, const double* state_in, double* state_out, double* world, uint32_t flags,
+                       int32_t* assign, double* track_out, double* dim_out, double* cov_out) {
+  int rc = track_update_check(h, W, M, D, det, n_det_stride, f, state_in, state_out, world, flags, track_out, dim_out, cov_out);
+  if (rc) return rc;
+  cilqr::HostPlan p(h->d_arena);
+  cilqr::plan_track_update(p, W, M, D, n_det ? (size_t)(W - 1) * (size_t)n_det_stride + 1 : 0, (flags & CILQR_TRACK_RESET) != 0, det, n_det,
+                           state_in, state_out, world, assign, track_out, dim_out, cov_out);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_track_update_device(h, h->stream, W, M, D, det, n_det, n_det_stride, f, state_in, state_out, world, flags, assign,
+                                     track_out, dim_out, cov_out);
+  });
+}
+
 // ---- chance-constraint tightening (cilqr_tighten.hip) ---------------------------------------------------------------------------------
 namespace {
 int tighten_check(const cilqr_handle* h, int B, int N, int M, const double* X, const double* sigma, const cilqr_obstacles* obs,

@@ -264,6 +264,37 @@ inline void plan_predict_obstacles(HostPlan& p, size_t T, size_t N, size_t M, co
   p.out(sigma_out, T * M * 16 * N);
 }
 
+// cilqr_track_update: 9 arrays at most.  In: the detections and their counts (`counts` int32: the span n_det_stride addresses, 0
+// without n_det).  The state travels both ways as one array where state_in == state_out, as an input and an output otherwise; under
+// CILQR_TRACK_RESET (`reset`) neither the incoming state nor the incoming world is read, so both are outputs only and state_in
+// becomes the place of state_out.  Per world 32·M doubles of state (64·M with a separate state_out), 5·D + D/2 for the detections and
+// assign, 9 for the world and 24·M for the three output tables: W·(88·M + 5.5·D + 9) at most, beside the counts.  With M <= the
+// handle's max_obstacles and D <= 64 that is within the 28·N + 6·M·N + M + 50 per unit of max_batch that host_arena_bytes reserves
+// below once max_horizon >= 15 (470 + 91·M against 361 + 88·M): every W <= max_batch fits there with one count per world, and the
+// 9 roundings stay within its 32 x 16 bytes and that margin.
+inline void plan_track_update(HostPlan& p, size_t W, size_t M, size_t D, size_t counts, bool reset, const double*& det,
+                              const int32_t*& n_det, const double*& state_in, double*& state_out, double*& world, int32_t*& assign,
+                              double*& track_out, double*& dim_out, double*& cov_out) {
+  const bool in_place = !reset && state_in == state_out;
+  p.in(det, W * D * 5);
+  p.in(n_det, counts);
+  if (!reset && !in_place) p.in(state_in, W * M * CILQR_TRACK_STATE);
+  if (in_place) {
+    p.inout(state_out, W * M * CILQR_TRACK_STATE);
+    state_in = state_out;
+  }
+  if (!reset) p.inout(world, W * CILQR_TRACK_WORLD_FIELDS);
+  if (!in_place) p.out(state_out, W * M * CILQR_TRACK_STATE);
+  if (reset) {
+    p.out(world, W * CILQR_TRACK_WORLD_FIELDS);
+    state_in = state_out;
+  }
+  p.out(assign, W * D);
+  p.out(track_out, W * M * 6);
+  p.out(dim_out, W * M * 2);
+  p.out(cov_out, W * M * 16);
+}
+
 // cilqr_tighten_obstacles: 8 arrays; obstacle weights are not read and do not travel; obs_cov travels as 3 doubles per entry of the
 // span.  Per solve, with dense obstacles, 20·N + 15·M·N + 24 doubles with obs_cov and pose_out and 20·N + 8·M·N + 24 without them,
 // against the 22·N + 6·M·N + M + 34 per unit of max_batch that host_arena_bytes reserves below: every B <= 2·max_batch/5 fits with

@@ -291,6 +291,26 @@ struct PredictArgs {
 hipError_t launch_predict_obstacles(const PredictArgs& a, hipStream_t stream);
 size_t predict_lds_bytes(int N);
 
+// One tick of the obstacle tracker (cilqr_track.hip; cilqr_track_update*): one wavefront per world, W workgroups.  The filter
+// travels by value in the kernel arguments.
+constexpr int TRACK_THREADS = 64;
+struct TrackArgs {
+  const double* det;        // [W][D][5] or null (D = 0)
+  const int32_t* n_det;     // count of world w at [w·n_det_stride], or null (D)
+  const double* state_in;   // [W][M][CILQR_TRACK_STATE]; not read under CILQR_TRACK_RESET
+  double* state_out;        // [W][M][CILQR_TRACK_STATE]; may equal state_in
+  double* world;            // [W][CILQR_TRACK_WORLD_FIELDS]
+  int32_t* assign;          // [W][D] or null
+  double* track_out;        // [W][M][6]
+  double* dim_out;          // [W][M][2]
+  double* cov_out;          // [W][M][16]
+  long long n_det_stride;
+  cilqr_track_filter f;
+  int32_t W, M, D;
+  uint32_t flags;           // CILQR_TRACK_*
+};
+hipError_t launch_track_update(const TrackArgs& a, hipStream_t stream);
+
 // Chance-constraint tightening (cilqr_tighten.hip; cilqr_tighten_obstacles*): every obstacle entry's dimensions grown by kappa
 // standard deviations of the relative position along the ellipse's axes.  One workgroup per solve; `s` first, as in ChanceArgs.
 constexpr int TIGHTEN_THREADS = 256;

@@ -104,11 +104,13 @@ iLQR::~iLQR() {
   if (block_dev_) (void)hipFree(block_dev_);
   if (map_dev_) (void)hipFree(map_dev_);
   if (mo_dev_) (void)hipFree(mo_dev_);
+  if (trk_dev_) (void)hipFree(trk_dev_);
   if (block_stream_) (void)hipStreamDestroy((hipStream_t)block_stream_);
   cilqr_destroy(h_);
 }
 
 void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
+  if (trk_on_) throw std::logic_error("set_map_tracker: the tracker is the one producer of obstacles while it is on: not with set_Obstacle");
   if ((int)obstacles.size() > max_obstacles_) throw std::runtime_error("set_Obstacle: more obstacles than max_obstacles");
   for (const Obstacle& o : obstacles)
     if (o.dimension.rows != 2 || o.relative_pos_array.rows != 4 || o.dimension.cols < params.horizon ||
@@ -122,6 +124,9 @@ void iLQR::set_Obstacle(const std::vector<Obstacle>& obstacles) {
 }
 
 void iLQR::clear_Obstacle() {
+  trk_reset_ = true;  // (the tracker starts over with the next map)
+  trk_owns_tracks_ = false;
+  last_tracks.clear();
   if (tracked_horizon_ >= 0) obs_cov_.clear();
   tracked_horizon_ = -1;
   tracks_.clear(); track_dims_.clear(); track_cov_.clear(); track_Q_.clear();
@@ -132,6 +137,7 @@ void iLQR::clear_Obstacle() {
 
 void iLQR::set_tracked_obstacles(const std::vector<double>& tracks, const std::vector<double>& dims, const std::vector<double>& cov,
                                  const std::vector<double>& Q) {
+  if (trk_on_) throw std::logic_error("set_map_tracker: one producer of tracks: not with set_tracked_obstacles");
   const size_t M = tracks.size() / 6;
   if (tracks.size() != 6 * M || dims.size() != 2 * M || (!cov.empty() && cov.size() != 16 * M) || (!Q.empty() && Q.size() != 16))
     throw std::runtime_error("set_tracked_obstacles: needs 6 values per track, 2 dimensions, 16 covariance values or none, and 16 of Q or none");
@@ -180,18 +186,122 @@ void iLQR::set_uncertainty_map(const Uncertainty& u) {
   apply_map(u);
   unc_ = u;  // (kept: set_map_tightening moves the layer between the handle's device copy and this object's)
   map_set_ = true;
-  if (mo_on_) { extract_map_obstacles(); append_map_rows(); }
+  if (mo_on_) {
+    extract_map_obstacles();
+    if (trk_on_) track_map_obstacles();
+    else append_map_rows();
+  }
 }
 
 void iLQR::set_map_obstacles(double occ_threshold, double gap, int min_cells, double max_size, double pad, int K, bool on) {
   if (on && (occ_threshold != occ_threshold || !(gap >= 0.0 && gap <= 1.7e308) || min_cells < 1 || !(max_size > 0.0) ||
              !(pad >= 0.0 && pad <= 1.7e308) || K < 1 || K > CILQR_MAX_POLYGONS))
     throw std::runtime_error("set_map_obstacles: needs a threshold that is not NaN, gap and pad >= 0 and finite, min_cells >= 1, max_size > 0 and K in 1 ... CILQR_MAX_POLYGONS");
+  if (trk_on_ && !on) throw std::logic_error("set_map_tracker: needs set_map_obstacles: switch the tracker off first");
+  if (trk_on_ && K > CILQR_TRACK_MAX_DETECTIONS) throw std::runtime_error("set_map_obstacles: K above CILQR_TRACK_MAX_DETECTIONS under set_map_tracker");
   mo_on_ = on;
   if (on) { mo_threshold_ = occ_threshold; mo_gap_ = gap; mo_min_cells_ = min_cells; mo_max_size_ = max_size; mo_pad_ = pad; mo_K_ = K; }
   if (on && map_set_) extract_map_obstacles();
   if (!on) { last_map_obstacles.clear(); memset(last_map_obstacle_counts, 0, sizeof(last_map_obstacle_counts)); }
+  if (trk_on_) return;  // (the rows reach the tracker with the next map; no static row is appended)
   if (on ? map_set_ : map_rows_ > 0) append_map_rows();
+}
+
+void iLQR::set_map_tracker(const cilqr_track_filter& f, int slots, bool on) {
+  if (!on) {
+    if (trk_on_) {
+      trk_on_ = false;
+      drop_tracker_tracks();
+      if (mo_on_ && map_set_) append_map_rows();  // the static rows again
+    }
+    return;
+  }
+  if (!mo_on_) throw std::logic_error("set_map_tracker: needs set_map_obstacles");
+  if (mo_K_ > CILQR_TRACK_MAX_DETECTIONS) throw std::runtime_error("set_map_tracker: the K of set_map_obstacles is above CILQR_TRACK_MAX_DETECTIONS");
+  if (slots < 1 || slots > CILQR_TRACK_MAX_SLOTS || slots > max_obstacles_)
+    throw std::runtime_error("set_map_tracker: slots outside 1 ... min(CILQR_TRACK_MAX_SLOTS, max_obstacles)");
+  if (!trk_on_ && (tracked_horizon_ >= 0 || !obs_cov_.empty()))
+    throw std::logic_error("set_map_tracker: one producer of tracks: not with set_tracked_obstacles or set_obstacle_covariance in force");
+  if (!trk_on_ && (int)obstacles_.size() > map_rows_)
+    throw std::logic_error("set_map_tracker: the tracker is the one producer of obstacles: call clear_Obstacle first");
+  if (!(f.dt > 0.0 && f.dt <= 1.7e308) || !(f.gate2 >= 0.0) || !(f.v_min >= 0.0) || !(f.theta_var_slow >= 0.0) || f.min_hits < 1 || f.max_misses < 0)
+    throw std::runtime_error("set_map_tracker: a filter cilqr_track_update rejects (dt > 0, gate2, v_min, theta_var_slow >= 0, min_hits >= 1, max_misses >= 0)");
+  if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error("set_map_tracker: hipSetDevice failed");
+  if (!trk_on_ || slots != trk_slots_) {
+    if (trk_dev_) (void)hipFree(trk_dev_);
+    trk_dev_ = nullptr;
+    const size_t need = ((size_t)slots * (CILQR_TRACK_STATE + 24) + CILQR_TRACK_WORLD_FIELDS) * sizeof(double) + CILQR_TRACK_MAX_DETECTIONS * sizeof(int32_t);
+    if (hipMalloc(&trk_dev_, need) != hipSuccess) throw std::runtime_error("set_map_tracker: hipMalloc failed");
+    trk_reset_ = true;
+  }
+  const bool was = trk_on_;
+  if (!was) {  // the static rows leave: the tracker's rows stand in their place
+    trk_reset_ = true;
+    obstacles_.erase(obstacles_.end() - map_rows_, obstacles_.end());
+    map_rows_ = 0;
+    pack_obstacles();
+  }
+  trk_f_ = f;
+  trk_slots_ = slots;
+  trk_on_ = true;
+  if (!was && map_set_) { extract_map_obstacles(); track_map_obstacles(); }  // (the map already set is the first tick)
+}
+
+void iLQR::drop_tracker_tracks() {
+  if (trk_owns_tracks_) {
+    if (tracked_horizon_ >= 0) obs_cov_.clear();
+    tracked_horizon_ = -1;
+    tracks_.clear(); track_dims_.clear(); track_cov_.clear(); track_Q_.clear();
+    obstacles_.clear();
+    map_rows_ = 0;
+    pack_obstacles();
+  }
+  trk_owns_tracks_ = false;
+  last_tracks.clear();
+  memset(last_track_counts, 0, sizeof(last_track_counts));
+}
+
+// One tick on the boxes extract_map_obstacles left on the device (null stream, behind them), then the table's output rows come back and
+// the confirmed ones are installed as set_tracked_obstacles would install them.
+void iLQR::track_map_obstacles() {
+  const size_t M = (size_t)trk_slots_;
+  double *state = (double*)trk_dev_, *world = state + M * CILQR_TRACK_STATE, *track = world + CILQR_TRACK_WORLD_FIELDS, *dim = track + M * 6,
+         *cov = dim + M * 2;
+  int32_t* assign = (int32_t*)(cov + M * 16);
+  check(cilqr_track_update_device(h_, nullptr, 1, trk_slots_, mo_K_, mo_boxes_dev_, mo_n_out_dev_ + 2, 4, &trk_f_, state, state, world,
+                                  trk_reset_ ? CILQR_TRACK_RESET : 0u, assign, track, dim, cov),
+        "cilqr_track_update_device");
+  trk_reset_ = false;
+  std::vector<double> host(M * (CILQR_TRACK_STATE + 24) + CILQR_TRACK_WORLD_FIELDS);
+  if (hipMemcpy(host.data(), trk_dev_, host.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error("set_map_tracker: HIP runtime call failed");
+  const double *hs = host.data(), *hw = hs + M * CILQR_TRACK_STATE, *ht = hw + CILQR_TRACK_WORLD_FIELDS, *hd = ht + M * 6, *hc = hd + M * 2;
+  memcpy(last_track_counts, hw, sizeof(last_track_counts));
+  last_tracks.clear();
+  std::vector<double> tracks, dims, covs;
+  for (size_t m = 0; m < M; ++m) {
+    const double* row = hs + m * CILQR_TRACK_STATE;
+    if (!(row[CILQR_TS_ID] >= 0.0 && row[CILQR_TS_HITS] >= (double)trk_f_.min_hits)) continue;  // filler
+    tracks.insert(tracks.end(), ht + 6 * m, ht + 6 * m + 6);
+    dims.insert(dims.end(), hd + 2 * m, hd + 2 * m + 2);
+    covs.insert(covs.end(), hc + 16 * m, hc + 16 * m + 16);
+    const double r[8] = {row[CILQR_TS_ID], ht[6 * m], ht[6 * m + 1], ht[6 * m + 2], ht[6 * m + 3], hd[2 * m], hd[2 * m + 1], (double)m};
+    last_tracks.insert(last_tracks.end(), r, r + 8);
+  }
+  if (tracks.empty()) {  // nothing confirmed: no obstacle at all
+    if (trk_owns_tracks_) {
+      if (tracked_horizon_ >= 0) obs_cov_.clear();
+      tracked_horizon_ = -1;
+      tracks_.clear(); track_dims_.clear(); track_cov_.clear(); track_Q_.clear();
+      obstacles_.clear();
+      pack_obstacles();
+    }
+    trk_owns_tracks_ = false;
+    return;
+  }
+  tracks_ = tracks; track_dims_ = dims; track_cov_ = covs; track_Q_.clear();
+  install_tracked();
+  trk_owns_tracks_ = true;
 }
 
 // The device forms on a block of this object's own (the layer, d2, work, label_out, then n_out, comp, boxes and the pose), grown when a
@@ -212,6 +322,7 @@ void iLQR::extract_map_obstacles() {
   float* layer = (float*)mo_dev_;
   int32_t *d2 = (int32_t*)mo_dev_ + cells, *work = d2 + cells, *label = work + cells, *n_out = label + cells;
   double *comp = (double*)((int32_t*)mo_dev_ + ints), *boxes = comp + K * CILQR_MAP_OBSTACLE_FIELDS, *pose_dev = boxes + K * 5;
+  mo_boxes_dev_ = boxes; mo_n_out_dev_ = n_out;  // (where set_map_tracker reads its detections and their count)
   const double r = mo_gap_ / g.res, r2 = floor(r * r);
   const int gap2 = r2 < 2147483646.0 ? (int)r2 : 2147483646;
   const double pose[3] = {unc_.pose_x, unc_.pose_y, unc_.pose_theta};
@@ -234,7 +345,7 @@ void iLQR::extract_map_obstacles() {
 void iLQR::append_map_rows() {
   obstacles_.erase(obstacles_.end() - map_rows_, obstacles_.end());
   map_rows_ = 0;
-  const int N = params.horizon, n = (int)(last_map_obstacles.size() / 5);
+  const int N = params.horizon, n = trk_on_ ? 0 : (int)(last_map_obstacles.size() / 5);  // (under set_map_tracker the rows reach the solve as tracks)
   if ((int)obstacles_.size() + n > max_obstacles_) {
     pack_obstacles();
     throw std::runtime_error("set_map_obstacles: the obstacles of set_Obstacle and the rows from the map exceed max_obstacles");
@@ -254,7 +365,8 @@ void iLQR::append_map_rows() {
 }
 
 void iLQR::check_map_obstacle_conflicts() const {
-  if (mo_on_ && (n_samples_ > 0 || tracked_horizon_ >= 0 || !obs_cov_.empty()))
+  if (trk_on_ && n_samples_ > 0) throw std::logic_error("set_map_tracker: the tracks have no samples: not with set_obstacle_samples");
+  if (mo_on_ && !trk_on_ && (n_samples_ > 0 || tracked_horizon_ >= 0 || !obs_cov_.empty()))
     throw std::logic_error("set_map_obstacles: the rows from the map have neither samples nor a covariance: not with set_obstacle_samples, "
                            "set_tracked_obstacles or set_obstacle_covariance");
 }
@@ -313,6 +425,7 @@ void iLQR::clear_uncertainty_map() {
   map_set_ = false;
   last_map_obstacles.clear();
   memset(last_map_obstacle_counts, 0, sizeof(last_map_obstacle_counts));
+  if (trk_on_) { drop_tracker_tracks(); trk_reset_ = true; }  // (the tracks go with their map, and the tracker starts over)
   if (map_rows_ > 0) append_map_rows();  // (the rows go with their map)
 }
 
@@ -824,6 +937,7 @@ void iLQR::check_track_map_conflicts() const {
 int iLQR::solve_obstacles() const { return modes().track_rounds() && !tm_ellipses_ ? 0 : (int)obstacles_.size(); }
 
 void iLQR::set_obstacle_covariance(const std::vector<double>& cov) {
+  if (trk_on_) throw std::logic_error("set_map_tracker: the tracks carry their own covariance: not with set_obstacle_covariance");
   obs_cov_ = cov;
   pack_obstacles();
 }

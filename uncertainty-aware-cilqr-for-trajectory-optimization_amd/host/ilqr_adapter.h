@@ -295,6 +295,20 @@ class iLQR {
   // set_obstacle_samples, set_tracked_obstacles or set_obstacle_covariance in force a run throws std::logic_error: the rows have
   // neither samples nor a covariance.  Off (the default): nothing changes for existing callers.
   void set_map_obstacles(double occ_threshold, double gap, int min_cells, double max_size, double pad, int K, bool on = true);
+  // Map tracker: the rows of set_map_obstacles followed across ticks, so that a moving vehicle reaches the solver with a velocity and
+  // a covariance and not as a box that stands where it is now.  It needs set_map_obstacles (std::logic_error without it) with
+  // K <= CILQR_TRACK_MAX_DETECTIONS, and 1 <= slots <= min(CILQR_TRACK_MAX_SLOTS, max_obstacles) (std::runtime_error otherwise, and for
+  // a filter cilqr_track_update rejects).  While it is on, every set_uncertainty_map runs cilqr_map_distance_device ->
+  // cilqr_map_obstacles_device -> cilqr_track_update_device(f, slots; the counts read where cilqr_map_obstacles left them), the first
+  // map after switching on or after clear_Obstacle with CILQR_TRACK_RESET.  The CONFIRMED rows are installed through the path of
+  // set_tracked_obstacles — predicted over params.horizon with their covariance, in slot order — and the static rows of
+  // set_map_obstacles are not appended: the judges that read tracks (set_obstacle_covariance_check, set_chance_tightening with the
+  // obstacles' covariance, set_track_map) have their input in the map-only configuration.  The tracker is the one producer of
+  // tracks: set_tracked_obstacles, set_Obstacle and set_obstacle_covariance beside it throw std::logic_error, and so does switching it
+  // on while tracks of set_tracked_obstacles are set.  last_tracks holds 8 values per confirmed row — (id, x, y, v, theta, length,
+  // width, slot) — and last_track_counts the world record (cilqr_track_world_field).  on = false removes the tracks and, with a map
+  // set, puts the static rows back.  Off (the default): nothing changes for existing callers.
+  void set_map_tracker(const cilqr_track_filter& f, int slots, bool on = true);
   // Test hook: cilqr_debug_uncertainty_cost on the map this object's handle holds right now, at n = states.size() / 4 states
   // (x, y, v, theta) -> n costs, then 2n of vx, then 3n of mx.  Throws std::runtime_error when no map is set.
   std::vector<double> debug_map_cost(const std::vector<double>& states) const;
@@ -364,6 +378,9 @@ class iLQR {
   // set_uncertainty_map under set_map_obstacles; empty / zero otherwise
   std::vector<double> last_map_obstacles;  // 5 per row: (x, y, yaw, size_x, size_y)
   int32_t last_map_obstacle_counts[4] = {0, 0, 0, 0};  // n_out of cilqr_map_obstacles
+  // set_uncertainty_map under set_map_tracker; empty / zero otherwise
+  std::vector<double> last_tracks;  // 8 per confirmed row: (id, x, y, v, theta, length, width, slot)
+  double last_track_counts[CILQR_TRACK_WORLD_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the world record of cilqr_track_update
 
  private:
   void pack_obstacles();
@@ -487,6 +504,16 @@ class iLQR {
   void append_map_rows();                      // replaces the map's entries of obstacles_ by last_map_obstacles, packs
   void refresh_map_rows() { if (map_rows_ && map_rows_horizon_ != params.horizon) append_map_rows(); }  // (the horizon changed)
   void check_map_obstacle_conflicts() const;   // throws std::logic_error, before a run enqueues anything
+  // map tracker (set_map_tracker): the table, the world record and the output rows live in trk_dev_; the detections are the boxes
+  // extract_map_obstacles left in mo_dev_ (mo_boxes_dev_, mo_n_out_dev_)
+  bool trk_on_ = false, trk_reset_ = true, trk_owns_tracks_ = false;
+  cilqr_track_filter trk_f_{};
+  int trk_slots_ = 0;
+  void* trk_dev_ = nullptr;
+  double* mo_boxes_dev_ = nullptr;
+  int32_t* mo_n_out_dev_ = nullptr;
+  void track_map_obstacles();  // one tick on the boxes in mo_dev_, then the confirmed rows installed as tracks
+  void drop_tracker_tracks();  // removes what track_map_obstacles installed
 };
 
 }  // namespace cilqr_host

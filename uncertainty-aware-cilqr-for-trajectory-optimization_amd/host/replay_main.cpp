@@ -3,7 +3,7 @@
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
 //   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]
-//                                                                                             → one line per tick on stdout
+//                [--map-tracker dt,q,r,gate2,min_hits,max_misses]                               → one line per tick on stdout
 //
 // --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
 // (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
@@ -18,6 +18,12 @@
 // --map-obstacles: iLQR::set_map_obstacles(thr, gap, min_cells, max_size, pad 0, K = 16): on every tick that carries a `map` record
 // the occupied cells of its layer (value > thr) are clustered into boxes, which are installed behind the tick's obstacles; the line
 // then ends with " map_obstacles <installed> <components>".  A tick without a map record clears the map (0 0).
+//
+// --map-tracker (with --map-obstacles): iLQR::set_map_tracker with 16 slots: the boxes are followed across the ticks by a constant-velocity
+// Kalman filter — dt seconds between ticks, Q built for dt from the white-acceleration intensity q (q dt^3/3, q dt^2/2, q dt per axis),
+// R = r^2 I, P_birth = diag(r^2, r^2, 16, 16), v_min 0.5 m/s, theta_var_slow 1 — and the confirmed tracks reach the solve predicted over
+// the horizon, in place of the standing boxes.  The line then ends with " tracks <n>" and per confirmed track " <id> <x> <y> <speed>
+// <heading>".  The ticks must carry no obstacles of their own.
 //
 // Log (whitespace-separated, '#' starts a comment line):
 //   cilqr-replay 1
@@ -78,16 +84,17 @@ struct Tokens {
 
 int main(int argc, char** argv) {
   std::vector<const char*> pos;  // the log and the device; options may stand anywhere
-  const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr;
+  const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr, *map_tracker = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
     else if (strcmp(argv[i], "--stop-fallback") == 0 && i + 1 < argc) stop = argv[++i];
     else if (strcmp(argv[i], "--map-obstacles") == 0 && i + 1 < argc) map_obstacles = argv[++i];
+    else if (strcmp(argv[i], "--map-tracker") == 0 && i + 1 < argc) map_tracker = argv[++i];
     else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
     else pos.push_back(argv[i]);
   }
   if (pos.empty() || pos.size() > 2) {
-    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]\n", argv[0]);
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size] [--map-tracker dt,q,r,gate2,min_hits,max_misses]\n", argv[0]);
     return 2;
   }
   try {
@@ -143,6 +150,25 @@ int main(int argc, char** argv) {
       if (sscanf(map_obstacles, "%lf,%lf,%d,%lf", &thr, &gap, &min_cells, &max_size) != 4) throw std::runtime_error("--map-obstacles takes thr,gap,min_cells,max_size");
       planner.set_map_obstacles(thr, gap, min_cells, max_size, 0.0, 16);
     }
+    if (map_tracker) {
+      if (!map_obstacles) throw std::runtime_error("--map-tracker needs --map-obstacles");
+      cilqr_track_filter tf{};
+      double q = 0.0, r = 0.0;
+      if (sscanf(map_tracker, "%lf,%lf,%lf,%lf,%d,%d", &tf.dt, &q, &r, &tf.gate2, &tf.min_hits, &tf.max_misses) != 6)
+        throw std::runtime_error("--map-tracker takes dt,q,r,gate2,min_hits,max_misses");
+      const double dt = tf.dt;
+      for (int a = 0; a < 2; ++a) {  // column-major, row <= column
+        tf.Q[a + 4 * a] = q * dt * dt * dt / 3.0;
+        tf.Q[a + 4 * (a + 2)] = q * dt * dt / 2.0;
+        tf.Q[(a + 2) + 4 * (a + 2)] = q * dt;
+        tf.R[a + 2 * a] = r * r;
+        tf.P_birth[a + 4 * a] = r * r;
+        tf.P_birth[(a + 2) + 4 * (a + 2)] = 16.0;
+      }
+      tf.v_min = 0.5;
+      tf.theta_var_slow = 1.0;
+      planner.set_map_tracker(tf, 16);
+    }
     bool map_on = false;
     while (!in.done()) {
       in.expect("tick");
@@ -164,7 +190,10 @@ int main(int argc, char** argv) {
         obstacles.emplace_back(params, dim, pose);
       }
       planner.set_global_plan(path);
-      if (M) planner.set_Obstacle(obstacles); else planner.clear_Obstacle();
+      if (map_tracker) {
+        if (M) throw std::runtime_error("--map-tracker: the tracker is the one producer of obstacles, and the tick carries its own");
+      } else if (M) planner.set_Obstacle(obstacles);
+      else planner.clear_Obstacle();
       if (!in.done() && in.t[in.at] == "map") {
         in.expect("map");
         double v[8];
@@ -200,6 +229,11 @@ int main(int argc, char** argv) {
         printf(" tighten %.17g %.17g %d %d %.17g", planner.last_tighten[CILQR_TG_MAX_DA], planner.last_tighten[CILQR_TG_MAX_DB],
                (int)planner.last_tighten[CILQR_TG_MAX_ENTRY], (int)planner.last_tighten[CILQR_TG_CAPPED], planner.last_tighten_risk_before[0]);
       if (map_obstacles) printf(" map_obstacles %d %d", planner.last_map_obstacle_counts[2], planner.last_map_obstacle_counts[0]);
+      if (map_tracker) {
+        printf(" tracks %d", (int)(planner.last_tracks.size() / 8));
+        for (size_t k = 0; k + 8 <= planner.last_tracks.size(); k += 8)
+          printf(" %d %.9g %.9g %.9g %.9g", (int)planner.last_tracks[k], planner.last_tracks[k + 1], planner.last_tracks[k + 2], planner.last_tracks[k + 3], planner.last_tracks[k + 4]);
+      }
       if (stop) printf(" stop %d %d %d", picked < 0 ? -1 : planner.last_stop_level >= 0 ? 1 : 0, planner.last_stop_level, planner.last_stop_pick);
       printf("\n");
     }
