@@ -1748,6 +1748,78 @@ int cilqr_track_update(cilqr_handle* h, int W, int M, int D, const double* det, 
                        const cilqr_track_filter* f, const double* state_in, double* state_out, double* world, uint32_t flags,
                        int32_t* assign, double* track_out, double* dim_out, double* cov_out);
 
+/* --- static layer: the cells of tracked movers taken out of the map (new) --------------------------------------------------------------
+ * A vehicle that cilqr_track_update has confirmed as moving is still in the layer the map calls read: a blob of occupied cells that
+ * stands where it is NOW for the whole horizon, while its track predicts it somewhere else (the complaint of the
+ * cilqr_rasterize_tracks section above).  cilqr_clear_movers(_device) separates static from dynamic occupancy: the cells that
+ * belong to the components of moving tracks, and a halo around them, are set to `fill`; everything else is a bit copy.  Its inputs
+ * are what the calls in front left in device memory; nothing is read back.
+ * L layers per call, float32, column-major (i + j*rows); layer and layer_stride as cilqr_inflate_map takes them; of g only rows and
+ * cols are read (res only has to pass that call's geometry check).
+ *
+ * Definitions.
+ *   label       [L][rows*cols] int32 (required): the label_out of cilqr_map_obstacles.  A cell with a value >= 0 is LINKED.
+ *   comp        [L][K][CILQR_MAP_OBSTACLE_FIELDS] (required), K in 1 ... CILQR_MAX_POLYGONS: only CILQR_MO_LABEL is read; a filler
+ *               row has -1.
+ *   movers      given in exactly ONE of two forms (both or neither, or half of the first: CILQR_ERR_ARG).
+ *     tracker   assign [L][K] int32 and state [L][M][CILQR_TRACK_STATE]: those of cilqr_track_update run with W = L and D = K, after
+ *               the tick; M in 1 ... CILQR_TRACK_MAX_SLOTS, min_hits >= 1, v_clear >= 0 (m/s).  Row k of layer l is a MOVER when its
+ *               comp label is >= 0, m = assign[l][k] lies in [0, M), state[l][m][ID] >= 0, state[l][m][DET] == k,
+ *               state[l][m][HITS] >= min_hits and hypot(VX, VY) >= v_clear, evaluated in double; a NaN fails.
+ *     mask      mask [L][K] int32, for a caller with a tracker of their own: row k is a MOVER when mask[l][k] != 0 and its comp
+ *               label is >= 0.  M, min_hits and v_clear are not read.
+ *   halo2       an integer in cells^2, 0 <= halo2 <= CILQR_CLEAR_MOVERS_MAX_HALO2; r = the largest integer with r*r <= halo2 (<= 32).
+ *   fill        a float, finite or NaN.
+ *   ownership   per cell c = (i, j): over the linked cells q = (i', j') of the layer with |i - i'| <= r and |j - j'| <= r take the
+ *               lexicographic minimum of ((i - i')^2 + (j - j')^2, label[q]).  If there is one and its squared distance is <= halo2,
+ *               the component with that label OWNS c; otherwise nobody does.  A linked cell owns itself.  EVERY linked cell
+ *               competes, whether or not its component got a row: a wall that max_size or K dropped keeps its own halo, and a cell
+ *               nearer to it than to a mover is not cleared.  Equal distance goes to the lower label.
+ *   layer_out   [L][rows*cols] float32 (required), dense.  A cell owned by a MOVER's component whose input is not NaN becomes `fill`;
+ *               every other cell is a bit copy of the input: unknown stays unknown.  layer_out may be the very buffer `layer` under
+ *               the rule of cilqr_inflate_map (L == 1 or layer_stride == rows*cols); any other overlap of the two is CILQR_ERR_ARG
+ *               (device form).
+ *   owner_out   [L][rows*cols] int32 or NULL: the owning label, -1 where nobody owns the cell.
+ *   fields      [L][CILQR_CLEAR_MOVERS_FIELDS] doubles (required), see the enum: exact integers, and one largest value.  A -0 input
+ *               counts as 0 for CM_MAX_VALUE and is reported as 0.
+ *   Determinism: integer sums and a lexicographic maximum: a layer's bits depend on that layer alone, whatever L, its place in the
+ *   batch, or layer_stride 0 against dense layers.
+ * What it is NOT.  A mover whose component merged with a wall gets a different box; the tracker will most likely not match it and
+ * it is not cleared — the conservative failure.  Blur that reaches beyond halo2 stays in the layer.  A cleared vehicle is GONE from
+ * the map: it must come back through the tracks (cilqr_rasterize_tracks, cilqr_chance_risk_cov, cilqr_footprint_check on the
+ * predicted table of cilqr_predict_obstacles), and the caller must keep those behind this call.
+ * Mapping: one 64*L-byte clear of `fields` and two launches, nothing allocated per call, no float atomics.  One workgroup per
+ * 64 x 16 tile, lane along i: a prologue, lane = row, decides the movers and sorts their labels into LDS; the tile's labels and an
+ * apron of r cells go to LDS; one pass along i leaves (|di|, label) per column, one pass along j the owner — the rule is separable:
+ * within a column the distance grows with |di|; each workgroup adds its counts into the layer's row by 64-bit integer atomics (sums
+ * and one maximum), and a second launch, lane = layer, turns the row into doubles.
+ * CILQR_ERR_ARG, decided before the handle is looked at: NULL layer, g, label, comp, layer_out or fields; L < 1, or a geometry or
+ * layer_stride cilqr_inflate_map rejects; K outside 1 ... CILQR_MAX_POLYGONS; not exactly one mover form; in the tracker form M
+ * outside 1 ... CILQR_TRACK_MAX_SLOTS, min_hits < 1, or v_clear negative or NaN; halo2 out of range; an infinite fill; a forbidden
+ * overlap; L*ceil(rows/64)*ceil(cols/16) beyond 2^31 - 1 workgroups.  CILQR_ERR_UNSUPPORTED for rows or cols > 1024, the bound of
+ * cilqr_map_obstacles.  The host-buffer form's arrays — the layers' span, label, layer_out and owner_out at 4 bytes a cell, 13
+ * doubles a row, and the mover form's — must fit the device arena reserved at create (CILQR_ERR_ARG otherwise, as for every host
+ * form; this call adds nothing to it). */
+#define CILQR_CLEAR_MOVERS_MAX_HALO2 1024
+#define CILQR_CLEAR_MOVERS_FIELDS 8
+typedef enum cilqr_clear_movers_field {
+  CILQR_CM_MOVERS = 0,        /* rows that are movers */
+  CILQR_CM_CLEARED = 1,       /* cells whose output bits differ from the input */
+  CILQR_CM_OWNED_LINKED = 2,  /* linked cells owned by movers */
+  CILQR_CM_OWNED_HALO = 3,    /* cells that are not linked and owned by movers */
+  CILQR_CM_MAX_VALUE = 4,     /* the largest finite input among the mover-owned cells, -1 when there is none */
+  CILQR_CM_MAX_CELL = 5,      /* the lowest cell i + j*rows that has it, -1 when there is none */
+  CILQR_CM_CONTESTED = 6,     /* cells, not linked, within halo2 of a mover's linked cell that a non-mover owns: kept */
+  CILQR_CM_KEPT_UNKNOWN = 7   /* NaN cells a mover owns: kept */
+} cilqr_clear_movers_field;
+int cilqr_clear_movers_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                              const int32_t* label, int K, const double* comp, int M, const int32_t* assign, const double* state,
+                              int min_hits, double v_clear, const int32_t* mask, int halo2, float fill, float* layer_out,
+                              int32_t* owner_out, double* fields);
+int cilqr_clear_movers(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* label,
+                       int K, const double* comp, int M, const int32_t* assign, const double* state, int min_hits, double v_clear,
+                       const int32_t* mask, int halo2, float fill, float* layer_out, int32_t* owner_out, double* fields);
+
 /* --- exact clearance of the ego rectangle to the occupied cells of the map (new) -----------------------------------------------------
  * The map counterpart of CILQR_FP_CLEARANCE: cilqr_footprint_check reports only whether the rectangle covers a cell above the
  * threshold; this call returns how far the nearest such cell is, so that min_clearance has something to act on where the map is

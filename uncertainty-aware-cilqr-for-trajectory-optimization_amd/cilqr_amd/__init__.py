@@ -84,6 +84,11 @@ TRACK_WORLD_FIELDS = 9
 (TW_NEXT_ID, TW_TICKS, TW_LIVE, TW_CONFIRMED, TW_MATCHED, TW_BORN, TW_DIED, TW_DROPPED,
  TW_INVALID) = range(TRACK_WORLD_FIELDS)
 TRACK_RESET = 1  # flags of `track_update`: every slot is free on entry
+# `cilqr_clear_movers_field`: a layer's record of `Solver.clear_movers`
+CLEAR_MOVERS_FIELDS = 8
+(CM_MOVERS, CM_CLEARED, CM_OWNED_LINKED, CM_OWNED_HALO, CM_MAX_VALUE, CM_MAX_CELL, CM_CONTESTED,
+ CM_KEPT_UNKNOWN) = range(CLEAR_MOVERS_FIELDS)
+CLEAR_MOVERS_MAX_HALO2 = 1024  # cells^2
 # `cilqr_map_clearance_field`: the columns of a map clearance row (`Solver.map_clearance`)
 MAP_CLEARANCE_FIELDS = 8
 (MC_CLEARANCE, MC_STEP, MC_CELL, MC_BELOW_STEPS, MC_FIRST_BELOW, MC_TOUCH_STEPS, MC_OFF_MAP_STEPS,
@@ -126,6 +131,7 @@ ABI_SYMBOLS = (
     "cilqr_map_distance", "cilqr_map_distance_device", "cilqr_inflate_map", "cilqr_inflate_map_device",
     "cilqr_map_obstacles", "cilqr_map_obstacles_device",
     "cilqr_track_update", "cilqr_track_update_device",
+    "cilqr_clear_movers", "cilqr_clear_movers_device",
     "cilqr_map_clearance", "cilqr_map_clearance_device",
     "cilqr_stop_plans", "cilqr_stop_plans_device",
 )
@@ -1220,6 +1226,70 @@ class Solver:
         _check(lib().cilqr_track_update_device(self._h, _vp(stream), int(W), int(M), int(D), _vp(det), _vp(n_det), C.c_int64(int(n_det_stride)),
                                                C.byref(filt), _vp(state_in), _vp(state_out), _vp(world), C.c_uint32(int(flags)),
                                                _vp(assign), _vp(track_out), _vp(dim_out), _vp(cov_out)))
+
+    # ---- static layer: the cells of tracked movers taken out of the map ----
+    def clear_movers(self, layers, geom, label, comp, halo2=0, fill=0.0, assign=None, state=None, min_hits=1, v_clear=0.0, mask=None,
+                     L=None, want_owner=True):
+        """`cilqr_clear_movers`: layers as `map_distance` takes them (one (rows, cols) layer with L given: the shared layer); label
+        (L, rows, cols) int32 and comp (L, K, MAP_OBSTACLE_FIELDS) as `map_obstacles` returns them.  The movers come in ONE of two
+        forms: assign (L, K) int32 and state (L, M, TRACK_STATE) as `track_update` returns them (W = L, D = K) with min_hits and
+        v_clear, or mask (L, K) int32.  Returns dict(layer (L, rows, cols) float32, owner (L, rows, cols) int32 — None with
+        want_owner=False — and fields (L, CLEAR_MOVERS_FIELDS)).  The arrays travel through the device arena: large maps and
+        batches take the device form."""
+        flat, n = self._layers(layers, geom)
+        stride = flat.shape[1]
+        if L is not None:
+            if n != 1:
+                raise CilqrError("clear_movers: L is given for ONE shared layer, not %d" % n)
+            n, stride = int(L), 0
+        label = np.asarray(label, dtype=np.int32)
+        if label.ndim == 2:
+            label = label[None]
+        if label.shape != (n, geom.rows, geom.cols):
+            raise CilqrError("clear_movers: label %s is not (%d, %d, %d)" % (label.shape, n, geom.rows, geom.cols))
+        label = np.ascontiguousarray(label.transpose(0, 2, 1)).reshape(n, -1)
+        comp = _np64(comp)
+        if comp.ndim == 2:
+            comp = comp[None]
+        if comp.ndim != 3 or comp.shape[0] != n or comp.shape[2] != MAP_OBSTACLE_FIELDS:
+            raise CilqrError("clear_movers: comp %s is not (%d, K, %d)" % (comp.shape, n, MAP_OBSTACLE_FIELDS))
+        K, M = int(comp.shape[1]), 0
+
+        def rows_of(a, name):
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            a = a[None] if a.ndim == 1 else a
+            if a.shape != (n, K):
+                raise CilqrError("clear_movers: %s %s is not (%d, %d)" % (name, a.shape, n, K))
+            return a
+
+        if assign is not None:
+            assign = rows_of(assign, "assign")
+        if mask is not None:
+            mask = rows_of(mask, "mask")
+        if state is not None:
+            state = _np64(state)
+            state = state[None] if state.ndim == 2 else state
+            if state.ndim != 3 or state.shape[0] != n or state.shape[2] != TRACK_STATE:
+                raise CilqrError("clear_movers: state %s is not (%d, M, %d)" % (state.shape, n, TRACK_STATE))
+            M = int(state.shape[1])
+        out = np.zeros((n, flat.shape[1]), dtype=np.float32)
+        owner = np.zeros((n, flat.shape[1]), dtype=np.int32) if want_owner else None
+        fields = np.zeros((n, CLEAR_MOVERS_FIELDS))
+        _check(lib().cilqr_clear_movers(self._h, n, _p(flat, _fp), C.c_int64(stride), C.byref(geom), _p(label, _ip), K, _p(comp), M,
+                                        _p(assign, _ip), _p(state), int(min_hits), C.c_double(v_clear), _p(mask, _ip), int(halo2),
+                                        C.c_float(fill), _p(out, _fp), _p(owner, _ip), _p(fields)))
+        shape = lambda a: None if a is None else a.reshape(n, geom.cols, geom.rows).transpose(0, 2, 1)
+        return dict(layer=shape(out), owner=shape(owner), fields=fields)
+
+    def clear_movers_device(self, stream, L, layer, layer_stride, geom, label, K, comp, layer_out, fields, halo2=0, fill=0.0, M=0,
+                            assign=0, state=0, min_hits=1, v_clear=0.0, mask=0, owner_out=0):
+        """`cilqr_clear_movers_device`: device addresses; label and owner_out (L, rows*cols) int32, comp (L, K, MAP_OBSTACLE_FIELDS),
+        assign / mask (L, K) int32, state (L, M, TRACK_STATE), layer_out (L, rows*cols) float32 — it may be `layer` itself when L == 1
+        or layer_stride == rows*cols —, fields (L, CLEAR_MOVERS_FIELDS) float64.  layer_out feeds `set_uncertainty_map_device`."""
+        _check(lib().cilqr_clear_movers_device(self._h, _vp(stream), int(L), _vp(layer), C.c_int64(int(layer_stride)), C.byref(geom),
+                                               _vp(label), int(K), _vp(comp), int(M), _vp(assign), _vp(state), int(min_hits),
+                                               C.c_double(v_clear), _vp(mask), int(halo2), C.c_float(fill), _vp(layer_out),
+                                               _vp(owner_out), _vp(fields)))
 
     def map_clearance(self, N, X, reach, S=1, margin=0.0, occ_threshold=float("inf"), min_clearance=0.0, base=None,
                       unknown_seeds=False, steps=True):

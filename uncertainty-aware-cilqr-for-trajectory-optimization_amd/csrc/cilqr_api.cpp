@@ -14,6 +14,7 @@
 
 #include "cilqr_handle.h"
 #include "costmap_components.hpp"
+#include "costmap_movers.hpp"
 
 namespace cilqr {
 thread_local std::string g_last_error;
@@ -1895,6 +1896,82 @@ int cilqr_map_obstacles(cilqr_handle* h, int L, const int32_t* d2, const cilqr_m
   for (int l = 0; l < L; ++l)
     if (counts[4 * l + 2] < 0) return fail(CILQR_ERR_INTERNAL, "cilqr_map_obstacles: a loop bound ran out in layer %d", l);
   return CILQR_OK;
+}
+
+// ---- static layer: the cells of tracked movers taken out of the map (costmap_movers.hip) -----------------------------------------------------
+namespace {
+// what needs no handle; *cells, *span and *tracker (which mover form) on success
+int clear_movers_args_check(int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* label, int K,
+                            const double* comp, int M, const int32_t* assign, const double* state, int min_hits, double v_clear,
+                            const int32_t* mask, int halo2, float fill, const float* layer_out, const double* fields, size_t* cells,
+                            size_t* span, bool* tracker) {
+  if (!layer || !g || !label || !comp || !layer_out || !fields) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: null required pointer");
+  if (g->rows > cilqr::MAP_OBSTACLES_MAX_SIDE || g->cols > cilqr::MAP_OBSTACLES_MAX_SIDE)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_clear_movers: %d x %d cells, more than %d along a side", g->rows, g->cols,
+                cilqr::MAP_OBSTACLES_MAX_SIDE);
+  int rc = map_layers_check("cilqr_clear_movers", L, layer, layer_stride, g, cells, span);
+  if (rc) return rc;
+  if (K < 1 || K > CILQR_MAX_POLYGONS) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: K = %d outside [1,%d]", K, CILQR_MAX_POLYGONS);
+  const bool by_tracker = assign && state && !mask, by_mask = mask && !assign && !state;
+  if (!by_tracker && !by_mask)
+    return fail(CILQR_ERR_ARG, "cilqr_clear_movers: the movers come as assign and state, or as mask: exactly one of the two forms");
+  if (by_tracker) {
+    if (M < 1 || M > CILQR_TRACK_MAX_SLOTS) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: M = %d outside [1,%d]", M, CILQR_TRACK_MAX_SLOTS);
+    if (min_hits < 1) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: min_hits = %d, must be at least 1", min_hits);
+    if (!(v_clear >= 0.0)) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: v_clear is negative or NaN");
+  }
+  if (halo2 < 0 || halo2 > CILQR_CLEAR_MOVERS_MAX_HALO2)
+    return fail(CILQR_ERR_ARG, "cilqr_clear_movers: halo2 = %d outside [0,%d]", halo2, CILQR_CLEAR_MOVERS_MAX_HALO2);
+  if (fill == fill && fill - fill != 0.0f) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: fill is infinite");
+  const int64_t tiles = (int64_t)((g->rows + cilqr::CM_TILE_I - 1) / cilqr::CM_TILE_I) * ((g->cols + cilqr::CM_TILE_J - 1) / cilqr::CM_TILE_J);
+  if ((int64_t)L * tiles > 0x7fffffff) return fail(CILQR_ERR_ARG, "cilqr_clear_movers: L = %d layers beyond 2^31 - 1 workgroups", L);
+  *tracker = by_tracker;
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_clear_movers_device(cilqr_handle* h, void* stream, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g,
+                              const int32_t* label, int K, const double* comp, int M, const int32_t* assign, const double* state,
+                              int min_hits, double v_clear, const int32_t* mask, int halo2, float fill, float* layer_out,
+                              int32_t* owner_out, double* fields) {
+  size_t cells = 0, span = 0;
+  bool tracker = false;
+  int rc = clear_movers_args_check(L, layer, layer_stride, g, label, K, comp, M, assign, state, min_hits, v_clear, mask, halo2, fill,
+                                   layer_out, fields, &cells, &span, &tracker);
+  if (rc) return rc;
+  // lane = cell reads its own cell and writes it: in place is fine where layer l of the output IS layer l of the input
+  const bool same = layer_out == layer && (L == 1 || (size_t)layer_stride == cells);
+  if (!same && layer_out < layer + span && layer < layer_out + (size_t)L * cells)
+    return fail(CILQR_ERR_ARG, "cilqr_clear_movers: layer_out overlaps layer without being the same layers");
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::ClearMoversArgs a = {};
+  a.layer = layer; a.layer_stride = layer_stride; a.label = label; a.comp = comp;
+  a.assign = tracker ? assign : nullptr; a.state = tracker ? state : nullptr; a.mask = tracker ? nullptr : mask;
+  a.layer_out = layer_out; a.owner_out = owner_out; a.fields = fields;
+  a.v_clear = v_clear; a.fill = fill;
+  a.L = L; a.rows = g->rows; a.cols = g->cols; a.K = K; a.M = tracker ? M : 0; a.min_hits = min_hits; a.halo2 = halo2;
+  a.r = cilqr::cm_isqrt(halo2);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_clear_movers(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_clear_movers(cilqr_handle* h, int L, const float* layer, int64_t layer_stride, const cilqr_map_geom* g, const int32_t* label,
+                       int K, const double* comp, int M, const int32_t* assign, const double* state, int min_hits, double v_clear,
+                       const int32_t* mask, int halo2, float fill, float* layer_out, int32_t* owner_out, double* fields) {
+  size_t cells = 0, span = 0;
+  bool tracker = false;
+  int rc = clear_movers_args_check(L, layer, layer_stride, g, label, K, comp, M, assign, state, min_hits, v_clear, mask, halo2, fill,
+                                   layer_out, fields, &cells, &span, &tracker);
+  if (rc) return rc;
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  cilqr::HostPlan p(h->d_arena);
+  // (in the arena the output has a place of its own, whatever the caller's two host addresses are)
+  cilqr::plan_clear_movers(p, L, cells, span, K, tracker ? M : 0, layer, label, comp, assign, state, mask, layer_out, owner_out, fields);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_clear_movers_device(h, h->stream, L, layer, layer_stride, g, label, K, comp, M, assign, state, min_hits, v_clear, mask,
+                                     halo2, fill, layer_out, owner_out, fields);
+  });
 }
 
 // ---- exact clearance of the ego rectangle to the occupied cells of the map (cilqr_map_clearance.hip) ---------------------------------------

@@ -431,6 +431,23 @@ inline void plan_map_obstacles(HostPlan& p, size_t L, size_t cells, size_t K, si
   p.out(dim_out, L * K * 2);
 }
 
+// cilqr_clear_movers: 8 arrays at most.  In: the layers' span, label, comp and the mover form (assign and M state rows a layer, or
+// mask); out: layer_out, owner_out and the fields rows.  Four arrays of 4 bytes a cell, 13 doubles and one or two int32 a row, 32·M
+// doubles a layer in the tracker form, 8 doubles a layer of fields; fits as plan_map_distance does.
+inline void plan_clear_movers(HostPlan& p, size_t L, size_t cells, size_t span, size_t K, size_t M, const float*& layer,
+                              const int32_t*& label, const double*& comp, const int32_t*& assign, const double*& state,
+                              const int32_t*& mask, float*& layer_out, int32_t*& owner_out, double*& fields) {
+  p.in(layer, span);
+  p.in(label, L * cells);
+  p.in(comp, L * K * CILQR_MAP_OBSTACLE_FIELDS);
+  p.in(assign, L * K);
+  p.in(state, L * M * CILQR_TRACK_STATE);
+  p.in(mask, L * K);
+  p.out(layer_out, L * cells);
+  p.out(owner_out, L * cells);
+  p.out(fields, L * CILQR_CLEAR_MOVERS_FIELDS);
+}
+
 // cilqr_map_clearance: 5 arrays; R = B·S rows; the map is the handle's.  Per row 5·N + 14 doubles with every output — X, base, the mc
 // row, step_clearance, total — against the 28·N + 50 per unit of max_batch that host_arena_bytes reserves below: every R <= max_batch
 // fits, and the 5 roundings stay within its 32 x 16 bytes.

@@ -464,6 +464,28 @@ struct MapObstaclesArgs {
 };
 hipError_t launch_map_obstacles(const MapObstaclesArgs& a, hipStream_t stream);
 
+// Static layer: the cells of the components that moving tracks own, taken out of L layers (costmap_movers.hip; cilqr_clear_movers*).
+// One 64·L-byte clear of `fields`, one launch with a workgroup per 64 x 16 tile (layer slowest) that adds its counts into `fields`
+// as raw 64-bit integers, and one launch, lane = layer, that turns them into doubles.  Outputs are dense, rows·cols apart.
+constexpr int CLEAR_MOVERS_THREADS = 256;
+struct ClearMoversArgs {
+  const float* layer;
+  long long layer_stride;
+  const int32_t* label;   // [L][rows·cols]
+  const double* comp;     // [L][K][CILQR_MAP_OBSTACLE_FIELDS]
+  const int32_t* assign;  // [L][K], tracker form; null in the mask form
+  const double* state;    // [L][M][CILQR_TRACK_STATE], tracker form
+  const int32_t* mask;    // [L][K], mask form; null in the tracker form
+  float* layer_out;       // [L][rows·cols]
+  int32_t* owner_out;     // [L][rows·cols] or null
+  double* fields;         // [L][CILQR_CLEAR_MOVERS_FIELDS]
+  double v_clear;
+  float fill;
+  int32_t L, rows, cols, K, M, min_hits, halo2, r;
+};
+hipError_t launch_clear_movers(const ClearMoversArgs& a, hipStream_t stream);
+size_t clear_movers_lds_bytes(int K, int r);
+
 // Exact clearance of the ego rectangle to the occupied cells of the map set on the handle (cilqr_map_clearance.hip;
 // cilqr_map_clearance*).  Two launches: wavefront = (row, step), FOOTPRINT_WAVES steps per workgroup, lanes over the cells of the
 // window; then one wavefront per row for the fold.  `s` carries B (SOLVES), N and unc; row r = b·S + s reads X at r and the layer and

@@ -186,10 +186,12 @@ void iLQR::set_uncertainty_map(const Uncertainty& u) {
   apply_map(u);
   unc_ = u;  // (kept: set_map_tightening moves the layer between the handle's device copy and this object's)
   map_set_ = true;
+  if (mv_on_) given_layer_ = u.layer;
   if (mo_on_) {
     extract_map_obstacles();
     if (trk_on_) track_map_obstacles();
     else append_map_rows();
+    if (mv_on_) clear_tracked_movers();
   }
 }
 
@@ -208,6 +210,7 @@ void iLQR::set_map_obstacles(double occ_threshold, double gap, int min_cells, do
 }
 
 void iLQR::set_map_tracker(const cilqr_track_filter& f, int slots, bool on) {
+  if (!on && trk_on_ && mv_on_) throw std::logic_error("set_mover_clearing: needs set_map_tracker: switch the clearing off first");
   if (!on) {
     if (trk_on_) {
       trk_on_ = false;
@@ -310,7 +313,7 @@ void iLQR::track_map_obstacles() {
 void iLQR::extract_map_obstacles() {
   const cilqr_map_geom& g = unc_.geom;
   const size_t cells = (size_t)g.rows * g.cols, ints = (4 * cells + 4 + 1) / 2 * 2, K = (size_t)mo_K_;
-  const size_t doubles = K * (CILQR_MAP_OBSTACLE_FIELDS + 5) + 3, need = ints * sizeof(int32_t) + doubles * sizeof(double);
+  const size_t doubles = K * (CILQR_MAP_OBSTACLE_FIELDS + 5) + 3 + CILQR_CLEAR_MOVERS_FIELDS, need = ints * sizeof(int32_t) + doubles * sizeof(double);
   const char* what = "set_map_obstacles: HIP runtime call failed";
   if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error(what);
   if (need > mo_dev_cap_) {
@@ -327,7 +330,8 @@ void iLQR::extract_map_obstacles() {
   const int gap2 = r2 < 2147483646.0 ? (int)r2 : 2147483646;
   const double pose[3] = {unc_.pose_x, unc_.pose_y, unc_.pose_theta};
   // (the null stream: each copy below waits for what was enqueued before it)
-  if (hipMemcpy(layer, unc_.layer.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+  const std::vector<float>& given = mv_on_ && given_layer_.size() == cells ? given_layer_ : unc_.layer;  // (under set_mover_clearing unc_ holds the cleared layer)
+  if (hipMemcpy(layer, given.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(pose_dev, pose, sizeof(pose), hipMemcpyHostToDevice) != hipSuccess)
     throw std::runtime_error(what);
   check(cilqr_map_distance_device(h_, nullptr, 1, layer, 0, &g, mo_threshold_, 0u, d2, nullptr), "cilqr_map_distance_device");
@@ -340,6 +344,66 @@ void iLQR::extract_map_obstacles() {
     throw std::runtime_error(what);
   if (last_map_obstacle_counts[2] < 0) throw std::runtime_error("set_map_obstacles: cilqr_map_obstacles ran out of a loop bound (CILQR_ERR_INTERNAL)");
   last_map_obstacles.assign(rows.begin(), rows.begin() + (size_t)5 * last_map_obstacle_counts[2]);
+}
+
+int iLQR::mover_halo2(double res) const {
+  const double r = mv_halo_ / res, r2 = floor(r * r);
+  if (!(r2 <= (double)CILQR_CLEAR_MOVERS_MAX_HALO2)) throw std::runtime_error("set_mover_clearing: halo beyond CILQR_CLEAR_MOVERS_MAX_HALO2 cells^2 at this map's resolution");
+  return (int)r2;
+}
+
+void iLQR::set_mover_clearing(double v_clear, double halo, float fill, bool on) {
+  if (!on) {
+    const bool was = mv_on_;
+    mv_on_ = false;
+    memset(last_mover_clearing, 0, sizeof(last_mover_clearing));
+    if (was && map_set_ && given_layer_.size() == unc_.layer.size()) {  // the layer as given is the map again
+      unc_.layer = given_layer_;
+      apply_map(unc_);
+    }
+    given_layer_.clear();
+    return;
+  }
+  if (!trk_on_) throw std::logic_error("set_mover_clearing: needs set_map_tracker");
+  if (!(v_clear >= 0.0) || !(halo >= 0.0 && halo <= 1.7e308) || (fill == fill && fill - fill != 0.0f))
+    throw std::runtime_error("set_mover_clearing: needs v_clear >= 0, halo >= 0 and finite, and a fill that is finite or NaN");
+  const double keep = mv_halo_;
+  mv_halo_ = halo;
+  if (map_set_) {
+    try { (void)mover_halo2(unc_.geom.res); } catch (...) { mv_halo_ = keep; throw; }
+  }
+  mv_v_clear_ = v_clear; mv_fill_ = fill;
+  const bool was = mv_on_;
+  mv_on_ = true;
+  if (!map_set_) return;
+  if (!was) given_layer_ = unc_.layer;
+  // (the map already set: its labels, rows and tracks are in the device blocks as the last tick left them; the layer as given goes up again)
+  const size_t cells = given_layer_.size();
+  if (hipSetDevice(device_) != hipSuccess || hipMemcpy(mo_dev_, given_layer_.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    throw std::runtime_error("set_mover_clearing: HIP runtime call failed");
+  clear_tracked_movers();
+}
+
+// Behind the tick (null stream): the layer as given is still at the head of mo_dev_, the labels and comp lie behind it, assign and the
+// table in trk_dev_.  In place on that copy; the cleared layer and the fields come back, and the cleared layer becomes the map.
+void iLQR::clear_tracked_movers() {
+  const cilqr_map_geom& g = unc_.geom;
+  const size_t cells = (size_t)g.rows * g.cols, ints = (4 * cells + 4 + 1) / 2 * 2, K = (size_t)mo_K_, M = (size_t)trk_slots_;
+  const int halo2 = mover_halo2(g.res);
+  float* layer = (float*)mo_dev_;
+  const int32_t* label = (const int32_t*)mo_dev_ + 3 * cells;
+  const double* comp = (const double*)((int32_t*)mo_dev_ + ints);
+  double* fields = (double*)comp + K * (CILQR_MAP_OBSTACLE_FIELDS + 5) + 3;
+  const double* state = (const double*)trk_dev_;
+  const int32_t* assign = (const int32_t*)(state + M * (CILQR_TRACK_STATE + 24) + CILQR_TRACK_WORLD_FIELDS);
+  check(cilqr_clear_movers_device(h_, nullptr, 1, layer, 0, &g, label, mo_K_, comp, trk_slots_, assign, state, trk_f_.min_hits, mv_v_clear_, nullptr,
+                                  halo2, mv_fill_, layer, nullptr, fields),
+        "cilqr_clear_movers_device");
+  unc_.layer.resize(cells);
+  if (hipMemcpy(unc_.layer.data(), layer, cells * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(last_mover_clearing, fields, sizeof(last_mover_clearing), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error("set_mover_clearing: HIP runtime call failed");
+  apply_map(unc_);
 }
 
 void iLQR::append_map_rows() {
@@ -426,6 +490,8 @@ void iLQR::clear_uncertainty_map() {
   last_map_obstacles.clear();
   memset(last_map_obstacle_counts, 0, sizeof(last_map_obstacle_counts));
   if (trk_on_) { drop_tracker_tracks(); trk_reset_ = true; }  // (the tracks go with their map, and the tracker starts over)
+  given_layer_.clear();
+  memset(last_mover_clearing, 0, sizeof(last_mover_clearing));
   if (map_rows_ > 0) append_map_rows();  // (the rows go with their map)
 }
 

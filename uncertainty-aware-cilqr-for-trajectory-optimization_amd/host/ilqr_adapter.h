@@ -309,6 +309,22 @@ class iLQR {
   // width, slot) — and last_track_counts the world record (cilqr_track_world_field).  on = false removes the tracks and, with a map
   // set, puts the static rows back.  Off (the default): nothing changes for existing callers.
   void set_map_tracker(const cilqr_track_filter& f, int slots, bool on = true);
+  // Mover clearing: the static layer.  Under set_map_tracker a vehicle confirmed as moving reaches the planner twice: as a track, which
+  // predicts it away, and as a blob of occupied cells that stands where it is now for the whole horizon; in the map-only configuration
+  // the blob wins.  It needs set_map_tracker (std::logic_error without it; the tracker cannot be switched off under it).  While it is
+  // on, every set_uncertainty_map runs cilqr_map_distance_device -> cilqr_map_obstacles_device -> cilqr_track_update_device on the layer
+  // AS GIVEN and then, in this object's own device block behind them, cilqr_clear_movers_device in its tracker form: the filter's
+  // min_hits, v_clear in m/s, halo2 = floor((halo/res)^2) cells^2 with halo in metres, evaluated in double as written — 0.3 / 0.1 is just below 3 there, so give a halo a little
+  // above the radius meant, 0.31 for three cells of 0.1 m — (std::runtime_error for a v_clear, halo or fill
+  // the call rejects, at the setter or, where the limit depends on the map's resolution, at the map), `fill` for the cleared cells.
+  // The CLEARED layer is then the map: it is set on the handle and is the "original" every later stage starts from and judges
+  // against — the solve, the rounds of set_map_tightening and set_track_map, set_map_risk_check, set_map_covariance_check, the map
+  // half of set_footprint_check and set_map_clearance_check.  A cleared vehicle is gone from the map: it comes back through its
+  // track only, so keep a judge that reads tracks behind it (set_footprint_check, set_obstacle_covariance_check, set_track_map).
+  // last_mover_clearing holds the CILQR_CLEAR_MOVERS_FIELDS of the last map (cilqr_clear_movers_field).  on = false, or
+  // clear_uncertainty_map, puts things back: with a map set the layer as given is the map again.  Off (the default): nothing changes
+  // for existing callers.
+  void set_mover_clearing(double v_clear, double halo, float fill = 0.0f, bool on = true);
   // Test hook: cilqr_debug_uncertainty_cost on the map this object's handle holds right now, at n = states.size() / 4 states
   // (x, y, v, theta) -> n costs, then 2n of vx, then 3n of mx.  Throws std::runtime_error when no map is set.
   std::vector<double> debug_map_cost(const std::vector<double>& states) const;
@@ -381,6 +397,8 @@ class iLQR {
   // set_uncertainty_map under set_map_tracker; empty / zero otherwise
   std::vector<double> last_tracks;  // 8 per confirmed row: (id, x, y, v, theta, length, width, slot)
   double last_track_counts[CILQR_TRACK_WORLD_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the world record of cilqr_track_update
+  // set_uncertainty_map under set_mover_clearing; zero otherwise
+  double last_mover_clearing[CILQR_CLEAR_MOVERS_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0};  // the fields of cilqr_clear_movers
 
  private:
   void pack_obstacles();
@@ -514,6 +532,14 @@ class iLQR {
   int32_t* mo_n_out_dev_ = nullptr;
   void track_map_obstacles();  // one tick on the boxes in mo_dev_, then the confirmed rows installed as tracks
   void drop_tracker_tracks();  // removes what track_map_obstacles installed
+  // mover clearing (set_mover_clearing): the layer as it was given is kept beside unc_, whose layer is then the cleared one; the call
+  // reads the layer, the labels and comp in mo_dev_ and assign and the table in trk_dev_, and leaves its fields behind the pose in mo_dev_
+  bool mv_on_ = false;
+  double mv_v_clear_ = 0.0, mv_halo_ = 0.0;
+  float mv_fill_ = 0.0f;
+  std::vector<float> given_layer_;
+  int mover_halo2(double res) const;  // throws std::runtime_error beyond CILQR_CLEAR_MOVERS_MAX_HALO2
+  void clear_tracked_movers();        // mo_dev_, trk_dev_ -> unc_.layer, last_mover_clearing, the handle's map
 };
 
 }  // namespace cilqr_host

@@ -3,7 +3,7 @@
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
 //   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]
-//                [--map-tracker dt,q,r,gate2,min_hits,max_misses]                               → one line per tick on stdout
+//                [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]]   → one line per tick on stdout
 //
 // --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
 // (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
@@ -24,6 +24,11 @@
 // R = r^2 I, P_birth = diag(r^2, r^2, 16, 16), v_min 0.5 m/s, theta_var_slow 1 — and the confirmed tracks reach the solve predicted over
 // the horizon, in place of the standing boxes.  The line then ends with " tracks <n>" and per confirmed track " <id> <x> <y> <speed>
 // <heading>".  The ticks must carry no obstacles of their own.
+//
+// --clear-movers (with --map-tracker): iLQR::set_mover_clearing(v_clear m/s, halo m, fill — default 0): on every tick that carries a map
+// the cells of the components that confirmed tracks at v_clear or faster own, and a halo around them, are taken out of the layer before
+// the solve reads it.  The line then ends with " clear_movers" and the eight fields of cilqr_clear_movers (movers, cleared, owned linked,
+// owned halo, largest value, its cell, contested, kept unknown).
 //
 // Log (whitespace-separated, '#' starts a comment line):
 //   cilqr-replay 1
@@ -84,17 +89,18 @@ struct Tokens {
 
 int main(int argc, char** argv) {
   std::vector<const char*> pos;  // the log and the device; options may stand anywhere
-  const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr, *map_tracker = nullptr;
+  const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr, *map_tracker = nullptr, *clear_movers = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
     else if (strcmp(argv[i], "--stop-fallback") == 0 && i + 1 < argc) stop = argv[++i];
     else if (strcmp(argv[i], "--map-obstacles") == 0 && i + 1 < argc) map_obstacles = argv[++i];
     else if (strcmp(argv[i], "--map-tracker") == 0 && i + 1 < argc) map_tracker = argv[++i];
+    else if (strcmp(argv[i], "--clear-movers") == 0 && i + 1 < argc) clear_movers = argv[++i];
     else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
     else pos.push_back(argv[i]);
   }
   if (pos.empty() || pos.size() > 2) {
-    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size] [--map-tracker dt,q,r,gate2,min_hits,max_misses]\n", argv[0]);
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size] [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]]\n", argv[0]);
     return 2;
   }
   try {
@@ -169,6 +175,12 @@ int main(int argc, char** argv) {
       tf.theta_var_slow = 1.0;
       planner.set_map_tracker(tf, 16);
     }
+    if (clear_movers) {
+      if (!map_tracker) throw std::runtime_error("--clear-movers needs --map-tracker");
+      double v_clear = 0.0, halo = 0.0, fill = 0.0;
+      if (sscanf(clear_movers, "%lf,%lf,%lf", &v_clear, &halo, &fill) < 2) throw std::runtime_error("--clear-movers takes v_clear,halo[,fill]");
+      planner.set_mover_clearing(v_clear, halo, (float)fill);
+    }
     bool map_on = false;
     while (!in.done()) {
       in.expect("tick");
@@ -233,6 +245,10 @@ int main(int argc, char** argv) {
         printf(" tracks %d", (int)(planner.last_tracks.size() / 8));
         for (size_t k = 0; k + 8 <= planner.last_tracks.size(); k += 8)
           printf(" %d %.9g %.9g %.9g %.9g", (int)planner.last_tracks[k], planner.last_tracks[k + 1], planner.last_tracks[k + 2], planner.last_tracks[k + 3], planner.last_tracks[k + 4]);
+      }
+      if (clear_movers) {
+        printf(" clear_movers");
+        for (double v : planner.last_mover_clearing) printf(" %.9g", v);
       }
       if (stop) printf(" stop %d %d %d", picked < 0 ? -1 : planner.last_stop_level >= 0 ? 1 : 0, planner.last_stop_level, planner.last_stop_pick);
       printf("\n");
