@@ -787,7 +787,8 @@ int oracle_solve_batch_form(const cilqr_params* p, int B, int N, int M, const do
  * ---------------------------------------------------------------------------------------------- */
 /* polyfit (:101-117) = Vandermonde + Eigen::ColPivHouseholderQR::solve (Eigen 3.2.10:
  * QR/ColPivHouseholderQR.h:425-545, Householder/Householder.h makeHouseholder/applyHouseholderOnTheLeft). */
-void oracle_polyfit(const double* x, const double* y, int n, int degree, double* coeffs) {
+/* The algorithm, from a Vandermonde matrix the caller formed: V[i + n*j] = x_i^j (column-major, left untouched). */
+void oracle_polyfit_powers(const double* V, const double* y, int n, int degree, double* coeffs) {
   const int rows = n, cols = degree + 1;
   const int size = rows < cols ? rows : cols;
   double* qr = (double*)malloc(sizeof(double) * ((size_t)rows * cols + 3 * (size_t)cols + rows));
@@ -799,7 +800,7 @@ void oracle_polyfit(const double* x, const double* y, int n, int degree, double*
   int* trans = perm + cols;
 #define QR(r, cc) qr[(r) + (size_t)rows * (cc)]
   for (int i = 0; i < rows; i++)
-    for (int j = 0; j < cols; j++) QR(i, j) = pow(x[i], (double)j);
+    for (int j = 0; j < cols; j++) QR(i, j) = V[i + (size_t)rows * j];
   double maxn = 0;
   for (int k = 0; k < cols; k++) {
     double s = 0;
@@ -878,16 +879,33 @@ void oracle_polyfit(const double* x, const double* y, int n, int degree, double*
   free(qr);
 }
 
-/* closest_point_index (:25-41), get_local_wpts (:47-60), get_local_plan (:66-85), get_local_plan_coeffs (:90-96) */
-int oracle_local_plan(const cilqr_params* p, const double* path, int P, const double* ego_state,
-                      double* coeffs, double* ref_traj) {
+/* The reference's own form: the powers are libm's (:107-111). */
+void oracle_polyfit(const double* x, const double* y, int n, int degree, double* coeffs) {
+  const int cols = degree + 1;
+  double* V = (double*)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1) * cols);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < cols; j++) V[i + (size_t)n * j] = pow(x[i], (double)j);
+  oracle_polyfit_powers(V, y, n, degree, coeffs);
+  free(V);
+}
+
+/* closest_point_index (:25-41) and the length of get_local_wpts' slice (:47-60).  A NaN ego compares false everywhere: index 0. */
+static int local_plan_slice(const cilqr_params* p, const double* path, int P, const double* ego_state, int* first) {
   double md = pow(ego_state[0] - path[0], 2) + pow(ego_state[1] - path[1], 2);
   int mi = 0;
   for (int i = 0; i < P; i++) {
     double t = pow(ego_state[0] - path[2 * i], 2) + pow(ego_state[1] - path[2 * i + 1], 2);
     if (t < md) { md = t; mi = i; }
   }
-  int n = (P - mi) < p->num_of_local_wpts ? (P - mi) : p->num_of_local_wpts;
+  *first = mi;
+  return (P - mi) < p->num_of_local_wpts ? (P - mi) : p->num_of_local_wpts;
+}
+
+/* closest_point_index (:25-41), get_local_wpts (:47-60), get_local_plan (:66-85), get_local_plan_coeffs (:90-96) */
+int oracle_local_plan(const cilqr_params* p, const double* path, int P, const double* ego_state,
+                      double* coeffs, double* ref_traj) {
+  int mi;
+  int n = local_plan_slice(p, path, P, ego_state, &mi);
   if (n < 1) return 0;  /* P >= 1 and num_of_local_wpts >= 1 are the caller's contract */
   double* xs = (double*)calloc(2 * (size_t)n, sizeof(double));
   double* ys = xs + n;
@@ -900,5 +918,30 @@ int oracle_local_plan(const cilqr_params* p, const double* path, int P, const do
     ref_traj[2 * i + 1] = ny;
   }
   free(xs);
+  return n;
+}
+
+/* oracle_local_plan with the powers handed in: powers[i * (poly_order + 1) + j] = path_x[i]^j, one row per path waypoint.  The same
+ * search and slice; the table's rows are the fit's Vandermonde rows and the powers of the fitted ref_traj row (ascending sum). */
+int oracle_local_plan_powers(const cilqr_params* p, const double* path, int P, const double* powers, const double* ego_state,
+                             double* coeffs, double* ref_traj) {
+  const int cols = p->poly_order + 1;
+  int mi;
+  int n = local_plan_slice(p, path, P, ego_state, &mi);
+  if (n < 1) return 0;
+  double* V = (double*)calloc((size_t)n * cols + n, sizeof(double));
+  double* ys = V + (size_t)n * cols;
+  for (int i = 0; i < n; i++) {
+    for (int j = 0; j < cols; j++) V[i + (size_t)n * j] = powers[(size_t)(mi + i) * cols + j];
+    ys[i] = path[2 * (mi + i) + 1];
+  }
+  oracle_polyfit_powers(V, ys, n, p->poly_order, coeffs);
+  for (int i = 0; i < n; i++) {
+    double ny = 0.0;
+    for (int j = 0; j < cols; j++) ny += coeffs[j] * powers[(size_t)(mi + i) * cols + j];
+    ref_traj[2 * i] = path[2 * (mi + i)];
+    ref_traj[2 * i + 1] = ny;
+  }
+  free(V);
   return n;
 }

@@ -119,9 +119,14 @@ int oracle_max_threads(void);
 
 /* I/LocalPlanner.cpp:101-117 with Eigen::ColPivHouseholderQR::solve semantics */
 void oracle_polyfit(const double* x, const double* y, int n, int degree, double* coeffs);
+/* The same algorithm from powers the caller formed, V[i + n*j] = x_i^j (oracle_polyfit fills V with libm's pow and calls this) */
+void oracle_polyfit_powers(const double* V, const double* y, int n, int degree, double* coeffs);
 /* I/LocalPlanner.cpp:25-96; returns number of local waypoints */
 int oracle_local_plan(const cilqr_params* p, const double* path, int P, const double* ego_state,
                       double* coeffs, double* ref_traj);
+/* The same with powers[i * (poly_order + 1) + j] = path_x[i]^j handed in, one row per path waypoint (fit and fitted ref_traj row) */
+int oracle_local_plan_powers(const cilqr_params* p, const double* path, int P, const double* powers, const double* ego_state,
+                             double* coeffs, double* ref_traj);
 
 /* Costmap warp: M/src/local_costmap.cpp:242-264 over G/grid_map_core index math
  * (GridMapMath.cpp:114-156, GridMap.cpp:45-62,160-166).  Returns the number of destination cells whose

@@ -178,6 +178,47 @@ def polyfit(x, y, degree):
     return c
 
 
+def exact_powers(x, degree):
+    """(x.size, degree + 1) table of correctly rounded powers: [i, j] = float(Fraction(x_i) ** j).  The power is formed in exact
+    rational arithmetic and rounded once by Python's big-integer division (round to nearest, ties to even) — what the device
+    kernel's double-double recurrence returns wherever x^degree stays in the normal range.  x must be finite."""
+    from fractions import Fraction
+    x = _f64(x).reshape(-1)
+    out = np.empty((x.size, degree + 1))
+    for i, xi in enumerate(x.tolist()):
+        f = Fraction(xi)
+        out[i] = [float(f ** j) for j in range(degree + 1)]
+        if xi == 0.0:  # Fraction drops the sign of -0.0; the odd powers of -0.0 are -0.0
+            out[i, 1::2] = xi
+    return out
+
+
+def polyfit_powers(V, y, degree):
+    """`oracle_polyfit_powers`: V (n, degree + 1) with V[i, j] = x_i^j as the caller formed it."""
+    V = np.asfortranarray(V, dtype=np.float64)
+    y = _f64(y)
+    assert V.shape == (y.size, degree + 1)
+    c = np.zeros(degree + 1)
+    lib().oracle_polyfit_powers(V.ctypes.data_as(c_double_p), _dp(y), int(y.size), int(degree), _dp(c))
+    return c
+
+
+def local_plan_exact(p, path, ego, powers=None):
+    """`local_plan` with exactly rounded Vandermonde entries (`exact_powers` of the path's abscissae, or `powers` when the
+    caller has the table already).  Returns what `local_plan` returns."""
+    path = _f64(path)
+    ego = _f64(ego)
+    P = path.size // 2
+    if powers is None:
+        powers = exact_powers(path.reshape(P, 2)[:, 0], p.poly_order)
+    powers = _f64(powers)
+    assert powers.shape == (P, p.poly_order + 1)
+    coeffs = np.zeros(p.poly_order + 1)
+    ref = np.zeros(2 * p.num_of_local_wpts)
+    n = lib().oracle_local_plan_powers(C.byref(p), _dp(path), P, _dp(powers), _dp(ego), _dp(coeffs), _dp(ref))
+    return coeffs, ref[:2 * n].reshape(n, 2)
+
+
 def map_geom(len_x, len_y, res, pos_x, pos_y):
     g = MapGeom()
     lib().oracle_map_geom_set(C.byref(g), C.c_double(len_x), C.c_double(len_y), C.c_double(res), C.c_double(pos_x),

@@ -4,7 +4,7 @@
     python tests/golden/make_golden.py
 
 Sources of the expected values
-  ref_params.json, ref_quu.json, ref_polyfit.json, ref_gridmap.json, ref_blur.json, ref_gridmap_linear.json
+  ref_params.json, ref_quu.json, ref_polyfit.json, ref_polyfit_edges.json, ref_gridmap.json, ref_blur.json, ref_gridmap_linear.json
       — produced by the REFERENCE's own code compiled in place (oracle/Makefile `make ref` → oracle/_ref/*.so):
         Parameters.cpp, the vendored Eigen 3.2.10 (EigenSolver, ColPivHouseholderQR) and grid_map_core.
   ref_live_maps.npz
@@ -112,6 +112,50 @@ def gen_polyfit():
     add(x * 0.37 - 3.0, rng.normal(size=20))             # noisy data
     dump("ref_polyfit.json", {"source": "I/LocalPlanner.cpp:101-117 over the reference's vendored Eigen 3.2.10 "
                                         "ColPivHouseholderQR", "cases": cases})
+
+
+def gen_polyfit_edges():
+    """The degenerate fits, where the column pivoting and the rank cut-off decide the answer (all degree 5)."""
+    L = O.ref_lib("eigen")
+    rng = np.random.Generator(np.random.PCG64(29))
+    cases = []
+
+    def add(name, x, y=None, deg=5):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if y is None:  # a smooth lateral profile over the waypoint index plus decimetre noise
+            i = np.arange(x.size)
+            y = rng.uniform(0.2, 1.5) * np.sin(rng.uniform(0.02, 0.3) * i + rng.uniform(0, 2 * np.pi)) + rng.uniform(-0.1, 0.1, x.size)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        c = np.zeros(deg + 1)
+        L.ref_polyfit(x.ctypes.data_as(dp), y.ctypes.data_as(dp), int(x.size), int(deg), c.ctypes.data_as(dp))
+        cases.append(dict(name=name, x=x.tolist(), y=y.tolist(), degree=deg, coeffs=c.tolist()))
+
+    def spaced(x0, n=20):
+        return x0 + np.cumsum(rng.uniform(0.5, 1.5, n))
+
+    add("all_equal", np.full(20, 7.25))
+    add("all_zero", np.zeros(20))
+    add("two_distinct", np.repeat([3.5, 4.75], 10))
+    x = spaced(2.0)
+    x[8:12] = x[8]
+    add("run_of_four", x)
+    x = spaced(10.0, 12)
+    add("doubled_back", np.concatenate([x, x[-2:2:-1]]))  # 12 out, 8 back over the same abscissae
+    for x0 in (1e3, 1e4, 5.3e5, -4.2e5):
+        add("at_%g" % x0, spaced(x0))
+    half = np.cumsum(rng.uniform(0.5, 1.5, 10))
+    add("symmetric_no_zero", np.concatenate([-half[::-1], half]))
+    add("symmetric_with_zero", np.concatenate([-half[:0:-1], [0.0], half]))
+    add("at_1e-3", 1e-3 + np.cumsum(rng.uniform(0.5e-4, 1.5e-4, 20)))
+    for n in (1, 2, 3, 5, 6, 7):                           # slices cut short by the path's end, x in [0, 20)
+        add("n_%d" % n, spaced(rng.uniform(0.0, 8.0), n))
+    # exact ties of the column norms (every power of ±1 is ±1): the first maximum is the pivot
+    add("all_one", np.ones(20))
+    add("all_minus_one", -np.ones(20))
+    add("plus_minus_one", np.tile([1.0, -1.0], 10))
+    add("plus_minus_one_n_5", np.tile([1.0, -1.0], 3)[:5])
+    dump("ref_polyfit_edges.json", {"source": "I/LocalPlanner.cpp:101-117 over the reference's vendored Eigen 3.2.10 "
+                                              "ColPivHouseholderQR", "cases": cases})
 
 
 def gen_gridmap():
@@ -292,6 +336,7 @@ if __name__ == "__main__":
     gen_params()
     gen_quu()
     gen_polyfit()
+    gen_polyfit_edges()
     gen_gridmap()
     gen_blur()
     gen_gridmap_linear()

@@ -884,6 +884,15 @@ def test_local_plan_batch_general_paths(cilqr, oracle, solver):
     assert same.mean() >= 0.90, same.mean()
     worst = max(np.max(np.abs(got["ref_traj"][b, :n[b], 1] - refs[b][:, 1])) for b in range(B))
     assert worst <= 1e-9, worst
+    # the oracle handed exactly rounded powers instead of libm's (oracle.exact_powers): the same matrix on both sides, so the
+    # coefficients and the fitted row are equal on bits in all 1024 fits
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint64)  # noqa: E731
+    powers = oracle.exact_powers(x, p.poly_order).reshape(B, P, p.poly_order + 1)
+    exact = [oracle.local_plan_exact(p, paths[b], egos[b], powers[b]) for b in range(B)]
+    same_exact = np.array([np.array_equal(bits(got["poly"][b]), bits(c)) and ref.shape[0] == n[b] and
+                           np.array_equal(bits(got["ref_traj"][b, :n[b]]), bits(ref)) for b, (c, ref) in enumerate(exact)])
+    print("local_plan general paths vs exact-power oracle: fits=%d bit_equal=%d" % (B, int(same_exact.sum())))
+    assert same_exact.all(), np.nonzero(~same_exact)[0][:16].tolist()
 
 
 def test_plan_then_solve_on_device_matches_oracle(cilqr, oracle, solver):
