@@ -857,6 +857,9 @@ __device__ __forceinline__ bool quu_inverse_general(double a, double b, double d
   const double bb = b * b;
   const double det0 = fma(a, d, -bb);
   if (!(det0 == det0) || !(a + d == a + d)) return false;
+  // an infinite entry that leaves det0 and the trace infinite, not NaN (l_uu = +inf from an overflowing control barrier, met at
+  // step 0, where no later step turns it into a NaN): not finite either, as the reference's test of every entry has it
+  if (!(fabs(a) <= DBL_MAX && fabs(b) <= DBL_MAX && fabs(d) <= DBL_MAX)) return false;
   if (det0 >= 0.0 && a + d >= 0.0) {
     quu_inverse_psd(a, b, d, lamb, bb, i00, i01, i11);
     return true;

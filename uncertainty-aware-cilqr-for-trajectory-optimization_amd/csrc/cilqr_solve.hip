@@ -641,7 +641,8 @@ __device__ __forceinline__ bool riccati_mfma(int N, const double* rec, double* k
   } else {
     step(oa);
   }
-  return __builtin_amdgcn_ballot_w64((signs_v | signs_s) < 0 || !(det0 == det0)) == 0;
+  // (step 0's det0 = +inf — an infinite l_uu there, which no later step turns into a NaN — is handed over like a NaN)
+  return __builtin_amdgcn_ballot_w64((signs_v | signs_s) < 0 || !(det0 <= DBL_MAX)) == 0;
 }
 
 // MfmaCursor through 32-bit LDS addresses: riccati_mfma_smem pins its cursors in vector registers, and a pinned generic pointer is a
@@ -834,7 +835,7 @@ __device__ __forceinline__ bool riccati_mfma_smem(int N, const double* rec, doub
     const double bb = b * b;
     const double det0 = fma(a, d, -bb);
     const int signs = __double2hiint(det0) | __double2hiint(a) | __double2hiint(d);
-    bad |= t < N && (signs < 0 || (t == 0 && !(det0 == det0)));
+    bad |= t < N && (signs < 0 || (t == 0 && !(det0 <= DBL_MAX)));  // (NaN, or +inf: an infinite l_uu at step 0, which no later step turns into a NaN)
   }
   return __builtin_amdgcn_ballot_w64(bad) == 0;
 }
@@ -2166,6 +2167,12 @@ __global__ __launch_bounds__(W * WAVE, UNC ? 2 : W) void cilqr_solve_share_kerne
   }
 
   // ---- the main wavefront ----------------------------------------------------------------------------------------------------------
+  // TWO ROUNDS: issue priority 1 from here to the end, set once and never flipped.  A SIMD arbitrates vector issue between its two
+  // wavefronts by priority, then age, and main's partner is another solve's aux wavefront, as often as not the older one: R and F,
+  // serial chains, lost slots to work that has slack (two rounds keep the aux wavefronts busy 5.8 k ticks per linearisation, 2-3 k of
+  // them beside some main's R).  `wave` is a readfirstlane value, so the aux branch above is scalar and never comes by here
+  // (profiles/r30_main_is_the_pole.txt: F 377-381 -> 365 ticks per step in the mean, the launch -1.9 ... -2.5 %).
+  if (TWO_ROUNDS) __builtin_amdgcn_s_setprio(1);
   CILQR_STAMP(c_pro)
   double J_old = DBL_MAX, lamb = 1.0, J_new = 0.0;
   int iters = 0, status = CILQR_EXIT_MAX_ITER, n_pass = 0;
