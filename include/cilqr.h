@@ -1290,6 +1290,21 @@ int cilqr_debug_closest_sample(cilqr_handle* h, int n, const double* queries, in
  * out = {half_major, half_minor, angle} per row.  Checked bit for bit against the reference's Eigen (ref_blur.json). */
 int cilqr_debug_blur_ellipse(cilqr_handle* h, int n, const double* abc, double* out);
 
+/* Test hook: the kernels' own elementary functions (the inline routines of csrc/cilqr_device.hpp that every kernel calls, not copies
+ * of them) on n rows, one lane per row (host buffers).
+ *   CILQR_MATH_EXP          in: n × x                        out: n × exp_full(x): the form that carries the contract at both ends
+ *   CILQR_MATH_SINCOS_FAST  in: n × x                        out: n × {sin, cos} by sincos_fast
+ *   CILQR_MATH_SINCOS_LOOP  in: n × x                        out: n × {sin, cos} by sincos_loop
+ *   CILQR_MATH_ROTATE       in: n × {theta0, delta_1..T}     out: n × T × {sin, cos}: sincos_loop(theta0), then one rotate_heading
+ *                                                            (delta_t) per step on the forward pass's constants (make_fwd_const
+ *                                                            on the handle's parameters)
+ *   CILQR_MATH_EXP_FAST     in: n × x                        out: n × exp_fast(x): the form for arguments bounded below (the same bits
+ *                                                            from -746 up; far below, whatever its arithmetic gives)
+ * T (1 ≤ T ≤ CILQR_MAX_HORIZON) is read for CILQR_MATH_ROTATE only.  The routines are called as they stand: sincos_loop and
+ * rotate_heading beyond the ranges their callers keep them to (MAX_HEADING0, MAX_TURN) return what the arithmetic gives. */
+enum { CILQR_MATH_EXP = 0, CILQR_MATH_SINCOS_FAST = 1, CILQR_MATH_SINCOS_LOOP = 2, CILQR_MATH_ROTATE = 3, CILQR_MATH_EXP_FAST = 4 };
+int cilqr_debug_math(cilqr_handle* h, int op, int n, int T, const double* in, double* out);
+
 /* Blocks until everything the host-pointer entry points enqueued on the handle's own stream has finished. */
 int cilqr_wait(cilqr_handle* h);
 

@@ -60,6 +60,10 @@ def check(notes):
                 bad.append((name, r, "more than %d vector registers: the workgroups of a CU halve" % budget))
             if not int((split or share).group(2)) and r["vgpr_spill"]:
                 bad.append((name, r, "a production instantiation spills vector registers"))
+        elif "debug_math_kernel" in name:
+            # (the test hook on the elementary functions must run them as the solve kernels do: from registers, nothing on a stack)
+            if r["scratch"] or r["vgpr_spill"] or r["sgpr_spill"]:
+                bad.append((name, r, "uses scratch memory or spills registers"))
     return bad
 
 

@@ -100,12 +100,15 @@ STOP_FIELDS = 8
  SP_LOST) = range(STOP_FIELDS)
 STOP_ALLOW_MOVING = 1  # flags of `stop_plans`: a row still moving at step N-1 keeps its cost
 STOP_MIN_ADVANCE = 1.0e-3  # metres: below this advance of the next step a row does not steer
+# `cilqr_debug_math`: which device routine `Solver.debug_math` runs
+MATH_EXP, MATH_SINCOS_FAST, MATH_SINCOS_LOOP, MATH_ROTATE, MATH_EXP_FAST = range(5)
+MAX_HORIZON = 384  # CILQR_MAX_HORIZON
 
 # every symbol include/cilqr.h declares
 ABI_SYMBOLS = (
     "cilqr_params_default", "cilqr_abi_version", "cilqr_device_count", "cilqr_last_error", "cilqr_default_control_seq",
     "cilqr_local_plan", "cilqr_local_plan_batch", "cilqr_local_plan_batch_device", "cilqr_create", "cilqr_destroy", "cilqr_host_alloc", "cilqr_host_free", "cilqr_solve_batch", "cilqr_solve_batch_device", "cilqr_solve_batch_obstacles", "cilqr_solve_batch_obstacles_device", "cilqr_solve_batch_sampled", "cilqr_solve_batch_sampled_device",
-    "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_blur_costmap_batch_device", "cilqr_map_geom_set",
+    "cilqr_argmin_device", "cilqr_wait", "cilqr_set_diag_buffer", "cilqr_set_pass_count_buffer", "cilqr_solve_family", "cilqr_solve_wavefronts", "cilqr_solve_sampled_wavefronts", "cilqr_debug_quu_inverse", "cilqr_debug_closest_sample", "cilqr_debug_blur_ellipse", "cilqr_debug_math", "cilqr_warp_costmap", "cilqr_warp_costmap_device", "cilqr_warp_costmap_batch_device", "cilqr_blur_costmap", "cilqr_blur_costmap_device", "cilqr_blur_costmap_batch_device", "cilqr_map_geom_set",
     "cilqr_occupancy_to_layer", "cilqr_occupancy_to_layer_device", "cilqr_layer_to_occupancy", "cilqr_layer_to_occupancy_device",
     "cilqr_costmap_frame_device", "cilqr_costmap_frame_batch_device",
     "cilqr_boxes_to_polygons", "cilqr_rasterize_polygons", "cilqr_rasterize_polygons_device", "cilqr_warp_costmap_polygons_device",
@@ -1471,6 +1474,23 @@ class Solver:
         abc = _np64(abc).reshape(-1, 3)
         out = np.zeros_like(abc)
         _check(lib().cilqr_debug_blur_ellipse(self._h, int(abc.shape[0]), _p(abc), _p(out)))
+        return out
+
+    def debug_math(self, op, x):
+        """`cilqr_debug_math`: the kernels' own exp_fast / sincos_fast / sincos_loop / rotate_heading on host data.  MATH_EXP (exp_full), MATH_EXP_FAST: x (n,)
+        → (n,); MATH_SINCOS_FAST, MATH_SINCOS_LOOP: x (n,) → (n, 2) = (sin, cos); MATH_ROTATE: x (n, T + 1) rows of (theta0,
+        delta_1..T) → (n, T, 2)."""
+        op = int(op)
+        if op == MATH_ROTATE:
+            x = _np64(x)
+            assert x.ndim == 2 and x.shape[1] >= 2
+            n, T = x.shape[0], x.shape[1] - 1
+            out = np.zeros((n, T, 2))
+        else:
+            x = _np64(x).reshape(-1)
+            n, T = x.shape[0], 0
+            out = np.zeros(n) if op in (MATH_EXP, MATH_EXP_FAST) else np.zeros((n, 2))
+        _check(lib().cilqr_debug_math(self._h, op, int(n), int(T), _p(x), _p(out)))
         return out
 
     def wait(self):

@@ -470,6 +470,24 @@ int cilqr_debug_blur_ellipse(cilqr_handle* h, int n, const double* abc, double* 
   return CILQR_OK;
 }
 
+int cilqr_debug_math(cilqr_handle* h, int op, int n, int T, const double* in, double* out) {
+  if (!h || n < 1 || !in || !out || op < CILQR_MATH_EXP || op > CILQR_MATH_EXP_FAST) return fail(CILQR_ERR_ARG, "cilqr_debug_math: bad argument");
+  const bool chain = op == CILQR_MATH_ROTATE;
+  if (chain && (T < 1 || T > CILQR_MAX_HORIZON)) return fail(CILQR_ERR_ARG, "cilqr_debug_math: T must lie in 1..CILQR_MAX_HORIZON");
+  const size_t n_in = (size_t)n * (chain ? (size_t)T + 1 : 1);
+  const size_t n_out = (size_t)n * (chain ? 2 * (size_t)T : op == CILQR_MATH_EXP || op == CILQR_MATH_EXP_FAST ? 1 : 2);
+  HIP_TRY(hipSetDevice(h->device));
+  void* v = nullptr;
+  int rc = cilqr::scratch_bytes(h, cilqr::SCR_DEBUG, sizeof(double) * (n_in + n_out), &v);
+  if (rc) return rc;
+  double *d_in = (double*)v, *d_out = d_in + n_in;
+  HIP_TRY(hipMemcpyAsync(d_in, in, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(cilqr::launch_debug_math(h->kp, op, n, chain ? T : 0, d_in, d_out, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CILQR_OK;
+}
+
 int cilqr_wait(cilqr_handle* h) {
   if (!h) return fail(CILQR_ERR_ARG, "null handle");
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -67,10 +67,21 @@ __device__ __forceinline__ double rcp_newton(double x) {
   return r;
 }
 
-// exp(x) in ≈21 instructions, ≤ ~2 ulp: x = n·ln2 + r with a two-part ln2 (|r| ≤ 0.347), degree-13 Taylor polynomial in
-// Horner form, scaling by 2^n with v_ldexp_f64 (gradual underflow to 0 for very negative x).  The library exp costs
+// exp(x) in ≈21 instructions: x = n·ln2 + r with a two-part ln2 (|r| ≤ 0.347), degree-13 Taylor polynomial in
+// Horner form, scaling by 2^n with v_ldexp_f64 (gradual underflow to +0, from x ≈ -745.2).  The library exp costs
 // ≈55 instructions; the barrier terms call it 2M + 4 times per (solve, step), which makes it the largest single item of
 // the linearisation for M ≥ 4 (and ≈60 % of the whole solve at M = 256).
+// Two forms.  exp_fast is for arguments that are bounded below by what the caller does: the control barriers (bounded by the
+// controls) and obstacle entries a lane has established it needs.  Far below its working range (-0 at x = -1e20, ±inf or NaN further
+// down) its reduction is rounding error of any size and sign and the polynomial over- or underflows before ldexp can flush it.
+// exp_full adds the select of the low end and carries the contract, each point exact: NaN → NaN; x > 709.782… (the result
+// overflows) and every x > 710 → +inf; every x ≤ -746, -inf included → +0, sign bit clear; never negative, never NaN for a number;
+// ±0 → 1.  It is what the callers with an unbounded argument use: the score kernel's obstacle barrier, the map cost, and
+// obs_terms in every instantiation but the LANE_EXACT ones, whose not-needed lanes get an exponent in range instead (obstacle_loop).  From -746 up both return the same bits.
+// Measured against mpmath (tests/test_device_math.py, profiles/r31_device_math.txt): within 1 ulp of the true value on
+// [-745.2, 709.78] — 0.87 ulp over the suite's 1.9·10⁵ points, 0.50 around every k·ln2, 0.87 around every (k + ½)·ln2, 0.77 units
+// of 2^-1074 where the result is subnormal; the tests hold it to 2.  The device returns the bits of the tests' operation-for-operation
+// host restatement (libm's fma) on every point.
 __device__ __forceinline__ double exp_fast(double x) {
   const double n = rint(x * 1.44269504088896338700e+00);
   double r = fma(-n, 6.93147180369123816490e-01, x);  // ln2 head (low bits zero: n·head exact for |n| < 2^21)
@@ -92,15 +103,24 @@ __device__ __forceinline__ double exp_fast(double x) {
   const double e = ldexp(p, (int)n);
   return x > 710.0 ? __builtin_huge_val() : e;  // beyond the overflow threshold the reduction itself is meaningless
 }
+// (selected on the result, as the high end is: a clamp of the argument would turn a NaN into a number)
+__device__ __forceinline__ double exp_full(double x) {
+  const double e = exp_fast(x);
+  return x < -746.0 ? 0.0 : e;
+}
 
 // ---- dynamics --------------------------------------------------------------------------------------------------------
 struct State {
   double x, y, v, th, c, s;
 };
 
-// sin and cos of one fp64 argument, ≤ ~1 ulp each: three-part Cody–Waite reduction by pi/2 (exact first step under fma for
+// sin and cos of one fp64 argument: three-part Cody–Waite reduction by pi/2 (exact first step under fma for
 // |x| < 2^20·pi/2) followed by the classic degree-13 / degree-14 minimax kernels on [-pi/4, pi/4].  Larger arguments (never
-// met by a heading angle) take the library path.
+// met by a heading angle), ±inf and NaN take the library path.
+// Measured against mpmath (tests/test_device_math.py, profiles/r31_device_math.txt): within 1.4 ulp of the true value for |x| < 1e6
+// (sin 1.38, cos 1.38 over the suite's 2·10⁵ points), and within 1.0 ulp — of the
+// true value, tiny as it is — two ulp either side of every k·pi/2 up to k = 636 619: the third part of the reduction delivers that.
+// |s² + c² − 1| ≤ 2^-52.  The tests hold both to 2 ulp.  sin(±0) = +0: the reduction's fma adds +0·head to x.
 __device__ __forceinline__ void sincos_fast(double x, double* sn, double* cs) {
   if (__builtin_expect(!(fabs(x) < 1.0e6), 0)) {
     sincos(x, sn, cs);
@@ -160,7 +180,8 @@ __device__ __forceinline__ void make_fwd_const(FwdConst& k, const KParams& kp) {
 
 // sincos_fast without its range guard (same arithmetic, same results for |x| < 1e6; callers track max|x| and hand the solve to
 // the GENERAL kernel if that bound was ever exceeded).  Off the per-step chain since the headings are advanced by rotation
-// (rotate_heading): used for a trajectory's first state and for turns of more than 1/4 rad per step.
+// (rotate_heading): used for a trajectory's first state and for turns of more than 1/4 rad per step.  "Same results" is tested bit
+// for bit on every point of tests/test_device_math.py with |x| ≤ MAX_HEADING0.
 __device__ __forceinline__ void sincos_loop(double x, double& sn, double& cs) {
   const double n = rint(x * 6.36619772367581382433e-01);
   double r = fma(-n, 1.57079632679489655800e+00, x);
@@ -189,8 +210,11 @@ __device__ __forceinline__ void sincos_loop(double x, double& sn, double& cs) {
 // cos and sin of the heading advanced by a small turn: (c, s) rotated by delta = w·dt through the addition formulas, with sin
 // delta and cos delta from their Taylor series (|delta| ≤ 1/4: truncation below 2e-18 relative) — 17 branch-free instructions
 // instead of the 35 of a range-reduced sincos of the new heading, on the serial chain of every forward step.  The rounding of
-// each rotation (≈1e-16) accumulates over the horizon instead of being redone from the rounded angle: ≈1e-15 after 80 steps,
-// far inside the parity tolerance.  Callers track the largest |delta| (MAX_TURN) and hand the solve to the GENERAL kernel —
+// each rotation (≤ 1.9e-16 in the first) accumulates over the horizon instead of being redone from the rounded angle: measured against
+// mpmath's sin and cos of theta0 plus the exact sum of the turns, ≤ 3.8e-15 over CILQR_MAX_HORIZON = 384 steps on the device (its host restatement from a correctly rounded start: 2.4e-15 after 80, 4.1e-15 after 384)
+// (constant, alternating and random turns up to MAX_TURN, turns of 1e-9, first headings up to MAX_HEADING0; the tests hold step t to
+// (4 + 4t)·2^-53), far inside the parity tolerance; a turn of 0 leaves both bits unchanged; the device returns the bits of the tests'
+// host restatement (tests/test_device_math.py, profiles/r31_device_math.txt).  Callers track the largest |delta| (MAX_TURN) and hand the solve to the GENERAL kernel —
 // which evaluates sincos of every heading — if a turn was larger (above 8 m/s at full lock with the reference's parameters); a
 // first heading beyond MAX_HEADING0 goes there too, so that |theta| stays in the range of sincos_loop over any horizon.
 constexpr double MAX_TURN = 0.25, MAX_HEADING0 = 9.99e5;
@@ -567,7 +591,7 @@ __device__ __forceinline__ double unc_cost_add(const UncArgs& u, const UncPose& 
       const double dj = a1 - a0;
       const double cqx = (-di * inv_res) * 0.01, cqy = (-dj * inv_res) * 0.01;
       const double cX = po.cp * cqx - po.sp * cqy, cY = po.sp * cqx + po.cp * cqy;
-      const double e = q1 * exp_fast(q2 * (o * 0.01 - 1.0));
+      const double e = q1 * exp_full(q2 * (o * 0.01 - 1.0));  // (a layer holds any finite float)
       const double sv = q2 * e, sm = q2 * q2 * e;
       sx += e;
       gx += sv * cX;
@@ -629,9 +653,16 @@ __device__ __forceinline__ void obs_prep(const ObsConsts& k, const ObsEntry& e, 
 }
 // false: both barrier exponents are at or below -64 — the entry contributes less than e^-64 times O(10) factors at this step
 __device__ __forceinline__ bool obs_needed(const ObsPrep& p) { return !(p.arg[0] <= -64.0) || !(p.arg[1] <= -64.0); }
+// The exponent of an entry that a lane does not need: `arg` itself where it does, else a value in (-1000.0005, -1000] — the high
+// word of -1000.0 over arg's low word, one select — at which exp_fast is +0 by ldexp's underflow.
+__device__ __forceinline__ double obs_arg_or_nothing(bool need, double arg) {
+  return __hiloint2double(need ? __double2hiint(arg) : (int)0xC08F4000, __double2loint(arg));
+}
 struct ObsTerms {  // one entry's gradient and Hessian terms (front + rear circle), before its weight
   double gx, gy, gxx, gxy, gyy;
 };
+// FULL: the exponents are whatever the entry gives (exp_full); false: the caller has bounded them below (exp_fast).
+template <bool FULL>
 __device__ __forceinline__ ObsTerms obs_terms(const ObsConsts& k, const ObsEntry& e, const ObsPrep& p) {
 #pragma clang fp contract(off)
   double gx = 0.0, gy = 0.0, gxx = 0.0, gxy = 0.0, gyy = 0.0;
@@ -639,7 +670,7 @@ __device__ __forceinline__ ObsTerms obs_terms(const ObsConsts& k, const ObsEntry
   for (int side = 0; side < 2; ++side) {
     const double h0 = __builtin_fma(e.co, p.g0[side], -(e.so * p.g1[side]));  // c-dot = -2 (h0, h1)
     const double h1 = __builtin_fma(e.so, p.g0[side], e.co * p.g1[side]);
-    const double ee = exp_fast(p.arg[side]);
+    const double ee = FULL ? exp_full(p.arg[side]) : exp_fast(p.arg[side]);
     const double sv = (side == 0 ? k.svf : k.svr) * ee;
     const double sm = (side == 0 ? k.smf : k.smr) * ee;
     gx = __builtin_fma(sv, h0, gx);
@@ -720,8 +751,20 @@ __device__ __forceinline__ void obstacle_loop(const ObsConsts& oc, int M, ObsAt 
   // the wave-wide vote of CULL: false when the entry is negligible at every step of the wavefront
   auto wanted = [&](const Prep& p) { return __builtin_amdgcn_ballot_w64(obs_needed(p)) != 0; };
   auto finish = [&](const ObsEntry& e, const Prep& p, double w, bool odd) {
-    if (CULL && LANE_EXACT) w = obs_needed(p) ? w : 0.0;
-    obs_accumulate(SPLIT && odd ? b : a, obs_terms(oc, e, p), w);
+    if (CULL && LANE_EXACT) {
+      // A step at which the entry is negligible adds exactly nothing: its two exponents are replaced by one at which exp_fast is +0,
+      // so every term is an exact zero whatever the entry's own exponents were, and the sums keep the bits that the zero weight of
+      // earlier versions gave them for every entry within exp_fast's range.  Below that range the zero weight was not enough:
+      // measured, an obstacle 1e25 m or more away moved U in the last bit on every kernel that takes this branch
+      // (tests/test_device_math.py holds them to bits now).  One select per exponent, as many as the zero weight took.
+      const bool need = obs_needed(p);
+      Prep q = p;
+      q.arg[0] = obs_arg_or_nothing(need, p.arg[0]);
+      q.arg[1] = obs_arg_or_nothing(need, p.arg[1]);
+      obs_accumulate(SPLIT && odd ? b : a, obs_terms<false>(oc, e, q), w);
+    }
+    // (without the vote every entry is evaluated; with it, a lane evaluates what OTHER steps voted for at its own exponents)
+    else obs_accumulate(SPLIT && odd ? b : a, obs_terms<true>(oc, e, p), w);
   };
   if (CULL && PAIRED) {
     // Entries in PAIRS: the geometry of both first — two independent dependency chains that interleave (a lone wavefront issues a

@@ -92,6 +92,8 @@ hipError_t launch_obstacle_table(const SolveArgs& a, hipStream_t stream);
 hipError_t launch_unc_cost(const UncArgs& u, int n, const double* states, double* cost, double* vx, double* mx, hipStream_t stream);
 hipError_t launch_quu_inverse(int n, const double* q, const double* lamb, double* out, int general, hipStream_t stream);
 hipError_t launch_closest_sample(int n, int S, const double* in, int32_t* out, hipStream_t stream);  // test hook (cilqr_debug_closest_sample)
+// Test hook (cilqr_debug_math): exp_fast, sincos_fast, sincos_loop or a rotate_heading chain of T steps on n rows, one lane per row.
+hipError_t launch_debug_math(const KParams& kp, int op, int n, int T, const double* in, double* out, hipStream_t stream);
 
 // Scoring of solved trajectories (cilqr_score.hip; cilqr_score_batch*, include/cilqr.h): one workgroup of SCORE_THREADS lanes per
 // solve.  `s` carries what the launch shares with a solve — U, poly, xplan_fl, the obstacle fields (strided, or the compact sampled

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void cilqr_score_kernel(ScoreArgs a)
       const ObsConsts oc = make_obs_consts(kp, Xb[4 * t], Xb[4 * t + 1], ect[t], est[t]);
       double cf, cr;
       circle_constraints(oc, en, cf, cr);
-      const double val = kp.q1_front * exp_fast(kp.q2_front * cf) + kp.q1_rear * exp_fast(kp.q2_rear * cr);
+      const double val = kp.q1_front * exp_full(kp.q2_front * cf) + kp.q1_rear * exp_full(kp.q2_rear * cr);  // (any obstacle, however far)
       obst = obst + w * val;
       cmax_merge(max_c, max_e, fmax(cf, cr), e);
       if (SAMPLED && (cf > 0.0 || cr > 0.0)) atomicAdd(&hits[o * N + t], 1);

@@ -1453,7 +1453,12 @@ __device__ __forceinline__ bool linearize_quads(const KParams& kp, int N, int M,
       obs_prep(oc, e, p);
       const bool need = m0 + sub < M && obs_needed(p);
       ObsTerms g{0.0, 0.0, 0.0, 0.0, 0.0};
-      if (__builtin_amdgcn_ballot_w64(need) != 0) g = obs_terms(oc, e, p);
+      if (__builtin_amdgcn_ballot_w64(need) != 0) {  // (a lane that does not need the entry: exact zeros, as obstacle_loop's LANE_EXACT forms them)
+        const bool mine = obs_needed(p);
+        p.arg[0] = obs_arg_or_nothing(mine, p.arg[0]);
+        p.arg[1] = obs_arg_or_nothing(mine, p.arg[1]);
+        g = obs_terms<false>(oc, e, p);
+      }
       const double we = need ? w : 0.0;  // (lin_step<…, LANE_EXACT>: a step that does not need the entry adds exactly nothing)
       obs_accumulate(a, ObsTerms{quad_bcast<0>(g.gx), quad_bcast<0>(g.gy), quad_bcast<0>(g.gxx), quad_bcast<0>(g.gxy), quad_bcast<0>(g.gyy)}, quad_bcast<0>(we));
       if (m0 + 1 < M) obs_accumulate(ao, ObsTerms{quad_bcast<1>(g.gx), quad_bcast<1>(g.gy), quad_bcast<1>(g.gxx), quad_bcast<1>(g.gxy), quad_bcast<1>(g.gyy)}, quad_bcast<1>(we));
@@ -2347,6 +2352,37 @@ __global__ void quu_inverse_kernel(int n, const double* q, const double* lamb, d
   out[4 * i] = ok ? i00 : nan; out[4 * i + 1] = ok ? i01 : nan; out[4 * i + 2] = ok ? i01 : nan; out[4 * i + 3] = ok ? i11 : nan;
 }
 
+// Test hook: the elementary functions of cilqr_device.hpp themselves, one lane per row (cilqr_debug_math, include/cilqr.h).
+// ROTATE: row i of `in` is {theta0, delta_1..T}; the chain starts from sincos_loop(theta0) as a forward pass does.
+__global__ void debug_math_kernel(KParams kp, int op, int n, int T, const double* in, double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (op == CILQR_MATH_EXP) {
+    out[i] = exp_full(in[i]);
+  } else if (op == CILQR_MATH_EXP_FAST) {
+    out[i] = exp_fast(in[i]);
+  } else if (op == CILQR_MATH_SINCOS_FAST) {
+    double sn, cs;
+    sincos_fast(in[i], &sn, &cs);
+    out[2 * (size_t)i] = sn; out[2 * (size_t)i + 1] = cs;
+  } else if (op == CILQR_MATH_SINCOS_LOOP) {
+    double sn, cs;
+    sincos_loop(in[i], sn, cs);
+    out[2 * (size_t)i] = sn; out[2 * (size_t)i + 1] = cs;
+  } else {
+    FwdConst k;
+    make_fwd_const(k, kp);
+    const double* row = in + (size_t)i * (T + 1);
+    double* o = out + (size_t)i * 2 * T;
+    double sn, cs;
+    sincos_loop(row[0], sn, cs);
+    for (int t = 0; t < T; ++t) {
+      rotate_heading(k, row[t + 1], sn, cs);
+      o[2 * t] = sn; o[2 * t + 1] = cs;
+    }
+  }
+}
+
 // Test hook: the closest-sample search on n independent queries (one lane each), beside the plain scan over ALL samples.
 // in[i] = {poly[6], x_first, x_last, px, py}; out[i] = {index by closest_sample, index by the full scan, 1 if the Newton search decided}.
 __global__ void closest_sample_kernel(int n, int S, const double* in, int32_t* out) {
@@ -2451,6 +2487,12 @@ hipError_t launch_closest_sample(int n, int S, const double* in, int32_t* out, h
 hipError_t launch_quu_inverse(int n, const double* q, const double* lamb, double* out, int general, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(quu_inverse_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, n, q, lamb, out, general);
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_math(const KParams& kp, int op, int n, int T, const double* in, double* out, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(debug_math_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, kp, op, n, T, in, out);
   return hipGetLastError();
 }
 
