@@ -295,6 +295,82 @@ int cilqr_solve_batch_obstacles_device(cilqr_handle* h, void* stream, int B, int
                                        const double* poly, const double* xplan_fl, const cilqr_obstacles* obs, double* X_out,
                                        double* J_out, int32_t* iters_out, int32_t* status_out, uint32_t flags);
 
+/* --- path-aligned planning frame ---------------------------------------------------------------------------------------
+ * The fit above is y(x) in map coordinates: ill-conditioned at |x| of a few hundred metres, and meaningless for a road that
+ * runs along y (its abscissae coincide).  The calls below plan in a frame of each solve's own instead.  Nothing in a solve,
+ * score, gains, risk or check kernel changes: they are handed framed inputs and their states are taken back out.
+ *
+ * Frame of solve b.  first = closest_point_index and n = the slice length, both exactly as cilqr_local_plan_batch has them.
+ *   origin  (ox, oy) = waypoint `first`;   chord  dx = x[first+n-1] - ox,  dy = y[first+n-1] - oy
+ *   h = sqrt(dx*dx + dy*dy)   (two rounded products, one rounded sum, a correctly rounded square root)
+ *   c = dx / h,  s = dy / h   (correctly rounded divisions),   phi = atan2(s, c)
+ * A frame record is CILQR_FRAME_DOUBLES doubles (ox, oy, c, s, phi).  When n < 2, h == 0 or h is not finite the frame is the
+ * translation alone (c = 1, s = 0, phi = 0) and the solve's info word carries CILQR_FRAME_DEGENERATE.  CILQR_FRAME_NOT_MONOTONE
+ * is set when the slice's framed abscissae are not strictly increasing, x'[i+1] > x'[i] false for some i (a NaN included): the
+ * slice turns by more than a quarter turn against its chord and the fit is as meaningless as the unframed one's.  It is
+ * reported, not repaired.
+ * Arithmetic, in this order, every product, sum and difference rounded on its own (no fused multiply-add):
+ *   into the frame    ux = x - ox,  uy = y - oy;   x' = (c*ux) + (s*uy),   y' = (c*uy) - (s*ux);   theta' = theta - phi
+ *   out of the frame  x = ((c*x') - (s*y')) + ox,  y = ((s*x') + (c*y')) + oy;                      theta  = theta' + phi
+ * Headings are not wrapped; v is untouched.
+ * NOT transformed by these calls: covariances of the EGO state (Sigma0, W of the chance risks, the rollout offsets).  A
+ * covariance whose position block is isotropic (the node's sigma_x = sigma_y = 0.16) is the same in every frame. */
+#define CILQR_FRAME_DOUBLES 5
+#define CILQR_FRAME_DEGENERATE 1   /* info bit: translation only */
+#define CILQR_FRAME_NOT_MONOTONE 2 /* info bit: framed abscissae of the slice not strictly increasing */
+#define CILQR_FRAME_TO 0           /* direction of cilqr_frame_states: map -> frame */
+#define CILQR_FRAME_FROM 1         /* frame -> map */
+#define CILQR_FRAME_GLOBAL_INFLATION 1u /* flags of cilqr_frame_obstacles, below */
+
+/* cilqr_local_plan_batch in the frame: the frame is chosen from the slice, every waypoint of the slice is taken into it and
+ * the Vandermonde rows are formed from the framed abscissae (the fit itself is the same code).  path, path_stride, ego, poly,
+ * ref_traj, n_out as there; frames [B][5], info [B], ego_out [B][4] = the ego state in the frame, the x0 of the solve;
+ * xplan_fl [B][2] and ref_traj are in frame coordinates; first_out [B] or NULL = closest_point_index.  ego_out must not be ego. */
+int cilqr_local_plan_frames(cilqr_handle* h, int B, int P, const double* path, int64_t path_stride, const double* ego,
+                            double* frames, int32_t* info, double* ego_out, double* poly, double* xplan_fl, double* ref_traj,
+                            int32_t* n_out, int32_t* first_out);
+int cilqr_local_plan_frames_device(cilqr_handle* h, void* stream, int B, int P, const double* path, int64_t path_stride,
+                                   const double* ego, double* frames, int32_t* info, double* ego_out, double* poly,
+                                   double* xplan_fl, double* ref_traj, int32_t* n_out, int32_t* first_out);
+
+/* Obstacle rows into the frames: the dense table pose_out [B][M][4N], dim_out [B][M][2N] (cilqr_solve_batch's layout) from
+ * obstacles in any strides; solve b uses the record at frames + b*frame_stride (frame_stride 5, or 0: one frame for the batch).
+ * Positions and headings as above; v is copied.  obs_cov (NULL, or (xx, xy, yy) per entry at obs_cov + 3e) is rotated to
+ * cov_out [B][M][3N] as T C T' with T = (c s; -s c):  m00 = c*xx + s*xy, m01 = c*xy + s*yy, m10 = c*xy - s*xx, m11 = c*yy - s*xy;
+ * xx' = m00*c + m01*s, xy' = m01*c - m00*s, yy' = m11*c - m10*s.  Obstacle weights are frame-free and not read.
+ * flags.  The reference inflates an obstacle's ellipse by |v cos theta_o| t_safe along and |v sin theta_o| t_safe across with
+ * theta_o in the PLANNING frame (I/Obstacle.cpp:42-43), so a moving obstacle gets a different ellipse in a turned frame.
+ *   0 (default): dim_out = dim; the reference's arithmetic simply runs in the frame.
+ *   CILQR_FRAME_GLOBAL_INFLATION: dim_out is compensated so that the solver forms the map frame's semi-axes:
+ *     L' = L + (2 t_safe) * (|v*cos theta_o| - |v*cos theta_o'|),  W' = W + (2 t_safe) * (|v*sin theta_o| - |v*sin theta_o'|),
+ *     sines and cosines by the kernels' own sincos (cilqr_debug_math, CILQR_MATH_SINCOS_FAST).
+ * Static obstacles (v = 0) are the same either way.
+ * pose_out, dim_out and cov_out must not overlap obs->pose, obs->dim and obs_cov: with shared strides many lanes read an entry that
+ * another lane's output would overwrite.  The host form takes every B <= max_batch, whatever the strides: its table travels through
+ * scratch the handle grows on first use, not through the arena of the other host forms. */
+int cilqr_frame_obstacles(cilqr_handle* h, int B, int N, int M, const double* frames, int64_t frame_stride,
+                          const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double* pose_out, double* dim_out,
+                          double* cov_out);
+int cilqr_frame_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* frames, int64_t frame_stride,
+                                 const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double* pose_out,
+                                 double* dim_out, double* cov_out);
+
+/* Rows [B*S][4(N+1)] of states into (CILQR_FRAME_TO) or out of (CILQR_FRAME_FROM) the frame of solve row / S: the X_out of a
+ * solve (S = 1), rollouts, stop rows.  X_out may be X_in.  B*S must not exceed max_batch. */
+int cilqr_frame_states(cilqr_handle* h, int B, int S, int N, const double* frames, int64_t frame_stride, int direction,
+                       const double* X_in, double* X_out);
+int cilqr_frame_states_device(cilqr_handle* h, void* stream, int B, int S, int N, const double* frames, int64_t frame_stride,
+                              int direction, const double* X_in, double* X_out);
+
+/* Poses (x, y, theta) into the frames: pose_in [B][K][3] at pose_in + b*pose_stride (pose_stride 0: one set [K][3] for the
+ * batch, else at least 3K) -> pose_out [B][K][3].  With K = 1 the map pose becomes the [B][3] `poses` of
+ * cilqr_set_uncertainty_map_device: the map cost, cilqr_rollout_risk_map, cilqr_footprint_check and cilqr_map_clearance then
+ * read the map from framed plans unchanged.  B*K must not exceed max_batch*max_horizon. */
+int cilqr_frame_poses(cilqr_handle* h, int B, int K, const double* frames, int64_t frame_stride, const double* pose_in,
+                      int64_t pose_stride, double* pose_out);
+int cilqr_frame_poses_device(cilqr_handle* h, void* stream, int B, int K, const double* frames, int64_t frame_stride,
+                             const double* pose_in, int64_t pose_stride, double* pose_out);
+
 /* --- costmap-lookup uncertainty cost ------------------------------------------------------------------
  * iLQR::set_uncertainty_map / clear_uncertainty_map (I/iLQR.cpp:28-35 → I/Constraints.cpp:520-528): while a map is set, every
  * later solve on the handle adds  w_uncertainty · (vx, mx)  of the map cost to l_x, l_xx at every step, exactly where

@@ -100,6 +100,11 @@ STOP_FIELDS = 8
  SP_LOST) = range(STOP_FIELDS)
 STOP_ALLOW_MOVING = 1  # flags of `stop_plans`: a row still moving at step N-1 keeps its cost
 STOP_MIN_ADVANCE = 1.0e-3  # metres: below this advance of the next step a row does not steer
+# path-aligned planning frame (`Solver.local_plan_frames`, `frame_obstacles`, `frame_states`, `frame_poses`)
+FRAME_DOUBLES = 5  # a frame record: (ox, oy, c, s, phi)
+FRAME_DEGENERATE, FRAME_NOT_MONOTONE = 1, 2  # bits of the info word
+FRAME_TO, FRAME_FROM = 0, 1  # direction of `frame_states`
+FRAME_GLOBAL_INFLATION = 1  # flags of `frame_obstacles`
 # `cilqr_debug_math`: which device routine `Solver.debug_math` runs
 MATH_EXP, MATH_SINCOS_FAST, MATH_SINCOS_LOOP, MATH_ROTATE, MATH_EXP_FAST = range(5)
 MAX_HORIZON = 384  # CILQR_MAX_HORIZON
@@ -137,6 +142,8 @@ ABI_SYMBOLS = (
     "cilqr_clear_movers", "cilqr_clear_movers_device",
     "cilqr_map_clearance", "cilqr_map_clearance_device",
     "cilqr_stop_plans", "cilqr_stop_plans_device",
+    "cilqr_local_plan_frames", "cilqr_local_plan_frames_device", "cilqr_frame_obstacles", "cilqr_frame_obstacles_device",
+    "cilqr_frame_states", "cilqr_frame_states_device", "cilqr_frame_poses", "cilqr_frame_poses_device",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -1374,6 +1381,106 @@ class Solver:
     def local_plan_batch_device(self, stream, B, P, path, path_stride, ego, poly, xplan_fl, ref_traj=0, n_out=0):
         _check(lib().cilqr_local_plan_batch_device(self._h, _vp(stream), int(B), int(P), _vp(path), C.c_int64(path_stride), _vp(ego),
                                                    _vp(poly), _vp(xplan_fl), _vp(ref_traj), _vp(n_out)))
+
+    # ---- the pre-step and its surroundings in a path-aligned planning frame ----
+    def local_plan_frames(self, path, ego):
+        """`cilqr_local_plan_frames`: path and ego as `local_plan_batch`.  Returns dict(frames (B, 5) = (ox, oy, c, s, phi), info (B,),
+        ego (B, 4) in the frame, poly (B, 6), xplan_fl (B, 2) and ref_traj (B, W, 2) in frame coordinates, n (B,), first (B,))."""
+        ego = _np64(ego).reshape(-1, 4)
+        B = ego.shape[0]
+        path = _np64(path)
+        if path.ndim == 3:
+            if path.shape[0] != B:
+                raise CilqrError("local_plan_frames: path batch dimension does not match ego")
+            P, stride = path.shape[1], 2 * path.shape[1]
+        else:
+            path = path.reshape(-1, 2)
+            P, stride = path.shape[0], 0
+        W = self.params.num_of_local_wpts
+        frames, info, ego_out = np.zeros((B, FRAME_DOUBLES)), np.zeros(B, dtype=np.int32), np.zeros((B, 4))
+        poly, fl, ref = np.zeros((B, POLY)), np.zeros((B, 2)), np.zeros((B, W, 2))
+        n, first = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        _check(lib().cilqr_local_plan_frames(self._h, B, int(P), _p(path), C.c_int64(stride), _p(ego), _p(frames), _p(info, _ip),
+                                             _p(ego_out), _p(poly), _p(fl), _p(ref), _p(n, _ip), _p(first, _ip)))
+        return dict(frames=frames, info=info, ego=ego_out, poly=poly, xplan_fl=fl, ref_traj=ref, n=n, first=first)
+
+    def local_plan_frames_device(self, stream, B, P, path, path_stride, ego, frames, info, ego_out, poly, xplan_fl, ref_traj=0,
+                                 n_out=0, first_out=0):
+        """`cilqr_local_plan_frames_device`: device addresses."""
+        _check(lib().cilqr_local_plan_frames_device(self._h, _vp(stream), int(B), int(P), _vp(path), C.c_int64(path_stride), _vp(ego),
+                                                    _vp(frames), _vp(info), _vp(ego_out), _vp(poly), _vp(xplan_fl), _vp(ref_traj),
+                                                    _vp(n_out), _vp(first_out)))
+
+    @staticmethod
+    def _frame_stride(frames, B):
+        frames = _np64(frames)
+        if frames.size == FRAME_DOUBLES and frames.ndim == 1:
+            return frames, 0
+        if frames.shape != (B, FRAME_DOUBLES):
+            raise CilqrError("frames %s are neither (%d,) nor (%d, %d)" % (frames.shape, FRAME_DOUBLES, B, FRAME_DOUBLES))
+        return frames, FRAME_DOUBLES
+
+    def frame_obstacles(self, B, N, frames, obs_pose, obs_dim, obs_cov=None, global_inflation=False):
+        """`cilqr_frame_obstacles`: frames (B, 5), or (5,) one frame for the batch; obstacles in any shape of `obstacle_strides`;
+        obs_cov None or (xx, xy, yy) per entry in the obstacles' own shape with 3 (or 3N) columns.  Returns dict(pose (B, M, 4N),
+        dim (B, M, 2N), cov (B, M, 3N) or None): the dense table of `solve_batch` in each solve's frame."""
+        frames, fs = self._frame_stride(frames, B)
+        M, obs, keep = self._obstacles(obs_pose, obs_dim, None, B, N)
+        obs_cov = None if obs_cov is None or M == 0 else _np64(obs_cov)
+        if obs_cov is not None and obs_cov.size * 4 != keep[0].size * 3:
+            raise CilqrError("frame_obstacles: obs_cov %s does not hold 3 values per entry of obs_pose %s" % (obs_cov.shape, keep[0].shape))
+        pose, dim = np.zeros((B, M, 4 * N)), np.zeros((B, M, 2 * N))
+        cov = None if obs_cov is None else np.zeros((B, M, 3 * N))
+        _check(lib().cilqr_frame_obstacles(self._h, int(B), int(N), int(M), _p(frames), C.c_int64(fs), None if obs is None else C.byref(obs),
+                                           _p(obs_cov), C.c_uint32(FRAME_GLOBAL_INFLATION if global_inflation else 0), _p(pose), _p(dim),
+                                           _p(cov)))
+        return dict(pose=pose, dim=dim, cov=cov)
+
+    def frame_obstacles_device(self, stream, B, N, M, frames, frame_stride, obs_pose, obs_dim, strides, pose_out, dim_out, obs_cov=0,
+                               cov_out=0, flags=0):
+        """`cilqr_frame_obstacles_device`: device addresses; strides (batch, obstacle, step) in entries."""
+        bs, ms, ts = (int(v) for v in tuple(strides)[:3])
+        obs = Obstacles(int(obs_pose) if obs_pose else None, int(obs_dim) if obs_dim else None, None, bs, ms, ts, 0)
+        _check(lib().cilqr_frame_obstacles_device(self._h, _vp(stream), int(B), int(N), int(M), _vp(frames), C.c_int64(frame_stride),
+                                                  C.byref(obs) if M else None, _vp(obs_cov), C.c_uint32(int(flags)), _vp(pose_out),
+                                                  _vp(dim_out), _vp(cov_out)))
+
+    def frame_states(self, N, frames, X, direction=FRAME_FROM, S=1):
+        """`cilqr_frame_states`: X (B*S, 4(N+1)) rows into (FRAME_TO) or out of (FRAME_FROM) the frame of solve row // S.  Returns the
+        transformed rows."""
+        X = _np64(X)
+        rows = X.size // (4 * (N + 1))
+        B = rows // int(S)
+        X = X.reshape(rows, 4 * (N + 1))
+        frames, fs = self._frame_stride(frames, B)
+        out = np.zeros_like(X)
+        _check(lib().cilqr_frame_states(self._h, int(B), int(S), int(N), _p(frames), C.c_int64(fs), int(direction), _p(X), _p(out)))
+        return out
+
+    def frame_states_device(self, stream, B, S, N, frames, frame_stride, direction, X_in, X_out):
+        """`cilqr_frame_states_device`: device addresses; X_out may be X_in."""
+        _check(lib().cilqr_frame_states_device(self._h, _vp(stream), int(B), int(S), int(N), _vp(frames), C.c_int64(frame_stride),
+                                               int(direction), _vp(X_in), _vp(X_out)))
+
+    def frame_poses(self, B, frames, poses):
+        """`cilqr_frame_poses`: poses (K, 3) shared by the batch or (B, K, 3) → (B, K, 3) in each solve's frame."""
+        poses = _np64(poses)
+        if poses.ndim == 3:
+            if poses.shape[0] != B or poses.shape[2] != 3:
+                raise CilqrError("frame_poses: poses %s are not (%d, K, 3)" % (poses.shape, B))
+            K, ps = poses.shape[1], 3 * poses.shape[1]
+        else:
+            poses = poses.reshape(-1, 3)
+            K, ps = poses.shape[0], 0
+        frames, fs = self._frame_stride(frames, B)
+        out = np.zeros((B, K, 3))
+        _check(lib().cilqr_frame_poses(self._h, int(B), int(K), _p(frames), C.c_int64(fs), _p(poses), C.c_int64(ps), _p(out)))
+        return out
+
+    def frame_poses_device(self, stream, B, K, frames, frame_stride, pose_in, pose_stride, pose_out):
+        """`cilqr_frame_poses_device`: device addresses."""
+        _check(lib().cilqr_frame_poses_device(self._h, _vp(stream), int(B), int(K), _vp(frames), C.c_int64(frame_stride), _vp(pose_in),
+                                              C.c_int64(pose_stride), _vp(pose_out)))
 
     def argmin_device(self, stream, B, J, out_pair):
         _check(lib().cilqr_argmin_device(self._h, _vp(stream), int(B), _vp(J), _vp(out_pair)))

@@ -2306,6 +2306,249 @@ int cilqr_local_plan_batch(cilqr_handle* h, int B, int P, const double* path, in
   return CILQR_OK;
 }
 
+// ---- path-aligned planning frame (local_plan.hip, cilqr_frame.hip) ---------------------------------------------------------------------
+namespace {
+int local_plan_frames_check(const cilqr_handle* h, int B, int P, const double* path, int64_t path_stride, const double* ego,
+                            const double* frames, const int32_t* info, const double* ego_out, const double* poly, const double* xplan_fl) {
+  if (!h) return fail(CILQR_ERR_ARG, "null handle");
+  if (!path || !ego || !frames || !info || !ego_out || !poly || !xplan_fl)
+    return fail(CILQR_ERR_ARG, "cilqr_local_plan_frames: null required pointer");
+  if (ego_out == ego) return fail(CILQR_ERR_ARG, "cilqr_local_plan_frames: ego_out must not be ego");
+  if (B < 1 || B > h->max_batch) return fail(CILQR_ERR_ARG, "cilqr_local_plan_frames: B=%d outside [1,%d]", B, h->max_batch);
+  if (P < 1) return fail(CILQR_ERR_ARG, "cilqr_local_plan_frames: P=%d must be at least 1", P);
+  if (path_stride < 0) return fail(CILQR_ERR_ARG, "cilqr_local_plan_frames: negative path_stride");
+  const cilqr_params& p = h->params;
+  if (p.num_of_local_wpts < 1 || p.poly_order < 0 || p.poly_order + 1 > CILQR_POLY_COEFFS)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_local_plan_frames: poly_order must be in [0, 5]");
+  if (cilqr::local_plan_lds_bytes(p.num_of_local_wpts, p.poly_order + 1) > 64 * 1024)
+    return fail(CILQR_ERR_UNSUPPORTED, "cilqr_local_plan_frames: num_of_local_wpts too large for the per-candidate LDS slot");
+  return CILQR_OK;
+}
+
+// frame_stride of the three transforms: `name` is the call's
+int frame_stride_check(const char* name, const double* frames, int64_t frame_stride) {
+  if (!frames) return fail(CILQR_ERR_ARG, "%s: frames is null", name);
+  if (frame_stride != 0 && frame_stride != CILQR_FRAME_DOUBLES)
+    return fail(CILQR_ERR_ARG, "%s: frame_stride=%lld is neither 0 nor %d", name, (long long)frame_stride, CILQR_FRAME_DOUBLES);
+  return CILQR_OK;
+}
+
+int frame_obstacles_check(const cilqr_handle* h, int B, int N, int M, const double* frames, int64_t frame_stride, const cilqr_obstacles* obs,
+                          const double* obs_cov, uint32_t flags, const double* pose_out, const double* dim_out, const double* cov_out,
+                          size_t* span) {
+  int rc = check_sizes(h, B, N, M);
+  if (rc) return rc;
+  rc = frame_stride_check("cilqr_frame_obstacles", frames, frame_stride);
+  if (rc) return rc;
+  if (flags & ~CILQR_FRAME_GLOBAL_INFLATION) return fail(CILQR_ERR_ARG, "cilqr_frame_obstacles: unknown flag bits 0x%x", flags);
+  if (M > 0 && !obs) return fail(CILQR_ERR_ARG, "cilqr_frame_obstacles: M = %d but obs is null", M);
+  if (M > 0 && (!pose_out || !dim_out)) return fail(CILQR_ERR_ARG, "cilqr_frame_obstacles: M = %d but pose_out or dim_out is null", M);
+  if (M > 0 && !obs_cov != !cov_out) return fail(CILQR_ERR_ARG, "cilqr_frame_obstacles: obs_cov and cov_out must be given together");
+  if (M > 0 && obs && (obs->batch_stride < 0 || obs->obstacle_stride < 0 || obs->step_stride < 0))
+    return fail(CILQR_ERR_ARG, "cilqr_frame_obstacles: negative stride in obs");
+  cilqr_obstacles o = M > 0 && obs ? *obs : cilqr_obstacles{};
+  o.weight = nullptr; o.weight_batch_stride = 0;  // not read
+  return check_obstacles(B, N, M, M > 0 && obs ? &o : nullptr, span, nullptr);
+}
+
+int frame_obstacles_launch(cilqr_handle* h, void* stream, int B, int N, int M, const double* frames, int64_t frame_stride,
+                           const cilqr_obstacles& o, const double* obs_cov, uint32_t flags, double* pose_out, double* dim_out,
+                           double* cov_out) {
+  cilqr::FrameObstaclesArgs a = {};
+  a.frames = frames; a.pose = o.pose; a.dim = o.dim; a.cov = obs_cov;
+  a.pose_out = pose_out; a.dim_out = dim_out; a.cov_out = cov_out;
+  a.bs = o.batch_stride; a.ms = o.obstacle_stride; a.ts = o.step_stride;
+  a.two_t_safe = 2.0 * h->kp.t_safe;
+  a.B = B; a.N = N; a.M = M; a.frame_stride = (int32_t)frame_stride; a.flags = flags;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_frame_obstacles(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int frame_states_check(const cilqr_handle* h, int B, int S, int N, const double* frames, int64_t frame_stride, int direction,
+                       const double* X_in, const double* X_out) {
+  int rc = check_sizes(h, B, N, 0);
+  if (rc) return rc;
+  rc = frame_stride_check("cilqr_frame_states", frames, frame_stride);
+  if (rc) return rc;
+  if (S < 1 || (int64_t)B * S > h->max_batch)
+    return fail(CILQR_ERR_ARG, "cilqr_frame_states: S=%d: B*S must be in [0,%d] and S at least 1", S, h->max_batch);
+  if (direction != CILQR_FRAME_TO && direction != CILQR_FRAME_FROM)
+    return fail(CILQR_ERR_ARG, "cilqr_frame_states: direction=%d is neither CILQR_FRAME_TO nor CILQR_FRAME_FROM", direction);
+  if (B > 0 && (!X_in || !X_out)) return fail(CILQR_ERR_ARG, "cilqr_frame_states: X_in or X_out is null");
+  return CILQR_OK;
+}
+
+int frame_poses_check(const cilqr_handle* h, int B, int K, const double* frames, int64_t frame_stride, const double* pose_in,
+                      int64_t pose_stride, const double* pose_out) {
+  int rc = check_sizes(h, B, 1, 0);
+  if (rc) return rc;
+  rc = frame_stride_check("cilqr_frame_poses", frames, frame_stride);
+  if (rc) return rc;
+  if (K < 1 || (int64_t)B * K > (int64_t)h->max_batch * h->max_horizon)
+    return fail(CILQR_ERR_ARG, "cilqr_frame_poses: K=%d: at least 1 and B*K at most %lld", K, (long long)h->max_batch * h->max_horizon);
+  if (pose_stride != 0 && pose_stride < 3 * (int64_t)K)
+    return fail(CILQR_ERR_ARG, "cilqr_frame_poses: pose_stride=%lld is neither 0 nor at least 3*K", (long long)pose_stride);
+  if (B > 0 && (!pose_in || !pose_out)) return fail(CILQR_ERR_ARG, "cilqr_frame_poses: pose_in or pose_out is null");
+  return CILQR_OK;
+}
+}  // namespace
+
+int cilqr_local_plan_frames_device(cilqr_handle* h, void* stream, int B, int P, const double* path, int64_t path_stride,
+                                   const double* ego, double* frames, int32_t* info, double* ego_out, double* poly,
+                                   double* xplan_fl, double* ref_traj, int32_t* n_out, int32_t* first_out) {
+  int rc = local_plan_frames_check(h, B, P, path, path_stride, ego, frames, info, ego_out, poly, xplan_fl);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  cilqr::LocalPlanFramesArgs a = {};
+  a.p.path = path; a.p.path_stride = path_stride; a.p.ego = ego;
+  a.p.poly = poly; a.p.xplan_fl = xplan_fl; a.p.ref_traj = ref_traj; a.p.n_out = n_out;
+  a.p.B = B; a.p.P = P; a.p.n_wpts = h->params.num_of_local_wpts; a.p.cols = h->params.poly_order + 1;
+  a.frames = frames; a.info = info; a.ego_out = ego_out; a.first_out = first_out;
+  HIP_TRY(cilqr::launch_local_plan_frames(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_local_plan_frames(cilqr_handle* h, int B, int P, const double* path, int64_t path_stride, const double* ego,
+                            double* frames, int32_t* info, double* ego_out, double* poly, double* xplan_fl, double* ref_traj,
+                            int32_t* n_out, int32_t* first_out) {
+  int rc = local_plan_frames_check(h, B, P, path, path_stride, ego, frames, info, ego_out, poly, xplan_fl);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t W = h->params.num_of_local_wpts, b = B;
+  const size_t n_path = path_stride ? (size_t)(B - 1) * path_stride + 2 * (size_t)P : 2 * (size_t)P;
+  // the scratch slots of cilqr_local_plan_batch; the block of doubles is followed by the three int32 arrays
+  void *vp = nullptr, *vio = nullptr;
+  rc = cilqr::scratch_bytes(h, cilqr::SCR_PLAN_PATH, n_path * sizeof(double), &vp);
+  if (rc) return rc;
+  const size_t o_ego = 0, o_poly = o_ego + b * 4, o_fl = o_poly + b * CILQR_POLY_COEFFS, o_ref = o_fl + b * 2, o_fr = o_ref + b * 2 * W,
+               o_eo = o_fr + b * CILQR_FRAME_DOUBLES, o_n = o_eo + b * 4;
+  rc = cilqr::scratch_bytes(h, cilqr::SCR_PLAN_IO, o_n * sizeof(double) + 3 * b * sizeof(int32_t), &vio);
+  if (rc) return rc;
+  double* d_path = (double*)vp;
+  double* io = (double*)vio;
+  int32_t* d_n = (int32_t*)(io + o_n);
+  int32_t *d_info = d_n + b, *d_first = d_n + 2 * b;
+  hipStream_t s = h->stream;
+  if (ref_traj) HIP_TRY(hipMemsetAsync(io + o_ref, 0, b * 2 * W * sizeof(double), s));
+  HIP_TRY(hipMemcpyAsync(d_path, path, n_path * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(io + o_ego, ego, b * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+  rc = cilqr_local_plan_frames_device(h, s, B, P, d_path, path_stride, io + o_ego, io + o_fr, d_info, io + o_eo, io + o_poly, io + o_fl,
+                                      ref_traj ? io + o_ref : nullptr, n_out ? d_n : nullptr, first_out ? d_first : nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(frames, io + o_fr, b * CILQR_FRAME_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(info, d_info, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(ego_out, io + o_eo, b * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(poly, io + o_poly, b * CILQR_POLY_COEFFS * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(xplan_fl, io + o_fl, b * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (ref_traj) HIP_TRY(hipMemcpyAsync(ref_traj, io + o_ref, b * 2 * W * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_out) HIP_TRY(hipMemcpyAsync(n_out, d_n, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (first_out) HIP_TRY(hipMemcpyAsync(first_out, d_first, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return CILQR_OK;
+}
+
+int cilqr_frame_obstacles_device(cilqr_handle* h, void* stream, int B, int N, int M, const double* frames, int64_t frame_stride,
+                                 const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double* pose_out,
+                                 double* dim_out, double* cov_out) {
+  int rc = frame_obstacles_check(h, B, N, M, frames, frame_stride, obs, obs_cov, flags, pose_out, dim_out, cov_out, nullptr);
+  if (rc) return rc;
+  if (B == 0 || M == 0) return CILQR_OK;
+  return frame_obstacles_launch(h, stream, B, N, M, frames, frame_stride, *obs, obs_cov, flags, pose_out, dim_out, cov_out);
+}
+
+int cilqr_frame_obstacles(cilqr_handle* h, int B, int N, int M, const double* frames, int64_t frame_stride,
+                          const cilqr_obstacles* obs, const double* obs_cov, uint32_t flags, double* pose_out, double* dim_out,
+                          double* cov_out) {
+  size_t span = 0;
+  int rc = frame_obstacles_check(h, B, N, M, frames, frame_stride, obs, obs_cov, flags, pose_out, dim_out, cov_out, &span);
+  if (rc) return rc;
+  if (B == 0 || M == 0) return CILQR_OK;
+  // Not through the arena: a dense table in and out is up to 18·M·N doubles per solve, three times what the arena reserves for
+  // one.  The two conversion scratch slots of the handle take it instead (grown on first use, like the pre-step's), so every
+  // B <= max_batch fits whatever the strides.
+  const size_t b = B, n_out = b * M * N, n_fr = frame_stride ? b * CILQR_FRAME_DOUBLES : (size_t)CILQR_FRAME_DOUBLES;
+  const size_t i_pose = n_fr, i_dim = i_pose + span * 4, i_cov = i_dim + span * 2, i_end = i_cov + (obs_cov ? span * 3 : 0);
+  const size_t o_dim = n_out * 4, o_cov = o_dim + n_out * 2, o_end = o_cov + (cov_out ? n_out * 3 : 0);
+  HIP_TRY(hipSetDevice(h->device));
+  void *vin = nullptr, *vout = nullptr;
+  rc = cilqr::scratch_bytes(h, cilqr::SCR_CONV_IN, i_end * sizeof(double), &vin);
+  if (rc == CILQR_OK) rc = cilqr::scratch_bytes(h, cilqr::SCR_CONV_OUT, o_end * sizeof(double), &vout);
+  if (rc) return rc;
+  double *in = (double*)vin, *out = (double*)vout;
+  hipStream_t s = h->stream;
+  HIP_TRY(hipMemcpyAsync(in, frames, n_fr * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(in + i_pose, obs->pose, span * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(in + i_dim, obs->dim, span * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (obs_cov) HIP_TRY(hipMemcpyAsync(in + i_cov, obs_cov, span * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  cilqr_obstacles o = *obs;
+  o.pose = in + i_pose; o.dim = in + i_dim; o.weight = nullptr;
+  rc = frame_obstacles_launch(h, s, B, N, M, in, frame_stride, o, obs_cov ? in + i_cov : nullptr, flags, out, out + o_dim,
+                              cov_out ? out + o_cov : nullptr);
+  if (rc) { (void)hipStreamSynchronize(s); return rc; }
+  HIP_TRY(hipMemcpyAsync(pose_out, out, n_out * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(dim_out, out + o_dim, n_out * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (cov_out) HIP_TRY(hipMemcpyAsync(cov_out, out + o_cov, n_out * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return CILQR_OK;
+}
+
+int cilqr_frame_states_device(cilqr_handle* h, void* stream, int B, int S, int N, const double* frames, int64_t frame_stride,
+                              int direction, const double* X_in, double* X_out) {
+  int rc = frame_states_check(h, B, S, N, frames, frame_stride, direction, X_in, X_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::FrameStatesArgs a = {};
+  a.frames = frames; a.X_in = X_in; a.X_out = X_out;
+  a.rows = (long long)B * S; a.S = S; a.N = N; a.frame_stride = (int32_t)frame_stride; a.direction = direction;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_frame_states(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_frame_states(cilqr_handle* h, int B, int S, int N, const double* frames, int64_t frame_stride, int direction,
+                       const double* X_in, double* X_out) {
+  int rc = frame_states_check(h, B, S, N, frames, frame_stride, direction, X_in, X_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  const size_t b = B, n = b * S * 4 * ((size_t)N + 1);
+  cilqr::HostPlan p(h->d_arena);
+  p.in(frames, frame_stride ? b * CILQR_FRAME_DOUBLES : (size_t)CILQR_FRAME_DOUBLES);
+  p.in(X_in, n);
+  p.out(X_out, n);  // (in place for the caller: two places in the arena)
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_frame_states_device(h, h->stream, B, S, N, frames, frame_stride, direction, X_in, X_out);
+  });
+}
+
+int cilqr_frame_poses_device(cilqr_handle* h, void* stream, int B, int K, const double* frames, int64_t frame_stride,
+                             const double* pose_in, int64_t pose_stride, double* pose_out) {
+  int rc = frame_poses_check(h, B, K, frames, frame_stride, pose_in, pose_stride, pose_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  cilqr::FramePosesArgs a = {};
+  a.frames = frames; a.pose_in = pose_in; a.pose_out = pose_out;
+  a.pose_stride = pose_stride; a.B = B; a.K = K; a.frame_stride = (int32_t)frame_stride;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(cilqr::launch_frame_poses(a, (hipStream_t)stream));
+  return CILQR_OK;
+}
+
+int cilqr_frame_poses(cilqr_handle* h, int B, int K, const double* frames, int64_t frame_stride, const double* pose_in,
+                      int64_t pose_stride, double* pose_out) {
+  int rc = frame_poses_check(h, B, K, frames, frame_stride, pose_in, pose_stride, pose_out);
+  if (rc) return rc;
+  if (B == 0) return CILQR_OK;
+  const size_t b = B;
+  cilqr::HostPlan p(h->d_arena);
+  p.in(frames, frame_stride ? b * CILQR_FRAME_DOUBLES : (size_t)CILQR_FRAME_DOUBLES);
+  p.in(pose_in, pose_stride ? (b - 1) * (size_t)pose_stride + 3 * (size_t)K : 3 * (size_t)K);
+  p.out(pose_out, b * K * 3);
+  return cilqr::host_call(h, p, [&] {
+    return cilqr_frame_poses_device(h, h->stream, B, K, frames, frame_stride, pose_in, pose_stride, pose_out);
+  });
+}
+
 int cilqr_occupancy_to_layer_device(cilqr_handle* h, void* stream, const int8_t* occ, int64_t n_cells, float* layer) {
   if (!h || n_cells < 0 || (n_cells > 0 && (!occ || !layer))) return fail(CILQR_ERR_ARG, "cilqr_occupancy_to_layer: bad argument");
   if (n_cells == 0) return CILQR_OK;

@@ -548,6 +548,49 @@ struct LocalPlanArgs {
 hipError_t launch_local_plan(const LocalPlanArgs& a, hipStream_t stream);
 size_t local_plan_lds_bytes(int n_wpts, int cols);
 
+// The same pre-step in the path-aligned frame of each candidate (include/cilqr.h, "path-aligned planning frame"): the frame
+// is chosen from the slice, the slice is taken into it and the fit runs on the framed abscissae.
+struct LocalPlanFramesArgs {
+  LocalPlanArgs p;      // ref_traj and xplan_fl receive frame coordinates
+  double* frames;       // [B][CILQR_FRAME_DOUBLES]
+  int32_t* info;        // [B] CILQR_FRAME_* bits
+  double* ego_out;      // [B][4]
+  int32_t* first_out;   // null or [B]
+};
+hipError_t launch_local_plan_frames(const LocalPlanFramesArgs& a, hipStream_t stream);
+
+// Rigid transforms into and out of the frames (cilqr_frame.hip): one lane per entry, per (row, step), per pose.
+struct FrameObstaclesArgs {
+  const double* frames;   // solve b reads frames + b*frame_stride
+  const double* pose;     // entries addressed by the strides below (cilqr_obstacles)
+  const double* dim;
+  const double* cov;      // null or 3 doubles per entry
+  double* pose_out;       // [B][M][4N]
+  double* dim_out;        // [B][M][2N]
+  double* cov_out;        // null or [B][M][3N]
+  long long bs, ms, ts;
+  double two_t_safe;      // 2·t_safe
+  int32_t B, N, M, frame_stride;
+  uint32_t flags;
+};
+hipError_t launch_frame_obstacles(const FrameObstaclesArgs& a, hipStream_t stream);
+struct FrameStatesArgs {
+  const double* frames;
+  const double* X_in;     // [B·S][4(N + 1)]
+  double* X_out;          // may be X_in
+  long long rows;         // B·S
+  int32_t S, N, frame_stride, direction;
+};
+hipError_t launch_frame_states(const FrameStatesArgs& a, hipStream_t stream);
+struct FramePosesArgs {
+  const double* frames;
+  const double* pose_in;  // solve b reads pose_in + b*pose_stride
+  double* pose_out;       // [B][K][3]
+  long long pose_stride;
+  int32_t B, K, frame_stride;
+};
+hipError_t launch_frame_poses(const FramePosesArgs& a, hipStream_t stream);
+
 // Min-cost selection (cilqr_select.hip).  out_pair {J_min, index} and/or out_triple {J_min, index, offset} (either may be null).
 hipError_t launch_argmin(const double* J, int B, double* out_pair, double* out_triple, double offset, hipStream_t stream,
                          double pair_offset = 0.0);

@@ -12,6 +12,7 @@
 // earlier glibc: always correctly rounded).
 #include <hip/hip_runtime.h>
 
+#include "cilqr_frame.hpp"
 #include "cilqr_internal.h"
 #include "vandermonde_qr.hpp"
 
@@ -107,6 +108,86 @@ __global__ __launch_bounds__(LPB) void local_plan_kernel(LocalPlanArgs a) {
   if (a.n_out) a.n_out[b] = n;
 }
 
+// The pre-step in the path-aligned frame of include/cilqr.h: the same search, slice, LDS slot and fit; between the slice and
+// the Vandermonde rows each waypoint is taken into the frame whose origin is the slice's first waypoint and whose x axis runs
+// along its chord.  A framed waypoint is three subtractions, four products and two sums, so it is formed again wherever it is
+// needed instead of being kept: the slot stays the one local_plan_lds_bytes sizes.
+template <int RM>
+__global__ __launch_bounds__(LPB) void local_plan_frames_kernel(LocalPlanFramesArgs fa) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const LocalPlanArgs& a = fa.p;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x * LPB + lane;
+  if (b >= a.B) return;
+  const int doubles_per_lane = a.n_wpts * (a.cols + 1) + 2 * a.cols;
+  LdsStore s;
+  s.d = lds + lane;
+  s.n = reinterpret_cast<int*>(lds + (size_t)doubles_per_lane * LPB) + lane;
+  s.rows_max = a.n_wpts;
+  s.cols = a.cols;
+
+  const double* path = a.path + (size_t)b * a.path_stride;
+  const double* ego = a.ego + 4 * (size_t)b;
+  const double ex = ego[0], ey = ego[1], ev = ego[2], eth = ego[3];
+  // closest_point_index and get_local_wpts in map coordinates, as local_plan_kernel has them
+  double dx = ex - path[0], dy = ey - path[1];
+  double best = dx * dx + dy * dy;
+  int first = 0;
+#pragma unroll 4
+  for (int i = 1; i < a.P; ++i) {
+    dx = ex - path[2 * i];
+    dy = ey - path[2 * i + 1];
+    const double dist = dx * dx + dy * dy;
+    if (dist < best) {
+      best = dist;
+      first = i;
+    }
+  }
+  const int n = (a.P - first) < a.n_wpts ? (a.P - first) : a.n_wpts;
+  const double* w = path + 2 * first;  // the slice
+  int info = 0;
+  const frame::Frame f = frame::make_frame(w[0], w[1], w[2 * (n - 1)], w[2 * (n - 1) + 1], n, &info);
+  double prev = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double x, y;
+    frame::point_to(f, w[2 * i], w[2 * i + 1], &x, &y);
+    if (i > 0 && !(x > prev)) info |= CILQR_FRAME_NOT_MONOTONE;
+    prev = x;
+    for (int j = 0; j < a.cols; ++j) s.m(i, j) = pow_small_int(x, j);
+    s.c(i) = y;
+  }
+  double coeffs[CILQR_POLY_COEFFS];
+  vandermonde_lstsq<RM>(s, n, a.cols, coeffs);
+  for (int j = 0; j < a.cols; ++j) a.poly[(size_t)b * CILQR_POLY_COEFFS + j] = coeffs[j];
+  for (int j = a.cols; j < CILQR_POLY_COEFFS; ++j) a.poly[(size_t)b * CILQR_POLY_COEFFS + j] = 0.0;
+  double x_first, x_last, unused;
+  frame::point_to(f, w[0], w[1], &x_first, &unused);
+  frame::point_to(f, w[2 * (n - 1)], w[2 * (n - 1) + 1], &x_last, &unused);
+  a.xplan_fl[2 * (size_t)b] = x_first;
+  a.xplan_fl[2 * (size_t)b + 1] = x_last;
+  if (a.ref_traj) {
+    double* r = a.ref_traj + (size_t)b * 2 * a.n_wpts;
+    for (int i = 0; i < n; ++i) {
+      double x, y;
+      frame::point_to(f, w[2 * i], w[2 * i + 1], &x, &y);
+      double fy = 0.0;
+      for (int j = 0; j < a.cols; ++j) fy += coeffs[j] * pow_small_int(x, j);
+      r[2 * i] = x;
+      r[2 * i + 1] = fy;
+    }
+  }
+  if (a.n_out) a.n_out[b] = n;
+  if (fa.first_out) fa.first_out[b] = first;
+  double* fr = fa.frames + (size_t)b * CILQR_FRAME_DOUBLES;
+  fr[0] = f.ox; fr[1] = f.oy; fr[2] = f.c; fr[3] = f.s; fr[4] = f.phi;
+  fa.info[b] = info;
+  double* eo = fa.ego_out + 4 * (size_t)b;
+  frame::point_to(f, ex, ey, &eo[0], &eo[1]);
+  eo[2] = ev;
+  eo[3] = eth - f.phi;
+}
+
 }  // namespace
 
 size_t local_plan_lds_bytes(int n_wpts, int cols) {
@@ -118,6 +199,15 @@ hipError_t launch_local_plan(const LocalPlanArgs& a, hipStream_t stream) {
   if (lds > 64 * 1024) return hipErrorInvalidValue;  // checked against the parameters at cilqr_create
   if (a.n_wpts == 20) local_plan_kernel<20><<<dim3((a.B + LPB - 1) / LPB), dim3(LPB), lds, stream>>>(a);
   else local_plan_kernel<0><<<dim3((a.B + LPB - 1) / LPB), dim3(LPB), lds, stream>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_local_plan_frames(const LocalPlanFramesArgs& a, hipStream_t stream) {
+  const size_t lds = local_plan_lds_bytes(a.p.n_wpts, a.p.cols);
+  if (lds > 64 * 1024) return hipErrorInvalidValue;
+  const dim3 grid((a.p.B + LPB - 1) / LPB);
+  if (a.p.n_wpts == 20) local_plan_frames_kernel<20><<<grid, dim3(LPB), lds, stream>>>(a);
+  else local_plan_frames_kernel<0><<<grid, dim3(LPB), lds, stream>>>(a);
   return hipGetLastError();
 }
 

@@ -103,6 +103,7 @@ iLQR::~iLQR() {
   if (block_stream_) (void)hipStreamSynchronize((hipStream_t)block_stream_);
   if (block_dev_) (void)hipFree(block_dev_);
   if (map_dev_) (void)hipFree(map_dev_);
+  if (frame_dev_) (void)hipFree(frame_dev_);
   if (mo_dev_) (void)hipFree(mo_dev_);
   if (trk_dev_) (void)hipFree(trk_dev_);
   if (block_stream_) (void)hipStreamDestroy((hipStream_t)block_stream_);
@@ -581,6 +582,7 @@ void iLQR::get_optimal_control_seq(const double x_0[4], Matrix& U, const double 
 
 void iLQR::run_step(const double ego_state[4]) {
   if (global_plan_.cols < 1) throw std::runtime_error("run_step: set_global_plan was not called");
+  if (frame_on_) { run_framed(1, std::vector<double>(ego_state, ego_state + 4), true); return; }
   double coeffs[CILQR_POLY_COEFFS];
   std::vector<double> ref(2 * (size_t)params.num_of_local_wpts);
   int n = 0;
@@ -700,6 +702,7 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   const CandidateModes m = modes();
   if (m.scov && m.track_rounds()) throw std::logic_error(kTrackMapWithSamples);
   if (m.stop_fallback && !m.footprint) throw std::logic_error(kStopFallbackWithoutFootprint);
+  if (frame_on_) return run_framed(B, ego_states, false);
   if (m.in_block()) return run_candidates_in_block(B, ego_states, m);
   // the unchecked path: the host-buffer forms on the handle's stream, the pick on the host
   Candidates c = plan_candidates(B, ego_states);
@@ -744,6 +747,117 @@ int iLQR::run_candidates(const std::vector<double>& ego_states) {
   install(s, control_seq_);
   ref_traj_result = Matrix(2, c.n_ref[best]);
   memcpy(ref_traj_result.a.data(), &c.ref[(size_t)best * 2 * params.num_of_local_wpts], ref_traj_result.a.size() * sizeof(double));
+  return best;
+}
+
+// ---- path-aligned planning frame -----------------------------------------------------------------------------------------------------
+namespace {
+const char kPathFrameInBlock[] =
+    "set_path_frame: the stages of the device block (noise, covariance and sampled checks, tightenings, track map, footprint, map "
+    "clearance, stop fallback), the tightened run_step and obstacle samples are not framed: switch them or set_path_frame off";
+}
+
+void iLQR::set_path_frame(bool on, bool global_inflation) {
+  frame_on_ = on;
+  frame_global_inflation_ = on && global_inflation;
+  last_frames.clear();
+  last_frame_info.clear();
+}
+
+// run_step and the unchecked path of run_candidates in the frames of their candidates: the host-buffer forms on the handle's stream,
+// the pick on the host, as there.  The solve, the score and the map cost are the unframed calls' own; only their inputs differ.
+int iLQR::run_framed(int B, const std::vector<double>& ego_states, bool step) {
+  const CandidateModes m = modes();
+  if (m.in_block() || m.chain() || m.track_rounds() || n_samples_) throw std::logic_error(kPathFrameInBlock);
+  if (step) {  // (run_candidates did these before it came here)
+    if (tracked_horizon_ >= 0 && tracked_horizon_ != params.horizon) install_tracked();
+    check_map_obstacle_conflicts();
+    refresh_map_rows();
+  }
+  const int N = params.horizon, M = (int)obstacles_.size();
+  const size_t W = params.num_of_local_wpts, b = B;
+  if (control_seq_.rows != 2 || control_seq_.cols != N) throw std::runtime_error("set_path_frame: the warm start must be 2×horizon");
+  std::vector<double> frames(b * CILQR_FRAME_DOUBLES), x0(b * 4), poly(b * CILQR_POLY_COEFFS), fl(b * 2), ref(b * 2 * W), U(b * 2 * N);
+  std::vector<int32_t> info(B), n_ref(B);
+  check(cilqr_local_plan_frames(h_, B, global_plan_.cols, global_plan_.a.data(), 0, ego_states.data(), frames.data(), info.data(), x0.data(),
+                                poly.data(), fl.data(), ref.data(), n_ref.data(), nullptr), "cilqr_local_plan_frames");
+  for (int c = 0; c < B; ++c) memcpy(&U[(size_t)c * 2 * N], control_seq_.a.data(), 2 * (size_t)N * sizeof(double));
+  // the obstacle rows: one set for every candidate in, one dense table per candidate out
+  std::vector<double> pose_f(b * M * 4 * N), dim_f(b * M * 2 * N);
+  cilqr_obstacles obs_f{pose_f.data(), dim_f.data(), nullptr, (int64_t)M * N, N, 1, 0};
+  if (M) {
+    const cilqr_obstacles obs = obstacle_strides();
+    check(cilqr_frame_obstacles(h_, B, N, M, frames.data(), CILQR_FRAME_DOUBLES, &obs, nullptr,
+                                frame_global_inflation_ ? CILQR_FRAME_GLOBAL_INFLATION : 0u, pose_f.data(), dim_f.data(), nullptr),
+          "cilqr_frame_obstacles");
+  }
+  // the map: its pose in every candidate's frame, behind a device copy of the layer; the handle gets its own map back afterwards
+  struct RestoreMap {
+    iLQR* self; bool armed;
+    ~RestoreMap() { if (armed) { try { self->apply_map(self->unc_); } catch (...) {} } }
+  } restore{this, false};
+  if (map_set_) {
+    const double pose[3] = {unc_.pose_x, unc_.pose_y, unc_.pose_theta};
+    std::vector<double> poses_f(b * 3);
+    check(cilqr_frame_poses(h_, B, 1, frames.data(), CILQR_FRAME_DOUBLES, pose, 0, poses_f.data()), "cilqr_frame_poses");
+    const size_t cells = (size_t)unc_.geom.rows * unc_.geom.cols, layer_bytes = (cells * sizeof(float) + 15) / 16 * 16;
+    const size_t need = layer_bytes + (size_t)max_candidates_ * 3 * sizeof(double);
+    if (hipSetDevice(device_) != hipSuccess) throw std::runtime_error("set_path_frame: hipSetDevice failed");
+    if (need > frame_dev_cap_) {
+      if (frame_dev_) (void)hipFree(frame_dev_);
+      frame_dev_ = nullptr; frame_dev_cap_ = 0;
+      if (hipMalloc(&frame_dev_, need) != hipSuccess) throw std::runtime_error("set_path_frame: hipMalloc failed");
+      frame_dev_cap_ = need;
+    }
+    double* poses_dev = (double*)((char*)frame_dev_ + layer_bytes);
+    if (hipMemcpy(frame_dev_, unc_.layer.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(poses_dev, poses_f.data(), poses_f.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("set_path_frame: hipMemcpy failed");
+    cilqr_uncertainty_map fm{};
+    fm.layer = (const float*)frame_dev_; fm.geom = unc_.geom; fm.poses = poses_dev; fm.layer_stride = 0;
+    fm.probes_l = unc_.probes_l; fm.probes_w = unc_.probes_w;
+    restore.armed = true;
+    check(cilqr_set_uncertainty_map_device(h_, &fm), "cilqr_set_uncertainty_map_device");
+  }
+  std::vector<double> X(b * 4 * (N + 1)), J(B), total;
+  std::vector<int32_t> iters(B), status(B);
+  check(cilqr_solve_batch_obstacles(h_, B, N, M, x0.data(), U.data(), poly.data(), fl.data(), M ? &obs_f : nullptr, X.data(), J.data(),
+                                    iters.data(), status.data(), CILQR_FLAG_NONE), "cilqr_solve_batch_obstacles");
+  if (!step) clear_candidate_fields();
+  std::vector<double> scores;
+  if (!step && m.min_total) {
+    scores.resize(b * CILQR_SCORE_FIELDS);
+    total.resize(B);
+    check(cilqr_score_batch(h_, B, N, M, X.data(), U.data(), poly.data(), fl.data(), M ? &obs_f : nullptr, max_collision_, scores.data(),
+                            total.data()), "cilqr_score_batch");
+    last_scores = scores;
+  }
+  last_frames = frames;
+  last_frame_info = info;
+  const std::vector<double>& rank = !step && m.min_total ? total : J;
+  int best = 0;
+  bool have = step;
+  if (!step)
+    for (int c = 0; c < B; ++c)
+      if (rank[c] == rank[c] && (!have || rank[c] < rank[best])) { best = c; have = true; }
+  if (!step && m.min_total && !have) return -1;
+  // the pick's states and fitted slice back in the map frame
+  const double* f = &frames[(size_t)best * CILQR_FRAME_DOUBLES];
+  Solved s;
+  s.X = Matrix(4, N + 1);
+  check(cilqr_frame_states(h_, 1, 1, N, f, 0, CILQR_FRAME_FROM, &X[(size_t)best * 4 * (N + 1)], s.X.a.data()), "cilqr_frame_states");
+  s.U.assign(&U[(size_t)best * 2 * N], &U[(size_t)best * 2 * N] + 2 * N);
+  s.J = J[best]; s.iters = iters[best]; s.status = status[best];
+  install(s, control_seq_);
+  const int n = n_ref[best];
+  ref_traj_result = Matrix(2, n);
+  for (int i = 0; i < n; ++i) {  // (the header's out-of-frame order, on the host: a 2 × n matrix has no heading column to carry)
+    const double xf = ref[((size_t)best * W + i) * 2], yf = ref[((size_t)best * W + i) * 2 + 1];
+    const double a = f[2] * xf, bb = f[3] * yf, c2 = f[3] * xf, d = f[2] * yf;
+    const double rx = a - bb, ry = c2 + d;
+    ref_traj_result(0, i) = rx + f[0];
+    ref_traj_result(1, i) = ry + f[1];
+  }
   return best;
 }
 

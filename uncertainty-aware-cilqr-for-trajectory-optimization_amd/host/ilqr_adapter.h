@@ -379,6 +379,19 @@ class iLQR {
   // run_candidates under set_stop_fallback; empty otherwise (last_stop_level: -1 whenever the published plan is a solved one)
   std::vector<double> last_stop, last_stop_footprint;  // CILQR_STOP_FIELDS / CILQR_FOOTPRINT_FIELDS per row = candidate * D + level
   int last_stop_pick = -1, last_stop_level = -1;
+
+  // Path-aligned planning frame (include/cilqr.h, "path-aligned planning frame").  While on, run_step and run_candidates on the
+  // unchecked path run: framed pre-step (cilqr_local_plan_frames) -> the obstacle rows into the frames (cilqr_frame_obstacles) ->
+  // the map pose into the frames while a map is set (cilqr_frame_poses) -> the unchanged solve, and the score under MinTotalCost ->
+  // X out of the frame (cilqr_frame_states).  X_result and ref_traj_result are in the map frame, as they are without the setter;
+  // U_result and the warm start are frame-free.  global_inflation: CILQR_FRAME_GLOBAL_INFLATION for moving obstacles.  Off, the
+  // default, every path is bit for bit what it is without this setter.  The stages that run in the device block
+  // (CandidateModes::in_block(): noise, covariance and sampled checks, the tightenings, the track map, footprint, map clearance, stop
+  // fallback), the tightened run_step and obstacle samples are not framed yet: with one of them and this setter both on, run_step /
+  // run_candidates throw std::logic_error naming set_path_frame.
+  void set_path_frame(bool on, bool global_inflation = false);
+  std::vector<double> last_frames;        // [B][CILQR_FRAME_DOUBLES] of the last framed call (B = 1 after run_step); empty when off
+  std::vector<int32_t> last_frame_info;   // [B] CILQR_FRAME_* bits
   // run_candidates under set_pose_covariance_check; empty otherwise
   std::vector<double> last_chance_risk, last_step_risk;  // CILQR_CHANCE_FIELDS per candidate; horizon per candidate
   // run_candidates with the map covariance check in effect (set_map_covariance_check); empty otherwise
@@ -473,6 +486,10 @@ class iLQR {
   double fp_min_clearance_ = 0.0, fp_threshold_ = 0.0, fp_margin_ = 0.0;
   // stop fallback (set_stop_fallback)
   bool stop_on_ = false;
+  bool frame_on_ = false, frame_global_inflation_ = false;
+  void* frame_dev_ = nullptr;   // while a map is set under set_path_frame: the layer and one framed pose per candidate
+  size_t frame_dev_cap_ = 0;    // bytes
+  int run_framed(int B, const std::vector<double>& ego_states, bool step);  // run_step (B = 1, step) and the unchecked run_candidates
   std::vector<double> stop_decel_;
   int stop_hold_ = 1;
   double stop_max_deviation_ = 0.5;

@@ -3,7 +3,11 @@
 // publishExperimentData), fed from a text log instead of ROS topics.
 //
 //   cilqr_replay <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size]
-//                [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]]   → one line per tick on stdout
+//                [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]] [--path-frame]   → one line per tick on stdout
+//
+// --path-frame: every tick runs under iLQR::set_path_frame(true): the pre-step, the obstacles and the map pose in a frame along the
+// tick's slice of the path, X back in the map frame; the line then ends with " frame <phi> <info>" (the frame's heading and its
+// CILQR_FRAME_* bits).  Not together with --tighten or --stop-fallback, whose stages are not framed.
 //
 // --tighten: every tick's solve is followed by `rounds` (default 1) rounds of chance-constraint tightening
 // (iLQR::set_chance_tightening) at a chance eps per obstacle entry, under the node's pose noise Sigma0 = diag(0.16^2, 0.16^2, 0,
@@ -90,17 +94,19 @@ struct Tokens {
 int main(int argc, char** argv) {
   std::vector<const char*> pos;  // the log and the device; options may stand anywhere
   const char *tighten = nullptr, *stop = nullptr, *map_obstacles = nullptr, *map_tracker = nullptr, *clear_movers = nullptr;
+  bool path_frame = false;
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--tighten") == 0 && i + 1 < argc) tighten = argv[++i];
     else if (strcmp(argv[i], "--stop-fallback") == 0 && i + 1 < argc) stop = argv[++i];
     else if (strcmp(argv[i], "--map-obstacles") == 0 && i + 1 < argc) map_obstacles = argv[++i];
     else if (strcmp(argv[i], "--map-tracker") == 0 && i + 1 < argc) map_tracker = argv[++i];
     else if (strcmp(argv[i], "--clear-movers") == 0 && i + 1 < argc) clear_movers = argv[++i];
+    else if (strcmp(argv[i], "--path-frame") == 0) path_frame = true;
     else if (strncmp(argv[i], "--", 2) == 0) pos.clear(), i = argc;
     else pos.push_back(argv[i]);
   }
   if (pos.empty() || pos.size() > 2) {
-    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size] [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <log> [device] [--tighten eps[,rounds]] [--stop-fallback d1[,d2...][:hold]] [--map-obstacles thr,gap,min_cells,max_size] [--map-tracker dt,q,r,gate2,min_hits,max_misses] [--clear-movers v_clear,halo[,fill]] [--path-frame]\n", argv[0]);
     return 2;
   }
   try {
@@ -140,6 +146,7 @@ int main(int argc, char** argv) {
       planner.set_footprint_check(0.0, INFINITY);
       planner.set_stop_fallback(levels, hold);
     }
+    if (path_frame) planner.set_path_frame(true);
     if (tighten) {
       char* rest = nullptr;
       const double eps = strtod(tighten, &rest);
@@ -250,6 +257,7 @@ int main(int argc, char** argv) {
         printf(" clear_movers");
         for (double v : planner.last_mover_clearing) printf(" %.9g", v);
       }
+      if (path_frame && !planner.last_frames.empty()) printf(" frame %.17g %d", planner.last_frames[4], (int)planner.last_frame_info[0]);
       if (stop) printf(" stop %d %d %d", picked < 0 ? -1 : planner.last_stop_level >= 0 ? 1 : 0, planner.last_stop_level, planner.last_stop_pick);
       printf("\n");
     }
